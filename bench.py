@@ -19,6 +19,12 @@ Launch:  python bench.py [--gpus N --steps K --warmup W]          (N > 1 without
 N = 1 runs BASELINE config C3 (one instance).  N > 1 runs BASELINE config C5's shape: independent
 case1354pegase-shaped scenarios, 16 per GPU (seeds 1354 + i), one process per GPU (weak scaling);
 the only collectives are a barrier and the aggregation of the timings (RCCL over xGMI).
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, ...).
+`--full` adds everything else the bench measures, after the timed steps: per-phase timings and the
+roofline, clocks, measured traffic, the C5 shape on one GPU, the end-to-end IPM runs, config C4 and
+the CPU baseline (each can be left out of a full run with its `--no-...` option).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see write_outputs).
 """
 from __future__ import annotations
 
@@ -80,19 +86,30 @@ def parse_args():
     ap.add_argument("--no-batch-api", action="store_true",
                     help="batch > 1: enqueue the factorizations one by one instead of through mnk_factorize_batch_begin/_end "
                          "(one merged persistent launch for all instances of a step: they fill each other's chain-bound ends)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure everything else as well: per-phase timings (ms_per_factorize / "
+                         "ms_per_solve / ms_assemble, per_rank_ms), roofline, clocks and the supplementary records below; "
+                         "off by default (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (solution, inertia and KKT values of every instance) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="keep roofline.traffic from the committed counter record instead of measuring it in this run (two child processes, ~15 s)")
+                    help="--full: keep roofline.traffic from the committed counter record instead of measuring it in this run (two child processes, ~15 s)")
     ap.add_argument("--no-c5-shape", action="store_true",
-                    help="skip the supplementary `c5_shape_per_gpu` record (16 instances per step on this GPU, ~15 s)")
-    ap.add_argument("--no-c4", action="store_true", help="skip the supplementary config-C4 record (case9241pegase shape, ~15 s)")
+                    help="--full: skip the supplementary `c5_shape_per_gpu` record (16 instances per step on this GPU, ~15 s)")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip the supplementary config-C4 record (case9241pegase shape, ~15 s)")
     ap.add_argument("--no-ipm-loop", action="store_true",
-                    help="skip the supplementary end-to-end IPM run (device-resident vectors) reported as `end_to_end_ipm`")
+                    help="--full: skip the supplementary end-to-end IPM run (device-resident vectors) reported as `end_to_end_ipm`")
     ap.add_argument("--cpu-baseline-budget", type=float, default=100.0,
-                    help="seconds of host time the cpu_baseline leg may spend (it drops the slowest legs first)")
+                    help="--full: seconds of host time the cpu_baseline leg may spend (it drops the slowest legs first)")
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="test-only: exercise the multi-process harness on CPU (gloo) without any kernel")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.cpu_dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs the real workload (the dry run computes nothing)")
     if args.batch is None:
         args.batch = 1 if args.gpus == 1 else 16
     return args
@@ -174,6 +191,27 @@ def gather_stats(vec, dist, world, device_tensor_fn):
     out = [t.clone() for _ in range(world)]
     dist.all_gather(out, t)
     return [[float(v) for v in o.tolist()] for o in out]
+
+
+DUMP_BUDGET_BYTES = 63 << 20   # (64 MB in all, less room for the .npy headers)
+
+
+def write_outputs(dirname, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """`--dump-outputs`: every array as `dirname/<name>.npy`, float64.  If they hold more than `budget_bytes` together, every array
+    is cut to the same fraction of its length by a fixed sample (rng seed 0, indices in ascending order): the same inputs give the
+    same files, run after run and build after build.  Returns {name: elements written}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = budget_bytes / total if total > budget_bytes else 1.0
+    written = {}
+    for name, a in arrays.items():
+        if frac < 1.0:
+            a = a.ravel()
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 # ---------------------------------------------------------------------------- supplementary end-to-end IPM run
@@ -657,7 +695,7 @@ def main():
     # N > 1: the denominator of the scaling curve is measured in the same run -- rank 0's GPU alone on its own 16 instances while the
     # other ranks wait at a barrier (`--gpus 1` is config C3, one instance; its value is NOT the per-GPU share of C5)
     solo = None
-    if dist is not None:
+    if dist is not None and args.full:
         for _ in range(args.warmup):
             step()
         sync()
@@ -680,10 +718,22 @@ def main():
             pass
         return rec or None
 
-    clk0 = clocks_now() if rank == 0 else None
+    clk0 = clocks_now() if rank == 0 and args.full else None
     # (the inertia of every factorization is checked inside the step: wrong inertia voids the numbers)
     elapsed = timed_region(step, args.steps, args.warmup, sync, dist, dt)
-    clk1 = clocks_now() if rank == 0 else None
+    clk1 = clocks_now() if rank == 0 and args.full else None
+
+    if args.dump_outputs:
+        # what the last timed step handed its caller, per instance: the solution of its last solve_linear_system!, the inertia of
+        # its factorization and the values of the condensed KKT matrix it assembled (aug_com, lower CSC); scenario g = rank * batch + b
+        sync()
+        arrays = {}
+        for bidx, (_, kb, _, din) in enumerate(insts):
+            pfx = "" if world * args.batch == 1 else f"inst{rank * args.batch + bidx:03d}_"
+            arrays[pfx + "x"] = din["x"].cpu().numpy()
+            arrays[pfx + "inertia"] = np.array(kb.linear_solver.inertia(), dtype=np.float64)
+            arrays[pfx + "kkt_nzval"] = kb.aug_com.nzval
+        write_outputs(args.dump_outputs, arrays, DUMP_BUDGET_BYTES // world)
 
     # per-phase breakdown, the reference's `timing_linear_solver` protocol (src/utils.jl:185-197):
     # each phase alone between device synchronizations, HIP events on the launch stream.
@@ -708,21 +758,16 @@ def main():
         d_x.copy_(d_rhs)
         ls.solve_linear_system(d_x)
 
-    reps = max(3, min(10, args.steps))
-    samples = {"assemble": phase_ms(assemble, reps), "factorize": phase_ms(ls.factorize_async, reps), "solve": phase_ms(one_solve, reps)}
-    ms = {k: float(np.mean(v)) for k, v in samples.items()}
-    allms = gather_stats([ms["assemble"], ms["factorize"], ms["solve"]], dist, world, dt)
+    if args.full:
+        reps = max(3, min(10, args.steps))
+        samples = {"assemble": phase_ms(assemble, reps), "factorize": phase_ms(ls.factorize_async, reps), "solve": phase_ms(one_solve, reps)}
+        ms = {k: float(np.mean(v)) for k, v in samples.items()}
+        allms = gather_stats([ms["assemble"], ms["factorize"], ms["solve"]], dist, world, dt)
 
     out = None
     if rank == 0:
         N = P.n
         flops = N ** 3 / 3.0
-        fact_ms = float(np.mean([a[1] for a in allms]))
-        ach = flops / (fact_ms * 1e-3) / 1e12
-        schedule = ls.get_stat("panel_algo")
-        # > 0: a device-side hand-off timed out and schedule 1 ran instead (INTEGRATION.md); summed over every instance of this rank
-        fallbacks = float(sum(it[1].linear_solver.get_stat("pp_fallbacks") for it in insts))
-        traffic, traffic_src = pmc_traffic(N, args, schedule)
         out = {
             "metric": METRIC, "value": world * args.batch * args.steps / elapsed, "unit": "it/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -742,6 +787,15 @@ def main():
                        "batch_api": ("mnk_factorize_batch_begin/_end: one merged persistent launch per step" if use_batch_api
                                      else ("off" if args.batch > 1 else "n/a (one instance)")),
                        "parallelism": f"{world} GPU(s) x {args.batch} independent instance(s)"},
+        }
+    if rank == 0 and args.full:
+        fact_ms = float(np.mean([a[1] for a in allms]))
+        ach = flops / (fact_ms * 1e-3) / 1e12
+        schedule = ls.get_stat("panel_algo")
+        # > 0: a device-side hand-off timed out and schedule 1 ran instead (INTEGRATION.md); summed over every instance of this rank
+        fallbacks = float(sum(it[1].linear_solver.get_stat("pp_fallbacks") for it in insts))
+        traffic, traffic_src = pmc_traffic(N, args, schedule)
+        out.update({
             "ms_per_factorize": fact_ms,
             # rank 0's own repetitions of the phase (the mean above is what `roofline` is computed from)
             "ms_per_factorize_min": float(np.min(samples["factorize"])), "ms_per_factorize_median": float(np.median(samples["factorize"])),
@@ -759,7 +813,7 @@ def main():
                          "schedule_panel_algo": schedule, "pp_fallbacks": fallbacks,
                          # host milliseconds lost to expired device-side waits in this process (0 on a healthy run)
                          "stall_ms_process": float(ls.get_stat("stall_ms_process"))},
-        }
+        })
         if world == 1 and args.batch == 1 and not args.no_live_traffic:
             # (child processes on the same GPU, after the timed region and the phase timings; ~15 s)
             lt = live_traffic(N, schedule)
@@ -834,7 +888,7 @@ def dry_run(args):
     dt = lambda v: torch.tensor(v, dtype=torch.float64)  # noqa: E731
     step = lambda: time.sleep(0.002 * (1 + rank))  # noqa: E731  (rank-dependent: MAX must pick the slowest)
     solo = None
-    if dist is not None:   # (the same solo phase as the GPU path: rank 0 alone between two barriers)
+    if dist is not None and args.full:   # (the same solo phase as the GPU path: rank 0 alone between two barriers)
         dist.barrier()
         if rank == 0:
             t0 = time.perf_counter()
@@ -843,7 +897,8 @@ def dry_run(args):
             solo = 3 / (time.perf_counter() - t0)
         dist.barrier()
     elapsed = timed_region(step, args.steps, args.warmup, lambda: None, dist, dt)
-    allms = gather_stats([1.0 + rank, 2.0 + rank, 3.0 + rank], dist, world, dt)
+    if args.full:
+        allms = gather_stats([1.0 + rank, 2.0 + rank, 3.0 + rank], dist, world, dt)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -852,10 +907,12 @@ def dry_run(args):
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-               "data": "dry-run (no kernels, not a measurement)", "per_rank_ms": allms,
-               "ms_per_factorize": 1.0, "ms_per_factorize_min": 1.0, "ms_per_factorize_median": 1.0,
-               "clocks": {"before_timed_region": shader_clock(0), "after_timed_region": shader_clock(0)},
+               "data": "dry-run (no kernels, not a measurement)",
                "config": {"workload": "cpu dry run", "batch_per_gpu": args.batch}}
+        if args.full:
+            out.update({"per_rank_ms": allms,
+                        "ms_per_factorize": 1.0, "ms_per_factorize_min": 1.0, "ms_per_factorize_median": 1.0,
+                        "clocks": {"before_timed_region": shader_clock(0), "after_timed_region": shader_clock(0)}})
         if world > 1 and solo is not None:
             out["per_gpu_value"] = out["value"] / world
             out["c5_shape_per_gpu"] = {"value": solo, "unit": "it/s per GPU", "instances_per_step": args.batch, "steps": 3}

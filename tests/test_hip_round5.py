@@ -359,7 +359,7 @@ def test_bench_py_on_two_gpus_over_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-c4", "--no-ipm-loop"]
+    common = ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-c4", "--no-ipm-loop"]
 
     def run(extra):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")

@@ -137,9 +137,6 @@ def test_option_keys_and_defaults_match_the_library():
         int(lib["single_rows"]), float(lib["pivot_tol"]), int(lib["panel_algo"]))
 
 
-REF = "/root/reference/src"
-
-
 def _first_julia_block(md: str) -> str:
     m = re.search(r"```julia\n(.*?)```", md, flags=re.S)
     assert m, "INTEGRATION.md has no julia snippet"
@@ -177,34 +174,28 @@ def test_documented_entry_point_selects_the_path():
     assert "RelaxEquality" in JL.split("length(ind_ineq) == m ||")[1][:400]
 
 
-def _reference_defines(name: str) -> bool:
-    """grep-level: `name` is defined (function / struct / abstract type / const / macro-generated enum member) or
-    imported somewhere under /root/reference/src."""
-    bare = name.rstrip("!")
-    n, b, end = re.escape(name), re.escape(bare), r"(?![A-Za-z_0-9!])"
-    pat = re.compile(
-        rf"(function\s+(MadNLP\.)?{n}{end}|^\s*{n}\(.*\)\s*(where.*)?=|struct\s+{b}{end}|abstract type\s+{b}{end}|"
-        rf"const\s+{b}{end}|@enum.*\b{b}{end}|^\s*{b}\s*(=|::)|\b{b}\s*=\s*\d+|import\s+\w+:.*\b{n}{end})", re.M)
-    for dp, _, fs in os.walk(REF):
-        for f in fs:
-            if f.endswith(".jl") and pat.search(open(os.path.join(dp, f)).read()):
-                return True
-    return False
+def _reference_defines(name: str, fx: dict) -> bool:
+    """grep-level: `name` is defined (function / struct / abstract type / const / macro-generated enum member) or imported somewhere
+    under the reference's src/.  The rule (tests/golden/make_reference_api_names.py: `full_name_pattern` on the name itself,
+    `bare_name_pattern` on the name without its trailing `!`) is applied to every identifier of the reference when the fixture is
+    written; `defined_names` / `defined_bare_names` hold the identifiers it matches."""
+    return name in fx["defined_names"] or name.rstrip("!") in fx["defined_bare_names"]
 
 
 def test_every_madnlp_name_the_glue_uses_exists_in_the_reference():
-    """Build box only (the reference tree is not shipped to the GPU box): every name the glue imports from MadNLP,
-    extends as `MadNLP.f(...)`, or reads as `MadNLP.X` must exist in /root/reference/src."""
-    import pytest
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present")
+    """Every name the glue imports from MadNLP, extends as `MadNLP.f(...)`, or reads as `MadNLP.X` must exist in the reference's src/
+    (fixture tests/golden/reference_api_names.json: the reference tree does not travel with the repository)."""
+    import json
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_api_names.json")))
+    fx = {k: set(fx[k]) for k in ("defined_names", "defined_bare_names")}
+    assert len(fx["defined_names"]) > 100 and len(fx["defined_bare_names"]) > 100, "fixture lost its definition lists"
     imported = re.search(r"import MadNLP: (.*?)\nimport LinearAlgebra", JL, flags=re.S).group(1)
     names = {n.strip() for n in imported.replace("\n", " ").split(",") if n.strip()}
     names |= set(re.findall(r"\bMadNLP\.([A-Za-z_][A-Za-z_0-9]*!?)", JL))
     names -= {"jl"}
     assert len(names) > 40
-    missing = sorted(n for n in names if not _reference_defines(n))
-    assert not missing, f"not found in {REF}: {missing}"
+    missing = sorted(n for n in names if not _reference_defines(n, fx))
+    assert not missing, f"not found in the reference's src/: {missing}"
 
 
 def _julia_code_without_comments():
@@ -218,7 +209,7 @@ def _julia_code_without_comments():
 
 def test_every_reference_name_the_glue_binds_to_exists_in_the_reference():
     """The glue cannot be executed (no Julia in any image), so the names it relies on are checked against a fixture of the reference's
-    identifiers (tests/golden/reference_api_names.json, written here by tests/golden/make_reference_api_names.py from /root/reference/src):
+    identifiers (tests/golden/reference_api_names.json, written by tests/golden/make_reference_api_names.py from the reference's src/):
     every `MadNLP.<name>`, every name of the `import MadNLP: ...` list, and every field read from the reference's
     `SchurComplementKKTSystem` (`inner.<field>`) -- the private fields VERDICT r5 pointed at."""
     import json

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out/prof_r02
 [ -z "$SKIP_BENCH" ] && rm -rf $R; mkdir -p $R
 cd /tmp
 B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-ipm-loop"
-timeout 300 rocprofv3 --kernel-trace -d $R/bench -o p -- $B --steps 10 --warmup 2 > $R/bench_under_rocprof.log 2>&1
+timeout 300 rocprofv3 --kernel-trace -d $R/bench -o p -- $B --full --steps 10 --warmup 2 > $R/bench_under_rocprof.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/fetch -o p -- $B --steps 2 --warmup 1 > $R/fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/write -o p -- $B --steps 2 --warmup 1 > $R/write.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d $R/mfma -o p -- $B --steps 2 --warmup 1 > $R/mfma.log 2>&1
@@ -17,8 +17,8 @@ python tools/pmc_report.py traffic $(db fetch) $(db write) $R/r02_pmc_traffic_fa
 python tools/pmc_report.py mfma $(db mfma) $R/r02_pmc_mfma_utilization.md "bench.py C3, N=11192" | tail -12
 grep '^{' $R/bench_under_rocprof.log | tail -1 > $R/r02_bench_N1_under_rocprof.json
 if [ -z "$SKIP_BENCH" ]; then
-python bench.py --steps 20 --warmup 5 > $R/r02_bench_N1.log 2>&1; grep '^{' $R/r02_bench_N1.log | tail -1 > $R/r02_bench_N1.json; cut -c1-600 $R/r02_bench_N1.json
-python bench.py --steps 5 --warmup 2 --batch 16 --no-cpu-baseline 2>&1 | grep '^{' | tail -1 > $R/r02_config_C5_batch16_per_gpu.json; cut -c1-400 $R/r02_config_C5_batch16_per_gpu.json
+python bench.py --full --steps 20 --warmup 5 > $R/r02_bench_N1.log 2>&1; grep '^{' $R/r02_bench_N1.log | tail -1 > $R/r02_bench_N1.json; cut -c1-600 $R/r02_bench_N1.json
+python bench.py --full --steps 5 --warmup 2 --batch 16 --no-cpu-baseline 2>&1 | grep '^{' | tail -1 > $R/r02_config_C5_batch16_per_gpu.json; cut -c1-400 $R/r02_config_C5_batch16_per_gpu.json
 fi
 rm -rf $R/bench $R/fetch $R/write $R/mfma
 tail -5 $R/r02_bench_kernel_stats.md

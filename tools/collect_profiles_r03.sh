@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT/gpurun_out/prof_r03
 rm -rf $R; mkdir -p $R
 cd /tmp
 B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-ipm-loop --no-c4"
-timeout 300 rocprofv3 --kernel-trace -d $R/bench -o p -- $B --steps 10 --warmup 2 > $R/bench_under_rocprof.log 2>&1
+timeout 300 rocprofv3 --kernel-trace -d $R/bench -o p -- $B --full --steps 10 --warmup 2 > $R/bench_under_rocprof.log 2>&1
 if [ -z "$SKIP_PMC" ]; then
 MNK_PANEL_ALGO=4 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/fetch -o p -- $B --steps 2 --warmup 1 > $R/fetch.log 2>&1
 MNK_PANEL_ALGO=4 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/write -o p -- $B --steps 2 --warmup 1 > $R/write.log 2>&1
@@ -25,8 +25,8 @@ python tools/pmc_report.py traffic $(db fetch) $(db write) $R/r03_pmc_traffic_fa
 python tools/pmc_report.py mfma $(db mfma) $R/r03_pmc_mfma_panel_algo4.md "bench.py C3 with MNK_PANEL_ALGO=4, N=11192" | tail -12
 fi
 grep '^{' $R/bench_under_rocprof.log | tail -1 > $R/r03_bench_N1_under_rocprof.json
-python bench.py --steps 20 --warmup 5 > $R/r03_bench_N1.log 2>&1; grep '^{' $R/r03_bench_N1.log | tail -1 > $R/r03_bench_N1.json; cut -c1-400 $R/r03_bench_N1.json
-python bench.py --steps 5 --warmup 2 --batch 16 --no-cpu-baseline 2>&1 | grep '^{' | tail -1 > $R/r03_config_C5_batch16_per_gpu.json; cut -c1-300 $R/r03_config_C5_batch16_per_gpu.json
+python bench.py --full --steps 20 --warmup 5 > $R/r03_bench_N1.log 2>&1; grep '^{' $R/r03_bench_N1.log | tail -1 > $R/r03_bench_N1.json; cut -c1-400 $R/r03_bench_N1.json
+python bench.py --full --steps 5 --warmup 2 --batch 16 --no-cpu-baseline 2>&1 | grep '^{' | tail -1 > $R/r03_config_C5_batch16_per_gpu.json; cut -c1-300 $R/r03_config_C5_batch16_per_gpu.json
 python tools/bench_configs.py c2 2>&1 | grep '^{' > $R/r03_config_C2_dense_condensed.jsonl; cat $R/r03_config_C2_dense_condensed.jsonl | cut -c1-400
 python tools/ipm_run_device.py dense 2048 512 0 2>&1 | grep '^{' > $R/r03_ipm_run_device_resident_C2_dense.jsonl
 python tools/dag_chain.py 11192 LDL > $R/dag_chain_C3.txt 2>&1

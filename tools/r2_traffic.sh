@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 timeout 600 python -m pytest tests/test_hip_parity.py -m gpu -q -x -k "gemm_nt or cholesky_vs_lapack or schedules or queue or dense_condensed_build" 2>&1 | tail -4
 B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline"
 for sw in 8 1 4 16; do
-  MNK_SUPER_W=$sw timeout 120 $B --steps 8 --warmup 2 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('sw=$sw factorize %.3f ms  it/s %.2f'%(d['ms_per_factorize'], d['value']))"
+  MNK_SUPER_W=$sw timeout 120 $B --full --steps 8 --warmup 2 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('sw=$sw factorize %.3f ms  it/s %.2f'%(d['ms_per_factorize'], d['value']))"
 done
 cd /tmp
 for sw in 8 1; do
