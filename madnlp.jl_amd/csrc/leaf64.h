@@ -419,7 +419,8 @@ __device__ __forceinline__ void potrf64v_core(v4d (&Lt)[4][4], int64_t j0, doubl
             }
             if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {   // (uniform values: all lanes or none)
                 // ---- a zero / non-finite / (Cholesky; early rejection) non-positive pivot in this group: the guarded scalar
-                // factorization of potrf64w_core (harmless pivot 1, the zero recorded); the selections below are the same
+                // factorization of potrf64w_core (harmless pivot 1, the zero recorded); the selections below are the same, as
+                // long as every candidate is finite (see the end of this branch)
                 Piv4 P;
                 double dg[4];
                 int fail;
@@ -432,7 +433,26 @@ __device__ __forceinline__ void potrf64v_core(v4d (&Lt)[4][4], int64_t j0, doubl
                 s0 = P.s0; s1 = P.s1; s2 = P.s2; s3 = P.s3;
                 c10 = P.c10; c20 = P.c20; c30 = P.c30; c21 = P.c21; c31 = P.c31; c32 = P.c32;
                 g0 = dg[0]; g1 = dg[1]; g2 = dg[2]; g3 = dg[3];
-                if (LDL) { x10 = c10 * s0; x20 = c20 * s0; x30 = c30 * s0; x21 = c21 * s1; x31 = c31 * s1; x32 = c32 * s2; }
+                if (LDL) {
+                    x10 = c10 * s0; x20 = c20 * s0; x30 = c30 * s0; x21 = c21 * s1; x31 = c31 * s1; x32 = c32 * s2;
+                    // An indicator sum is a selection only for finite candidates: here a NaN / Inf entry of the group reaches
+                    // c / x, and NaN * 0 would carry it into the entry of EVERY lane -- pivots recorded as NaN instead of their
+                    // values or 0, dinv NaN, the whole group's rows poisoned.  So every lane keeps the candidates of its own
+                    // entry only (0 elsewhere), and the entries of row 2 / 3 of inv(L44) that the code below composes from
+                    // several of them are composed here and handed on through the one candidate that carries them: the sums
+                    // below then give each lane the entry potrf64w_core selects (up to the sign of a zero), NaN only where that
+                    // entry is NaN.  Everything here stays inside this branch: the unguarded path keeps its code and registers.
+                    // (Cholesky needs nothing of this: `info` is settled by this group, the factor is void.)
+                    // (the recorded pivots g are finite: zero / non-finite ones are recorded as 0)
+                    auto own = [](double ind, double v) { return ind != 0.0 ? v : 0.0; };
+                    c10 = own(I10, c10); c20 = own(I20, c20); c30 = own(I30, c30);
+                    c21 = own(I21, c21); c31 = own(I31, c31); c32 = own(I32, c32);
+                    const double y20 = fma(x21, x10, -x20);
+                    x30 = own(I30, -fma(x32, -y20, -fma(x31, -x10, x30)));
+                    x20 = own(I20, -y20);
+                    x31 = own(I31, -fma(x32, x21, -x31));
+                    x10 = own(I10, x10); x21 = own(I21, x21); x32 = own(I32, x32);
+                }
             }
             double aop, ssel, vpiv, lpiv;
             // V = L D (LDL^T) / L (Cholesky) on the pivot rows: one indicator sum

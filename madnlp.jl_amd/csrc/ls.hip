@@ -953,11 +953,13 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
         child->probe = 0;
         child->accept_only_pd = 1;
         child->early_reject = 1;
-        child->pivot_tol = ls->pivot_tol;
         ls->probe_ls = child;
         ls->probe_order = m;
     }
     mnk_ls* c = ls->probe_ls;
+    // (the options that decide a verdict follow the parent's at every probe, not at the child's creation: a pivot_tol lowered
+    // since then would otherwise count a small positive pivot of the block as zero and reject what the parent accepts)
+    c->pivot_tol = ls->pivot_tol;
     int rc = mnk_ls_factorize_sc_async(c, sc);
     if (!rc) rc = mnk_ls_fetch_info(c);
     if (rc) return rc;

@@ -613,7 +613,11 @@ int mnk_sc_save_diagonals(mnk_sc* sc) {
     mnk_sc_spmv_data* sp = spmv_of(sc);
     MNK_REQUIRE(sp->have_diag, "mnk_sc_save_diagonals: call mnk_sc_set_aug_diagonal first");
     const size_t npr = (size_t)v.npr, ndu = (size_t)v.ndu;
-    if (sp->saved_diag.n < 2 * npr + ndu && sp->saved_diag.alloc(2 * npr + ndu)) return -1;
+    if (sp->saved_diag.n < 2 * npr + ndu && sp->saved_diag.alloc(2 * npr + ndu)) {
+        const std::string why = mnk_last_error_string();   // (the allocation's own message: which hipMalloc failed and why)
+        set_error("mnk_sc_save_diagonals: no device memory for the saved diagonals: %s", why.c_str());
+        return -1;
+    }
     hipStream_t s = sc->ctx->stream;
     MNK_HIP(hipMemcpyAsync(sp->saved_diag.p, v.reg, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
     MNK_HIP(hipMemcpyAsync(sp->saved_diag.p + npr, v.pr_diag, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
