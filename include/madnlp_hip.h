@@ -45,8 +45,9 @@ enum { MNK_HOST = 0, MNK_DEVICE = 1 };
 
 /* Same order as the reference's `@enum LinearFactorization`
  * (`src/LinearSolvers/linearsolvers.jl:139-147`): BUNCHKAUFMAN LU QR CHOLESKY LDL EVD.
- * Implemented on device: CHOLESKY (dpotrf semantics) and LDL (static-pivot
- * LDL^T, inertia from sign(D); stands in for BUNCHKAUFMAN = dsytrf). */
+ * Implemented on device: CHOLESKY (dpotrf semantics), LDL (static-pivot
+ * LDL^T, inertia from sign(D); stands in for BUNCHKAUFMAN = dsytrf) and QR
+ * (blocked Householder QR of the full symmetric matrix, dgeqrf conventions; no inertia). */
 enum { MNK_BUNCHKAUFMAN = 1, MNK_LU = 2, MNK_QR = 3, MNK_CHOLESKY = 4, MNK_LDL = 5, MNK_EVD = 6 };
 
 typedef struct mnk_ctx mnk_ctx; /* device, stream(s), scratch */
@@ -139,8 +140,13 @@ int mnk_dc_get_aug(mnk_dc* dc, double* out, int loc);
 /* ------------------------------------------------- linear solver (ls) ------- */
 /* Replaces `LapackCPUSolver(A; opt)` `src/LinearSolvers/lapack.jl:21-43` /
  * `LapackROCmSolver` `lib/MadNLPGPU/ext/MadNLPGPUAMDGPUExt/rocsolver.jl`:
- * allocates the private N x N factor buffer.  algo = MNK_CHOLESKY or MNK_LDL
- * (MNK_BUNCHKAUFMAN is accepted as an alias of MNK_LDL). */
+ * allocates the private N x N factor buffer.  algo = MNK_CHOLESKY, MNK_LDL or MNK_QR
+ * (MNK_BUNCHKAUFMAN is accepted as an alias of MNK_LDL).  MNK_QR (solve_qr!, reference `lapack.jl:187-209`):
+ * factorize! mirrors the transferred lower triangle to the full matrix (tril_to_full!) and runs a blocked
+ * Householder QR (dgeqrf conventions, 64-column compact-WY panels); info is always 0 and a singular matrix
+ * shows up in the solve; mnk_ls_inertia returns an error (no inertia); it is never merged into a factorization
+ * batch nor queued in a solve batch (it runs when called); the options that steer the LDL^T / Cholesky schedules
+ * are accepted and ignored. */
 int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out);
 int mnk_ls_destroy(mnk_ls* ls);
 /* Options: "pivot_tol" (LDL: |d| <= pivot_tol counts as a zero pivot; default 0),
@@ -221,7 +227,9 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);
  * (SolveException of the contract, reference src/LinearSolvers/linearsolvers.jl:133-137.) */
 int mnk_ls_check_solve(mnk_ls* ls);
 /* Debug / tests: copy the factor (N x N, ld = N; L in the lower triangle, for
- * LDL unit-lower L with D returned separately) and D (N entries, may be NULL). */
+ * LDL unit-lower L with D returned separately) and D (N entries, may be NULL).
+ * QR: dgeqrf's layout -- R on and above the diagonal, the Householder vectors below it
+ * (unit leading entry implicit) -- and tau in D. */
 int mnk_ls_get_factor(mnk_ls* ls, double* L, double* D, int loc);
 
 /* BUNCHKAUFMAN is served in two tiers: the static-pivot blocked LDL^T (fast path), and -- when that breaks down on

@@ -185,9 +185,15 @@ struct mnk_ls {
                                  // only happened if that factorization ran to its end (info == 0)
     int info = 0;
     int64_t npos = 0, nzero = 0, nneg = 0;
+    // QR (qr.hip): V of the current panel, the T of every panel (kept for the solves), split-K partials of W^T = A2^T V and
+    // W^T T, partial sums of the panel / solve kernels
+    mnk::DevBuf<double> qr_v, qr_t, qr_w, qr_p;
 };
 
 int64_t mnk_ls_effective_nbo(const mnk_ls* ls);
+int mnk_qr_alloc(mnk_ls* ls);    // qr.hip: the QR solver's buffers
+int mnk_qr_factor(mnk_ls* ls);   // qr.hip: tril_to_full! + blocked Householder QR of the transferred matrix (enqueued only)
+int mnk_qr_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // qr.hip: x <- R^-1 Q^T x
 int mnk_ls_run_factorization(mnk_ls* ls);
 int mnk_ls_run_factorization_now(mnk_ls* ls);      // factor.hip: the launch part (the schedule has been chosen; batches call it for leftovers)
 int mnk_ls_launch_finish_info(mnk_ls* ls, hipStream_t s);   // factor.hip: inertia / growth words / info -> pinned host words

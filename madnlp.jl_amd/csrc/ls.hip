@@ -598,8 +598,8 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     MNK_REQUIRE(N > 0, "mnk_ls_create: N must be positive");
     const bool bk_requested = algo == MNK_BUNCHKAUFMAN;
     if (bk_requested) algo = MNK_LDL;  // tier 1: static-pivot blocked LDL^T; tier 2 on breakdown: bk.hip
-    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL,
-                "mnk_ls_create: CHOLESKY, LDL and BUNCHKAUFMAN are implemented on device");
+    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_QR,
+                "mnk_ls_create: CHOLESKY, LDL, BUNCHKAUFMAN and QR are implemented on device");
     MNK_HIP(hipSetDevice(ctx->device));
     mnk_ls* ls = new mnk_ls();
     ls->ctx = ctx;
@@ -656,6 +656,10 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     }
     rc |= ls->info_dev.alloc(4);   // info | which bounded device-side wait expired (info = -7) / last valid pivot (info = -9) | early-rejection switch | -
     rc |= ls->inertia_dev.alloc(3);
+    if (algo == MNK_QR) {
+        rc |= mnk_qr_alloc(ls);
+        ls->prefill = 0;   // (qr.hip overwrites the whole factor buffer's upper triangle: no background zero-fill)
+    }
     if (rc) { delete ls; return -2; }
     MNK_HIP(hipMemsetAsync(ls->fact.p, 0, ((size_t)ls->ld * ls->Np + SLACK) * sizeof(double), ctx->stream));
     mnk_ctx_child_added(ctx);
@@ -1151,6 +1155,7 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
 
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
     MNK_REQUIRE(ls, "mnk_ls_inertia: NULL argument");
+    MNK_REQUIRE(ls->algo != MNK_QR, "mnk_ls_inertia: a QR factorization reveals no inertia (is_inertia is false for QR)");
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
     MNK_REQUIRE(ls->factorized, "mnk_ls_inertia: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
@@ -1208,6 +1213,7 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
     { int rc_f = ensure_complete_factor(ls, "mnk_ls_solve"); if (rc_f) return rc_f; }
     MNK_REQUIRE(nrhs >= 1 && ldx >= ls->N, "mnk_ls_solve: bad nrhs/ldx");
     MNK_HIP(hipSetDevice(ls->ctx->device));
+    if (ls->algo == MNK_QR) return mnk_qr_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
     if (ls->solve_abort && *ls->solve_abort != 0) {
         // a previous solve on device-resident vectors gave up (its result is invalid): fail loudly now and use
         // the stepwise solve from here on

@@ -194,6 +194,8 @@ extern "C" {
 int mnk_schur_create(mnk_ctx* ctx, int64_t ns_local, int64_t blk, int64_t nd, int algo, mnk_schur** out) {
     MNK_REQUIRE(ctx && out, "mnk_schur_create: NULL argument");
     MNK_REQUIRE(ns_local >= 0 && blk > 0 && nd > 0, "mnk_schur_create: bad dimensions");
+    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_BUNCHKAUFMAN,
+                "mnk_schur_create: CHOLESKY, LDL and BUNCHKAUFMAN are implemented for the Schur-complement system");
     MNK_HIP(hipSetDevice(ctx->device));
     mnk_schur* h = new mnk_schur();
     h->ctx = ctx;

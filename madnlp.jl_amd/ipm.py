@@ -10,7 +10,8 @@ reference closely enough that iteration counts and residual histories are meanin
   regular!               src/IPM/solver.jl:216-298
   update_barrier!        src/IPM/barrier.jl:12-34 (monotone), src/IPM/kernels.jl:697-713
   set_aug_diagonal!/rhs  src/IPM/kernels.jl:4-27,113-130,818-823
-  inertia_correction!    src/IPM/solver.jl:611-670 (InertiaBased)
+  inertia_correction!    src/IPM/solver.jl:611-670 (InertiaBased), :672-737 (InertiaFree, with curv_test :785-788),
+                         :739-783 (InertiaIgnore); the method is chosen at construction as IPM.jl:203-207 does
   solve_refine_wrapper!  src/IPM/factorization.jl:1-19 + backsolve.jl
   filter_line_search!    src/IPM/line_search.jl:6-123 (+ second-order correction solver.jl:547-608)
   restore!               src/IPM/solver.jl:300-411 (soft restoration, get_F kernels.jl:572-610)
@@ -19,7 +20,7 @@ reference closely enough that iteration counts and residual histories are meanin
 
 Not implemented: NLP
 scaling (problems used here have gradients below nlp_scaling_max_gradient, so the reference's
-scaling factors are 1), inertia-free regularization, quasi-Newton.
+scaling factors are 1), quasi-Newton.
 
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
 mirror (`madnlp_jl_amd.kkt`) or, in the tests, the CPU oracle.
@@ -89,6 +90,10 @@ class IPMOptions:
     mu_linear_decrease_factor: float = 0.2
     mu_superlinear_decrease_power: float = 1.5
     rho: float = 1000.0                                  # options.jl:195
+    # options.jl:153-154: "auto" (InertiaAuto: inertia_based if the linear solver reveals the inertia, else inertia_free),
+    # "inertia_based", "inertia_free", "ignore"
+    inertia_correction_method: str = "auto"
+    inertia_free_tol: float = 0.0
     soft_resto_pderror_reduction_factor: float = 0.9999  # options.jl:178
     required_infeasibility_reduction: float = 0.9        # options.jl:179
 
@@ -123,6 +128,27 @@ class RobustRestorer:
     tau_R: float = 0.0
     zeta: float = 0.0
     filter: list = field(default_factory=list)
+
+
+INERTIA_CORRECTION_METHODS = ("auto", "inertia_based", "inertia_free", "ignore")
+
+
+@dataclass
+class InertiaFreeCorrector:
+    """`InertiaFree` inertiacorrector.jl:7-20: right-hand side / solution of the normal step, the tangential step t, the
+    Hessian product wx and the barrier gradient g."""
+    p0: object
+    d0: object
+    t: np.ndarray
+    wx: np.ndarray
+    g: np.ndarray
+
+
+def curv_test(t, n, g, kkt, wx, inertia_free_tol):
+    """`curv_test` solver.jl:785-788: t'Wt + max(t'W n - g'n, 0) - tol t't >= 0 (W: the Hessian block with its diagonal)."""
+    kkt.mul_hess_blk(wx, t)
+    return float(np.dot(wx, t)) + max(float(np.dot(wx, n)) - float(np.dot(g, n)), 0.0) - \
+        inertia_free_tol * float(np.dot(t, t)) >= 0
 
 
 @dataclass
@@ -199,6 +225,15 @@ class MadNLPSolver:
         self.x_trial, self.c_trial = np.zeros(nt), np.zeros(m)
         V = lambda: UnreducedKKTVector(nt, m, len(self.ind_lb), len(self.ind_ub), self.ind_lb, self.ind_ub)  # noqa: E731
         self.d, self.p, self._w1, self._w4 = V(), V(), V(), V()
+        method = o.inertia_correction_method
+        if method not in INERTIA_CORRECTION_METHODS:
+            raise ValueError(f"inertia_correction_method must be one of {INERTIA_CORRECTION_METHODS}, not {method!r}")
+        if method == "auto":   # IPM.jl:203-207
+            method = "inertia_based" if self.kkt.linear_solver.is_inertia() else "inertia_free"
+        self.inertia_correction_method = method
+        if method == "inertia_free":   # the corrector's storage, inertiacorrector.jl:7-20 / solver.jl:756-765
+            self._ifr = InertiaFreeCorrector(V(), V(), np.zeros(nt), np.zeros(nt), np.zeros(nt))
+            self._w3 = V()
         self.iterator = RichardsonIterator(self.kkt, tol=o.tol)
         self.cnt = Counters()
         self.filter = []
@@ -369,6 +404,10 @@ class MadNLPSolver:
 
     # ------------------------------------------------------------------ inertia_correction! (solver.jl:611-670)
     def inertia_correction(self):
+        if self.inertia_correction_method == "inertia_free":
+            return self._inertia_correction_free()
+        if self.inertia_correction_method == "ignore":
+            return self._inertia_correction_ignore()
         o, k = self.opt, self.kkt
         n_trial = 0
         dw_prev = dc_prev = 0.0
@@ -392,6 +431,84 @@ class MadNLPSolver:
             self.factorize_wrapper()
             inertia = k.linear_solver.inertia()
             ok = self.solve_refine_wrapper(self.d, self.p, self._w4) if k.is_inertia_correct(*inertia) else False
+            n_trial += 1
+        if self.del_w != 0:
+            self.del_w_last = self.del_w
+        return True
+
+    def _next_perturbation(self, n_trial):
+        """del_w of trial n_trial + 1 (the schedule shared by all three correctors); False: too big, restoration."""
+        o = self.opt
+        if n_trial == 0:
+            self.del_w = (o.first_hessian_perturbation if self.del_w_last == 0 else
+                          max(o.min_hessian_perturbation, o.perturb_dec_fact * self.del_w_last))
+        else:
+            self.del_w *= o.perturb_inc_fact_first if self.del_w_last == 0 else o.perturb_inc_fact
+            if self.del_w > o.max_hessian_perturbation:
+                self.cnt.k += 1
+                return False
+        self.del_c = o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
+        return True
+
+    def _set_g_ifr(self, g):
+        """`set_g_ifr!` kernels.jl:242-248."""
+        with np.errstate(divide="ignore"):
+            g[:] = self.f - self.mu / (self.x - self.xl) + self.mu / (self.xu - self.x) + self.jacl
+
+    def _set_aug_rhs_ifr(self, p0):
+        """`set_aug_rhs_ifr!` kernels.jl:233-240."""
+        p0.primal()[:] = 0.0
+        p0.dual_lb()[:] = 0.0
+        p0.dual_ub()[:] = 0.0
+        p0.dual()[:] = -self.c
+
+    def _ifr_solves(self):
+        """The two solves of one inertia-free trial: the normal step d0 (p0 = (0, -c, 0, 0)) and the search direction; the
+        tangential component t = dx - n."""
+        ic = self._ifr
+        ok = (self.solve_refine_wrapper(ic.d0, ic.p0, self._w3) and
+              self.solve_refine_wrapper(self.d, self.p, self._w4))
+        ic.t[:] = self._dx() - ic.d0.primal()
+        return ok
+
+    def _inertia_correction_free(self):
+        """`inertia_correction!(::InertiaFree)` solver.jl:672-737: a trial is accepted when both solves succeed and the
+        curvature test holds for the tangential component of the step."""
+        k, ic = self.kkt, self._ifr
+        n_trial = 0
+        dw_prev = dc_prev = 0.0
+        self.del_w = self.del_c = 0.0
+        self._set_g_ifr(ic.g)
+        self._set_aug_rhs_ifr(ic.p0)
+        self.factorize_wrapper()
+        ok = self._ifr_solves()
+        while not curv_test(ic.t, ic.d0.primal(), ic.g, k, ic.wx, self.opt.inertia_free_tol) or not ok:
+            if not self._next_perturbation(n_trial):
+                return False
+            k.regularize_diagonal(self.del_w - dw_prev, self.del_c - dc_prev)
+            dw_prev, dc_prev = self.del_w, self.del_c
+            self.factorize_wrapper()
+            ok = self._ifr_solves()
+            n_trial += 1
+        if self.del_w != 0:
+            self.del_w_last = self.del_w
+        return True
+
+    def _inertia_correction_ignore(self):
+        """`inertia_correction!(::InertiaIgnore)` solver.jl:739-783: perturb only when the solve fails."""
+        k = self.kkt
+        n_trial = 0
+        dw_prev = dc_prev = 0.0
+        self.del_w = self.del_c = 0.0
+        self.factorize_wrapper()
+        ok = self.solve_refine_wrapper(self.d, self.p, self._w4)
+        while not ok:
+            if not self._next_perturbation(n_trial):
+                return False
+            k.regularize_diagonal(self.del_w - dw_prev, self.del_c - dc_prev)
+            dw_prev, dc_prev = self.del_w, self.del_c
+            self.factorize_wrapper()
+            ok = self.solve_refine_wrapper(self.d, self.p, self._w4)
             n_trial += 1
         if self.del_w != 0:
             self.del_w_last = self.del_w

@@ -206,6 +206,12 @@ class DeviceOPFCallbacks:
 class DeviceMadNLPSolver(MadNLPSolver):
     def __init__(self, nlp, kkt_factory, opt: IPMOptions | None = None, device="cuda", sparse=True):
         super().__init__(nlp, kkt_factory, opt, sparse=sparse)
+        if self.inertia_correction_method != "inertia_based":
+            if hasattr(self.kkt, "close"):
+                self.kkt.close()
+            raise NotImplementedError(
+                f"DeviceMadNLPSolver runs the inertia-based correction only (resolved method: {self.inertia_correction_method}; "
+                f"a linear solver without inertia selects inertia_free): use MadNLPSolver for inertia-free or ignore")
         assert not sparse or self.ns == self.m, "device driver: all-inequality (RelaxEquality) sparse condensed systems"
         self.dev = torch.device(device)
         self._on_device = False

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib as L
 
 BUNCHKAUFMAN, LU, QR, CHOLESKY, LDL, EVD = "BUNCHKAUFMAN", "LU", "QR", "CHOLESKY", "LDL", "EVD"
-_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL}
+_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL, QR: L.MNK_QR}
 
 
 class LinearSolverException(Exception):
@@ -148,7 +148,8 @@ def _ptr(a):
 @dataclass
 class HipSolverOptions:
     """Analogue of `LapackOptions` (reference `src/LinearSolvers/lapack.jl:1-3`).
-    BUNCHKAUFMAN (the reference default) maps to the static-pivot LDL^T."""
+    BUNCHKAUFMAN (the reference default) maps to the static-pivot LDL^T.  QR (blocked Householder, dgeqrf conventions)
+    reveals no inertia: the IPM then corrects inertia-free.  The schedule options below do not apply to QR (ignored)."""
     lapack_algorithm: str = BUNCHKAUFMAN
     pivot_tol: float = 0.0
     outer_block: int = 0          # 0: by size (512; 1024 from 32 768 rows on)
@@ -174,7 +175,7 @@ class HipLinearSolver:
         self.opt = opt or HipSolverOptions()
         if self.opt.lapack_algorithm not in _ALGO:
             raise SymbolicException(
-                f"algorithm {self.opt.lapack_algorithm} is not implemented on device (CHOLESKY, LDL/BUNCHKAUFMAN)")
+                f"algorithm {self.opt.lapack_algorithm} is not implemented on device (CHOLESKY, LDL/BUNCHKAUFMAN, QR)")
         self.A = A
         self.ctx = ctx or getattr(A, "ctx", None) or HipContext()
         self.n = _order_of(A)
@@ -212,7 +213,8 @@ class HipLinearSolver:
         return np.dtype(dtype) == np.float64
 
     def is_inertia(self) -> bool:
-        return True
+        """reference `is_inertia(::LapackCPUSolver)`: false for QR (no inertia from a QR factorization)."""
+        return self.opt.lapack_algorithm != QR
 
     def factorize(self):
         """`factorize!(M)`: transfer_matrix! + factorization; never raises on a numerical
@@ -255,6 +257,8 @@ class HipLinearSolver:
         return self
 
     def inertia(self):
+        if not self.is_inertia():
+            raise InertiaException(f"{self.opt.lapack_algorithm} reveals no inertia")
         p, z, n = C.c_int64(), C.c_int64(), C.c_int64()
         rc = L.lib().mnk_ls_inertia(self._h, C.byref(p), C.byref(z), C.byref(n))
         if rc:
@@ -314,7 +318,8 @@ class HipLinearSolver:
         L.check(L.lib().mnk_ls_set_option(self._h, key.encode(), float(value)), "mnk_ls_set_option")
 
     def get_factor(self):
-        """(L, D) on the host, for tests."""
+        """(L, D) on the host, for tests.  QR: dgeqrf's layout (R on and above the diagonal, Householder vectors below it)
+        and tau."""
         Lm = np.zeros((self.n, self.n), order="F")
         D = np.zeros(self.n)
         L.check(L.lib().mnk_ls_get_factor(self._h, Lm.ctypes.data, D.ctypes.data, L.MNK_HOST), "mnk_ls_get_factor")
