@@ -571,6 +571,13 @@ int mnk_debug_dag_tasks(int ntile, int chunk, int band_tiles, int js2, int taper
 int mnk_debug_dag_merged_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period,
                                int* out, int cap);
 
+/* Diagnostics / tests (host only): the envelope per 128-row tile row that a solver of order `order` (<= the handle's n) uses when
+ * it factors this KKT handle's condensed matrix: tile_env[I] = (first nonzero column over the rows of tile I) / 128, truncated to
+ * the (order + 127) / 128 tiles of that order.  At most `cap` entries written; returns the number of tiles (negative: bad arguments). */
+int mnk_sc_debug_tile_env(mnk_sc* sc, int64_t order, int32_t* out, int cap);
+/* ... and the one mnk_ls_factorize_csc derives from a lower CSC matrix of order n. */
+int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap);
+
 /* Diagnostics (tools/microbench_update.py): time `reps` lower-tile trailing updates C -= A*A^T under the
  * schedules the factorization uses (static tiling / tile queue; context, update, update+panel streams). */
 int mnk_debug_update(mnk_ctx* ctx, int variant, int64_t M, int64_t K, const double* A, int64_t lda,

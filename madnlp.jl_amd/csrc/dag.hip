@@ -66,6 +66,8 @@ struct DagInst {
     unsigned long long* vmax;   // growth monitor of the static-pivot LDL^T (factor.hip growth_fold): receives max|V|, or NULL
     double* zfill;        // DAG_FILL tasks: the buffer that becomes the NEXT factorization's zeroed factor buffer (or NULL)
     int64_t N;            // order of the matrix (rows / columns N .. Np - 1 are padding: unit diagonal)
+    const int* env;       // envelope per tile row (mnk_sc::tile_env): L(I, k) = 0 for tile columns k < env[I]; NULL: dense
+    const int* envgate;   // != 0: a NaN / Inf entry was transferred, the envelope is off for this factorization (mnk_ls::env_word)
 };
 
 // (read through the constant address space: the fields are uniform and never written while a bulk kernel runs, so every use
@@ -340,13 +342,17 @@ __global__ void dag_gate_kernel(const int* __restrict__ word, int target, int* _
     }
 }
 
+// (`envw`: the solver's mnk_ls::env_word -- the verdict of the transfer on its finiteness becomes this factorization's, and the word
+// the next transfer marks is cleared)
 __global__ __launch_bounds__(256) void dag_reset_kernel(int* __restrict__ flags, int64_t n, int* __restrict__ info, DagInst rec,
-                                                        DagInst* __restrict__ rec_dst, const SmallSysRec* __restrict__ recs = nullptr) {
+                                                        DagInst* __restrict__ rec_dst, const SmallSysRec* __restrict__ recs = nullptr,
+                                                        int* __restrict__ envw = nullptr) {
     if (recs != nullptr) {   // (a batch of small systems: blockIdx.y = system; the instance records are uploaded by the host)
         const SmallSysRec r = recs[blockIdx.y];
         flags = r.flags; n = r.nflags; info = r.info;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && rec_dst != nullptr) *rec_dst = rec;   // the instance record the bulk kernel reads
+    if (blockIdx.x == 0 && threadIdx.x == 0 && envw != nullptr) { envw[1] = envw[0]; envw[0] = 0; }
     int4* f4 = reinterpret_cast<int4*>(flags);   // (hipMalloc alignment; the tail is done word by word)
     const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) f4[i] = make_int4(0, 0, 0, 0);
@@ -376,6 +382,14 @@ __device__ __forceinline__ void dag_fill_tile(IP in, int I, int J, int tid) {
         }
         *reinterpret_cast<double2*>(Z + row + col * ld) = v;
     }
+}
+
+// Zero the 128 x 128 tile at (row0, col0) of V: the tile-closing task of a structurally zero tile.  F holds the zeros of the fill
+// there, V is never refilled and may hold anything the previous factorization of this solver (any source) left.
+__device__ __forceinline__ void dag_zero_tile(double* Z, int64_t ld, int64_t row0, int64_t col0, int tid) {
+    const int r2 = (tid & 63) * 2, cg = tid >> 6;
+#pragma unroll 4
+    for (int c = cg; c < 128; c += 4) *reinterpret_cast<double2*>(Z + row0 + r2 + (col0 + c) * ld) = make_double2(0.0, 0.0);
 }
 
 template <bool LDL>
@@ -430,20 +444,30 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
         __syncthreads();
         auto run_task = [&]() __attribute__((always_inline)) -> bool {
         if (dead) return false;
+        // the envelope of this instance's factorization (as in dag_bulk_kernel1)
+        int eI = 0, k0 = kbeg;
+        if (in->env != nullptr && __builtin_amdgcn_readfirstlane(*in->envgate) == 0) {
+            eI = __builtin_amdgcn_readfirstlane(in->env[I]);
+            k0 = min(kend, max(kbeg, max(eI, __builtin_amdgcn_readfirstlane(in->env[J]))));
+        }
         // k-tiles [0, limit) of this chunk have final operands; the gate blocks at the first k-tile of a tile column that is
         // not final yet (a rare event: the queue is sorted by readiness)
         int limit = 0;
+        auto gate_at = [&](int kc) -> int {
+            const unsigned long long w0 = tr ? wall_clock64() : 0;
+            const int r = dag_wait_front(in, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kc, kend, &s_val);
+            if (tr) { const unsigned long long w1 = wall_clock64(); tr[2] = w1; tr[6] += 1; tr[7] += w1 - w0; s_stat[1] += w1 - w0; }
+            return r;
+        };
         auto gate = [&](int kt) -> bool {
             if (kt < limit) return true;
-            const unsigned long long w0 = tr ? wall_clock64() : 0;
-            const int r = dag_wait_front(in, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kbeg + (kt >> 4), kend, &s_val);
-            if (tr) { const unsigned long long w1 = wall_clock64(); tr[2] = w1; tr[6] += 1; tr[7] += w1 - w0; s_stat[1] += w1 - w0; }
+            const int r = gate_at(k0 + (kt >> 4));
             if (r < 0) return false;
-            limit = (__builtin_amdgcn_readfirstlane(r) - kbeg) * 16;
+            limit = (__builtin_amdgcn_readfirstlane(r) - k0) * 16;
             return true;
         };
-        const double* Ak = in->F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)128 * kbeg * in->ld;
-        const double* Bk = (LDL ? in->V : in->F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)128 * kbeg * in->ld;
+        const double* Ak = in->F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)128 * k0 * in->ld;
+        const double* Bk = (LDL ? in->V : in->F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)128 * k0 * in->ld;
         auto wait_chunk_order = [&]() -> bool {   // the chunks of one tile are applied in order
             if (flags & DAG_FIRST) return true;
             const int* word = in->tprog + (int64_t)I * a.ntile + J;
@@ -461,6 +485,11 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             // the tile as the earlier chunks left it goes into the accumulators BEFORE the wait for the row's previous tile
             // column: its load is off the critical path; the K-loop then subtracts (NEG)
             if (!wait_chunk_order()) return false;
+            if (J < eI) {   // structurally zero tile (as in dag_bulk_kernel1)
+                if (kend > kbeg && gate_at(kbeg) < 0) return false;
+                if (LDL) dag_zero_tile(in->V, in->ld, row0, col0, tid);
+                return true;
+            }
             v4f64 X[8][2];
             {
                 const int lane = tid & 63, w = tid >> 6;
@@ -474,8 +503,8 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
                         X[cb][1][r] = cp[16];
                     }
             }
-            if (kend > kbeg && !gate(0)) return false;   // one tile column: its operands are final at once
-            (void)gemm_nt_mainloop3<2, 8, true>(X, Ak, in->ld, Bk, in->ld, (kend - kbeg) * 16, smem_raw, tid);
+            if (kend > kbeg && gate_at(kbeg) < 0) return false;   // one tile column: its operands are final at once
+            if (kend > k0) (void)gemm_nt_mainloop3<2, 8, true>(X, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid);
             // (new live ranges: the register pressure of the finalization below must not push the accumulators of the
             // K-loop above into scratch)
 #pragma unroll
@@ -486,7 +515,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             if (tr) { tr[4] = wall_clock64(); s_stat[1] += tr[4] - tr[3]; }
             dag_finalize_tile<LDL>(in, row0, col0, 2 * J, smem_raw, tid, X, tr);
             if (tr) s_stat[3] += wall_clock64() - tr[4];
-        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > kbeg)) {
+        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > k0)) {
             v4f64 acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -495,11 +524,11 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             // the last chunk of a band tile is on the critical path of the chain: it issues first
             if (flags & DAG_FINAL) __builtin_amdgcn_s_setprio(3);
             // (the two-buffer loop: the three-buffer one is ~10 % slower at three workgroups per CU -- tools/hip/time_kstep.hip)
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - kbeg) * 16, smem_raw, tid, gate)) return false;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             if (!wait_chunk_order()) return false;
             // C(I, J) -= acc
-            if (kend > kbeg)
+            if (kend > k0)
                 gemm_nt_epilogue<2, 2, 4, 2, false, true>(acc, row0, col0, (int64_t)1 << 40, (int64_t)1 << 40, in->F, in->ld, nullptr, nullptr, 0, tid);
             if (tr) tr[3] = wall_clock64();
         } else {
@@ -513,7 +542,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             __builtin_amdgcn_s_setprio(3);   // (every chunk: the next one of the tile -- in the end the chain -- waits for it)
             if (!wait_chunk_order()) return false;
             gemm_nt_load_neg_lower<2, 2, 4>(acc, row0, col0, in->F, in->ld, tid);
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - kbeg) * 16, smem_raw, tid, gate)) return false;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             gemm_nt_store_neg_lower<2, 2, 4>(acc, row0, col0, in->F, in->ld, tid);
             if (tr) tr[3] = wall_clock64();
@@ -570,6 +599,8 @@ struct DagArgs1 {
     int fake_share;             // DIAGNOSTIC (env MNK_DAG_FAKE_SHARE, wrong results): every chunk reads the operand rows of tile rows 0..n-1
     double* zfill;              // DAG_FILL tasks: the buffer of the next factorization (or NULL)
     int64_t N;
+    const int* env;             // (as in DagInst)
+    const int* envgate;
 #if MNK_DIAG_BULK_DBG
     int* bdbg;                  // 16 words per workgroup: {task, stage, words, target, value, spins >> 18, tasks done, -, the 4 front words seen}
 #endif
@@ -589,6 +620,8 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
     // per-workgroup statistics of the trace option live in LDS (thread 0 only): no registers across the task loop
     __shared__ unsigned long long s_stat[4];  // first grab, ticks waited, tasks, ticks in the finalization
     if (threadIdx.x < 4) s_stat[threadIdx.x] = 0;
+    // the envelope of this factorization (NULL: dense -- no envelope, or a NaN / Inf entry)
+    const int* __restrict__ env = a.env != nullptr && __builtin_amdgcn_readfirstlane(*a.envgate) == 0 ? a.env : nullptr;
     __syncthreads();
     for (;;) {
         int tid = threadIdx.x;
@@ -628,20 +661,32 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             continue;
         }
 
+        // Envelope: the tile columns k < max(env[I], env[J]) of L(I, k) or of V(J, k) are exact zeros -- the K-loop starts
+        // behind them (k0; an empty chunk still keeps its place in the tile's chunk order), and a tile-closing task of a tile
+        // with J < env[I] has nothing to compute
+        int eI = 0, k0 = kbeg;
+        if (env != nullptr) {
+            eI = __builtin_amdgcn_readfirstlane(env[I]);
+            k0 = min(kend, max(kbeg, max(eI, __builtin_amdgcn_readfirstlane(env[J]))));
+        }
         // k-tiles [0, limit) of this chunk have final operands; the gate blocks at the first k-tile of a tile column that is
         // not final yet (a rare event: the queue is sorted by readiness)
         int limit = 0;
+        auto gate_at = [&](int kc) -> int {   // tile columns [kc, return value) final for all four strips
+            const unsigned long long w0 = tr ? wall_clock64() : 0;
+            const int r = dag_wait_front(&a, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kc, kend, &s_val, MNK_BDBG(a));
+            if (tr) { const unsigned long long w1 = wall_clock64(); tr[2] = w1; tr[6] += 1; tr[7] += w1 - w0; s_stat[1] += w1 - w0; }
+            return r;
+        };
         auto gate = [&](int kt) -> bool {
             if (kt < limit) return true;
-            const unsigned long long w0 = tr ? wall_clock64() : 0;
-            const int r = dag_wait_front(&a, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kbeg + (kt >> 4), kend, &s_val, MNK_BDBG(a));
-            if (tr) { const unsigned long long w1 = wall_clock64(); tr[2] = w1; tr[6] += 1; tr[7] += w1 - w0; s_stat[1] += w1 - w0; }
+            const int r = gate_at(k0 + (kt >> 4));
             if (r < 0) return false;
-            limit = (__builtin_amdgcn_readfirstlane(r) - kbeg) * 16;
+            limit = (__builtin_amdgcn_readfirstlane(r) - k0) * 16;
             return true;
         };
-        const double* Ak = a.F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)128 * kbeg * a.ld;
-        const double* Bk = (LDL ? a.V : a.F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)128 * kbeg * a.ld;
+        const double* Ak = a.F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)128 * k0 * a.ld;
+        const double* Bk = (LDL ? a.V : a.F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)128 * k0 * a.ld;
         auto wait_chunk_order = [&]() -> bool {   // the chunks of one tile are applied in order
             if (flags & DAG_FIRST) return true;
             const int* word = a.tprog + (int64_t)I * a.ntile + J;
@@ -659,6 +704,13 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             // the tile as the earlier chunks left it goes into the accumulators BEFORE the wait for the row's previous tile
             // column: its load is off the critical path; the K-loop then subtracts (NEG)
             if (!wait_chunk_order()) return;
+            if (J < eI) {
+                // structurally zero tile: only V needs its zeros.  (The wait of the K-step all the same: the row's closing tasks
+                // publish front[2I] in column order.)
+                if (kend > kbeg && gate_at(kbeg) < 0) return;
+                if (LDL) dag_zero_tile(a.V, a.ld, row0, col0, tid);
+                goto publish;
+            }
             v4f64 X[8][2];
             {
                 const int lane = tid & 63, w = tid >> 6;
@@ -672,8 +724,8 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
                         X[cb][1][r] = cp[16];
                     }
             }
-            if (kend > kbeg && !gate(0)) return;   // one tile column: its operands are final at once
-            (void)gemm_nt_mainloop3<2, 8, true>(X, Ak, a.ld, Bk, a.ld, (kend - kbeg) * 16, smem_raw, tid);
+            if (kend > kbeg && gate_at(kbeg) < 0) return;   // one tile column: its operands are final at once
+            if (kend > k0) (void)gemm_nt_mainloop3<2, 8, true>(X, Ak, a.ld, Bk, a.ld, (kend - k0) * 16, smem_raw, tid);
             // (new live ranges: the register pressure of the finalization below must not push the accumulators of the
             // K-loop above into scratch)
 #pragma unroll
@@ -684,7 +736,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             if (tr) { tr[4] = wall_clock64(); s_stat[1] += tr[4] - tr[3]; }
             dag_finalize_tile<LDL>(&a, row0, col0, 2 * J, smem_raw, tid, X, tr);
             if (tr) s_stat[3] += wall_clock64() - tr[4];
-        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > kbeg)) {
+        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > k0)) {
             v4f64 acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -693,11 +745,11 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             // the last chunk of a band tile is on the critical path of the chain: it issues first
             if (flags & DAG_FINAL) __builtin_amdgcn_s_setprio(3);
             // (the two-buffer loop: the three-buffer one is ~10 % slower at three workgroups per CU -- tools/hip/time_kstep.hip)
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - kbeg) * 16, smem_raw, tid, gate)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - k0) * 16, smem_raw, tid, gate)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             if (!wait_chunk_order()) return;
             // C(I, J) -= acc
-            if (kend > kbeg)
+            if (kend > k0)
                 gemm_nt_epilogue<2, 2, 4, 2, false, true>(acc, row0, col0, (int64_t)1 << 40, (int64_t)1 << 40, a.F, a.ld, nullptr, nullptr, 0, tid);
             if (tr) tr[3] = wall_clock64();
         } else {
@@ -711,11 +763,12 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             __builtin_amdgcn_s_setprio(3);   // (every chunk: the next one of the tile -- in the end the chain -- waits for it)
             if (!wait_chunk_order()) return;
             gemm_nt_load_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - kbeg) * 16, smem_raw, tid, gate)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - k0) * 16, smem_raw, tid, gate)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             gemm_nt_store_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
             if (tr) tr[3] = wall_clock64();
         }
+    publish:
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) {
@@ -906,7 +959,7 @@ static int launch_dag_bulk(hipStream_t s, bool ldl, const DagInst& one, const Da
     static const int fake = getenv("MNK_DAG_FAKE_SHARE") ? atoi(getenv("MNK_DAG_FAKE_SHARE")) : 0;
     if (insts == nullptr) {
         DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
-                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N};
+                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate};
 #if MNK_DIAG_BULK_DBG
         a.bdbg = g_diag_bdbg;
 #endif
@@ -982,8 +1035,11 @@ static mnk::DagInst dag_instance(mnk_ls* ls) {
     // the spare factor buffer is zeroed by the queue's DAG_FILL tasks when the NEXT transfer will want it (a sparse source was
     // transferred for this factorization: mnk_ls::spare_pending) and no background fill of it is in flight
     double* zfill = (ls->dag_fill && ls->dag_has_fill && ls->spare_pending && ls->fact_spare.p && !ls->spare_zeroed) ? ls->fact_spare.p : nullptr;
+    // the envelope of a sparse source (ls.hip: set_envelope); the bulk kernel reads the verdict on its finiteness (env_word[1])
+    const bool env = ls->envelope && ls->env_dev != nullptr && ls->env_word.p != nullptr;
     return mnk::DagInst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
-                        front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N};
+                        front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N, env ? ls->env_dev : nullptr,
+                        env ? ls->env_word.p + 1 : nullptr};
 }
 
 // Buffers of the task-DAG schedule: the task list (built once per matrix order and option set), the progress words and,
@@ -1069,8 +1125,11 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
     // progress words and `info` in ONE launch (two memsets are two fill kernels, ~8 us each in front of the pivot chain)
     const mnk::DagInst inst = dag_instance(ls);
     ls->dag_filled = inst.zfill != nullptr;
+    ls->env_used = inst.env != nullptr;
     hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, s,
-                       ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr);
+                       ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
+                       ls->env_word.p);
+    ls->env_armed = false;
     int* qctr = ls->dag_flags.p;
     int* front = inst.front;
     const long spin_limit = mnk_ls_dag_spin_limit(ls);
@@ -1243,9 +1302,12 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
         for (mnk_ls* ls : g) {
             hin.push_back(dag_instance(ls));
             ls->dag_filled = hin.back().zfill != nullptr;
+            ls->env_used = hin.back().env != nullptr;
             // (the instance's record for the bulk kernel rides along with the reset of its progress words)
             hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, h,
-                               ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1));
+                               ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1),
+                               (const mnk::SmallSysRec*)nullptr, ls->env_word.p);
+            ls->env_armed = false;
         }
         MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
         hipStream_t sp[2] = {c0->sp_dag, c0->sp_dagB}, su = c0->su_dagB;
@@ -1392,6 +1454,9 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
                 mnk_ls* ls = g[r0 + i];
                 hin.push_back(dag_instance(ls));
                 ls->dag_filled = hin.back().zfill != nullptr;
+                hin.back().env = nullptr;   // (batches of small systems run dense: their bulk tasks only accumulate band tiles)
+                hin.back().envgate = nullptr;
+                ls->env_used = false;
                 fronts.push_back(hin.back().front);
                 afs.push_back(hin.back().af);
                 st_inst[i] = hin.back();

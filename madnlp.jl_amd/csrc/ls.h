@@ -14,6 +14,11 @@ struct mnk_sc {
     int64_t nnz_jt = 0, nnz_hess = 0, nnz_aug = 0, len_jptr = 0;
     // host copies of the derived structures (0-based)
     std::vector<int32_t> jt_colptr, jt_rowval, h_colptr, h_rowval, aug_colptr, aug_rowval;
+    // ENVELOPE per 128-row tile row of the condensed matrix (padding rows of a solver's order are their own first nonzero):
+    // tile_env[I] = (first nonzero column over the rows of tile I) / 128.  Row i of a static-pivot L is zero left of row i's
+    // first nonzero, so the tiles L(I, J), J < tile_env[I], are exact zeros (the task-DAG bulk kernel skips them, dag.hip)
+    std::vector<int32_t> tile_env;
+    mnk::DevBuf<int32_t> d_tile_env;
     std::vector<int64_t> jt_map, h_map;
     std::vector<int32_t> d_dst, d_src, hp_dst, hp_src, j_dst, j_c, j_k, j_l;
     // device: COO -> CSC segmented transfer (sources grouped by destination slot)
@@ -31,6 +36,23 @@ struct mnk_sc {
     // weak reference and refuses to touch a destroyed handle
     std::shared_ptr<int> alive = std::make_shared<int>(0);
 };
+
+// tile_env (see mnk_sc) of a lower-triangular pattern of order n: entries (row[k], col[k]), col <= row; entries outside the
+// order are ignored.  One entry per 128-row tile of the padded order.
+inline std::vector<int32_t> mnk_tile_envelope(int64_t n, const int32_t* row, const int32_t* col, int64_t nnz) {
+    std::vector<int32_t> fnz(n);
+    for (int64_t i = 0; i < n; ++i) fnz[i] = (int32_t)i;
+    for (int64_t k = 0; k < nnz; ++k)
+        if (row[k] >= 0 && row[k] < n && col[k] < fnz[row[k]]) fnz[row[k]] = col[k];
+    const int64_t ntile = (n + 127) / 128;
+    std::vector<int32_t> env(ntile);
+    for (int64_t I = 0; I < ntile; ++I) {
+        int32_t f = (int32_t)(128 * I);   // (a padding row is its own first nonzero)
+        for (int64_t i = 128 * I; i < std::min<int64_t>(n, 128 * I + 128); ++i) f = std::min(f, fnz[i]);
+        env[I] = f / 128;
+    }
+    return env;
+}
 
 struct mnk_dc {
     mnk_ctx* ctx = nullptr;
@@ -107,6 +129,17 @@ struct mnk_ls {
     int dag_chunk = 64;           // tile columns (of 128) per bulk task behind the doubling taper 1, 2, 4, ... (every task ends with a read-modify-write of its tile; C3 at the end of round 3: 12 -> 9.58 ms, 48 / 64 / 88 / 128 / 1024 -> 9.30; N = 16 384: 26.3 -> 25.9 ms, N = 24 576: 82.0 / 82.5 ms; in the middle of the round, with slower closing tasks, 10-16 was the optimum)
     int64_t dag_min_rows = 1280;  // smaller systems keep the launch-per-panel schedules (round 6, LDL: N = 1024 0.441 (schedule 4) / 0.452 ms (this one), N = 1280 0.573 / 0.551; rounds 3-5: 1536)
     int64_t dag_deep_rows = 5376; // systems up to this order put every row into the chain's band (and at most 64 x MNK_DAG_CUS2 rows); larger ones: band + bulk kernel
+    // Envelope of the matrix being factored (option "envelope"; dag.hip): the device array tile_env of the source of the
+    // last transfer (a KKT handle's, or env_own for a lower CSC), nullptr for dense sources.  Only the task-DAG schedule uses it.
+    int envelope = 1;
+    const int32_t* env_dev = nullptr;
+    std::vector<int32_t> env_host;   // its host copy (statistics)
+    mnk::DevBuf<int32_t> env_own;
+    // [0] set by a transfer that met a NaN / Inf entry, [1] that verdict for the factorization being run: dag_reset_kernel moves
+    // [0] into [1] and clears [0]; the bulk kernel skips nothing when [1] != 0 (a NaN spreads through 0 * NaN in the dense order)
+    mnk::DevBuf<int> env_word;
+    bool env_used = false;           // the last task-DAG factorization was launched with an envelope (statistics)
+    bool env_armed = false;          // a transfer may have marked env_word[0] since a task-DAG factorization last consumed it
     int64_t dag_max_rows = 30720; // larger ones too: their trailing updates already run at the update kernel's rate (round 6, LDL, schedule 4 / this one: N = 24 576 87.4 / 81.7 ms, 28 672 133.6 / 128.6, 32 768 188.2 / 190.2; rounds 3-5: 24 576)
     int panel_algo = 5;  // 5: task-DAG schedule (dag.hip: persistent pivot chain + persistent left-looking bulk kernel); 4: persistent panel kernel per 256 columns + one trailing update per outer panel (also what 5 uses outside [dag_min_rows, dag_max_rows]); 1: one launch per piece, the fallback of 4 and 5
     int persistent_solve = 1;  // both sweeps of a solve in one launch (solve.hip); 0: one launch per step

@@ -58,12 +58,13 @@ __device__ __forceinline__ void wave_absmax_to(unsigned long long* word, double 
 // leading-block probe of mnk_ls_factorize_sc_async)
 __global__ void scatter_csc_kernel(double* __restrict__ F, int64_t ld, const int32_t* __restrict__ row,
                                    const int32_t* __restrict__ col, const double* __restrict__ nz, int64_t nnz,
-                                   unsigned long long* __restrict__ amax, int32_t lim = INT32_MAX) {
+                                   unsigned long long* __restrict__ amax, int32_t lim = INT32_MAX, int* __restrict__ nonfinite = nullptr) {
     const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     double v = 0.0;
     if (k < nnz && row[k] < lim && col[k] < lim) {
         v = nz[k];
         F[row[k] + (int64_t)col[k] * ld] = v;
+        if (nonfinite != nullptr && !(fabs(v) <= DBL_MAX)) *nonfinite = 1;   // (mnk_ls::env_word: the envelope is off for this matrix)
     }
     if (amax != nullptr) wave_absmax_to(amax + AMAX_SLOT0 + AMAX_STRIDE * (blockIdx.x & (AMAX_SLOTS - 1)), v);
 }
@@ -710,6 +711,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
             return 0;
         }
     if (!strcmp(key, "pivot_tol")) { ls->pivot_tol = value; return 0; }
+    if (!strcmp(key, "envelope")) { ls->envelope = value != 0.0; return 0; }   // 0: the task-DAG bulk kernel multiplies the structurally zero tiles of sparse sources too
     if (!strcmp(key, "split_a")) { ls->split_a = (int)value; return 0; }
     if (!strcmp(key, "tail_rows")) { ls->tail_rows = (int64_t)value; return 0; }
     if (!strcmp(key, "tail_nbo")) { ls->tail_nbo = (int64_t)value; return 0; }
@@ -924,13 +926,36 @@ int mnk_ls_prefill_spare(mnk_ls* ls) {
 }
 extern "C" {
 
+// The envelope of a sparse source for the factorization that follows (mnk_ls::env_dev; nullptr: none), and the word its
+// transfer marks when it meets a NaN / Inf entry.  `env_host`: the envelope of the source's order, truncated to this solver's
+// tiles (a leading principal block of the source has the leading part of its envelope).
+static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host) {
+    ls->env_dev = nullptr;
+    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR) return nullptr;
+    if (!ls->env_word.p) {
+        if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();   // (no envelope then)
+            ls->env_word.release();
+            return nullptr;
+        }
+    }
+    // (a transfer whose mark no task-DAG factorization consumed -- another schedule ran, or the pivoted tier transferred the
+    // matrix again -- must not close the envelope of this one)
+    if (ls->env_armed && hipMemsetAsync(ls->env_word.p, 0, sizeof(int), ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    ls->env_armed = true;
+    ls->env_dev = env_dev;
+    ls->env_host.assign(env_host.begin(), env_host.begin() + std::min<size_t>(env_host.size(), (size_t)(ls->Np / 128)));
+    return ls->env_word.p;
+}
+
 static int transfer_sc(mnk_ls* ls, mnk_sc* sc) {
     int rc = prepare_fill(ls);
     if (rc) return rc;
     const int64_t nnz = sc->nnz_aug;
+    int* nonfinite = set_envelope(ls, sc->d_tile_env.p, sc->tile_env);
     hipLaunchKernelGGL(scatter_csc_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ls->ctx->stream,
                        ls->fact.p, ls->ld, sc->aug_row.p, sc->aug_col.p, sc->aug_nz.p, nnz, amax_word(ls),
-                       ls->N < sc->n ? (int32_t)ls->N : INT32_MAX);
+                       ls->N < sc->n ? (int32_t)ls->N : INT32_MAX, nonfinite);
     MNK_HIP(hipGetLastError());
     return 0;
 }
@@ -964,6 +989,7 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
     // (the options that decide a verdict follow the parent's at every probe, not at the child's creation: a pivot_tol lowered
     // since then would otherwise count a small positive pivot of the block as zero and reject what the parent accepts)
     c->pivot_tol = ls->pivot_tol;
+    c->envelope = ls->envelope;
     int rc = mnk_ls_factorize_sc_async(c, sc);
     if (!rc) rc = mnk_ls_fetch_info(c);
     if (rc) return rc;
@@ -1019,6 +1045,7 @@ int mnk_ls_factorize_sc_async(mnk_ls* ls, mnk_sc* sc) {
 }
 
 static int transfer_dense(mnk_ls* ls, const double* Adev, int64_t lda) {
+    ls->env_dev = nullptr;   // (no envelope: the dense order)
     dim3 grid((unsigned)ls->Np, (unsigned)((ls->Np + 1023) / 1024));
     hipLaunchKernelGGL(copy_lower_kernel, grid, dim3(256), 0, ls->ctx->stream, ls->fact.p, ls->ld, Adev, lda,
                        ls->N, ls->Np, amax_word(ls));
@@ -1128,15 +1155,19 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
     int rc = drow.upload(row, ls->ctx->stream);
     rc |= dcol.upload(col, ls->ctx->stream);
     rc |= dnz.upload(nzv, ls->ctx->stream);
+    // the envelope of this pattern (only the task-DAG schedule reads it)
+    const std::vector<int32_t> env = ls->envelope ? mnk_tile_envelope(N, row.data(), col.data(), nnz) : std::vector<int32_t>();
+    if (ls->envelope) rc |= ls->env_own.upload(env, ls->ctx->stream);
     if (rc) return -2;
     rc = ensure_wbuf(ls);
     if (rc) return rc;
-    auto transfer = [ls, nnz, &drow, &dcol, &dnz]() -> int {
+    auto transfer = [ls, nnz, &drow, &dcol, &dnz, &env]() -> int {
         int r = prepare_fill(ls);
         if (r) return r;
+        int* nonfinite = set_envelope(ls, env.empty() ? nullptr : ls->env_own.p, env);
         if (nnz > 0)
             hipLaunchKernelGGL(scatter_csc_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ls->ctx->stream,
-                               ls->fact.p, ls->ld, drow.p, dcol.p, dnz.p, nnz, amax_word(ls));
+                               ls->fact.p, ls->ld, drow.p, dcol.p, dnz.p, nnz, amax_word(ls), INT32_MAX, nonfinite);
         MNK_HIP(hipGetLastError());
         return 0;
     };
@@ -1151,6 +1182,18 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
     }
     ls->retransfer = nullptr;  // the staging buffers die with this call
     return rc;
+}
+
+int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap) {
+    if (n <= 0 || colptr == nullptr || rowval == nullptr || cap < 0) return -1;
+    const int64_t nnz = colptr[n] - index_base;
+    std::vector<int32_t> row(nnz), col(nnz);
+    for (int64_t c = 0; c < n; ++c)
+        for (int64_t k = colptr[c] - index_base; k < colptr[c + 1] - index_base; ++k) { row[k] = rowval[k] - index_base; col[k] = (int32_t)c; }
+    const std::vector<int32_t> env = mnk_tile_envelope(n, row.data(), col.data(), nnz);
+    if (out != nullptr)
+        for (int I = 0; I < std::min((int)env.size(), cap); ++I) out[I] = env[I];
+    return (int)env.size();
 }
 
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
@@ -1371,6 +1414,26 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "dag_ntasks")) { *value = ls->dag_ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
     if (!strcmp(key, "dag_ntasks1")) { *value = ls->dag_ntasks1; return 0; }  // ... of them in the first phase, ...
     if (!strcmp(key, "dag_js2")) { *value = ls->dag_js2; return 0; }          // ... first strip-column of the second phase
+    if (!strcmp(key, "env_ksteps") || !strcmp(key, "env_ksteps_skipped")) {
+        // task-DAG schedule: 128-column k-steps of the bulk tasks (tile columns of the chunks' K-loops, one per closing task) in
+        // the task list / of them skipped by the last factorization as structurally zero (0 without an envelope, with the
+        // envelope off, or when a NaN / Inf entry closed it)
+        int64_t total = 0, skipped = 0;
+        int gate = 1;
+        if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
+        const std::vector<int>& h = ls->dag_host_tasks;
+        const int ne = (int)ls->env_host.size();
+        for (size_t t = 0; t + 3 < h.size(); t += 4) {
+            const int flags = h[t] & 255, I = h[t + 1] & 0xffff, J = h[t + 2], kb = h[t + 3] & 0xffff, ke = h[t + 3] >> 16;
+            if (flags & 8) continue;   // (DAG_FILL)
+            total += ke - kb;
+            if (!ls->env_used || gate != 0 || I >= ne || J >= ne) continue;
+            const int e = std::max(ls->env_host[I], ls->env_host[J]);
+            skipped += std::min(ke, std::max(kb, e)) - kb;
+        }
+        *value = (double)(!strcmp(key, "env_ksteps") ? total : skipped);
+        return 0;
+    }
     set_error("mnk_ls_get_stat: unknown key '%s'", key);
     return -1;
 }
