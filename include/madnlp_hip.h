@@ -46,8 +46,9 @@ enum { MNK_HOST = 0, MNK_DEVICE = 1 };
 /* Same order as the reference's `@enum LinearFactorization`
  * (`src/LinearSolvers/linearsolvers.jl:139-147`): BUNCHKAUFMAN LU QR CHOLESKY LDL EVD.
  * Implemented on device: CHOLESKY (dpotrf semantics), LDL (static-pivot
- * LDL^T, inertia from sign(D); stands in for BUNCHKAUFMAN = dsytrf) and QR
- * (blocked Householder QR of the full symmetric matrix, dgeqrf conventions; no inertia). */
+ * LDL^T, inertia from sign(D); stands in for BUNCHKAUFMAN = dsytrf), QR
+ * (blocked Householder QR of the full symmetric matrix, dgeqrf conventions; no inertia) and LU
+ * (blocked LU with partial pivoting of the full symmetric matrix, dgetrf conventions; no inertia). */
 enum { MNK_BUNCHKAUFMAN = 1, MNK_LU = 2, MNK_QR = 3, MNK_CHOLESKY = 4, MNK_LDL = 5, MNK_EVD = 6 };
 
 typedef struct mnk_ctx mnk_ctx; /* device, stream(s), scratch */
@@ -146,7 +147,11 @@ int mnk_dc_get_aug(mnk_dc* dc, double* out, int loc);
  * Householder QR (dgeqrf conventions, 64-column compact-WY panels); info is always 0 and a singular matrix
  * shows up in the solve; mnk_ls_inertia returns an error (no inertia); it is never merged into a factorization
  * batch nor queued in a solve batch (it runs when called); the options that steer the LDL^T / Cholesky schedules
- * are accepted and ignored. */
+ * are accepted and ignored.  MNK_LU (solve_lu!, reference `lapack.jl:174-187`): factorize! mirrors the transferred
+ * lower triangle to the full matrix and factors P A = L U with partial pivoting (dgetrf conventions: idamax's pivot,
+ * the smallest row on a tie; 64-column panels); info is dgetrf's (1-based index of the first exactly zero pivot, 0 if
+ * none; the elimination goes on past it and factorize! does not fail on it); solve! is dgetrs('N'); mnk_ls_inertia
+ * returns an error; batches and ignored options as for MNK_QR. */
 int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out);
 int mnk_ls_destroy(mnk_ls* ls);
 /* Options: "pivot_tol" (LDL: |d| <= pivot_tol counts as a zero pivot; default 0),
@@ -229,8 +234,12 @@ int mnk_ls_check_solve(mnk_ls* ls);
 /* Debug / tests: copy the factor (N x N, ld = N; L in the lower triangle, for
  * LDL unit-lower L with D returned separately) and D (N entries, may be NULL).
  * QR: dgeqrf's layout -- R on and above the diagonal, the Householder vectors below it
- * (unit leading entry implicit) -- and tau in D. */
+ * (unit leading entry implicit) -- and tau in D.
+ * LU: dgetrf's layout -- U on and above the diagonal, the unit-lower L below it -- and diag(U) in D. */
 int mnk_ls_get_factor(mnk_ls* ls, double* L, double* D, int loc);
+/* LU only (an error for every other algorithm): dgetrf's ipiv, 1-based -- row k (1-based) was swapped with row ipiv[k-1]
+ * in step k -- N entries, on the host or the device (loc). */
+int mnk_ls_get_pivots(mnk_ls* ls, int64_t* ipiv, int loc);
 
 /* BUNCHKAUFMAN is served in two tiers: the static-pivot blocked LDL^T (fast path), and -- when that breaks down on
  * a matrix that is not quasi-definite in the given order -- a Bunch-Kaufman factorization with 1x1 / 2x2 pivots and

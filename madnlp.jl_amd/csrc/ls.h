@@ -221,12 +221,23 @@ struct mnk_ls {
     // QR (qr.hip): V of the current panel, the T of every panel (kept for the solves), split-K partials of W^T = A2^T V and
     // W^T T, partial sums of the panel / solve kernels
     mnk::DevBuf<double> qr_v, qr_t, qr_w, qr_p;
+    // LU (lu.hip): U12^T of the current panel (B operand of the trailing update), the panel's pivot candidates (64 entries and
+    // the row per 256-row block, two sets used alternately) and the row the next pivot replaces; the pivots (0-based), the
+    // row permutation they compose to (what the solves gather with) and getrf's info
+    mnk::DevBuf<double> lu_ut, lu_p;
+    mnk::DevBuf<int> lu_cand, lu_ipiv, lu_perm, lu_info;
 };
 
 int64_t mnk_ls_effective_nbo(const mnk_ls* ls);
 int mnk_qr_alloc(mnk_ls* ls);    // qr.hip: the QR solver's buffers
 int mnk_qr_factor(mnk_ls* ls);   // qr.hip: tril_to_full! + blocked Householder QR of the transferred matrix (enqueued only)
 int mnk_qr_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // qr.hip: x <- R^-1 Q^T x
+int mnk_launch_tril_to_full(hipStream_t s, double* F, int64_t ld, int64_t N, int64_t Np);   // qr.hip: upper(F) = lower(F)^T
+int mnk_launch_upper_bsolve(hipStream_t s, const double* F, int64_t ld, int64_t Np, double* y, double* x);   // qr.hip: x = U^-1 y (y is overwritten)
+int mnk_lu_alloc(mnk_ls* ls);    // lu.hip: the LU solver's buffers
+int mnk_lu_factor(mnk_ls* ls);   // lu.hip: tril_to_full! + blocked LU with partial pivoting of the transferred matrix (enqueued only)
+int mnk_lu_fetch_info(mnk_ls* ls);   // lu.hip: getrf's info of the last factorization (waits for it)
+int mnk_lu_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // lu.hip: x <- U^-1 L^-1 P x
 int mnk_ls_run_factorization(mnk_ls* ls);
 int mnk_ls_run_factorization_now(mnk_ls* ls);      // factor.hip: the launch part (the schedule has been chosen; batches call it for leftovers)
 int mnk_ls_launch_finish_info(mnk_ls* ls, hipStream_t s);   // factor.hip: inertia / growth words / info -> pinned host words

@@ -599,8 +599,8 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     MNK_REQUIRE(N > 0, "mnk_ls_create: N must be positive");
     const bool bk_requested = algo == MNK_BUNCHKAUFMAN;
     if (bk_requested) algo = MNK_LDL;  // tier 1: static-pivot blocked LDL^T; tier 2 on breakdown: bk.hip
-    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_QR,
-                "mnk_ls_create: CHOLESKY, LDL, BUNCHKAUFMAN and QR are implemented on device");
+    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_QR || algo == MNK_LU,
+                "mnk_ls_create: CHOLESKY, LDL, BUNCHKAUFMAN, QR and LU are implemented on device");
     MNK_HIP(hipSetDevice(ctx->device));
     mnk_ls* ls = new mnk_ls();
     ls->ctx = ctx;
@@ -660,6 +660,10 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     if (algo == MNK_QR) {
         rc |= mnk_qr_alloc(ls);
         ls->prefill = 0;   // (qr.hip overwrites the whole factor buffer's upper triangle: no background zero-fill)
+    }
+    if (algo == MNK_LU) {
+        rc |= mnk_lu_alloc(ls);
+        ls->prefill = 0;   // (lu.hip, likewise)
     }
     if (rc) { delete ls; return -2; }
     MNK_HIP(hipMemsetAsync(ls->fact.p, 0, ((size_t)ls->ld * ls->Np + SLACK) * sizeof(double), ctx->stream));
@@ -931,7 +935,7 @@ extern "C" {
 // tiles (a leading principal block of the source has the leading part of its envelope).
 static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host) {
     ls->env_dev = nullptr;
-    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR) return nullptr;
+    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR || ls->algo == MNK_LU) return nullptr;
     if (!ls->env_word.p) {
         if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
             (void)hipGetLastError();   // (no envelope then)
@@ -1199,6 +1203,7 @@ int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowv
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
     MNK_REQUIRE(ls, "mnk_ls_inertia: NULL argument");
     MNK_REQUIRE(ls->algo != MNK_QR, "mnk_ls_inertia: a QR factorization reveals no inertia (is_inertia is false for QR)");
+    MNK_REQUIRE(ls->algo != MNK_LU, "mnk_ls_inertia: an LU factorization reveals no inertia (is_inertia is false for LU)");
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
     MNK_REQUIRE(ls->factorized, "mnk_ls_inertia: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
@@ -1257,6 +1262,7 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
     MNK_REQUIRE(nrhs >= 1 && ldx >= ls->N, "mnk_ls_solve: bad nrhs/ldx");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     if (ls->algo == MNK_QR) return mnk_qr_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
+    if (ls->algo == MNK_LU) return mnk_lu_solve(ls, x, nrhs, ldx, loc);   // (likewise)
     if (ls->solve_abort && *ls->solve_abort != 0) {
         // a previous solve on device-resident vectors gave up (its result is invalid): fail loudly now and use
         // the stepwise solve from here on

@@ -417,6 +417,23 @@ int mnk_qr_alloc(mnk_ls* ls) {
     return rc;
 }
 
+// (lu.hip) the same mirror and the same block back substitution for the LU solver
+int mnk_launch_tril_to_full(hipStream_t s, double* F, int64_t ld, int64_t N, int64_t Np) {
+    hipLaunchKernelGGL(qr_mirror_kernel, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(256), 0, s, F, ld, N);
+    MNK_HIP(hipGetLastError());
+    return 0;
+}
+
+int mnk_launch_upper_bsolve(hipStream_t s, const double* F, int64_t ld, int64_t Np, double* y, double* x) {
+    for (int q = (int)(Np / QB) - 1; q >= 0; --q) {
+        const int64_t d0 = (int64_t)q * QB;
+        const unsigned g = (unsigned)std::max<int64_t>(1, (d0 + QR_RB - 1) / QR_RB);
+        hipLaunchKernelGGL(qr_rsolve_kernel, dim3(g), dim3(256), 0, s, F, ld, q, y, x);
+    }
+    MNK_HIP(hipGetLastError());
+    return 0;
+}
+
 // factorize! of a QR solver: the matrix has been transferred (lower triangle); mirror it and factor it (see the top).
 int mnk_qr_factor(mnk_ls* ls) {
     hipStream_t s = ls->ctx->stream;

@@ -19,7 +19,10 @@ import numpy as np
 from . import _lib as L
 
 BUNCHKAUFMAN, LU, QR, CHOLESKY, LDL, EVD = "BUNCHKAUFMAN", "LU", "QR", "CHOLESKY", "LDL", "EVD"
-_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL, QR: L.MNK_QR}
+_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL, QR: L.MNK_QR, LU: L.MNK_LU}
+_NO_INERTIA = (QR, LU)
+# HipLinearSolver keeps the algorithms it has always served (it refuses LU); LU, with its row interchanges, is HipLUSolver
+_HIP_LINEAR_SOLVER_ALGOS = (BUNCHKAUFMAN, CHOLESKY, LDL, QR)
 
 
 class LinearSolverException(Exception):
@@ -149,7 +152,8 @@ def _ptr(a):
 class HipSolverOptions:
     """Analogue of `LapackOptions` (reference `src/LinearSolvers/lapack.jl:1-3`).
     BUNCHKAUFMAN (the reference default) maps to the static-pivot LDL^T.  QR (blocked Householder, dgeqrf conventions)
-    reveals no inertia: the IPM then corrects inertia-free.  The schedule options below do not apply to QR (ignored)."""
+    reveals no inertia: the IPM then corrects inertia-free; LU (partial pivoting, dgetrf conventions; HipLUSolver) likewise.  The schedule
+    options below do not apply to QR and LU (ignored)."""
     lapack_algorithm: str = BUNCHKAUFMAN
     pivot_tol: float = 0.0
     outer_block: int = 0          # 0: by size (512; 1024 from 32 768 rows on)
@@ -171,11 +175,15 @@ class HipLinearSolver:
     one of our KKT systems, a dense numpy array (column-major, lower triangle
     read) or a `(colptr, rowval, nzval)` lower-triangular CSC triple (0-based)."""
 
+    _algorithms = _HIP_LINEAR_SOLVER_ALGOS
+
     def __init__(self, A, ctx: HipContext | None = None, opt: HipSolverOptions | None = None):
         self.opt = opt or HipSolverOptions()
-        if self.opt.lapack_algorithm not in _ALGO:
+        if self.opt.lapack_algorithm not in self._algorithms:
+            hint = " (LU: HipLUSolver)" if self.opt.lapack_algorithm == LU else ""
             raise SymbolicException(
-                f"algorithm {self.opt.lapack_algorithm} is not implemented on device (CHOLESKY, LDL/BUNCHKAUFMAN, QR)")
+                f"algorithm {self.opt.lapack_algorithm} is not served by {type(self).__name__} "
+                f"({', '.join(self._algorithms)}){hint}")
         self.A = A
         self.ctx = ctx or getattr(A, "ctx", None) or HipContext()
         self.n = _order_of(A)
@@ -213,8 +221,8 @@ class HipLinearSolver:
         return np.dtype(dtype) == np.float64
 
     def is_inertia(self) -> bool:
-        """reference `is_inertia(::LapackCPUSolver)`: false for QR (no inertia from a QR factorization)."""
-        return self.opt.lapack_algorithm != QR
+        """reference `is_inertia(::LapackCPUSolver)`: false for QR and LU (no inertia from those factorizations)."""
+        return self.opt.lapack_algorithm not in _NO_INERTIA
 
     def factorize(self):
         """`factorize!(M)`: transfer_matrix! + factorization; never raises on a numerical
@@ -319,11 +327,18 @@ class HipLinearSolver:
 
     def get_factor(self):
         """(L, D) on the host, for tests.  QR: dgeqrf's layout (R on and above the diagonal, Householder vectors below it)
-        and tau."""
+        and tau.  LU: dgetrf's layout (U on and above the diagonal, unit-lower L below it) and diag(U)."""
         Lm = np.zeros((self.n, self.n), order="F")
         D = np.zeros(self.n)
         L.check(L.lib().mnk_ls_get_factor(self._h, Lm.ctypes.data, D.ctypes.data, L.MNK_HOST), "mnk_ls_get_factor")
         return Lm, D
+
+    def get_pivots(self):
+        """LU only (HipError otherwise): dgetrf's ipiv (1-based, int64) on the host -- row k was swapped with row ipiv[k] - 1
+        in step k."""
+        ipiv = np.zeros(self.n, dtype=np.int64)
+        L.check(L.lib().mnk_ls_get_pivots(self._h, ipiv.ctypes.data, L.MNK_HOST), "mnk_ls_get_pivots")
+        return ipiv
 
     def get_factor_device(self):
         """(L, D) as torch tensors on the solver's device (column-major image in a row-major tensor is transposed back), for
@@ -351,6 +366,18 @@ class HipLinearSolver:
             self.close()
         except Exception:
             pass
+
+
+class HipLUSolver(HipLinearSolver):
+    """`HipLUSolver(A; opt)`: lapack_algorithm = LU on the MI355X (csrc/lu.hip) -- `getrf` / `getrs` of the reference's
+    LapackCPUSolver / LapackROCmSolver: the lower triangle of `A` is mirrored to the full matrix and factored P A = L U with
+    partial pivoting (dgetrf's pivots, layout and info).  No inertia: `is_inertia()` is False and the IPM corrects
+    inertia-free.  Same sources and interface as HipLinearSolver, plus `get_pivots()`; pass it to a KKT system as
+    `linear_solver=HipLUSolver`.  `opt` defaults to lapack_algorithm = LU and must name LU."""
+    _algorithms = (LU,)
+
+    def __init__(self, A, ctx: HipContext | None = None, opt: HipSolverOptions | None = None):
+        super().__init__(A, ctx=ctx, opt=opt or HipSolverOptions(lapack_algorithm=LU))
 
 
 class DeviceCSC:
