@@ -47,8 +47,9 @@ enum { MNK_HOST = 0, MNK_DEVICE = 1 };
  * (`src/LinearSolvers/linearsolvers.jl:139-147`): BUNCHKAUFMAN LU QR CHOLESKY LDL EVD.
  * Implemented on device: CHOLESKY (dpotrf semantics), LDL (static-pivot
  * LDL^T, inertia from sign(D); stands in for BUNCHKAUFMAN = dsytrf), QR
- * (blocked Householder QR of the full symmetric matrix, dgeqrf conventions; no inertia) and LU
- * (blocked LU with partial pivoting of the full symmetric matrix, dgetrf conventions; no inertia). */
+ * (blocked Householder QR of the full symmetric matrix, dgeqrf conventions; no inertia), LU
+ * (blocked LU with partial pivoting of the full symmetric matrix, dgetrf conventions; no inertia) and EVD
+ * (two-sided block Jacobi eigendecomposition, dsyevd('V', 'L') semantics; inertia from the signs of the eigenvalues). */
 enum { MNK_BUNCHKAUFMAN = 1, MNK_LU = 2, MNK_QR = 3, MNK_CHOLESKY = 4, MNK_LDL = 5, MNK_EVD = 6 };
 
 typedef struct mnk_ctx mnk_ctx; /* device, stream(s), scratch */
@@ -151,7 +152,12 @@ int mnk_dc_get_aug(mnk_dc* dc, double* out, int loc);
  * lower triangle to the full matrix and factors P A = L U with partial pivoting (dgetrf conventions: idamax's pivot,
  * the smallest row on a tie; 64-column panels); info is dgetrf's (1-based index of the first exactly zero pivot, 0 if
  * none; the elimination goes on past it and factorize! does not fail on it); solve! is dgetrs('N'); mnk_ls_inertia
- * returns an error; batches and ignored options as for MNK_QR. */
+ * returns an error; batches and ignored options as for MNK_QR.  MNK_EVD (solve_evd!, reference `lapack.jl:211-234`):
+ * factorize! computes A = Q diag(lambda) Q^T of the lower triangle (lambda ascending); info is 0, or 1 when the sweep cap
+ * was reached (non-finite input); factorize! never fails on a numerical reason and runs to its end before it returns, the
+ * *_async entry points included (one host synchronization per sweep); mnk_ls_inertia is (count(lambda > 0), the rest,
+ * count(lambda < 0)) over the N eigenvalues, whatever info says; solve! is x <- Q ((Q^T x) ./ lambda) with IEEE division;
+ * batches and ignored options as for MNK_QR. */
 int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out);
 int mnk_ls_destroy(mnk_ls* ls);
 /* Options: "pivot_tol" (LDL: |d| <= pivot_tol counts as a zero pivot; default 0),
@@ -235,7 +241,8 @@ int mnk_ls_check_solve(mnk_ls* ls);
  * LDL unit-lower L with D returned separately) and D (N entries, may be NULL).
  * QR: dgeqrf's layout -- R on and above the diagonal, the Householder vectors below it
  * (unit leading entry implicit) -- and tau in D.
- * LU: dgetrf's layout -- U on and above the diagonal, the unit-lower L below it -- and diag(U) in D. */
+ * LU: dgetrf's layout -- U on and above the diagonal, the unit-lower L below it -- and diag(U) in D.
+ * EVD: the eigenvectors Q (full N x N, one per column) and the eigenvalues, ascending, in D. */
 int mnk_ls_get_factor(mnk_ls* ls, double* L, double* D, int loc);
 /* LU only (an error for every other algorithm): dgetrf's ipiv, 1-based -- row k (1-based) was swapped with row ipiv[k-1]
  * in step k -- N entries, on the host or the device (loc). */

@@ -19,7 +19,7 @@ module MadNLPHIP
 import MadNLP
 import MadNLP: AbstractLinearSolver, AbstractCondensedKKTSystem, AbstractKKTVector, MadNLPLogger,
     LinearFactorization, SymbolicException, FactorizationException, SolveException, InertiaException,
-    BUNCHKAUFMAN, CHOLESKY, LDL, LU, QR, SparseCallback, AbstractCallback, SparseMatrixCOO,
+    BUNCHKAUFMAN, CHOLESKY, EVD, LDL, LU, QR, SparseCallback, AbstractCallback, SparseMatrixCOO,
     ExactHessian, QuasiNewtonOptions, create_quasi_newton, build_hessian_structure, create_array,
     _jac_sparsity_wrapper!, force_lower_triangular!, transfer!, default_options,
     full, primal, dual, dual_lb, dual_ub
@@ -29,7 +29,7 @@ import SparseArrays: SparseMatrixCSC, nnz
 const libmadnlp_hip = get(ENV, "MADNLP_HIP_LIB", "libmadnlp_hip.so")
 const MNK_HOST = Cint(0)
 const MNK_DEVICE = Cint(1)
-const MNK_ALGO = Dict(BUNCHKAUFMAN => Cint(1), LU => Cint(2), QR => Cint(3), CHOLESKY => Cint(4), LDL => Cint(5))
+const MNK_ALGO = Dict(BUNCHKAUFMAN => Cint(1), LU => Cint(2), QR => Cint(3), CHOLESKY => Cint(4), LDL => Cint(5), EVD => Cint(6))
 const MNK_SC_JT, MNK_SC_HESS, MNK_SC_AUG = Cint(0), Cint(1), Cint(2)
 
 lasterr() = unsafe_string(ccall((:mnk_last_error_string, libmadnlp_hip), Cstring, ()))

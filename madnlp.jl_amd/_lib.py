@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of a diagnostic build of the same ABI (tools/ab_*.sh); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip"]
 HEADERS = ["common.h", "ls.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "gemm_macro.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1

@@ -1377,6 +1377,7 @@ int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t
 int mnk_ls_run_factorization(mnk_ls* ls) {
     if (ls->algo == MNK_QR) return mnk_qr_factor(ls);   // (not merged into a factorization batch: runs when called)
     if (ls->algo == MNK_LU) return mnk_lu_factor(ls);   // (likewise)
+    if (ls->algo == MNK_EVD) return mnk_evd_factor(ls);   // (likewise; it also runs to its end before it returns)
     mnk_ctx* ctx = ls->ctx;
     hipStream_t s = ctx->stream;
     const int64_t Np = ls->Np;
@@ -1731,6 +1732,7 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         return 0;
     }
     if (ls->algo == MNK_LU) return mnk_lu_fetch_info(ls);   // getrf's info: the first exactly zero pivot (1-based), 0 if none
+    if (ls->algo == MNK_EVD) return mnk_evd_fetch_info(ls);   // 0, or 1 at the sweep cap; the inertia is the signs of lambda
     hipStream_t s = ls->ctx->stream;
     if (ls->bk_active) {
         MNK_HIP(hipMemsetAsync(ls->inertia_dev.p, 0, 3 * sizeof(unsigned long long), s));

@@ -68,6 +68,8 @@ struct mnk_dc {
     std::shared_ptr<int> alive = std::make_shared<int>(0);  // (see mnk_sc::alive)
 };
 
+constexpr int EVD_BLOCK = 32;   // evd.hip: columns per block of the block Jacobi (a pivot block is 64 x 64: twice in LDS)
+
 struct mnk_ls {
     mnk_ctx* ctx = nullptr;
     int64_t N = 0, Np = 0, ld = 0, ldw = 0, nbo = 512;
@@ -226,6 +228,15 @@ struct mnk_ls {
     // row permutation they compose to (what the solves gather with) and getrf's info
     mnk::DevBuf<double> lu_ut, lu_p;
     mnk::DevBuf<int> lu_cand, lu_ipiv, lu_perm, lu_info;
+    // EVD (evd.hip): the work matrix (full, Np x Np) that the block Jacobi sweeps diagonalize and the accumulated eigenvectors,
+    // the transposed 64 x 64 rotations of a round's block pairs and their "identity" marks, per-column sums of squares of the
+    // stop test, the unsorted eigenvalues and their ranks, the 64-column partial sums of x = Q t
+    mnk::DevBuf<double> evd_a, evd_v, evd_rt, evd_colsum, evd_lam, evd_part;
+    mnk::DevBuf<int> evd_ident, evd_rank;
+    int evd_sweep_cap = 60;      // sweeps after which factorize! gives up (info = 1).  Measured: 5-13 on random matrices, 17 and 23 on
+                                 // the bench's matrices, whose off-norm falls 2-4 x per sweep through a long linear phase before the
+                                 // quadratic end; 60 still serves a rate of 1.7 x per sweep
+    int evd_sweeps = 0;          // sweeps of the last factorization (get_stat "evd_sweeps")
 };
 
 int64_t mnk_ls_effective_nbo(const mnk_ls* ls);
@@ -238,6 +249,10 @@ int mnk_lu_alloc(mnk_ls* ls);    // lu.hip: the LU solver's buffers
 int mnk_lu_factor(mnk_ls* ls);   // lu.hip: tril_to_full! + blocked LU with partial pivoting of the transferred matrix (enqueued only)
 int mnk_lu_fetch_info(mnk_ls* ls);   // lu.hip: getrf's info of the last factorization (waits for it)
 int mnk_lu_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // lu.hip: x <- U^-1 L^-1 P x
+int mnk_evd_alloc(mnk_ls* ls);    // evd.hip: the EVD solver's buffers
+int mnk_evd_factor(mnk_ls* ls);   // evd.hip: block Jacobi eigendecomposition of the transferred matrix (runs to its end: one host synchronization per sweep)
+int mnk_evd_fetch_info(mnk_ls* ls);   // evd.hip: info (0 / 1: sweep cap) and the spectral inertia of the last factorization
+int mnk_evd_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // evd.hip: x <- Q diag(1 / lambda) Q^T x
 int mnk_ls_run_factorization(mnk_ls* ls);
 int mnk_ls_run_factorization_now(mnk_ls* ls);      // factor.hip: the launch part (the schedule has been chosen; batches call it for leftovers)
 int mnk_ls_launch_finish_info(mnk_ls* ls, hipStream_t s);   // factor.hip: inertia / growth words / info -> pinned host words

@@ -599,8 +599,8 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     MNK_REQUIRE(N > 0, "mnk_ls_create: N must be positive");
     const bool bk_requested = algo == MNK_BUNCHKAUFMAN;
     if (bk_requested) algo = MNK_LDL;  // tier 1: static-pivot blocked LDL^T; tier 2 on breakdown: bk.hip
-    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_QR || algo == MNK_LU,
-                "mnk_ls_create: CHOLESKY, LDL, BUNCHKAUFMAN, QR and LU are implemented on device");
+    MNK_REQUIRE(algo == MNK_CHOLESKY || algo == MNK_LDL || algo == MNK_QR || algo == MNK_LU || algo == MNK_EVD,
+                "mnk_ls_create: unknown algorithm (BUNCHKAUFMAN, LU, QR, CHOLESKY, LDL and EVD are implemented on device)");
     MNK_HIP(hipSetDevice(ctx->device));
     mnk_ls* ls = new mnk_ls();
     ls->ctx = ctx;
@@ -664,6 +664,10 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     if (algo == MNK_LU) {
         rc |= mnk_lu_alloc(ls);
         ls->prefill = 0;   // (lu.hip, likewise)
+    }
+    if (algo == MNK_EVD) {
+        rc |= mnk_evd_alloc(ls);
+        ls->prefill = 0;   // (evd.hip writes Q over the whole factor buffer)
     }
     if (rc) { delete ls; return -2; }
     MNK_HIP(hipMemsetAsync(ls->fact.p, 0, ((size_t)ls->ld * ls->Np + SLACK) * sizeof(double), ctx->stream));
@@ -935,7 +939,7 @@ extern "C" {
 // tiles (a leading principal block of the source has the leading part of its envelope).
 static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host) {
     ls->env_dev = nullptr;
-    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR || ls->algo == MNK_LU) return nullptr;
+    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR || ls->algo == MNK_LU || ls->algo == MNK_EVD) return nullptr;
     if (!ls->env_word.p) {
         if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
             (void)hipGetLastError();   // (no envelope then)
@@ -1263,6 +1267,7 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
     MNK_HIP(hipSetDevice(ls->ctx->device));
     if (ls->algo == MNK_QR) return mnk_qr_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
     if (ls->algo == MNK_LU) return mnk_lu_solve(ls, x, nrhs, ldx, loc);   // (likewise)
+    if (ls->algo == MNK_EVD) return mnk_evd_solve(ls, x, nrhs, ldx, loc);   // (likewise)
     if (ls->solve_abort && *ls->solve_abort != 0) {
         // a previous solve on device-resident vectors gave up (its result is invalid): fail loudly now and use
         // the stepwise solve from here on
@@ -1414,6 +1419,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "growth")) { *value = ls->last_growth; return 0; }  // BUNCHKAUFMAN: max|d_k| / max|a_ij| of the static-pivot tier
     if (!strcmp(key, "sign_changes")) { *value = (double)ls->last_sign_changes; return 0; }  // ... and sign changes along its pivots
     if (!strcmp(key, "bk_count")) { *value = ls->bk_count; return 0; }
+    if (!strcmp(key, "evd_sweeps")) { *value = ls->evd_sweeps; return 0; }   // EVD: block Jacobi sweeps of the last factorization
     if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk_multi_last ? 1.0 : 0.0; return 0; }
     if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk_mw_fallbacks; return 0; }
     if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain

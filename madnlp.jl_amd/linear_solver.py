@@ -19,10 +19,10 @@ import numpy as np
 from . import _lib as L
 
 BUNCHKAUFMAN, LU, QR, CHOLESKY, LDL, EVD = "BUNCHKAUFMAN", "LU", "QR", "CHOLESKY", "LDL", "EVD"
-_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL, QR: L.MNK_QR, LU: L.MNK_LU}
+_ALGO = {BUNCHKAUFMAN: L.MNK_BUNCHKAUFMAN, CHOLESKY: L.MNK_CHOLESKY, LDL: L.MNK_LDL, QR: L.MNK_QR, LU: L.MNK_LU, EVD: L.MNK_EVD}
 _NO_INERTIA = (QR, LU)
-# HipLinearSolver keeps the algorithms it has always served (it refuses LU); LU, with its row interchanges, is HipLUSolver
-_HIP_LINEAR_SOLVER_ALGOS = (BUNCHKAUFMAN, CHOLESKY, LDL, QR)
+# HipLinearSolver refuses LU (LU, with its row interchanges, is HipLUSolver); EVD reveals inertia and is served by it
+_HIP_LINEAR_SOLVER_ALGOS = (BUNCHKAUFMAN, CHOLESKY, LDL, QR, EVD)
 
 
 class LinearSolverException(Exception):
@@ -153,7 +153,9 @@ class HipSolverOptions:
     """Analogue of `LapackOptions` (reference `src/LinearSolvers/lapack.jl:1-3`).
     BUNCHKAUFMAN (the reference default) maps to the static-pivot LDL^T.  QR (blocked Householder, dgeqrf conventions)
     reveals no inertia: the IPM then corrects inertia-free; LU (partial pivoting, dgetrf conventions; HipLUSolver) likewise.  The schedule
-    options below do not apply to QR and LU (ignored)."""
+    options below do not apply to QR and LU (ignored).  EVD (block Jacobi eigendecomposition, dsyevd semantics: csrc/evd.hip)
+    reveals the exact spectral inertia (signs of the eigenvalues, with a real num_zero), so the IPM stays inertia-based; it costs
+    ~100 N^3 flop against N^3 / 3 for LDL^T, and the schedule options are ignored for it too."""
     lapack_algorithm: str = BUNCHKAUFMAN
     pivot_tol: float = 0.0
     outer_block: int = 0          # 0: by size (512; 1024 from 32 768 rows on)
@@ -317,7 +319,8 @@ class HipLinearSolver:
         return True, cnt.value, perm, doff
 
     def get_stat(self, key: str) -> float:
-        """`mnk_ls_get_stat`: "panel_algo" (algorithm that produced the current factor), "pp_fallbacks"."""
+        """`mnk_ls_get_stat`: "panel_algo" (algorithm that produced the current factor), "pp_fallbacks", "evd_sweeps" (EVD:
+        block Jacobi sweeps of the last factorization), ..."""
         v = C.c_double(0.0)
         L.check(L.lib().mnk_ls_get_stat(self._h, key.encode(), C.byref(v)), "mnk_ls_get_stat")
         return v.value
@@ -327,7 +330,8 @@ class HipLinearSolver:
 
     def get_factor(self):
         """(L, D) on the host, for tests.  QR: dgeqrf's layout (R on and above the diagonal, Householder vectors below it)
-        and tau.  LU: dgetrf's layout (U on and above the diagonal, unit-lower L below it) and diag(U)."""
+        and tau.  LU: dgetrf's layout (U on and above the diagonal, unit-lower L below it) and diag(U).  EVD: dsyevd's output
+        (the eigenvectors Q in the columns, full matrix) and the eigenvalues in ascending order."""
         Lm = np.zeros((self.n, self.n), order="F")
         D = np.zeros(self.n)
         L.check(L.lib().mnk_ls_get_factor(self._h, Lm.ctypes.data, D.ctypes.data, L.MNK_HOST), "mnk_ls_get_factor")
