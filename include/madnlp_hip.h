@@ -139,6 +139,38 @@ int64_t mnk_dc_order(mnk_dc* dc);
 /* Copy aug_com (order x order, column-major, ld = order) out. */
 int mnk_dc_get_aug(mnk_dc* dc, double* out, int loc);
 
+/* Dense quasi-Newton Hessians, hessian_approximation = BFGS / DampedBFGS on the dense KKT systems (csrc/qn.hip).  The
+ * approximation IS the handle's Hessian buffer (kkt.hess, n x n, column-major), which mnk_dc_build reads: it is updated
+ * in place on the device and never uploaded.  mnk_dc_set_hess overwrites it.
+ *
+ * mnk_dc_qn_init replaces `create_quasi_newton` `src/quasi_newton.jl:94-110,144-161` (workspace: allocated here, once per
+ * handle) and `init!` `:194-206`: hess = 2 rho0 I with rho0 = 1 if g0'g0 < sqrt(eps), 1 / g0'g0 if f0 == 0, else
+ * |f0| / g0'g0 (g0: n entries on the device).  With g0 = NULL the matrix the handle holds is adopted as it is (it counts
+ * as instantiated: no diagonal reset in front of the next update).  Asynchronous on the context's stream.
+ *
+ * mnk_dc_qn_update replaces `update!(::BFGS)` `:112-130` / `update!(::DampedBFGS)` `:163-192` (s, y: n entries on the
+ * device): BFGS skips the update when s'y < 1e-8, DampedBFGS never does; the first performed update first overwrites the
+ * diagonal with s'y / s's.  Asynchronous on the context's stream: the dot products, the skip test, theta and the
+ * reciprocals stay on the device, nothing is allocated, nothing is copied to the host.  Like the reference's dsymv / dsyr
+ * with 'L' it reads and writes the LOWER triangle of hess only; the strict upper triangle keeps what it held.  Every
+ * consumer of hess reads the lower triangle (the factorizations through the lower triangle of aug_com, mnk_dc_mul, the
+ * QR / LU solvers after tril_to_full!); the non-condensed mnk_dc_build copies both triangles of hess into aug_com, so
+ * after an update only the lower triangle of that aug_com is meaningful.
+ *
+ * mnk_dc_qn_status is the one call that synchronizes: updates performed / skipped since mnk_dc_qn_init, and
+ * last = [s'y, s'Bs, theta, r's] of the last update (r = y and theta = 1 for BFGS; s'Bs = 0 after a skipped one).
+ * mnk_dc_get_hess copies kkt.hess (n x n, column-major, leading dimension ld) out. */
+enum { MNK_QN_BFGS = 1, MNK_QN_DAMPED_BFGS = 2 };
+int mnk_dc_qn_init(mnk_dc* dc, int kind, const double* g0, double f0);
+int mnk_dc_qn_update(mnk_dc* dc, const double* s, const double* y);
+int mnk_dc_qn_status(mnk_dc* dc, int64_t* updates, int64_t* skipped, double* last);
+/* The secant pair of the quasi-Newton method of `eval_lag_hess_wrapper!` (`src/IPM/callbacks.jl:162-174,184-186`) from device
+ * vectors of n entries, in one launch: s = x - last_x, y = ((g - last_g) + jl) - jv with jl = J(x)' l, jv = J(last_x)' l
+ * (both NULL without constraints), then the backups last_x = x, last_g = g.  Asynchronous on the context's stream. */
+int mnk_dc_qn_secant(mnk_dc* dc, const double* x, const double* g, const double* jl, const double* jv, double* last_x,
+                     double* last_g, double* s, double* y);
+int mnk_dc_get_hess(mnk_dc* dc, double* out, int64_t ld, int loc);
+
 /* ------------------------------------------------- linear solver (ls) ------- */
 /* Replaces `LapackCPUSolver(A; opt)` `src/LinearSolvers/lapack.jl:21-43` /
  * `LapackROCmSolver` `lib/MadNLPGPU/ext/MadNLPGPUAMDGPUExt/rocsolver.jl`:

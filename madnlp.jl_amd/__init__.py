@@ -14,6 +14,9 @@ from .kkt import (  # noqa: F401
     UnreducedKKTVector, SparseCondensedKKTSystem, DenseCondensedKKTSystem, DenseKKTSystem, ScenarioBatch,
 )
 from .backsolve import RichardsonIterator  # noqa: F401
+from ._lib import MNK_QN_BFGS, MNK_QN_DAMPED_BFGS  # noqa: F401
+from .quasi_newton import HESSIAN_APPROXIMATIONS  # noqa: F401
+HESSIAN_EXACT, HESSIAN_BFGS, HESSIAN_DAMPED_BFGS = HESSIAN_APPROXIMATIONS   # the values of IPMOptions.hessian_approximation
 
 __version__ = "0.1.0"
 from .schur import SchurDenseStage  # noqa: F401,E402

@@ -14,12 +14,13 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of a diagnostic build of the same ABI (tools/ab_*.sh); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip"]
 HEADERS = ["common.h", "ls.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "gemm_macro.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
 MNK_BUNCHKAUFMAN, MNK_LU, MNK_QR, MNK_CHOLESKY, MNK_LDL, MNK_EVD = 1, 2, 3, 4, 5, 6
 MNK_SC_JT, MNK_SC_HESS, MNK_SC_AUG, MNK_SC_DIAGBUF = 0, 1, 2, 3
+MNK_QN_BFGS, MNK_QN_DAMPED_BFGS = 1, 2
 
 
 def _stale() -> bool:
@@ -106,6 +107,11 @@ SIGNATURES = {
     "mnk_dc_build": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "mnk_dc_order": (C.c_int64, [_vp]),
     "mnk_dc_get_aug": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_dc_qn_init": (C.c_int, [_vp, C.c_int, _vp, C.c_double]),
+    "mnk_dc_qn_update": (C.c_int, [_vp, _vp, _vp]),
+    "mnk_dc_qn_secant": (C.c_int, [_vp] + [_vp] * 8),
+    "mnk_dc_qn_status": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_double)]),
+    "mnk_dc_get_hess": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
     "mnk_ls_create": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp)]),
     "mnk_ls_destroy": (C.c_int, [_vp]),
     "mnk_ls_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),

@@ -307,6 +307,7 @@ int mnk_dc_destroy(mnk_dc* dc) {
     (void)mnk::stream_wait(dc->ctx->stream);
     delete extra_of(dc);
     dc->extra = nullptr;
+    mnk_dc_qn_release(dc);
     mnk_ctx* ctx = dc->ctx;
     delete dc;
     mnk_ctx_child_gone(ctx);

@@ -65,8 +65,10 @@ struct mnk_dc {
     mnk::DevBuf<double> jis;  // sqrt(D)-scaled, zero-padded inequality Jacobian^T workspace
     int64_t ld_jis = 0, kpad = 0, npad = 0;
     void* extra = nullptr;  // unit-private device structures (dense_kkt.hip), owned by the handle
+    void* qn = nullptr;     // quasi-Newton state (qn.hip: scalar block + workspace), owned by the handle; NULL until mnk_dc_qn_init
     std::shared_ptr<int> alive = std::make_shared<int>(0);  // (see mnk_sc::alive)
 };
+void mnk_dc_qn_release(mnk_dc* dc);   // qn.hip: frees mnk_dc::qn
 
 constexpr int EVD_BLOCK = 32;   // evd.hip: columns per block of the block Jacobi (a pivot block is 64 x 64: twice in LDS)
 

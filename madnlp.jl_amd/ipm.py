@@ -20,7 +20,8 @@ reference closely enough that iteration counts and residual histories are meanin
 
 Not implemented: NLP
 scaling (problems used here have gradients below nlp_scaling_max_gradient, so the reference's
-scaling factors are 1), quasi-Newton.
+scaling factors are 1).  Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems):
+`quasi_newton.py` and `eval_lag_hess` below (src/IPM/callbacks.jl:145-190).
 
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
 mirror (`madnlp_jl_amd.kkt`) or, in the tests, the CPU oracle.
@@ -34,6 +35,7 @@ import numpy as np
 
 from .backsolve import RichardsonIterator
 from .kkt import UnreducedKKTVector
+from .quasi_newton import HESSIAN_APPROXIMATIONS, create_quasi_newton
 
 INF = float("inf")
 EPS = np.finfo(np.float64).eps
@@ -96,6 +98,9 @@ class IPMOptions:
     inertia_free_tol: float = 0.0
     soft_resto_pderror_reduction_factor: float = 0.9999  # options.jl:178
     required_infeasibility_reduction: float = 0.9        # options.jl:179
+    # options.jl `hessian_approximation`: "exact" (ExactHessian), "bfgs" (BFGS), "damped_bfgs" (DampedBFGS); the last two on
+    # the dense KKT systems only (the reference has no dense BFGS for sparse systems, and CompactLBFGS is not part of this project)
+    hessian_approximation: str = "exact"
 
     @property
     def mu_min(self):
@@ -112,6 +117,8 @@ class Counters:
     unsuccessful_iterate: int = 0
     restoration_fail_count: int = 0
     t: int = 0
+    lag_hess_cnt: int = 0     # exact Lagrangian Hessians evaluated: stays 0 in a quasi-Newton run (test/madnlp_quasi_newton.jl:33)
+    obj_grad_cnt: int = 0     # objective gradients evaluated (the quasi-Newton update starts with the second one)
 
 
 @dataclass
@@ -209,7 +216,12 @@ class MadNLPSolver:
     def __init__(self, nlp, kkt_factory, opt: IPMOptions | None = None, sparse=True):
         self.nlp, self.opt, self.sparse = nlp, opt or IPMOptions(), sparse
         o = self.opt
+        if o.hessian_approximation not in HESSIAN_APPROXIMATIONS:
+            raise ValueError(f"hessian_approximation must be one of {HESSIAN_APPROXIMATIONS}, not {o.hessian_approximation!r}")
+        if o.hessian_approximation != "exact" and sparse:
+            raise ValueError(f"hessian_approximation = {o.hessian_approximation!r} needs a dense KKT system (sparse=False)")
         n, m = nlp.n, nlp.m
+        self.qn = None if o.hessian_approximation == "exact" else create_quasi_newton(o.hessian_approximation, n)
         idx = parse_indexes(np.asarray(nlp.lvar, float), np.asarray(nlp.uvar, float), np.asarray(nlp.lcon, float),
                             np.asarray(nlp.ucon, float), enforce_equality=not o.relax_equality)
         self.idx = idx
@@ -251,6 +263,7 @@ class MadNLPSolver:
     def eval_grad(self, x):
         self.f[:self.n] = self.nlp.grad(x[:self.n])
         self.f[self.n:] = 0.0
+        self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
         c[:] = self.nlp.cons(x[:self.n])
@@ -266,11 +279,43 @@ class MadNLPSolver:
 
     def eval_lag_hess(self, x, y, is_resto=False):
         """`eval_lag_hess_wrapper!` callbacks.jl:77-95: objective weight 0 in the robust restoration phase."""
+        if self.qn is not None:
+            return self._eval_lag_hess_qn(x, y)
         w = 0.0 if is_resto else 1.0
         if self.sparse:
             self.kkt.get_hessian()[:] = self.nlp.hess_coord(x[:self.n], y, w)
         else:
             self.kkt.get_hessian()[...] = self.nlp.hess_dense(x[:self.n], y, w)
+        self.kkt.compress_hessian()
+        self.cnt.lag_hess_cnt += 1
+
+    def _model_jtprod(self, x, l):
+        """`_eval_jtprod_wrapper!`: J(x)' l through the model's `jtprod` where it has one."""
+        if hasattr(self.nlp, "jtprod"):
+            return np.asarray(self.nlp.jtprod(x, l), dtype=float)
+        return self.nlp.jac_dense(x).T @ l
+
+    def _eval_lag_hess_qn(self, x, y):
+        """The quasi-Newton method of `eval_lag_hess_wrapper!` (callbacks.jl:145-190): no second derivative is evaluated.
+        The first call (inside `initialize`, one gradient evaluated) starts the approximation, every later one updates it
+        with the secant pair s = x+ - x, y = grad f+ - grad f + (J+' - J') l+ over the n variables (no slacks).  `is_resto`
+        is ignored, as in the reference: robust! goes on updating the same matrix."""
+        qn, n = self.qn, self.n
+        B = self.kkt.get_hessian()
+        if self.cnt.obj_grad_cnt >= 2:
+            sk = x[:n] - qn.last_x
+            yk = self.f[:n] - qn.last_g
+            if self.m > 0:
+                # jacl already is J(x+)' l+: regular! / restore! / robust! call jtprod! with this Jacobian and these multipliers
+                # right in front of this call (the reference computes it once more, callbacks.jl:170: the same bits)
+                yk = yk + self.jacl[:n]
+                qn.last_jv = self._model_jtprod(qn.last_x, y)
+                yk = yk - qn.last_jv
+            qn.update(B, sk, yk)
+        else:
+            qn.init(B, self.f[:n], self.obj_val)
+        qn.last_x = x[:n].copy()
+        qn.last_g = self.f[:n].copy()
         self.kkt.compress_hessian()
 
     # ------------------------------------------------------------------ views

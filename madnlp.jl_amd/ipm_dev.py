@@ -11,7 +11,10 @@ right-hand sides live in HBM; per iteration only scalars cross PCIe.  Same algor
 Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as the reference's preset does) and
 `DenseCondensedKKTSystem` (equalities allowed), with models whose callbacks can be evaluated on the device: the AC-OPF NLP
 (`DeviceOPFCallbacks`), the sparse QP through the KKT handle's own SpMV on the compressed Jacobian / Hessian, the dense QP
-through `mnk_ipm_gemv` on device copies of P and A.  Initialization runs once on the host (the base class) and is uploaded."""
+through `mnk_ipm_gemv` on device copies of P and A.  Initialization runs once on the host (the base class) and is uploaded.
+
+With `hessian_approximation = "bfgs" / "damped_bfgs"` (dense systems) the Hessian approximation lives in the KKT handle's
+device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model's Hessian is never loaded."""
 from __future__ import annotations
 
 
@@ -122,6 +125,11 @@ class DeviceDenseQPCallbacks:
             self.K.gemv(1, self.m, self.n, 1.0, self.A_cm, self.m, y, 0.0, out_x)
         else:
             self.K.vec_fill(out_x, 0.0)
+
+    def jtprod_at(self, x, y, out_x):
+        """out_x = J(x)' y (`_eval_jtprod_wrapper!` of the quasi-Newton update, callbacks.jl:172); the constraints are linear:
+        `x` is not used."""
+        self.jtprod_x(out_x, y)
 
     def load_jac(self, x=None):
         if self.m > 0:
@@ -237,7 +245,10 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self.kkt.device_kkt_ops = True
         if not self.sparse:          # the dense handle reads Hessian / Jacobian from its own device copies
             self.cb.load_jac()
-            self.cb.load_hess()
+            if self.qn is None:
+                self.cb.load_hess()
+            else:
+                self._qn_upload()
         self._on_device = True
         self._sync = ctx.synchronize
 
@@ -258,6 +269,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
             return super().eval_grad(x)
         self.cb.grad(self.f[:self.n], x[:self.n])
         self.K.vec_fill(self.f[self.n:], 0.0)
+        self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
         if not self._on_device:
@@ -277,7 +289,37 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_lag_hess(self, x, y, is_resto=False):
         if not self._on_device:
             return super().eval_lag_hess(x, y, is_resto)
+        if self.qn is not None:
+            return self._eval_lag_hess_qn_device(x, y)
         self.cb.load_hess(x[:self.n], y, 0.0 if is_resto else 1.0)   # objective weight 0 in robust!
+        self.cnt.lag_hess_cnt += 1
+
+    # ------------------------------------------------------------------ quasi-Newton Hessian in the handle's device buffer
+    def _qn_upload(self):
+        """The host initialization has run `init!` on the host copy; the device buffer gets its own `init!` from the
+        uploaded gradient and objective (`mnk_dc_qn_init`), and the backups of callbacks.jl:184-186 become device vectors.
+        From here on the approximation exists on the device only: it is never loaded from the host or from the model."""
+        from types import SimpleNamespace
+        n = self.n
+        self.kkt.qn_init_device(self.qn.kind, self.f[:n], self.obj_val)
+        d = SimpleNamespace(**{k: self._new_vec(n) for k in ("sk", "yk", "last_x", "last_g", "last_jv")})
+        self.K.vec_copy(d.last_x, self.x[:n])
+        self.K.vec_copy(d.last_g, self.f[:n])
+        self.qn_dev = d
+
+    def _eval_lag_hess_qn_device(self, x, y):
+        """`MadNLPSolver._eval_lag_hess_qn` on device vectors: one transposed Jacobian product of the callbacks, one launch for
+        s, y and the backups (`mnk_dc_qn_secant`: the same operations in the same order as the host mirror), then
+        `mnk_dc_qn_update`; nothing crosses PCIe."""
+        n, d = self.n, self.qn_dev
+        assert self.cnt.obj_grad_cnt >= 2, "the first call (init!) belongs to the host initialization"
+        jl = jv = None
+        if self.m > 0:
+            jl = self.jacl[:n]                                      # J(x+)' l+ (current: see the host mirror)
+            self.cb.jtprod_at(d.last_x, y, d.last_jv)
+            jv = d.last_jv
+        self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
+        self.kkt.qn_update_device(d.sk, d.yk)
 
     def jtprod(self, out, y):
         """`jtprod!` reference src/KKT/Sparse/condensed.jl:150-156."""
@@ -659,7 +701,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
         reg = pr_diag = 1, du_diag = 0, l_diag = u_diag = 1, l_lower = u_lower = 0 through the feeder (x = 0, xl = 1,
         xu = -1, zl = zu = 0, primal_reg = 1)."""
         self.kkt.initialize()
-        self.cb.zero_hess()
+        self.cb.zero_hess()        # (a quasi-Newton run too: the reference's initialize!(kkt) zeroes its approximation here)
         nt = self.nt
         z = np.zeros(nt)
         self.kkt.set_aug_diagonal_device(z, np.ones(nt), -np.ones(nt), z, z, 1.0, 0.0)

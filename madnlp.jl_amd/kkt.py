@@ -524,6 +524,68 @@ class _DenseBase(_KKTCommon):
         if self.m > 0:
             L.check(lib.mnk_dc_set_jac(self._h, self.jac.ctypes.data, self.jac.shape[0], L.MNK_HOST), "mnk_dc_set_jac")
 
+    # ---- quasi-Newton Hessian kept in the handle's device `hess` buffer (csrc/qn.hip).  NOTE: the host `build_kkt()` below
+    # uploads the host `hess` and thereby overwrites the device approximation; `build_kkt_device()` reads the device buffer
+    # as it is.  A device-resident quasi-Newton run therefore builds with `build_kkt_device()` only.
+    def qn_init_device(self, kind, g0=None, f0=0.0):
+        """`init!` (reference `src/quasi_newton.jl:194-206`) on the device buffer: hess = 2 rho0 I from the gradient `g0`
+        (device tensor or host array of n entries) and the objective `f0`.  `kind`: `MNK_QN_BFGS` / `MNK_QN_DAMPED_BFGS`
+        (or "bfgs" / "damped_bfgs").  With `g0=None` the matrix the handle holds (e.g. after `set_hess_device`) is adopted
+        as the current approximation."""
+        from .quasi_newton import QN_KIND
+        kind = QN_KIND.get(kind, kind)
+        if g0 is None:
+            L.check(L.lib().mnk_dc_qn_init(self._h, int(kind), None, float(f0)), "mnk_dc_qn_init")
+            return
+        g = self._qn_dev(g0)
+        L.check(L.lib().mnk_dc_qn_init(self._h, int(kind), g.data_ptr(), float(f0)), "mnk_dc_qn_init")
+        if g is not g0:
+            self.ctx.synchronize()     # a temporary upload must outlive the kernels that read it
+
+    def _qn_dev(self, v):
+        """`v` as a device tensor of n doubles (host arrays are uploaded: tests and the host drivers; the device-resident
+        driver passes device tensors)."""
+        import torch
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            assert v.dtype == torch.float64 and v.is_contiguous() and v.numel() == self.hess.shape[0]
+            return v
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        assert a.shape == (self.hess.shape[0],)
+        return torch.from_numpy(a).to("cuda")
+
+    def qn_update_device(self, s, y):
+        """`update!` (reference `src/quasi_newton.jl:112-130,163-192`) of the device buffer with the secant pair `s`, `y`.
+        With device tensors the call only enqueues kernels on the context's stream (no synchronization, no copy)."""
+        sd, yd = self._qn_dev(s), self._qn_dev(y)
+        L.check(L.lib().mnk_dc_qn_update(self._h, sd.data_ptr(), yd.data_ptr()), "mnk_dc_qn_update")
+        if sd is not s or yd is not y:
+            self.ctx.synchronize()
+
+    def qn_secant_device(self, x, g, jl, jv, last_x, last_g, s, y):
+        """s = x - last_x, y = ((g - last_g) + jl) - jv (`jl`, `jv`: J(x)' l and J(last_x)' l, or both None), then last_x = x,
+        last_g = g (reference `src/IPM/callbacks.jl:162-174,184-186`); device tensors of n doubles, one launch."""
+        p = [None if v is None else self._qn_dev(v).data_ptr() for v in (x, g, jl, jv, last_x, last_g, s, y)]
+        L.check(L.lib().mnk_dc_qn_secant(self._h, *p), "mnk_dc_qn_secant")
+
+    def qn_status(self):
+        """(updates performed, updates skipped, [s'y, s'Bs, theta, r's] of the last update); synchronizes."""
+        u, k = C.c_int64(), C.c_int64()
+        last = (C.c_double * 4)()
+        L.check(L.lib().mnk_dc_qn_status(self._h, C.byref(u), C.byref(k), last), "mnk_dc_qn_status")
+        return u.value, k.value, np.array(last[:])
+
+    def set_hess_device(self, hess=None):
+        """Upload `hess` (default: the host buffer) into the device buffer (`mnk_dc_set_hess`)."""
+        h = self.hess if hess is None else np.asfortranarray(hess, dtype=np.float64)
+        L.check(L.lib().mnk_dc_set_hess(self._h, h.ctypes.data, h.shape[0], L.MNK_HOST), "mnk_dc_set_hess")
+
+    def get_hess(self):
+        """Host copy of the device `hess` buffer (n x n, Fortran order); tests."""
+        n = self.hess.shape[0]
+        out = np.zeros((n, n), order="F")
+        L.check(L.lib().mnk_dc_get_hess(self._h, out.ctypes.data, n, L.MNK_HOST), "mnk_dc_get_hess")
+        return out
+
     def build_kkt(self):
         """`build_kkt!` (reference `src/KKT/Dense/condensed.jl:157-186` /
         `src/KKT/Dense/augmented.jl:147-156`).  The callbacks wrote `hess`/`jac` on the host."""
