@@ -618,6 +618,11 @@ int mnk_debug_dag_tasks(int ntile, int chunk, int band_tiles, int js2, int taper
  * zero-fill tasks of the next factorization's buffer if `fill`): the instance index sits in bits 16.. of the second int. */
 int mnk_debug_dag_merged_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period,
                                int* out, int cap);
+/* ... and that list dealt into `nq` per-XCD queues per phase, as the bulk kernel of a single factorization pops them (options
+ * dag_xcd_queues, dag_gang; ninst > 1: the merged list, one phase).  tasks_out: the list (4 ints per task); order: list positions,
+ * queue after queue, first phase first; off: 2 x (nq + 1) offsets into `order`.  Returns the number of tasks. */
+int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period, int nq, int gang,
+                       int* tasks_out, int* order, int cap, int* off, int* first_phase);
 
 /* Diagnostics / tests (host only): the envelope per 128-row tile row that a solver of order `order` (<= the handle's n) uses when
  * it factors this KKT handle's condensed matrix: tile_env[I] = (first nonzero column over the rows of tile I) / 128, truncated to

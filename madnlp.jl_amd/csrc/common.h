@@ -279,5 +279,13 @@ int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const d
 int dag_build_tasks(int ntile, int chunk, int band_tiles, int js2, std::vector<int>& out, int taper0, std::vector<int>* ready);
 int dag_add_fill_tasks(int ntile, std::vector<int>& tasks, std::vector<int>& ready, int n1);
 void dag_merge_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int ninst, int period, std::vector<int>& out);
+// The tasks [t0, t1) of a finished list dealt into `nq` queues, each a subsequence of the list in list order: `order` receives the list
+// positions queue after queue, `off` the nq + 1 offsets of the queues in it.  `gang`: tasks of one group (same B rows, same k-range) that
+// go to one queue together; 1: every task on its own; < 0: everything to queue 0 (tests of the steal path).
+constexpr int DAG_NQ = 8;             // queues of the bulk kernel: one per XCD
+constexpr int DAG_QHEAD_STRIDE = 32;  // ints between two queue heads (128 bytes)
+constexpr int DAG_QHEAD_WORDS = (DAG_NQ + 1) * DAG_QHEAD_STRIDE;   // the heads of one launch and, behind them, its count of stolen tasks
+void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
+                    std::vector<int>& off);
 
 }  // namespace mnk

@@ -18,7 +18,8 @@
 //   * order: tasks are drawn from ONE queue sorted by the chain position at which they become ready (the last tile
 //     column they read), band tiles and rows next to the band first: a drawn task can start at once or nearly so, and a
 //     workgroup that holds a task only ever waits for tasks drawn before it, so any number of resident workgroups makes
-//     progress.
+//     progress.  (A single factorization deals that list into one queue per XCD, each a subsequence of it popped from its head:
+//     dag_deal_tasks / dag_pop below.)
 //   * progress: front[t] = number of leading 128-column tile columns for which the 64-row strip t of L is final
 //     (monotone; zeroed per factorization); af[] = "band tile accumulated"; tprog[I, J] = chunks applied to tile (I, J).
 //     Producer: stores -> barrier -> one lane's
@@ -346,7 +347,7 @@ __global__ void dag_gate_kernel(const int* __restrict__ word, int target, int* _
 // the next transfer marks is cleared)
 __global__ __launch_bounds__(256) void dag_reset_kernel(int* __restrict__ flags, int64_t n, int* __restrict__ info, DagInst rec,
                                                         DagInst* __restrict__ rec_dst, const SmallSysRec* __restrict__ recs = nullptr,
-                                                        int* __restrict__ envw = nullptr) {
+                                                        int* __restrict__ envw = nullptr, int* __restrict__ qheads = nullptr, int nqh = 0) {
     if (recs != nullptr) {   // (a batch of small systems: blockIdx.y = system; the instance records are uploaded by the host)
         const SmallSysRec r = recs[blockIdx.y];
         flags = r.flags; n = r.nflags; info = r.info;
@@ -357,6 +358,7 @@ __global__ __launch_bounds__(256) void dag_reset_kernel(int* __restrict__ flags,
     const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) f4[i] = make_int4(0, 0, 0, 0);
     if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < nqh; i += blockDim.x) qheads[i] = 0;   // (the heads of the per-XCD queues and the count of stolen tasks)
         if (threadIdx.x < (unsigned)(n - 4 * n4)) flags[4 * n4 + threadIdx.x] = 0;
         if (threadIdx.x == 0) { info[0] = 0; info[1] = 0; }
     }
@@ -601,8 +603,14 @@ struct DagArgs1 {
     int64_t N;
     const int* env;             // (as in DagInst)
     const int* envgate;
+    // per-XCD queues (dag_deal_tasks): nq > 0: `tasks` is the dealt copy of the list, queue x = tasks [qoff[x], qoff[x + 1]), its head
+    // qheads[x * DAG_QHEAD_STRIDE]; a task's position in the LIST (the index of its trace record) rides in the third word above
+    // the tile column.  nq == 0: one queue, the list as built, popped through `qctr`.
+    const int* qoff;
+    int* qheads;
+    int nq;
 #if MNK_DIAG_BULK_DBG
-    int* bdbg;                  // 16 words per workgroup: {task, stage, words, target, value, spins >> 18, tasks done, -, the 4 front words seen}
+    int* bdbg;                 // 16 words per workgroup: {task, stage, words, target, value, spins >> 18, tasks done, -, the 4 front words seen}
 #endif
 };
 
@@ -613,10 +621,47 @@ int* g_diag_bdbg = nullptr;   // (set by the host side before a launch; diagnost
 #define MNK_BDBG(a) nullptr
 #endif
 
+// The next task of a workgroup (one thread) with per-XCD queues: the head of the queue of its own XCD (sq[0] >= 0: that queue;
+// -1 - queue once it was found empty), and only when that one is exhausted the head of the queue with the most tasks left.  Own
+// pops and steals both advance a head by one atomic add -- what has been taken of a queue is always a prefix of it, nothing comes
+// from the middle: the premise of the progress argument.  An index past a queue's end is a miss (another
+// workgroup was faster), not the end of the work: the heads are scanned again.  INT_MAX: every head is past its end.
+// sq[1] counts this workgroup's stolen tasks, the word behind the heads those of the launch (statistic dag_steals).
+__device__ __forceinline__ int dag_pop(const int* __restrict__ qoff, int* __restrict__ qheads, int nq, int* sq) {
+    const int h = sq[0];
+    if (h >= 0) {
+        const int beg = qoff[h], n = qoff[h + 1] - beg;
+        const int i = atomicAdd(qheads + h * DAG_QHEAD_STRIDE, 1);
+        if (i < n) return beg + i;
+        sq[0] = -1 - h;
+    }
+    for (;;) {
+        int best = -1, most = 0;
+        for (int x = 0; x < nq; ++x) {
+            const int left = qoff[x + 1] - qoff[x] - __hip_atomic_load(qheads + x * DAG_QHEAD_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (left > most) { most = left; best = x; }
+        }
+        if (best < 0) return INT_MAX;
+        const int i = atomicAdd(qheads + best * DAG_QHEAD_STRIDE, 1);
+        if (i < qoff[best + 1] - qoff[best]) {
+            sq[1] += 1;
+            atomicAdd(qheads + nq * DAG_QHEAD_STRIDE, 1);
+            return qoff[best] + i;
+        }
+    }
+}
+
 template <bool LDL>
 __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __shared__ int s_val;
+    __shared__ int s_q[2];   // per-XCD queues: {own queue (dag_pop), tasks stolen}
+    if (threadIdx.x == 0) {
+        unsigned xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        s_q[0] = a.nq > 0 ? (int)(xcc & 15u) % a.nq : 0;
+        s_q[1] = 0;
+    }
     // per-workgroup statistics of the trace option live in LDS (thread 0 only): no registers across the task loop
     __shared__ unsigned long long s_stat[4];  // first grab, ticks waited, tasks, ticks in the finalization
     if (threadIdx.x < 4) s_stat[threadIdx.x] = 0;
@@ -627,7 +672,9 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));  // (keeps the thread-id arithmetic out of the task loop's live ranges, as in gemm_nt_tile)
         if (tid == 0)
-            s_val = __hip_atomic_load(a.info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? INT_MAX : atomicAdd(a.qctr, 1);
+            s_val = __hip_atomic_load(a.info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0
+                        ? INT_MAX
+                        : (a.nq > 0 ? dag_pop(a.qoff, a.qheads, a.nq, s_q) : atomicAdd(a.qctr, 1));
         __syncthreads();
         const int t = s_val;
         __syncthreads();
@@ -635,6 +682,8 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             if (a.wgstat != nullptr && tid == 0) {
                 unsigned long long* w = a.wgstat + (int64_t)blockIdx.x * 8;
                 w[0] = s_stat[0]; w[1] = wall_clock64(); w[2] = s_stat[1]; w[3] = s_stat[2]; w[4] = s_stat[3];
+                // (per-XCD queues: 1 + the workgroup's own queue, the tasks it took from other queues)
+                w[5] = a.nq > 0 ? (unsigned long long)(1 + (s_q[0] >= 0 ? s_q[0] : -1 - s_q[0])) : 0; w[6] = (unsigned long long)s_q[1];
             }
             return;
         }
@@ -651,10 +700,13 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
 #endif
         const int4 tk = a.tasks[t];
         const int flags = __builtin_amdgcn_readfirstlane(tk.x) & 255, q = __builtin_amdgcn_readfirstlane(tk.x) >> 8;
-        const int I = __builtin_amdgcn_readfirstlane(tk.y), J = __builtin_amdgcn_readfirstlane(tk.z);
+        const int I = __builtin_amdgcn_readfirstlane(tk.y), J = __builtin_amdgcn_readfirstlane(tk.z) & 0xfff;
         const int kbeg = __builtin_amdgcn_readfirstlane(tk.w) & 0xffff, kend = __builtin_amdgcn_readfirstlane(tk.w) >> 16;
         const int64_t row0 = (int64_t)128 * I, col0 = (int64_t)128 * J;
-        unsigned long long* tr = a.trace != nullptr && tid == 0 ? a.trace + (int64_t)t * 8 : nullptr;
+        // (the trace is indexed by the task's position in the list, whichever queue it came from)
+        unsigned long long* tr = a.trace != nullptr && tid == 0
+                                     ? a.trace + (int64_t)(a.nq > 0 ? (int)((unsigned)__builtin_amdgcn_readfirstlane(tk.z) >> 12) : t) * 8
+                                     : nullptr;
         if (tr) { tr[0] = wall_clock64(); tr[6] = 0; tr[7] = 0; }
         if (flags & DAG_FILL) {   // zero-fill of the next factorization's buffer (see dag_fill_tile)
             if (a.zfill != nullptr) dag_fill_tile(&a, I, J, tid);
@@ -920,6 +972,54 @@ void dag_merge_tasks(const std::vector<int>& tasks, const std::vector<int>& read
     }
 }
 
+// Per-XCD queues.  Neighbours in the list are chunks of one tile column with the same [kbeg, kend): they walk the same B rows
+// V(J, kbeg..kend).  Popped from one counter by workgroups that the dispatcher deals round-robin over the eight XCDs, they land in
+// eight different L2s; dealt to the queue of ONE XCD they can share that stream.  The list is only PARTITIONED: every queue is a
+// subsequence of the list in list order and no task changes, so every tile still sees its chunks in the same order (same bits),
+// and a queue popped from its head keeps the list's progress argument.
+//   * group: a maximal run of consecutive chunk tasks (body chunks, band accumulation) with the same (ready, class, J, kbeg, kend);
+//     it is cut into gangs of `gang` consecutive tasks.  Tile-closing tasks, zero-fill tasks and runs of one are gangs of one.
+//   * a gang goes whole to the queue with the fewest k-steps dealt so far (ties: round-robin), so the queues carry equal work at
+//     every position of the list: the heaviest and the lightest differ by at most one gang.
+// The envelope is ignored (gang-mates whose K-loops start later join the shared stream later): one deal serves every matrix of an order.
+void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
+                    std::vector<int>& off) {
+    nq = std::max(nq, 1);
+    std::vector<std::vector<int>> qs(nq);
+    std::vector<int64_t> load(nq, 0);
+    int rr = 0;
+    auto cls = [&](int t) { const int f = tasks[4 * (size_t)t] & 255; return (f & DAG_FILL) ? 3 : ((f & DAG_BANDACC) ? 0 : ((f & DAG_FINAL) ? 1 : 2)); };
+    auto ksteps = [&](int t) { return (tasks[4 * (size_t)t] & DAG_FILL) ? 0 : (tasks[4 * (size_t)t + 3] >> 16) - (tasks[4 * (size_t)t + 3] & 0xffff); };
+    auto same = [&](int x, int y) {   // (the instance too: the second word carries it in a merged list)
+        return ready[x] == ready[y] && cls(x) == cls(y) && tasks[4 * (size_t)x + 2] == tasks[4 * (size_t)y + 2] &&
+               tasks[4 * (size_t)x + 3] == tasks[4 * (size_t)y + 3] && (tasks[4 * (size_t)x + 1] >> 16) == (tasks[4 * (size_t)y + 1] >> 16);
+    };
+    auto deal = [&](int b, int e) {   // the gang [b, e)
+        int q = 0;
+        if (gang >= 0) {
+            q = rr % nq;
+            for (int i = 1; i < nq; ++i)
+                if (load[(rr + i) % nq] < load[q]) q = (rr + i) % nq;
+            rr = q + 1;
+        }
+        for (int t = b; t < e; ++t) { qs[q].push_back(t); load[q] += ksteps(t); }
+    };
+    for (int i = t0; i < t1;) {
+        int j = i + 1;
+        const int c = cls(i);
+        if (gang > 1 && (c == 0 || c == 2))
+            while (j < t1 && same(i, j)) ++j;
+        for (int b = i; b < j; b += std::max(gang, 1)) deal(b, std::min(j, b + std::max(gang, 1)));
+        i = j;
+    }
+    order.clear();
+    off.assign(1, 0);
+    for (int q = 0; q < nq; ++q) {
+        order.insert(order.end(), qs[q].begin(), qs[q].end());
+        off.push_back((int)order.size());
+    }
+}
+
 template <bool LDL>
 static int launch_bulk_t(hipStream_t s, const DagArgs& a, int nwg) {
     const size_t smem = TILE3_LDS_BYTES;  // three k-tile buffers of the tile-closing tasks (gemm_nt_mainloop3); chunks use two, the finalization 32 KB
@@ -954,12 +1054,14 @@ static int launch_bulk1_t(hipStream_t s, const DagArgs1& a, int nwg) {
 
 // `insts` == nullptr: one factorization (dag_bulk_kernel1, the record `one` flattened into its argument block); otherwise a batch
 static int launch_dag_bulk(hipStream_t s, bool ldl, const DagInst& one, const DagInst* insts, const int* tasks, int ntasks, int ntile,
-                           int* qctr, long spin_limit, int nwg, unsigned long long* trace, unsigned long long* wgstat) {
+                           int* qctr, long spin_limit, int nwg, unsigned long long* trace, unsigned long long* wgstat,
+                           const int* qoff = nullptr, int* qheads = nullptr, int nq = 0) {
     if (ntasks <= 0) return 0;
     static const int fake = getenv("MNK_DAG_FAKE_SHARE") ? atoi(getenv("MNK_DAG_FAKE_SHARE")) : 0;
     if (insts == nullptr) {
         DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
-                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate};
+                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate,
+                   qoff, qheads, nq};
 #if MNK_DIAG_BULK_DBG
         a.bdbg = g_diag_bdbg;
 #endif
@@ -1027,6 +1129,15 @@ long mnk_ls_dag_spin_limit(const mnk_ls* ls) {
     return (long)std::min(16777216.0, std::max(floor_polls, polls));
 }
 
+// XCDs that have a CU among the CUs [first, num_cu) of the context (mask bit b is a CU of XCD b % 8: ls.hip)
+static int bulk_xcds(const mnk_ctx* c, int first) {
+    bool has[8] = {false, false, false, false, false, false, false, false};
+    for (int b = std::max(first, 0); b < c->num_cu; ++b) has[(c->cu_first + b) % 8] = true;
+    int n = 0;
+    for (bool x : has) n += x ? 1 : 0;
+    return n;
+}
+
 static mnk::DagInst dag_instance(mnk_ls* ls) {
     const int ntile = (int)(ls->Np / 128), nblk = (int)(ls->Np / NBI);
     int* front = ls->dag_flags.p + 2;
@@ -1057,6 +1168,8 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         (void)hipGetLastError();
         ls->dag_tasks.release();
         ls->dag_flags.release();
+        ls->dag_qoff.release();
+        ls->dag_qheads.release();
         ls->vfull.release();
         return 1;
     };
@@ -1083,10 +1196,35 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         if (ls->dag_has_fill && h.empty()) ls->dag_has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
         if (ls->dag_has_fill) ls->dag_ntasks1 = mnk::dag_add_fill_tasks(ntile, h, ls->dag_host_ready, ls->dag_ntasks1);
         ls->dag_ntasks = (int)(h.size() / 4);
+        // Per-XCD queues: the device list is the host list dealt per phase (dag_deal_tasks; the host list stays as built -- the
+        // statistics and the merged queue of a batch read it).  A phase keeps ONE queue when its bulk grid might leave an XCD
+        // without a workgroup -- a queue nobody owns is only served by thieves, which come when their own queues are empty, and
+        // the progress argument needs an owner -- or when a list position does not fit beside the tile column (20 | 12 bits).
+        std::vector<int> dev_list = h, qoff(32, 0);
+        ls->dag_nq[0] = ls->dag_nq[1] = 0;
+        if (ls->dag_xcd_queues && ls->dag_ntasks < (1 << 20) && ntile < 4096) {
+            const int part[3] = {0, ls->dag_ntasks1, ls->dag_ntasks};
+            const int chain_cus[2] = {ctx->dag_cus, ctx->dag_cus2};
+            for (int ph = 0; ph < 2; ++ph) {
+                const int t0 = part[ph], t1 = part[ph + 1];
+                if (t1 - t0 < mnk_ctx_bulk_wgs(ctx, chain_cus[ph], 3) || bulk_xcds(ctx, chain_cus[ph]) != mnk::DAG_NQ) continue;
+                std::vector<int> order, off;
+                mnk::dag_deal_tasks(h, ls->dag_host_ready, t0, t1, mnk::DAG_NQ, ls->dag_gang, order, off);
+                for (int p = 0; p < t1 - t0; ++p) {
+                    for (int k = 0; k < 4; ++k) dev_list[4 * (size_t)(t0 + p) + k] = h[4 * (size_t)order[p] + k];
+                    dev_list[4 * (size_t)(t0 + p) + 2] |= (order[p] - t0) << 12;
+                }
+                for (int x = 0; x <= mnk::DAG_NQ; ++x) qoff[16 * ph + x] = off[x];
+                ls->dag_nq[ph] = mnk::DAG_NQ;
+            }
+        }
         if (ls->dag_tasks.alloc(h.size() + 4)) return give_up();
+        if (!ls->dag_qoff.p && ls->dag_qoff.alloc(qoff.size())) return give_up();
+        if (!ls->dag_qheads.p && ls->dag_qheads.alloc(2 * (size_t)mnk::DAG_QHEAD_WORDS)) return give_up();
         {
             mnk::H2DGuard h2d;   // (a pageable upload beside another context's persistent group would stop that group: common.h)
-            if (!h.empty() && hipMemcpyAsync(ls->dag_tasks.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
+            if (!h.empty() && hipMemcpyAsync(ls->dag_tasks.p, dev_list.data(), dev_list.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
+            if (hipMemcpyAsync(ls->dag_qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
             if (mnk::stream_wait(s) != hipSuccess) return give_up();
         }
         if (ls->dag_flags.alloc(nflags)) return give_up();
@@ -1128,7 +1266,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
     ls->env_used = inst.env != nullptr;
     hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, s,
                        ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
-                       ls->env_word.p);
+                       ls->env_word.p, ls->dag_qheads.p, ls->dag_qheads.p ? 2 * mnk::DAG_QHEAD_WORDS : 0);
     ls->env_armed = false;
     int* qctr = ls->dag_flags.p;
     int* front = inst.front;
@@ -1162,9 +1300,14 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
 #if MNK_DIAG_BULK_DBG
         mnk::g_diag_bdbg = ls->dag_debug && ls->dag_dbg.p ? ls->dag_dbg.p + 8 * 128 : nullptr;
 #endif
+        const int ph = (int)(counter - qctr), nq = ls->dag_nq[ph];
+        // (per-XCD queues: every queue needs workgroups of its own XCD -- the grid the list was dealt for, see mnk_ls_dag_prepare)
+        MNK_REQUIRE(nq == 0 || (ntask >= mnk_ctx_bulk_wgs(ctx, chain_cus, 3) && bulk_xcds(ctx, chain_cus) == nq),
+                    "task-DAG schedule: the bulk grid does not cover the XCDs the task list was dealt for");
         rc = mnk::launch_dag_bulk(su, ldl, inst, nullptr, ls->dag_tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
                                   std::min(ntask, mnk_ctx_bulk_wgs(ctx, chain_cus, 3)), trace ? trace + 8 * (size_t)task0 : nullptr,
-                                  trace ? trace + (size_t)ls->dag_ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr);
+                                  trace ? trace + (size_t)ls->dag_ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
+                                  ls->dag_qoff.p + 16 * ph, ls->dag_qheads.p + ph * mnk::DAG_QHEAD_WORDS, nq);
         if (rc) return rc;
         // Once the bulk kernel has run out of tasks every tile-closing task is done, hence every strip-column that still
         // had rows below the band is final: its diagonal blocks are inverted for the solves here, behind the bulk kernel
@@ -1629,5 +1772,42 @@ extern "C" int mnk_debug_dag_merged_tasks(int ntile, int chunk, int band_tiles, 
     const int n = (int)(merged.size() / 4);
     if (out != nullptr)
         for (int i = 0; i < std::min(n, cap) * 4; ++i) out[i] = merged[i];
+    return n;
+}
+
+// Diagnostics / tests: the list above (with the zero-fill tasks if `fill`; merged over `ninst` > 1 instances with shift `period`)
+// dealt into `nq` queues per phase as the single-factorization bulk kernel pops them (dag_deal_tasks; nq <= 1: the list itself).
+// order: the list positions, queue after queue -- the first phase's queues, then the second phase's; off: 2 x (nq + 1) offsets into
+// `order`.  Returns the number of tasks; at most `cap` positions are written.  Host only.
+extern "C" int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period, int nq,
+                                  int gang, int* tasks_out, int* order, int cap, int* off, int* first_phase) {
+    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0 || ninst <= 0 || period < 0 || nq <= 0 || nq > 64 || gang == 0) return -1;
+    std::vector<int> h, ready;
+    int n1 = mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, &ready);
+    if (fill) n1 = mnk::dag_add_fill_tasks(ntile, h, ready, n1);
+    if (ninst > 1) {   // (the merged list of a batch: one part; `ready` of a merged task is its key of the merge)
+        std::vector<int> merged, mready, pos(ninst, 0);
+        mnk::dag_merge_tasks(h, ready, ninst, period, merged);
+        for (size_t t = 0; t < merged.size() / 4; ++t) { const int i = merged[4 * t + 1] >> 16; mready.push_back(i * period + ready[pos[i]++]); }
+        h.swap(merged);
+        ready.swap(mready);
+        n1 = (int)ready.size();
+    }
+    const int n = (int)ready.size();
+    if (first_phase != nullptr) *first_phase = n1;
+    const int part[3] = {0, n1, n};
+    int written = 0;
+    for (int ph = 0; ph < 2; ++ph) {
+        std::vector<int> ord, o;
+        mnk::dag_deal_tasks(h, ready, part[ph], part[ph + 1], nq, gang, ord, o);
+        for (int x = 0; x <= nq; ++x)
+            if (off != nullptr) off[ph * (nq + 1) + x] = part[ph] + o[x];
+        for (int v : ord) {
+            if (order != nullptr && written < cap) order[written] = v;
+            ++written;
+        }
+    }
+    if (tasks_out != nullptr)
+        for (int i = 0; i < std::min(n, cap) * 4; ++i) tasks_out[i] = h[i];
     return n;
 }

@@ -121,6 +121,13 @@ struct mnk_ls {
     bool ev_info_recorded = false;
     hipEvent_t ev_defer = nullptr;   // batch: "matrix transferred" on this solver's stream / "batch done"
     bool deferred = false;        // a factorize! call of this solver is pending in an open batch
+    // Per-XCD queues of the single-factorization bulk kernel (dag.hip: dag_deal_tasks): the device task list is dealt into DAG_NQ
+    // subsequences, a workgroup pops the head of its own XCD's queue and steals from the head of another once that one is empty.
+    int dag_xcd_queues = 1;       // option: 0 = one queue popped by every workgroup
+    int dag_gang = 4;             // option: tasks of one group (same B rows, same k-range) dealt to one queue together; < 0: all tasks to queue 0 (tests)
+    int dag_nq[2] = {0, 0};       // queues of the current device list per phase (0: one queue, the list as built)
+    mnk::DevBuf<int> dag_qoff;    // per phase 16 ints: the nq + 1 offsets of the queues in the phase's part of the device list
+    mnk::DevBuf<int> dag_qheads;  // per phase DAG_QHEAD_WORDS ints: the queue heads, 128 bytes apart, then the count of stolen tasks; zeroed per factorization
     mnk::DevBuf<int> dag_flags;   // [queue counter | front: Np/64 | af: 4 * Np/128], zeroed per factorization
     mnk::DevBuf<double> vfull;    // LDL^T: V = L D of every column, same layout as `fact` (B operand of the left-looking updates)
     mnk::DevBuf<unsigned long long> dag_trace;  // diagnostics (option dag_trace): time stamps per bulk task / chain strip

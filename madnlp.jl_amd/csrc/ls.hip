@@ -786,6 +786,14 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         return 0;
     }
     if (!strcmp(key, "dag_fill")) { ls->dag_fill = value != 0.0; ls->dag_tasks.release(); return 0; }   // zero-fill of the spare buffer as tasks of the bulk queue
+    // per-XCD queues of the bulk kernel (dag.hip: dag_deal_tasks); the task list is dealt again
+    if (!strcmp(key, "dag_xcd_queues")) { ls->dag_xcd_queues = value != 0.0; ls->dag_tasks.release(); return 0; }   // 0: one queue, popped by every workgroup
+    if (!strcmp(key, "dag_gang")) {   // tasks of one group that go to one queue together; negative: every task to queue 0 (tests of the steal path)
+        MNK_REQUIRE(value <= 64.0 && value != 0.0 && (double)(int)value == value, "dag_gang must be an integer in 1..64 (or negative)");
+        ls->dag_gang = (int)value;
+        ls->dag_tasks.release();
+        return 0;
+    }
     if (!strcmp(key, "batch_period")) { ls->batch_period = (int)value; return 0; }
     if (!strcmp(key, "dag_trace")) { ls->dag_trace_on = value != 0.0; return 0; }  // diagnostics: tools/dag_timeline.py
     if (!strcmp(key, "dag_max_rows")) { ls->dag_max_rows = (int64_t)value; return 0; }
@@ -998,6 +1006,11 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
     // since then would otherwise count a small positive pivot of the block as zero and reject what the parent accepts)
     c->pivot_tol = ls->pivot_tol;
     c->envelope = ls->envelope;
+    if (c->dag_xcd_queues != ls->dag_xcd_queues || c->dag_gang != ls->dag_gang) {
+        c->dag_xcd_queues = ls->dag_xcd_queues;
+        c->dag_gang = ls->dag_gang;
+        c->dag_tasks.release();
+    }
     int rc = mnk_ls_factorize_sc_async(c, sc);
     if (!rc) rc = mnk_ls_fetch_info(c);
     if (rc) return rc;
@@ -1426,6 +1439,15 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "dag_ntasks")) { *value = ls->dag_ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
     if (!strcmp(key, "dag_ntasks1")) { *value = ls->dag_ntasks1; return 0; }  // ... of them in the first phase, ...
     if (!strcmp(key, "dag_js2")) { *value = ls->dag_js2; return 0; }          // ... first strip-column of the second phase
+    if (!strcmp(key, "dag_nq")) { *value = std::max(ls->dag_nq[0], ls->dag_nq[1]); return 0; }   // ... queues the device list is dealt into (0: one)
+    if (!strcmp(key, "dag_steals")) {   // ... tasks the last factorization's workgroups took from another XCD's queue
+        int st[2] = {0, 0};
+        if (ls->dag_qheads.p != nullptr)
+            for (int ph = 0; ph < 2; ++ph)
+                MNK_HIP(mnk::d2h_copy(&st[ph], ls->dag_qheads.p + ph * mnk::DAG_QHEAD_WORDS + mnk::DAG_NQ * mnk::DAG_QHEAD_STRIDE, sizeof(int), ls->ctx->stream));
+        *value = (double)st[0] + (double)st[1];
+        return 0;
+    }
     if (!strcmp(key, "env_ksteps") || !strcmp(key, "env_ksteps_skipped")) {
         // task-DAG schedule: 128-column k-steps of the bulk tasks (tile columns of the chunks' K-loops, one per closing task) in
         // the task list / of them skipped by the last factorization as structurally zero (0 without an envelope, with the

@@ -3,7 +3,7 @@ task ORDERS on the CPU before spending GPU time: 720 workgroup slots pop the tas
 progress words as the kernel (front per row, per-tile chunk order, band-tile flags); chunk compute shares the machine
 (processor sharing with a per-workgroup ceiling), the tile-closing tasks and the chain steps are latency-bound.
 
-usage: python tools/dag_sim.py [ntile] [order ...]      orders: ready (the shipped one), col, mix:<beta>, ...
+usage: python tools/dag_sim.py [ntile] [order ...]      orders: ready (the shipped one), col, mix:<beta>, xcd:<gang>, ...
 Calibration constants at the top were set from the traces of round 3 (profiles/r03_dag_timeline_C3.md)."""
 import heapq
 import sys
@@ -83,7 +83,7 @@ def order_key(order, ntile, band_tiles):
         return lambda t: (t["ready"], t["cls"], t["J"], t["I"])
     if order.startswith("three:"):
         return lambda t: (t["ready"], t["cls"], t["J"], t["I"])
-    if order.startswith("two:"):   # handled by the caller (queue assignment), order inside a queue: by readiness
+    if order.startswith("two:") or order.startswith("xcd:"):   # handled by the caller (queue assignment), order inside a queue: by readiness
         return lambda t: (t["ready"], t["cls"], t["J"], t["I"])
     raise SystemExit("unknown order " + order)
 
@@ -96,6 +96,25 @@ def assign_queues(ts, order):
         for k in ts:
             k["queue"] = k["cls"]
         return [int(nb), int(nc), SLOTS - int(nb) - int(nc)]
+    if order.startswith("xcd:"):     # xcd:<g>  the per-XCD queues of csrc/dag.hip (dag_deal_tasks): gangs of g chunks with the same B rows
+        g, nq = int(order[4:]), 8    # and k-range go whole to the queue with the fewest k-steps dealt so far (ties: round-robin)
+        load, rr, i = [0] * nq, 0, 0
+        while i < len(ts):
+            j = i + 1
+            key = lambda k: (k["ready"], k["cls"], k["J"], k["kb"], k["ke"])  # noqa: E731
+            if g > 1 and ts[i]["cls"] != 1:
+                while j < len(ts) and key(ts[j]) == key(ts[i]):
+                    j += 1
+            for b in range(i, j, max(g, 1)):
+                q = min(range(nq), key=lambda x: (load[(rr + x) % nq], x))
+                q = (rr + q) % nq
+                rr = q + 1
+                for k in ts[b:min(j, b + max(g, 1))]:
+                    k["queue"] = q
+                    load[q] += k["ke"] - k["kb"]
+            i = j
+        print(f"  xcd queues, gang {g}: k-steps per queue {load}")
+        return [SLOTS // nq] * nq
     if not order.startswith("two:"):
         return None
     _, H, nU = order.split(":")
@@ -270,8 +289,9 @@ def simulate(ntile, ts, band_tiles=8, verbose=False, pools=None, dyn=None):
             try_start(got[1])
         for q in range(nq if dyn is None else 0):
             while freeq[q] > 0:
-                src = q if qpos[q] < len(queues[q]) else next((z for z in range(nq) if qpos[z] < len(queues[z])), None)
-                if src is None:
+                # (own queue first; once it is exhausted the head of the queue with the most tasks left, as the kernel steals)
+                src = q if qpos[q] < len(queues[q]) else max(range(nq), key=lambda z: len(queues[z]) - qpos[z])
+                if qpos[src] >= len(queues[src]):
                     break
                 freeq[q] -= 1
                 i = queues[src][qpos[src]]

@@ -20,6 +20,10 @@ with torch.cuda.stream(s):
         ls.set_option("dag_js2", int(os.environ["DAG_JS2"]))
     if os.environ.get("DAG_MIN_ROWS"):
         ls.set_option("dag_min_rows", int(os.environ["DAG_MIN_ROWS"]))
+    if os.environ.get("DAG_XCD_QUEUES"):   # 0: one queue popped by every workgroup (csrc/dag.hip: dag_deal_tasks)
+        ls.set_option("dag_xcd_queues", int(os.environ["DAG_XCD_QUEUES"]))
+    if os.environ.get("DAG_GANG"):
+        ls.set_option("dag_gang", int(os.environ["DAG_GANG"]))
     for _ in range(3):
         ls.factorize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

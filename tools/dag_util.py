@@ -27,6 +27,10 @@ with torch.cuda.stream(s):
     ls.set_option("dag_chunk", chunk)
     ls.set_option("dag_band", band)
     ls.set_option("dag_taper0", taper0)
+    if os.environ.get("DAG_XCD_QUEUES"):   # 0: one queue popped by every workgroup
+        ls.set_option("dag_xcd_queues", int(os.environ["DAG_XCD_QUEUES"]))
+    if os.environ.get("DAG_GANG"):
+        ls.set_option("dag_gang", int(os.environ["DAG_GANG"]))
     ls.factorize(); s.synchronize()
     ls.set_option("dag_fill", 0)   # (the trace is indexed by task: the list without the zero-fill tasks is the one tools/dag_tasks.py mirrors)
     ls.set_option("dag_trace", 1)
@@ -65,6 +69,12 @@ wait = W[:, 2] / 100.0
 fin = W[:, 4] / 100.0
 print(f"{len(W)} workgroups: lifetime mean {life.mean():.0f} us (min {life.min():.0f}, max {life.max():.0f}); waited mean {wait.mean():.0f} us "
       f"({100*wait.sum()/life.sum():.1f} % of the slot-time); finalization {fin.mean():.0f} us ({100*fin.sum()/life.sum():.1f} %); tasks/WG {W[:,3].mean():.1f}")
+if W[:, 5].any():   # per-XCD queues (option dag_xcd_queues): 1 + the workgroup's own queue, the tasks it stole from other queues
+    print("queue | workgroups | tasks | of them stolen | waited us (mean) | lifetime us (mean)")
+    for q in range(1, int(W[:, 5].max()) + 1):
+        m = W[:, 5] == q
+        print(f"{q - 1:5d} | {m.sum():10d} | {int(W[m, 3].sum()):5d} | {int(W[m, 6].sum()):14d} | {wait[m].mean():16.0f} | {life[m].mean():18.0f}")
+    print(f"stolen in all: {int(W[:, 6].sum())} of {int(W[:, 3].sum())} tasks")
 span = (W[:, 1].max() - W[:, 0].min()) / 100.0
 print(f"kernel span {span:.0f} us; slot-time not waiting/finalizing: {100*(life.sum()-wait.sum()-fin.sum())/(len(W)*span):.1f} % of slots x span")
 
