@@ -25,6 +25,11 @@ scaling factors are 1).  Quasi-Newton Hessians (`hessian_approximation = "bfgs" 
 
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
 mirror (`madnlp_jl_amd.kkt`) or, in the tests, the CPU oracle.
+
+The whole driver -- regular!, the inertia correction loop, both line searches, the second-order correction, restore!, robust! --
+is written once, here, against the vector primitives named in `BACKEND_PRIMITIVES`: numpy in this class, the `mnk_ipm_*`
+kernels on device tensors in `ipm_dev.DeviceMadNLPSolver`, which adds no control flow of its own beyond its first correction
+trial (the `probe` option and the speculative pair).
 """
 from __future__ import annotations
 
@@ -210,6 +215,22 @@ def _initialize_variables(x, xl, xu, bound_push, bound_fac):
             x[i] = max(l + bound_push * max(1, abs(l)), x[i])
         elif u != INF:
             x[i] = min(u - bound_push * max(1, abs(u)), x[i])
+
+
+# What a back-end of `MadNLPSolver` supplies: the methods that touch vectors.  The host class implements them with numpy; a
+# subclass that keeps its vectors elsewhere (`ipm_dev.DeviceMadNLPSolver`) overrides ALL of them -- none may fall back to numpy
+# on its vectors (tests/test_ipm_driver_structure.py).  The inertia-free corrector's kernels (`_set_g_ifr`, `_set_aug_rhs_ifr`,
+# `_ifr_solves`, `curv_test`) are not in the list: that method is host-only so far.
+BACKEND_PRIMITIVES = (
+    "eval_f", "eval_grad", "eval_cons", "eval_jac", "eval_lag_hess", "factorize_wrapper", "solve_refine_wrapper",
+    "set_aug_diagonal", "set_aug_rhs", "inf_compl", "varphi", "alpha_max",
+    "_primal", "_dual", "_dual_lb", "_dual_ub", "_new_vec", "_clone", "_vcopy", "_vaxpy", "_vaxpby", "_vfill", "_theta",
+    "_norm_inf", "_norm2", "_regularize", "_sd_sc", "_inf_du", "_iteration_scalars", "_jtprod", "_alpha_z", "_bound_dual_axpy",
+    "_bound_dual_fill", "_adjust_boundary", "_reset_bound_dual", "_get_F", "_set_initial_rhs", "_kkt_initialize",
+    "_rel_search_norm", "_line_search_scalars", "_trial_scalars",
+    "_rr_init_vectors", "_rr_obj_val", "_rr_theta", "_rr_inf_pr", "_rr_inf_du", "_rr_inf_compl", "_rr_varphi", "_rr_varphi_d",
+    "_rr_alpha_max", "_rr_alpha_z", "_rr_set_aug", "_rr_set_rhs", "_rr_finish", "_rr_set_f", "_rr_reset_slack_duals",
+)
 
 
 class MadNLPSolver:
@@ -447,42 +468,63 @@ class MadNLPSolver:
                 a = min(a, ((-x[pos] + xu[pos]) * tau / dx[pos]).min())
         return a
 
-    # ------------------------------------------------------------------ inertia_correction! (solver.jl:611-670)
+    # ------------------------------------------------------------------ inertia_correction! (solver.jl:611-670, :672-737, :739-783)
+    on_trial = None   # diagnostics: callable(solver, n_trial, inertia, inertia_correct, accepted) after every trial of inertia_correction
+
     def inertia_correction(self):
-        if self.inertia_correction_method == "inertia_free":
-            return self._inertia_correction_free()
-        if self.inertia_correction_method == "ignore":
-            return self._inertia_correction_ignore()
-        o, k = self.opt, self.kkt
-        n_trial = 0
-        dw_prev = dc_prev = 0.0
+        """The loop the three correctors share: try the matrix as it is, then perturb, factorize and try again until a trial
+        is accepted.  What a trial is (`_trial_<method>`) is all that differs between them."""
         self.del_w = self.del_c = 0.0
-        self.factorize_wrapper()
-        inertia = k.linear_solver.inertia()
-        ok = self.solve_refine_wrapper(self.d, self.p, self._w4) if k.is_inertia_correct(*inertia) else False
+        if self.inertia_correction_method == "inertia_free":   # once per correction: solver.jl:692-693
+            self._set_g_ifr(self._ifr.g)
+            self._set_aug_rhs_ifr(self._ifr.p0)
+        n_trial, inertia, ok = self._first_trial()
+        dw_prev, dc_prev = self.del_w, self.del_c
         while not ok:
-            if n_trial == 0:
-                self.del_w = (o.first_hessian_perturbation if self.del_w_last == 0 else
-                              max(o.min_hessian_perturbation, o.perturb_dec_fact * self.del_w_last))
-            else:
-                self.del_w *= o.perturb_inc_fact_first if self.del_w_last == 0 else o.perturb_inc_fact
-                if self.del_w > o.max_hessian_perturbation:
-                    self.cnt.k += 1
-                    return False
-            self.del_c = (o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
-                          if k.should_regularize_dual(*inertia) else 0.0)
-            k.regularize_diagonal(self.del_w - dw_prev, self.del_c - dc_prev)
+            if not self._next_perturbation(n_trial, inertia):
+                return False
+            self._regularize(self.del_w - dw_prev, self.del_c - dc_prev)
             dw_prev, dc_prev = self.del_w, self.del_c
             self.factorize_wrapper()
-            inertia = k.linear_solver.inertia()
-            ok = self.solve_refine_wrapper(self.d, self.p, self._w4) if k.is_inertia_correct(*inertia) else False
             n_trial += 1
+            inertia, ok = self._trial(n_trial)
         if self.del_w != 0:
             self.del_w_last = self.del_w
         return True
 
-    def _next_perturbation(self, n_trial):
-        """del_w of trial n_trial + 1 (the schedule shared by all three correctors); False: too big, restoration."""
+    def _first_trial(self):
+        """Factorize and try the unperturbed matrix: (trials made after it, last inertia, accepted).  A back-end that has
+        tried perturbations already leaves them in `del_w`, `del_c` (and on the KKT diagonals) and counts them."""
+        self.factorize_wrapper()
+        return (0,) + self._trial(0)
+
+    def _trial(self, n_trial):
+        """One trial on the current factorization: (inertia, accepted); inertia is None for the methods that have none."""
+        inertia, correct, ok = getattr(self, "_trial_" + self.inertia_correction_method)()
+        if self.on_trial is not None:
+            self.on_trial(self, n_trial, inertia, correct, ok)
+        return inertia, ok
+
+    def _trial_inertia_based(self):
+        """`inertia_correction!(::InertiaBased)` solver.jl:611-670: solve only if the inertia is the right one."""
+        inertia = self.kkt.linear_solver.inertia()
+        correct = self.kkt.is_inertia_correct(*inertia)
+        return inertia, correct, self._solve_newton() if correct else False
+
+    def _trial_inertia_free(self):
+        """`inertia_correction!(::InertiaFree)` solver.jl:672-737: a trial is accepted when both solves succeed and the
+        curvature test holds for the tangential component of the step."""
+        ic = self._ifr
+        ok = self._ifr_solves()
+        return None, None, curv_test(ic.t, ic.d0.primal(), ic.g, self.kkt, ic.wx, self.opt.inertia_free_tol) and ok
+
+    def _trial_ignore(self):
+        """`inertia_correction!(::InertiaIgnore)` solver.jl:739-783: perturb only when the solve fails."""
+        return None, None, self._solve_newton()
+
+    def _next_perturbation(self, n_trial, inertia):
+        """del_w, del_c of the trial after `n_trial` perturbed ones (the schedule of all three correctors, solver.jl:640-653);
+        False: del_w too big, restoration.  Without an inertia (None) del_c is set unconditionally."""
         o = self.opt
         if n_trial == 0:
             self.del_w = (o.first_hessian_perturbation if self.del_w_last == 0 else
@@ -492,7 +534,8 @@ class MadNLPSolver:
             if self.del_w > o.max_hessian_perturbation:
                 self.cnt.k += 1
                 return False
-        self.del_c = o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
+        self.del_c = (o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
+                      if inertia is None or self.kkt.should_regularize_dual(*inertia) else 0.0)
         return True
 
     def _set_g_ifr(self, g):
@@ -515,49 +558,6 @@ class MadNLPSolver:
               self.solve_refine_wrapper(self.d, self.p, self._w4))
         ic.t[:] = self._dx() - ic.d0.primal()
         return ok
-
-    def _inertia_correction_free(self):
-        """`inertia_correction!(::InertiaFree)` solver.jl:672-737: a trial is accepted when both solves succeed and the
-        curvature test holds for the tangential component of the step."""
-        k, ic = self.kkt, self._ifr
-        n_trial = 0
-        dw_prev = dc_prev = 0.0
-        self.del_w = self.del_c = 0.0
-        self._set_g_ifr(ic.g)
-        self._set_aug_rhs_ifr(ic.p0)
-        self.factorize_wrapper()
-        ok = self._ifr_solves()
-        while not curv_test(ic.t, ic.d0.primal(), ic.g, k, ic.wx, self.opt.inertia_free_tol) or not ok:
-            if not self._next_perturbation(n_trial):
-                return False
-            k.regularize_diagonal(self.del_w - dw_prev, self.del_c - dc_prev)
-            dw_prev, dc_prev = self.del_w, self.del_c
-            self.factorize_wrapper()
-            ok = self._ifr_solves()
-            n_trial += 1
-        if self.del_w != 0:
-            self.del_w_last = self.del_w
-        return True
-
-    def _inertia_correction_ignore(self):
-        """`inertia_correction!(::InertiaIgnore)` solver.jl:739-783: perturb only when the solve fails."""
-        k = self.kkt
-        n_trial = 0
-        dw_prev = dc_prev = 0.0
-        self.del_w = self.del_c = 0.0
-        self.factorize_wrapper()
-        ok = self.solve_refine_wrapper(self.d, self.p, self._w4)
-        while not ok:
-            if not self._next_perturbation(n_trial):
-                return False
-            k.regularize_diagonal(self.del_w - dw_prev, self.del_c - dc_prev)
-            dw_prev, dc_prev = self.del_w, self.del_c
-            self.factorize_wrapper()
-            ok = self.solve_refine_wrapper(self.d, self.p, self._w4)
-            n_trial += 1
-        if self.del_w != 0:
-            self.del_w_last = self.del_w
-        return True
 
     # ------------------------------------------------------------------ barrier (barrier.jl:12-34)
     def update_barrier(self, sc):
@@ -592,42 +592,34 @@ class MadNLPSolver:
                (varphi_trial <= varphi - o.gamma_phi * theta + 10 * EPS * abs(varphi))
         return "h" if suff else " "
 
-    def filter_line_search(self):
+    def _alpha_min(self, theta, varphi_d):
+        """`get_alpha_min` kernels.jl:715-741: the step below which the line search gives up."""
         o = self.opt
-        dx = self.d.primal()
-        theta = np.abs(self.c).sum()
-        varphi = self.varphi(self.obj_val, self.x)
-        with np.errstate(divide="ignore"):
-            varphi_d = float(((self.f - self.mu / (self.x - self.xl) + self.mu / (self.xu - self.x)) * dx).sum())
-        alpha_max = self.alpha_max(dx)
-        dzl, dzu = self.d.dual_lb(), self.d.dual_ub()
-        az = 1.0
-        if (dzl < 0).any():
-            az = min(az, (-self.zl_r[dzl < 0] * self.tau / dzl[dzl < 0]).min())
-        if (dzu < 0).any():
-            az = min(az, (-self.zu_r[dzu < 0] * self.tau / dzu[dzu < 0]).min())
-        self.alpha_z = az
         if varphi_d < 0:
             if theta <= self.theta_min:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, o.gamma_phi * theta / (-varphi_d),
-                                                   o.delta * _pow(theta, o.s_theta) / _pow(-varphi_d, o.s_phi))
-            else:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, -o.gamma_phi * theta / varphi_d)
-        else:
-            alpha_min = o.alpha_min_frac * o.gamma_theta
+                return o.alpha_min_frac * min(o.gamma_theta, o.gamma_phi * theta / (-varphi_d),
+                                              o.delta * _pow(theta, o.s_theta) / _pow(-varphi_d, o.s_phi))
+            return o.alpha_min_frac * min(o.gamma_theta, -o.gamma_phi * theta / varphi_d)
+        return o.alpha_min_frac * o.gamma_theta
+
+    def filter_line_search(self):
+        o = self.opt
+        dx = self._dx()
+        theta, varphi, varphi_d, alpha_max, self.alpha_z, rel_norm = self._line_search_scalars()
+        alpha_min = self._alpha_min(theta, varphi_d)
         self.cnt.l = 1
         self.alpha = alpha_max
-        small = (np.abs(dx) / (1 + np.abs(self.x))).max(initial=0.0) < 10 * EPS
+        small = rel_norm < 10 * EPS
         switching = varphi_d < 0 and self.alpha * _pow(-varphi_d, o.s_phi) > o.delta * 2.0 ** o.s_theta
         armijo = False
         unsuccessful = False
         theta_trial = varphi_trial = 0.0
+        norm_dx = None
         while True:
-            self.x_trial[:] = self.x + self.alpha * dx
+            self._vaxpby(self.x_trial, self.x, self.alpha, dx)
             self.obj_val_trial = self.eval_f(self.x_trial)
             self.eval_cons(self.c_trial, self.x_trial)
-            theta_trial = np.abs(self.c_trial).sum()
-            varphi_trial = self.varphi(self.obj_val_trial, self.x_trial)
+            theta_trial, varphi_trial = self._trial_scalars()
             armijo = varphi_trial <= varphi + o.eta_phi * self.alpha * varphi_d
             if small:
                 break
@@ -636,7 +628,7 @@ class MadNLPSolver:
                 break
             if self.cnt.l == 1 and theta_trial >= theta:
                 if self._second_order_correction(alpha_max, theta, varphi, theta_trial, varphi_d, switching):
-                    theta_trial = np.abs(self.c_trial).sum()
+                    theta_trial = self._theta(self.c_trial)
                     varphi_trial = self.varphi(self.obj_val_trial, self.x_trial)
                     break
             unsuccessful = True
@@ -645,7 +637,9 @@ class MadNLPSolver:
             if self.alpha < alpha_min:
                 self.cnt.k += 1
                 return "RESTORE"
-            if self.alpha * np.linalg.norm(dx) < EPS * 10:
+            if norm_dx is None:   # at most one reduction per line search
+                norm_dx = self._norm2(dx)
+            if self.alpha * norm_dx < EPS * 10:
                 return "SEARCH_DIRECTION_BECOMES_TOO_SMALL"
         if unsuccessful:
             self.cnt.unsuccessful_iterate += 1
@@ -666,18 +660,18 @@ class MadNLPSolver:
         w1 = self._w1
         # wy IS dual(_w1) in the reference (solver.jl:552-554): the solve below overwrites it, and the
         # next correction starts from that overwritten vector.  Mirrored on purpose.
-        wy = w1.dual()
-        wy[:] = self.c_trial + alpha_max * self.c
+        wy = self._dual(w1)
+        self._vaxpby(wy, self.c_trial, alpha_max, self.c)
         theta_soc_old = theta_trial
         for _ in range(o.max_soc):
             self.set_aug_rhs(wy)
             self.solve_refine_wrapper(w1, self.p, self._w4)
-            wx = w1.primal()
+            wx = self._primal(w1)
             alpha_soc = self.alpha_max(wx)
-            self.x_trial[:] = self.x + alpha_soc * wx
+            self._vaxpby(self.x_trial, self.x, alpha_soc, wx)
             self.eval_cons(self.c_trial, self.x_trial)
             self.obj_val_trial = self.eval_f(self.x_trial)
-            theta_soc = np.abs(self.c_trial).sum()
+            theta_soc = self._theta(self.c_trial)
             varphi_soc = self.varphi(self.obj_val_trial, self.x_trial)
             if not self._filter_ok(theta_soc, varphi_soc):
                 break
@@ -696,13 +690,18 @@ class MadNLPSolver:
             theta_soc_old = theta_soc
         return False
 
-    # ------------------------------------------------------------------ vector primitives shared with the device driver
-    # (the restoration phases below are written once against these; `ipm_dev.DeviceMadNLPSolver` overrides them with the
-    # `mnk_ipm_*` kernels on device tensors)
-    def _dx(self): return self.d.primal()
-    def _dy(self): return self.d.dual()
-    def _dzl(self): return self.d.dual_lb()
-    def _dzu(self): return self.d.dual_ub()
+    # ------------------------------------------------------------------ back-end primitives (`BACKEND_PRIMITIVES`)
+    # The phases above and below are written once against these; `ipm_dev.DeviceMadNLPSolver` overrides every one of them
+    # with the `mnk_ipm_*` kernels on device tensors.  Slices of a KKT vector (reference src/KKT/rhs.jl:90-150):
+    def _primal(self, v): return v.primal()
+    def _dual(self, v): return v.dual()
+    def _dual_lb(self, v): return v.dual_lb()
+    def _dual_ub(self, v): return v.dual_ub()
+
+    def _dx(self): return self._primal(self.d)
+    def _dy(self): return self._dual(self.d)
+    def _dzl(self): return self._dual_lb(self.d)
+    def _dzu(self): return self._dual_ub(self.d)
 
     def _new_vec(self, n): return np.zeros(n)
 
@@ -712,11 +711,17 @@ class MadNLPSolver:
 
     def _vaxpy(self, y, a, x): y += a * x            # axpy!
 
+    def _vaxpby(self, dst, x, a, d): dst[:] = x + a * d   # a trial point in one step
+
     def _vfill(self, v, value): v[:] = value         # fill!
 
     def _theta(self, c): return float(np.abs(c).sum())
 
     def _norm_inf(self, v): return float(np.abs(v).max(initial=0.0))
+
+    def _norm2(self, v): return float(np.linalg.norm(v))
+
+    def _regularize(self, dw, dc): self.kkt.regularize_diagonal(dw, dc)
 
     def _sd_sc(self):
         o, nl, nu = self.opt, len(self.ind_lb), len(self.ind_ub)
@@ -899,6 +904,19 @@ class MadNLPSolver:
 
     def _rel_search_norm(self): return float((np.abs(self._dx()) / (1 + np.abs(self.x))).max(initial=0.0))
 
+    def _line_search_scalars(self):
+        """theta, varphi, varphi_d, alpha_max, alpha_z, the relative norm of the step: what `filter_line_search` reads of the
+        iterate and the direction before its first trial point (line_search.jl:7-31)."""
+        dx = self._dx()
+        with np.errstate(divide="ignore"):
+            varphi_d = float(((self.f - self.mu / (self.x - self.xl) + self.mu / (self.xu - self.x)) * dx).sum())
+        return (self._theta(self.c), self.varphi(self.obj_val, self.x), varphi_d, self.alpha_max(dx),
+                self._alpha_z(self.tau), self._rel_search_norm())
+
+    def _trial_scalars(self):
+        """theta and varphi of the trial point (`c_trial`, `x_trial`, `obj_val_trial`)."""
+        return self._theta(self.c_trial), self.varphi(self.obj_val_trial, self.x_trial)
+
     # ------------------------------------------------------------------ restore! (solver.jl:300-411)
     def restore(self):
         o = self.opt
@@ -1054,14 +1072,7 @@ class MadNLPSolver:
         varphi_d_R = self._rr_varphi_d()
         alpha_max = self._rr_alpha_max()
         self.alpha_z = self._rr_alpha_z()
-        if varphi_d_R < 0:
-            if theta_R <= self.theta_min:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, o.gamma_phi * theta_R / (-varphi_d_R),
-                                                   o.delta * _pow(theta_R, o.s_theta) / _pow(-varphi_d_R, o.s_phi))
-            else:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, -o.gamma_phi * theta_R / varphi_d_R)
-        else:
-            alpha_min = o.alpha_min_frac * o.gamma_theta
+        alpha_min = self._alpha_min(theta_R, varphi_d_R)
         self.alpha = alpha_max
         self.cnt.l = 1
         small = self._rel_search_norm() < 10 * EPS

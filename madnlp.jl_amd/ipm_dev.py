@@ -1,6 +1,7 @@
-"""Device-resident regular phase of the IPM mirror: the iterate, the multipliers, the KKT vectors and the
-right-hand sides live in HBM; per iteration only scalars cross PCIe.  Same algorithm, same order of operations as
-`madnlp_jl_amd.ipm.MadNLPSolver` (which documents the reference lines); the vector work goes through
+"""Device-resident back-end of the IPM mirror: the iterate, the multipliers, the KKT vectors and the
+right-hand sides live in HBM; per iteration only scalars cross PCIe.  The algorithm is `madnlp_jl_amd.ipm.MadNLPSolver`'s
+(which documents the reference lines): `DeviceMadNLPSolver` overrides its vector primitives (`ipm.BACKEND_PRIMITIVES`) and
+nothing of its control flow except the first trial of the inertia correction.  The vector work goes through
 
   * the KKT handle:   `set_aug_diagonal!`, `regularize_diagonal!`, `build_kkt!`, `factorize!`, `solve_kkt!`, `mul!`, SpMV
   * `mnk_ipm_*`:      the reductions and elementwise pieces of reference `src/IPM/kernels.jl`, and the loop's plain vector
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .ipm import EPS, INF, IPMOptions, MadNLPSolver, _pow
+from .ipm import IPMOptions, MadNLPSolver
 from .ipm_device import IPMDeviceKernels
 
 
@@ -234,7 +235,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self._lw = nt + m + nlb + nub
         self.K = IPMDeviceKernels(nt, self.ind_lb, self.ind_ub, ctx=ctx)
         self.K.set_perturbation_sets(self.ind_llb, self.ind_uub)
-        self.dv, self.pv, self.w1v, self.w4v = (self._new_vec(self._lw) for _ in range(4))
+        self.d, self.p, self._w1, self._w4 = (self._new_vec(self._lw) for _ in range(4))   # flat device KKT vectors
         if hasattr(self.nlp, "arc_coef"):
             assert self.sparse, "the AC-OPF callbacks feed the sparse condensed handle"
             cls = DeviceOPFCallbacks
@@ -252,7 +253,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self._on_device = True
         self._sync = ctx.synchronize
 
-    # slices of a KKT vector (reference src/KKT/rhs.jl:90-150)
+    # slices of a flat KKT vector (reference src/KKT/rhs.jl:90-150)
     def _primal(self, v): return v[:self.nt]
     def _dual(self, v): return v[self.nt:self.nt + self.m]
     def _dual_lb(self, v): return v[self.nt + self.m:self.nt + self.m + len(self.ind_lb)]
@@ -399,7 +400,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
                                          o.default_dual_regularization)
 
     def set_aug_rhs(self, c):
-        p = self.pv
+        p = self.p
         self.K.set_aug_rhs(self.f, self.zl, self.zu, self.jacl, c, self.x, self.xl, self.xu, self.mu, self._primal(p),
                            self._dual(p), self._dual_lb(p), self._dual_ub(p))
         self.K.dual_inf_perturbation(self._primal(p), self.mu, self.opt.kappa_d)
@@ -412,8 +413,6 @@ class DeviceMadNLPSolver(MadNLPSolver):
 
     def alpha_max(self, dx):
         return self.K.get_alpha_max(self.x, self.xl, self.xu, dx, self.tau)
-
-    on_trial = None   # diagnostics: callable(solver, n_trial, inertia, inertia_correct, accepted) after every trial of inertia_correction
 
     # SPECULATIVE first correction (round 6).  On the AC-OPF run of the bench line 17 of 20 iterations take exactly two trials: the
     # unperturbed matrix is rejected, the first perturbation is accepted -- and that perturbation is known BEFORE the verdict on the
@@ -457,190 +456,51 @@ class DeviceMadNLPSolver(MadNLPSolver):
         return (self._on_device and self.speculate and self.del_w_last != 0 and hasattr(k, "ensure_spare_solver")
                 and k.should_regularize_dual(0, 0, 0) and k.should_regularize_dual(0, 1, 0))
 
-    def inertia_correction(self):
+    def _first_trial(self):
+        """The first trial of the base class's correction loop, with what belongs to this back-end: the `probe` option of the
+        linear solver and, when armed, the speculative pair."""
         from .linear_solver import factorize_batch
         o, k = self.opt, self.kkt
-        n_trial = 0
-        dw_prev = dc_prev = 0.0
-        self.del_w = self.del_c = 0.0
         if self._on_device and getattr(self, "_probe_applied", None) != self.probe and hasattr(k.linear_solver, "set_option"):
             k.linear_solver.set_option("probe", 1 if self.probe else 0)
             self._probe_applied = self.probe
-        spec = self._can_speculate()
-        if spec:
-            dw1 = max(o.min_hessian_perturbation, o.perturb_dec_fact * self.del_w_last)
-            dc1 = o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
-            spare = k.ensure_spare_solver()
-            k.save_diagonals_device()
-            with factorize_batch():
-                k.build_kkt_device()
-                k.linear_solver.factorize_async()       # trial 0: the matrix as it is
-                k.regularize_diagonal_device(dw1, dc1)  # trial 1: exactly the sequential loop's first correction (dw1 - 0, dc1 - 0)
-                k.build_kkt_device()
-                spare.factorize_async()
-            self.cnt.factorization_cnt += 1
-            self.speculative_factorizations += 1
-        else:
-            self.factorize_wrapper()
+        if not self._can_speculate():
+            return super()._first_trial()
+        dw1 = max(o.min_hessian_perturbation, o.perturb_dec_fact * self.del_w_last)
+        dc1 = o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
+        spare = k.ensure_spare_solver()
+        k.save_diagonals_device()
+        with factorize_batch():
+            k.build_kkt_device()
+            k.linear_solver.factorize_async()       # trial 0: the matrix as it is
+            k.regularize_diagonal_device(dw1, dc1)  # trial 1: exactly the sequential loop's first correction (dw1 - 0, dc1 - 0)
+            k.build_kkt_device()
+            spare.factorize_async()
+        self.cnt.factorization_cnt += 1
+        self.speculative_factorizations += 1
         inertia = k.linear_solver.inertia()
         correct = k.is_inertia_correct(*inertia)
-        if spec and correct:
+        if correct:
             # trial 0 stands: the handle goes back to the unperturbed system (diagonals bit for bit, matrix and condensation
-            # buffers rebuilt from them)
+            # buffers rebuilt from them) before the solve, whose refinement multiplies with that matrix
             k.restore_diagonals_device()
             k.build_kkt_device()
             self.speculative_wasted += 1
-            spec = False
-        ok = self.solve_refine_wrapper(self.dv, self.pv, self.w4v) if correct else False
+        ok = self._solve_newton() if correct else False
         if self.on_trial is not None:
-            self.on_trial(self, n_trial, inertia, correct, ok)
-        if spec:
-            # trial 0 rejected: the speculative factorization IS the sequential loop's next trial (the handle's diagonals and
-            # matrix are already that trial's)
-            self.del_w, self.del_c = dw1, dc1
-            dw_prev, dc_prev = dw1, dc1
-            k.swap_solvers()
-            self.cnt.factorization_cnt += 1
-            inertia = k.linear_solver.inertia()
-            correct = k.is_inertia_correct(*inertia)
-            ok = self.solve_refine_wrapper(self.dv, self.pv, self.w4v) if correct else False
-            n_trial = 1
-            if self.on_trial is not None:
-                self.on_trial(self, n_trial, inertia, correct, ok)
-        while not ok:
-            if n_trial == 0:
-                self.del_w = (o.first_hessian_perturbation if self.del_w_last == 0 else
-                              max(o.min_hessian_perturbation, o.perturb_dec_fact * self.del_w_last))
-            else:
-                self.del_w *= o.perturb_inc_fact_first if self.del_w_last == 0 else o.perturb_inc_fact
-                if self.del_w > o.max_hessian_perturbation:
-                    self.cnt.k += 1
-                    return False
-            self.del_c = (o.jacobian_regularization_value * self.mu ** o.jacobian_regularization_exponent
-                          if k.should_regularize_dual(*inertia) else 0.0)
-            k.regularize_diagonal_device(self.del_w - dw_prev, self.del_c - dc_prev)
-            dw_prev, dc_prev = self.del_w, self.del_c
-            self.factorize_wrapper()
-            inertia = k.linear_solver.inertia()
-            correct = k.is_inertia_correct(*inertia)
-            ok = self.solve_refine_wrapper(self.dv, self.pv, self.w4v) if correct else False
-            n_trial += 1
-            if self.on_trial is not None:
-                self.on_trial(self, n_trial, inertia, correct, ok)
-        if self.del_w != 0:
-            self.del_w_last = self.del_w
-        return True
+            self.on_trial(self, 0, inertia, correct, ok)
+        if correct:
+            return 0, inertia, ok
+        # trial 0 rejected: the speculative factorization IS the sequential loop's next trial (the handle's diagonals and
+        # matrix are already that trial's)
+        self.del_w, self.del_c = dw1, dc1
+        k.swap_solvers()
+        self.cnt.factorization_cnt += 1
+        return (1,) + self._trial(1)
 
-    # ------------------------------------------------------------------ filter line search
-    def filter_line_search(self):
-        o, K = self.opt, self.K
-        dx = self._primal(self.dv)
-        with K.batch():     # six reductions, one synchronization
-            b_n = K.get_norms(self.c)
-            b_v = K.get_varphi(self.obj_val, self.x, self.xl, self.xu, self.mu)
-            b_d = K.get_varphi_d(self.f, self.x, self.xl, self.xu, dx, self.mu)
-            b_a = K.get_alpha_max(self.x, self.xl, self.xu, dx, self.tau)
-            b_z = K.get_alpha_z(self.zl, self.zu, self._dual_lb(self.dv), self._dual_ub(self.dv), self.tau)
-            b_r = K.get_rel_search_norm(self.x, dx)
-        theta, varphi, varphi_d, alpha_max, self.alpha_z, rel_norm = b_n[1], b_v[0], b_d[0], b_a[0], b_z[0], b_r[0]
-        if varphi_d < 0:
-            if theta <= self.theta_min:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, o.gamma_phi * theta / (-varphi_d),
-                                                   o.delta * _pow(theta, o.s_theta) / _pow(-varphi_d, o.s_phi))
-            else:
-                alpha_min = o.alpha_min_frac * min(o.gamma_theta, -o.gamma_phi * theta / varphi_d)
-        else:
-            alpha_min = o.alpha_min_frac * o.gamma_theta
-        self.cnt.l = 1
-        self.alpha = alpha_max
-        small = rel_norm < 10 * EPS
-        switching = varphi_d < 0 and self.alpha * _pow(-varphi_d, o.s_phi) > o.delta * 2.0 ** o.s_theta
-        armijo = False
-        unsuccessful = False
-        theta_trial = varphi_trial = 0.0
-        norm_dx = None
-        while True:
-            K.vec_axpby(self.x_trial, 1.0, self.x, self.alpha, dx)
-            self.obj_val_trial = self.eval_f(self.x_trial)
-            self.eval_cons(self.c_trial, self.x_trial)
-            with K.batch():
-                b_n = K.get_norms(self.c_trial)
-                b_v = K.get_varphi(self.obj_val_trial, self.x_trial, self.xl, self.xu, self.mu)
-            theta_trial, varphi_trial = b_n[1], b_v[0]
-            armijo = varphi_trial <= varphi + o.eta_phi * self.alpha * varphi_d
-            if small:
-                break
-            ftype = self._ftype(theta, theta_trial, varphi, varphi_trial, switching, armijo)
-            if ftype in ("f", "h"):
-                break
-            if self.cnt.l == 1 and theta_trial >= theta:
-                if self._second_order_correction(alpha_max, theta, varphi, theta_trial, varphi_d, switching):
-                    theta_trial = K.get_norms(self.c_trial)[1]
-                    varphi_trial = self.varphi(self.obj_val_trial, self.x_trial)
-                    break
-            unsuccessful = True
-            self.alpha /= 2
-            self.cnt.l += 1
-            if self.alpha < alpha_min:
-                self.cnt.k += 1
-                return "RESTORE"
-            if norm_dx is None:
-                norm_dx = K.get_norm2(dx)
-            if self.alpha * norm_dx < EPS * 10:
-                return "SEARCH_DIRECTION_BECOMES_TOO_SMALL"
-        if unsuccessful:
-            self.cnt.unsuccessful_iterate += 1
-            if self.cnt.unsuccessful_iterate >= 4:
-                if self.theta_max / 10 > theta_trial:
-                    self.theta_max /= 10
-                    self.filter = [(self.theta_max, -INF)]
-                self.cnt.unsuccessful_iterate = 0
-        else:
-            self.cnt.unsuccessful_iterate = 0
-        if not switching or not armijo:
-            self.filter.append(((1 - o.gamma_theta) * theta_trial, varphi_trial - o.gamma_theta * theta_trial))
-        return "LINESEARCH_SUCCEEDED"
-
-    def _second_order_correction(self, alpha_max, theta, varphi, theta_trial, varphi_d, switching):
-        o, K = self.opt, self.K
-        w1 = self.w1v
-        wy = self._dual(w1)
-        K.vec_axpby(wy, 1.0, self.c_trial, alpha_max, self.c)
-        theta_soc_old = theta_trial
-        for _ in range(o.max_soc):
-            self.set_aug_rhs(wy)
-            self.solve_refine_wrapper(w1, self.pv, self.w4v)
-            wx = self._primal(w1)
-            alpha_soc = self.alpha_max(wx)
-            K.vec_axpby(self.x_trial, 1.0, self.x, alpha_soc, wx)
-            self.eval_cons(self.c_trial, self.x_trial)
-            self.obj_val_trial = self.eval_f(self.x_trial)
-            theta_soc = K.get_norms(self.c_trial)[1]
-            varphi_soc = self.varphi(self.obj_val_trial, self.x_trial)
-            if not self._filter_ok(theta_soc, varphi_soc):
-                break
-            if theta <= self.theta_min and switching:
-                if varphi_soc <= varphi + o.eta_phi * self.alpha * varphi_d:
-                    self.alpha = alpha_soc
-                    return True
-            else:
-                suff = (self.m > 0 and theta_soc <= (1 - o.gamma_theta) * theta + 10 * EPS * abs(theta)) or \
-                       (varphi_soc <= varphi - o.gamma_phi * theta + 10 * EPS * abs(varphi))
-                if suff:
-                    self.alpha = alpha_soc
-                    return True
-            if theta_soc > o.kappa_soc * theta_soc_old:
-                break
-            theta_soc_old = theta_soc
-        return False
-
-    # ------------------------------------------------------------------ vector primitives (see `ipm.MadNLPSolver`): the regular
-    # phase, restore! and robust! of the base class run unchanged on device tensors through these
-    def _dx(self): return self._primal(self.dv)
-    def _dy(self): return self._dual(self.dv)
-    def _dzl(self): return self._dual_lb(self.dv)
-    def _dzu(self): return self._dual_ub(self.dv)
-
+    # ------------------------------------------------------------------ back-end primitives (`ipm.BACKEND_PRIMITIVES`): the whole
+    # driver of the base class -- regular!, its line search and corrections, restore!, robust! -- runs unchanged on device tensors
+    # through these
     def _new_vec(self, n):
         v = torch.empty(n, dtype=torch.float64, device=self.dev)
         self.K.vec_fill(v, 0.0)
@@ -655,11 +515,17 @@ class DeviceMadNLPSolver(MadNLPSolver):
 
     def _vaxpy(self, y, a, x): self.K.vec_axpby(y, 1.0, y, a, x)
 
+    def _vaxpby(self, dst, x, a, d): self.K.vec_axpby(dst, 1.0, x, a, d)
+
     def _vfill(self, v, value): self.K.vec_fill(v, value)
 
     def _theta(self, c): return self.K.get_norms(c)[1]
 
     def _norm_inf(self, v): return self.K.get_norms(v)[0]
+
+    def _norm2(self, v): return self.K.get_norm2(v)
+
+    def _regularize(self, dw, dc): self.kkt.regularize_diagonal_device(dw, dc)
 
     def _sd_sc(self): return self.K.get_sd_sc(self.y, self.zl, self.zu, self.opt.s_max)
 
@@ -693,7 +559,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
         return self.K.get_F(self.c, self.f, self.zl, self.zu, self.jacl, self.x, self.xl, self.xu, self.mu)
 
     def _set_initial_rhs(self):
-        p = self.pv
+        p = self.p
         self.K.set_initial_rhs(self.f, self.zl, self.zu, self._primal(p), self._dual(p), self._dual_lb(p), self._dual_ub(p))
 
     def _kkt_initialize(self):
@@ -706,10 +572,26 @@ class DeviceMadNLPSolver(MadNLPSolver):
         z = np.zeros(nt)
         self.kkt.set_aug_diagonal_device(z, np.ones(nt), -np.ones(nt), z, z, 1.0, 0.0)
 
-    def _solve_newton(self):
-        return self.solve_refine_wrapper(self.dv, self.pv, self.w4v)
-
     def _rel_search_norm(self): return self.K.get_rel_search_norm(self.x, self._dx())
+
+    def _line_search_scalars(self):
+        """the six reductions in front of the line search in ONE synchronization."""
+        K, dx = self.K, self._dx()
+        with K.batch():
+            b_n = K.get_norms(self.c)
+            b_v = K.get_varphi(self.obj_val, self.x, self.xl, self.xu, self.mu)
+            b_d = K.get_varphi_d(self.f, self.x, self.xl, self.xu, dx, self.mu)
+            b_a = K.get_alpha_max(self.x, self.xl, self.xu, dx, self.tau)
+            b_z = K.get_alpha_z(self.zl, self.zu, self._dzl(), self._dzu(), self.tau)
+            b_r = K.get_rel_search_norm(self.x, dx)
+        return b_n[1], b_v[0], b_d[0], b_a[0], b_z[0], b_r[0]
+
+    def _trial_scalars(self):
+        K = self.K
+        with K.batch():
+            b_n = K.get_norms(self.c_trial)
+            b_v = K.get_varphi(self.obj_val_trial, self.x_trial, self.xl, self.xu, self.mu)
+        return b_n[1], b_v[0]
 
     # robust restorer (`mnk_ipm_*_R`)
     def _rr_init_vectors(self, RR, mu_R, rho):
@@ -755,7 +637,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
                                    o.default_primal_regularization, o.default_dual_regularization)
 
     def _rr_set_rhs(self):
-        p, RR = self.pv, self.RR
+        p, RR = self.p, self.RR
         self.K.set_aug_rhs_RR(RR.f_R, self.zl, self.zu, self.jacl, self.c, self.y, RR.pp, RR.nn, RR.zp, RR.zn, self.x, self.xl,
                               self.xu, RR.mu_R, self.opt.rho, self._primal(p), self._dual(p), self._dual_lb(p), self._dual_ub(p))
 

@@ -1,0 +1,396 @@
+"""Bit-exact record of IPM runs, for A/B comparisons of two versions of the driver (`madnlp.jl_amd/ipm.py`, `ipm_dev.py`).
+
+  python tools/ipm_trajectory_dump.py --out A.json                       host driver (MadNLPSolver) on the CPU oracle back-end
+  python tools/ipm_trajectory_dump.py --device --out A.json              DeviceMadNLPSolver on the HIP KKT systems (needs a GPU)
+  python tools/ipm_trajectory_dump.py --device --time 3 --out T.json     wall clock of the two runs bench.py's `ipm_loop` times
+  python tools/ipm_trajectory_dump.py --compare A.json B.json            identical, or per field the largest relative difference
+  ... --package DIR                                                      take the package from DIR (a copy of another commit's
+                                                                         `madnlp.jl_amd/`; with MNK_LIBPATH the same built library)
+
+Per run: status, counters, every `IterRecord` field and the final x, y, zl, zu, floats as `float.hex()`; a SHA-256 over all runs.
+Two versions that perform the same IEEE operations in the same order write identical files.
+
+By wrapping (nothing in the product counts), per run: which branches of the line search and of the inertia correction were
+reached; in --device mode also the result-returning `mnk_ipm_*` calls made outside a batch (one host synchronization each),
+the `mnk_ipm_batch_end` calls (one synchronization per batch) and the `vec_*` launches -- integers fixed by the control flow.
+The host mode refuses to write unless its runs reach every branch a driver refactor moves (`REQUIRED`)."""
+import argparse
+import hashlib
+import importlib.util
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+
+KINDS = ("dense", "dense_condensed", "sparse_condensed")
+# branch counters the host list must reach at least this often (a refactor of the driver moves every one of them)
+REQUIRED = {"soc_accepted": 1, "soc_rejected": 1, "ls_backtracked": 1, "ls_restore": 1, "ic_3_trials_inertia_based": 1,
+            "ic_3_trials_inertia_free": 1, "ic_overflow": 1}
+
+
+def load_package(pkg_dir):
+    """`madnlp_jl_amd` from the repository, or from `pkg_dir` (loaded the way the repository's import shim loads its own)."""
+    sys.path.insert(0, ROOT)
+    if pkg_dir:
+        pkg_dir = os.path.abspath(pkg_dir)
+        spec = importlib.util.spec_from_file_location("madnlp_jl_amd", os.path.join(pkg_dir, "__init__.py"),
+                                                      submodule_search_locations=[pkg_dir])
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["madnlp_jl_amd"] = mod
+        spec.loader.exec_module(mod)
+    import madnlp_jl_amd
+    return madnlp_jl_amd
+
+
+class DuplicateRowQP:
+    """min 0.5 |x|^2 s.t. x1 + x2 = 1, twice: a rank-deficient Jacobian, so the unperturbed KKT matrix is singular and a solve
+    on its LU factor fails -- the one thing that makes the `ignore` corrector perturb."""
+    n, m = 2, 2
+    x0, y0 = np.zeros(2), np.zeros(2)
+    lvar, uvar = np.full(2, -np.inf), np.full(2, np.inf)
+    lcon = ucon = np.ones(2)
+    jac_I, jac_J = np.array([0, 0, 1, 1]), np.array([0, 1, 0, 1])
+    hess_I, hess_J = np.array([0, 1]), np.array([0, 1])
+
+    def obj(self, x): return 0.5 * float(x @ x)
+    def grad(self, x): return np.array(x, dtype=float)
+    def cons(self, x): return np.array([x[0] + x[1], x[0] + x[1]])
+    def jac_coord(self, x): return np.ones(4)
+    def jac_dense(self, x): return np.ones((2, 2), order="F")
+    def hess_coord(self, x, y, w=1.0): return np.array([w, w])
+    def hess_dense(self, x, y, w=1.0): return np.array([[w, 0.0], [0.0, w]], order="F")
+
+
+def counted(cls, counts):
+    """`cls` with the line search and the inertia correction wrapped: counts the branches they take into `counts`."""
+    def bump(key):
+        counts[key] = counts.get(key, 0) + 1
+
+    class Counted(cls):
+        def _second_order_correction(self, *a):
+            ok = super()._second_order_correction(*a)
+            bump("soc_accepted" if ok else "soc_rejected")
+            return ok
+
+        def filter_line_search(self):
+            st = super().filter_line_search()
+            if self.cnt.l > 1:
+                bump("ls_backtracked")
+            if st == "RESTORE":
+                bump("ls_restore")
+            return st
+
+        def inertia_correction(self):
+            f0 = self.cnt.factorization_cnt
+            ok = super().inertia_correction()
+            if not ok:
+                bump("ic_overflow")
+            if self.cnt.factorization_cnt - f0 >= 3:
+                bump("ic_3_trials_" + self.inertia_correction_method)
+            if self.cnt.factorization_cnt - f0 >= 2 and self.inertia_correction_method == "ignore":
+                bump("ic_ignore_perturbed")
+            return ok
+    return Counted
+
+
+class Forced:
+    """The regular phase reports a line-search failure at iteration 2 (-> restore!) and an inertia-correction failure at
+    iteration 5 (-> robust!), once each: a convex QP walks through both restoration phases (as tests/test_ipm_restoration_driver.py)."""
+    _f1 = _f2 = False
+
+    def filter_line_search(self):
+        st = super().filter_line_search()
+        if self.cnt.k == 2 and not self._f1 and st == "LINESEARCH_SUCCEEDED":
+            self._f1 = True
+            self.cnt.k += 1
+            return "RESTORE"
+        return st
+
+    def inertia_correction(self):
+        ok = super().inertia_correction()
+        if self.status == "REGULAR" and self.cnt.k >= 5 and not self._f2:
+            self._f2 = True
+            return False
+        return ok
+
+
+def hexes(v):
+    return [float(a).hex() for a in np.asarray(v, dtype=float).ravel()]
+
+
+def record(s, state, counts):
+    x, y, zl, zu = state
+    return {"status": s.status, "k": s.cnt.k, "factorizations": s.cnt.factorization_cnt, "backsolves": s.cnt.backsolve_cnt,
+            "history": [[r.k, r.phase, r.ls] + hexes([r.obj, r.inf_pr, r.inf_du, r.inf_compl, r.mu, r.del_w, r.alpha])
+                        for r in s.history],
+            "x": hexes(x), "y": hexes(y), "zl": hexes(zl), "zu": hexes(zu), "branches": dict(sorted(counts.items()))}
+
+
+def finish(out, path, extra=None):
+    blob = json.dumps(out, sort_keys=True)
+    doc = {"sha256": hashlib.sha256(blob.encode()).hexdigest(), "runs": out}
+    doc.update(extra or {})
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(doc, f, sort_keys=True, indent=0)
+    return doc["sha256"]
+
+
+# ------------------------------------------------------------------------------------------------ host: CPU oracle back-end
+def host_cases():
+    from madnlp_jl_amd.problems import (CubicDiskModel, DenseQPModel, HS15Model, InfeasibleModel, LootsmaModel, SparseQPModel,
+                                        WachterBieglerModel)
+    from oracle.lapack_cpu import BUNCHKAUFMAN, LU
+    cubic = lambda: CubicDiskModel(2.636, [-4.9627, -2.877])  # noqa: E731
+    cases = []
+    for kind in KINDS:
+        for alg in (BUNCHKAUFMAN, LU):       # auto: inertia_based with BUNCHKAUFMAN, inertia_free with LU
+            for name, mk in (("hs15", HS15Model), ("lootsma", LootsmaModel), ("infeasible", InfeasibleModel), ("cubic2.636", cubic)):
+                cases.append((f"{name}-{kind}-{alg}", kind, mk, alg, {}))
+    dqp = lambda: DenseQPModel(20, 15, 2)  # noqa: E731
+    cases += [("hs15-dense-ignore", "dense", HS15Model, LU, {"inertia_correction_method": "ignore"}),
+              ("duplicate-row-dense-ignore", "dense", DuplicateRowQP, LU, {"inertia_correction_method": "ignore"}),
+              ("wachter-biegler-dense", "dense", WachterBieglerModel, BUNCHKAUFMAN, {}),
+              ("cubic1.0178-dense", "dense", lambda: CubicDiskModel(1.0178, [-1.7068, 1.069]), BUNCHKAUFMAN, {}),
+              ("sparse-qp-case30", "sparse_condensed", lambda: SparseQPModel("case30"), BUNCHKAUFMAN, {}),
+              ("dense-qp-bfgs", "dense_condensed", dqp, BUNCHKAUFMAN, {"hessian_approximation": "bfgs"}),
+              ("dense-qp-damped-bfgs", "dense_condensed", dqp, BUNCHKAUFMAN, {"hessian_approximation": "damped_bfgs"}),
+              ("cubic2.636-dense-max-perturbation-1", "dense", cubic, BUNCHKAUFMAN, {"max_hessian_perturbation": 1.0})]
+    return cases
+
+
+def oracle_factory(kind, nlp, alg):
+    from oracle.dense import DenseCondensedKKTSystem, DenseKKTSystem
+    from oracle.lapack_cpu import LapackCPUSolver
+    from oracle.sparse_condensed import SparseCondensedKKTSystem
+    fac = lambda A: LapackCPUSolver(A, alg)  # noqa: E731
+
+    def make(info):
+        if kind == "sparse_condensed":
+            return SparseCondensedKKTSystem(info["n"], info["m"], nlp.jac_I, nlp.jac_J, nlp.hess_I, nlp.hess_J,
+                                            info["ind_ineq"], info["ind_lb"], info["ind_ub"], fac)
+        if kind == "dense_condensed":
+            return DenseCondensedKKTSystem(info["n"], info["m"], info["ind_ineq"], info["ind_eq"], info["ind_lb"],
+                                           info["ind_ub"], fac)
+        return DenseKKTSystem(info["n"], info["m"], info["ind_ineq"], info["ind_lb"], info["ind_ub"], fac)
+    return make
+
+
+def options(IPMOptions, sparse, **kw):
+    o = IPMOptions(tol=1e-6 if sparse else 1e-8, **kw)
+    if sparse:  # preset of SparseCondensedKKTSystem (reference src/IPM/options.jl:146-147,160,226)
+        o.relax_equality, o.dual_initialization = True, "zero"
+    return o
+
+
+def run_host(args):
+    from madnlp_jl_amd.ipm import IPMOptions, MadNLPSolver
+    out, total = {}, {}
+    for name, kind, mk, alg, kw in host_cases():
+        nlp, sparse, counts = mk(), kind == "sparse_condensed", {}
+        s = counted(MadNLPSolver, counts)(nlp, oracle_factory(kind, nlp, alg), options(IPMOptions, sparse, max_iter=300, **kw),
+                                          sparse=sparse)
+        with np.errstate(all="ignore"):
+            s.solve()
+        out[name] = record(s, (s.x, s.y, s.zl, s.zu), counts)
+        for k, v in counts.items():
+            total[k] = total.get(k, 0) + v
+        print(f"{name}: {s.status}, {s.cnt.k} iterations, {s.cnt.factorization_cnt} factorizations {counts}", flush=True)
+    missing = {k: (total.get(k, 0), v) for k, v in REQUIRED.items() if total.get(k, 0) < v}
+    if missing:
+        sys.exit(f"refusing to write: branches not reached often enough (reached, required): {missing}")
+    total.setdefault("ic_ignore_perturbed", 0)     # 0: a perturbation inside the `ignore` loop is not exercised
+    digest = finish(out, args.out, {"branches": dict(sorted(total.items())), "cases": sorted(out),
+                                    "iteration_records": sum(len(r["history"]) for r in out.values())})
+    print(f"sha256 {digest}  {len(out)} runs  branches {dict(sorted(total.items()))}")
+
+
+# ------------------------------------------------------------------------------------------------ device: HIP KKT systems
+def count_launches(mj_ipm_device, counts):
+    """Wrap `IPMDeviceKernels` so that `counts` holds: unbatched result calls, batch ends, vec_* launches."""
+    K, B = mj_ipm_device.IPMDeviceKernels, mj_ipm_device._Batch
+    call, leave = K._call, B.__exit__
+
+    def _call(self, name, *a, **k):
+        if not self._batching:
+            counts["unbatched_results"] += 1
+        return call(self, name, *a, **k)
+
+    def __exit__(self, *exc):
+        counts["batch_ends"] += 1
+        return leave(self, *exc)
+    K._call, B.__exit__ = _call, __exit__
+    for name in [n for n in vars(K) if n.startswith("vec_")]:
+        def wrap(f):
+            def g(self, *a, **k):
+                counts["vec_launches"] += 1
+                return f(self, *a, **k)
+            return g
+        setattr(K, name, wrap(getattr(K, name)))
+
+
+def device_cases(mj):
+    from madnlp_jl_amd.problems import ACOPFModel, DenseQPModel, InfeasibleModel, SparseQPModel
+    acopf = lambda: ACOPFModel("case1354pegase")  # noqa: E731
+    dqp = lambda: DenseQPModel(20, 15, 2)  # noqa: E731
+    return [("acopf-case1354pegase", acopf, True, False, {}, {}),
+            ("acopf-case1354pegase-speculate", acopf, True, False, {}, {"speculate": True}),
+            ("sparse-qp-case30-forced", lambda: SparseQPModel("case30"), True, True, {}, {}),
+            ("sparse-qp-case118-forced", lambda: SparseQPModel("case118"), True, True, {}, {}),
+            ("infeasible", InfeasibleModel, True, False, {}, {}),
+            ("dense-qp-exact", dqp, False, False, {}, {}),
+            ("dense-qp-bfgs", dqp, False, False, {"hessian_approximation": "bfgs"}, {})]
+
+
+def hip_factory(mj, nlp, ctx, sparse):
+    opt = lambda: mj.HipSolverOptions(lapack_algorithm=mj.BUNCHKAUFMAN)  # noqa: E731
+
+    def make(info):
+        if sparse:
+            return mj.SparseCondensedKKTSystem(info["n"], info["m"], nlp.jac_I, nlp.jac_J, nlp.hess_I, nlp.hess_J, info["ind_ineq"],
+                                               info["ind_lb"], info["ind_ub"], ctx=ctx, opt_linear_solver=opt(), device_kkt_ops=True)
+        return mj.DenseCondensedKKTSystem(info["n"], info["m"], info["ind_ineq"], info["ind_eq"], info["ind_lb"], info["ind_ub"],
+                                          ctx=ctx, opt_linear_solver=opt(), device_kkt_ops=True)
+    return make
+
+
+def close(s):
+    s.cb.close()
+    s.K.close()
+    s.kkt.close()
+
+
+def run_device(args, mj):
+    import torch
+    from madnlp_jl_amd import ipm_device
+    from madnlp_jl_amd.ipm import IPMOptions
+    from madnlp_jl_amd.ipm_dev import DeviceMadNLPSolver
+    assert torch.cuda.is_available(), "--device needs a GPU"
+    st = torch.cuda.Stream()
+    torch.cuda.set_stream(st)       # torch and the library share one stream
+    ctx = mj.HipContext(0, stream=st.cuda_stream)
+    launches = {}
+    count_launches(ipm_device, launches)
+    out = {}
+    for name, mk, sparse, forced, kw, attrs in device_cases(mj):
+        nlp, counts = mk(), {}
+        cls = counted(DeviceMadNLPSolver, counts)
+        if forced:
+            cls = type("ForcedDevice", (Forced, cls), {})
+        launches.update(unbatched_results=0, batch_ends=0, vec_launches=0)
+        s = cls(nlp, hip_factory(mj, nlp, ctx, sparse), options(IPMOptions, sparse, **kw), sparse=sparse)
+        for k, v in attrs.items():
+            setattr(s, k, v)
+        s.solve()
+        rec = record(s, s.host_state(), counts)
+        rec.update(launches=dict(launches), probe_hits=int(s.probe_hits), probe_misses=int(s.probe_misses),
+                   speculative_factorizations=int(s.speculative_factorizations), speculative_wasted=int(s.speculative_wasted))
+        out[name] = rec
+        print(f"{name}: {s.status}, {s.cnt.k} iterations, {s.cnt.factorization_cnt} factorizations, {s.cnt.backsolve_cnt} "
+              f"back-solves, {launches}, {counts}", flush=True)
+        close(s)
+    print(f"sha256 {finish(out, args.out, {'cases': sorted(out)})}  {len(out)} runs")
+    ctx.close()
+
+
+def time_device(args, mj):
+    """it/s as bench.py's `ipm_loop` measures it (initialize, upload, synchronize, host clock around solve + synchronize): one
+    warm-up run, then `args.time` timed runs, for the AC-OPF NLP and for the QP with its sparsity."""
+    import torch
+    from madnlp_jl_amd.ipm import IPMOptions
+    from madnlp_jl_amd.ipm_dev import DeviceMadNLPSolver
+    from madnlp_jl_amd.problems import ACOPFModel, SparseQPModel
+    ctx = mj.HipContext(0)
+    out = {}
+    for key, nlp in (("end_to_end_ipm", ACOPFModel("case1354pegase")), ("end_to_end_ipm_qp", SparseQPModel("case1354pegase"))):
+        samples = []
+        for i in range(1 + args.time):
+            s = DeviceMadNLPSolver(nlp, hip_factory(mj, nlp, ctx, True), options(IPMOptions, True))
+            s.initialize()
+            s._upload()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s.solve()
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            if i:
+                samples.append(s.cnt.k / wall)
+            status, k = s.status, s.cnt.k
+            close(s)
+        out[key] = {"status": status, "iterations": k, "it_per_s": samples}
+        print(f"{key}: {status}, {k} iterations, it/s {['%.2f' % v for v in samples]}, median {statistics.median(samples):.2f}", flush=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+    ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ compare two dumps
+def compare(a_path, b_path):
+    """Exit status 0: every integer, status, phase and branch / launch count equal.  Prints `identical` when the floats are too,
+    else per field the largest relative difference."""
+    A, B = json.load(open(a_path)), json.load(open(b_path))
+    if A["sha256"] == B["sha256"]:
+        print(f"identical: sha256 {A['sha256']} ({len(A['runs'])} runs)")
+        return 0
+    bad, worst = [], {}
+
+    def rel(field, xa, xb):
+        if len(xa) != len(xb):
+            bad.append(f"{field}: lengths {len(xa)} != {len(xb)}")
+            return
+        for u, v in zip(xa, xb):
+            u, v = float.fromhex(u), float.fromhex(v)
+            if u != v:
+                d = abs(u - v) / max(abs(u), abs(v)) if np.isfinite(u) and np.isfinite(v) else float("inf")
+                worst[field] = max(worst.get(field, 0.0), d)
+    if sorted(A["runs"]) != sorted(B["runs"]):
+        bad.append("different case lists")
+    for name in sorted(set(A["runs"]) & set(B["runs"])):
+        ra, rb = A["runs"][name], B["runs"][name]
+        for key in sorted(set(ra) | set(rb)):
+            if key in ("x", "y", "zl", "zu"):
+                rel(f"{name}.{key}", ra[key], rb[key])
+            elif key == "history":
+                if [h[:3] for h in ra[key]] != [h[:3] for h in rb[key]]:
+                    bad.append(f"{name}: iteration numbers / phases / line-search counts differ")
+                else:
+                    for i, fld in enumerate(("obj", "inf_pr", "inf_du", "inf_compl", "mu", "del_w", "alpha")):
+                        rel(f"{name}.{fld}", [h[3 + i] for h in ra[key]], [h[3 + i] for h in rb[key]])
+            elif ra.get(key) != rb.get(key):
+                bad.append(f"{name}.{key}: {ra.get(key)} != {rb.get(key)}")
+    for f, d in sorted(worst.items()):
+        print(f"float field differs: {f}: largest relative difference {d:.3e}")
+    for msg in bad:
+        print("DIFFERENT:", msg)
+    print(json.dumps({"identical": False, "integers_equal": not bad, "largest_relative_difference": max(worst.values(), default=0.0)}))
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out")
+    ap.add_argument("--package", help="directory to load as madnlp_jl_amd instead of the repository's madnlp.jl_amd/")
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--time", type=int, default=0, help="with --device: timed runs per problem (after one warm-up run)")
+    ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    args = ap.parse_args()
+    if args.compare:
+        sys.exit(compare(*args.compare))
+    if not args.out:
+        ap.error("--out is required")
+    mj = load_package(args.package)
+    if args.device and args.time:
+        time_device(args, mj)
+    elif args.device:
+        run_device(args, mj)
+    else:
+        run_host(args)
+
+
+if __name__ == "__main__":
+    main()
