@@ -556,6 +556,10 @@ int mnk_schur_build_local(mnk_schur* h, const double* S0, int64_t lds0, int loc_
 int mnk_schur_factorize_s(mnk_schur* h, const double* S, int64_t lds, int loc, int* info);
 int mnk_schur_inertia_s(mnk_schur* h, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg);
 int mnk_schur_scenario_inertia(mnk_schur* h, int64_t k, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg);
+/* Which tier produced scenario k's current factor (mnk_ls_bk_info of its solver): *active = 1 when the pivoted Bunch-Kaufman
+ * tier was taken -- mnk_schur_build_local then forms that scenario's term column by column (T_k = A_k^-1 C_dk') instead of on
+ * the grouped path; *count = how many factorizations of this scenario took it so far.  Either pointer may be NULL. */
+int mnk_schur_scenario_bk_info(mnk_schur* h, int64_t k, int* active, int* count);
 int mnk_schur_forward(mnk_schur* h, double* rhs_k, double* contrib_d);
 int mnk_schur_solve_s(mnk_schur* h, double* rhs_d);
 int mnk_schur_backward(mnk_schur* h, double* rhs_k, const double* x_d);

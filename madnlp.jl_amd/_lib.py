@@ -213,6 +213,7 @@ SIGNATURES = {
     "mnk_schur_factorize_s": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
     "mnk_schur_inertia_s": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
     "mnk_schur_scenario_inertia": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p]),
+    "mnk_schur_scenario_bk_info": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mnk_schur_forward": (C.c_int, [_vp, _vp, _vp]),
     "mnk_schur_solve_s": (C.c_int, [_vp, _vp]),
     "mnk_schur_backward": (C.c_int, [_vp, _vp, _vp]),

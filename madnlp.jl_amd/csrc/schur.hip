@@ -415,6 +415,11 @@ int mnk_schur_scenario_inertia(mnk_schur* h, int64_t k, int64_t* num_pos, int64_
     return mnk_ls_inertia(h->ls_k[k], num_pos, num_zero, num_neg);
 }
 
+int mnk_schur_scenario_bk_info(mnk_schur* h, int64_t k, int* active, int* count) {
+    MNK_REQUIRE(h && k >= 0 && k < h->ns, "mnk_schur_scenario_bk_info: bad argument");
+    return mnk_ls_bk_info(h->ls_k[k], active, count, nullptr, nullptr);
+}
+
 // The solves above run on device-resident vectors and return before the device is done.  A one-launch (persistent) solve
 // that gives up raises a pinned abort word: every stage checks its solvers once at its end (one stream synchronization) and
 // reports the failure now -- the solver has then switched to the stepwise solve, the caller repeats the stage.

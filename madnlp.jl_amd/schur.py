@@ -131,6 +131,13 @@ class SchurDenseStage:
         L.check(L.lib().mnk_schur_scenario_inertia(self._h, k, C.byref(p), C.byref(z), C.byref(n)), "scenario inertia")
         return (p.value, z.value, n.value)
 
+    def scenario_bk_active(self, k):
+        """True when scenario k's current factor came from the pivoted Bunch-Kaufman tier (`mnk_schur_scenario_bk_info`): the
+        build then takes the column-by-column fallback for it, the solves the tier's own solve."""
+        act = C.c_int(0)
+        L.check(L.lib().mnk_schur_scenario_bk_info(self._h, k, C.byref(act), None), "mnk_schur_scenario_bk_info")
+        return bool(act.value)
+
     def is_inertia_correct(self, num_pos, num_zero, num_neg):
         """reference :901-903."""
         return num_zero == 0 and num_pos == self.nd

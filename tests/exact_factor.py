@@ -58,8 +58,10 @@ class ExactCase:
         return int(bad[0]) + 1 if len(bad) else 0
 
 
-def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool = True, per_row: int = 6) -> ExactCase:
-    """`breakdowns`: {column: new d_k}.  `positive`: every other pivot > 0 (else random signs)."""
+def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool = True, per_row: int = 6,
+               exponents: tuple = (-2, 3)) -> ExactCase:
+    """`breakdowns`: {column: new d_k}.  `positive`: every other pivot > 0 (else random signs).  `exponents`: the range
+    (inclusive) of e in |d_k| = 4^e."""
     rng = np.random.default_rng(seed)
     src = rng.random(n) < 0.5
     src[0] = True
@@ -79,7 +81,7 @@ def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool
         Nmat = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
     else:
         Nmat = sp.csc_matrix((n, n))
-    d = 4.0 ** rng.integers(-2, 4, size=n)
+    d = 4.0 ** rng.integers(exponents[0], exponents[1] + 1, size=n)
     if not positive:
         d *= rng.choice([-1.0, 1.0], size=n)
     for k, v in (breakdowns or {}).items():
