@@ -532,6 +532,45 @@ int mnk_opf_cons(mnk_opf* opf, const double* x, double* c);
 int mnk_opf_jac_coord(mnk_opf* opf, const double* x, double* jac);
 int mnk_opf_hess_coord(mnk_opf* opf, const double* x, const double* y, double obj_weight, double* hess);
 
+/* ---- device evaluation of ANY NLP written as patterns: expression tapes (csrc/tape_eval.hip) -----
+ * The general form of mnk_opf_*: a model is a list of patterns, each one scalar expression applied to R rows of index and
+ * parameter data (objective pattern: f += sum_r e_r; constraint pattern: c[rows[r]] += e_r, several patterns may feed one
+ * row, rows fed by none evaluate to 0).  `madnlp_jl_amd.tape_model` compiles an expression to the three tapes a pattern is
+ * added with -- 0 value (one output), 1 first derivatives (out_j[o] = local variable), 2 second derivatives (out_j[o] >=
+ * out_l[o] = local pair) -- and is the host mirror.  A tape is straight-line code: `code` holds (op, dst_slot, a, b) per
+ * instruction, op 0 add 1 sub 2 mul 3 div 4 neg 5 sin 6 cos 7 exp 8 log 9 sqrt (4 .. 9 read `a` only); an operand is
+ * kind << 24 | index with kind 0 slot (< nslot <= 32), 1 local variable (< k <= 8), 2 parameter column (< q <= 8),
+ * 3 constant (< nconst).  var_index is R x k and params R x q, row-major; all index arrays are host, 0-based; a row of
+ * var_index names k distinct variables.  mnk_tape_add_pattern checks everything a kernel will index with and returns
+ * non-zero (mnk_last_error_string says what) for a bad tape; nothing is uploaded before mnk_tape_finalize.
+ * COO layout: pattern-major, output-major, then row -- entry = base[pattern] + o * R + r; Jacobian (rows[r],
+ * var_index[r, out_j[o]]), Hessian at (max, min) of the pair's global indices; duplicates across patterns are expected.
+ * cons / grad add the contributions of a destination in term order (no atomics).  x, y and every output are device
+ * vectors; the evaluation calls are asynchronous on the context's stream. */
+/* The handle is an opaque mnk_tape*.  TEMPORARY: the prototypes below spell it void* (mnk_tape_create: void* out = mnk_tape**),
+ * at the cost of C type checking on this one handle family, because the static header check of tests/test_julia_glue.py knows
+ * the handle types by a fixed list of names; the follow-up adds `tape` to that list and types these prototypes
+ * (mnk_tape* / mnk_tape**), which does not change the binary interface. */
+typedef struct mnk_tape mnk_tape;
+int mnk_tape_create(mnk_ctx* ctx, int64_t n, int64_t m, void* out);
+int mnk_tape_destroy(void* tape);
+int mnk_tape_add_pattern(void* tape, int kind /* 0 objective, 1 constraint */, int64_t R, int k, int q,
+                         const int32_t* var_index, const double* params, const int32_t* rows,
+                         int64_t ninstr0, const int32_t* code0, int64_t nconst0, const double* consts0, int64_t nout0,
+                         const int32_t* out_operand0, const int32_t* out_j0, const int32_t* out_l0, int nslot0,
+                         int64_t ninstr1, const int32_t* code1, int64_t nconst1, const double* consts1, int64_t nout1,
+                         const int32_t* out_operand1, const int32_t* out_j1, const int32_t* out_l1, int nslot1,
+                         int64_t ninstr2, const int32_t* code2, int64_t nconst2, const double* consts2, int64_t nout2,
+                         const int32_t* out_operand2, const int32_t* out_j2, const int32_t* out_l2, int nslot2);
+int mnk_tape_finalize(void* tape);
+int mnk_tape_sizes(void* tape, int64_t* n, int64_t* m, int64_t* nterms, int64_t* nnzj, int64_t* nnzh);
+int mnk_tape_get_structure(void* tape, int32_t* jac_I, int32_t* jac_J, int32_t* hess_I, int32_t* hess_J);
+int mnk_tape_obj_terms(void* tape, const double* x, double* terms /* nterms; obj = sum(terms) */);
+int mnk_tape_grad(void* tape, const double* x, double* g);
+int mnk_tape_cons(void* tape, const double* x, double* c);
+int mnk_tape_jac_coord(void* tape, const double* x, double* jac);
+int mnk_tape_hess_coord(void* tape, const double* x, const double* y, double obj_weight, double* hess);
+
 /* ---- dense S stage of the Schur-complement KKT system ----------------------------------------------
  * Reference: `SchurComplementKKTSystem` src/KKT/Schur/schur.jl -- `build_kkt!` :927-1001 (phase 1: factor every
  * scenario block A_k and form A_k^-1 C_dk'; phase 2: S -= C_dk A_k^-1 C_dk'), `factorize_kkt!` :1003-1005, steps 3-5 of

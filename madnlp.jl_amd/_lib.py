@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of a diagnostic build of the same ABI (tools/ab_*.sh); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "factor.hip", "solve.hip", "ls.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip"]
 HEADERS = ["common.h", "ls.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "gemm_macro.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
@@ -194,6 +194,18 @@ SIGNATURES = {
     "mnk_opf_cons": (C.c_int, [_vp, _vp, _vp]),
     "mnk_opf_jac_coord": (C.c_int, [_vp, _vp, _vp]),
     "mnk_opf_hess_coord": (C.c_int, [_vp, _vp, _vp, C.c_double, _vp]),
+    "mnk_tape_create": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp]),
+    "mnk_tape_destroy": (C.c_int, [_vp]),
+    "mnk_tape_add_pattern": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp]
+                             + [C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int] * 3),
+    "mnk_tape_finalize": (C.c_int, [_vp]),
+    "mnk_tape_sizes": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mnk_tape_get_structure": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mnk_tape_obj_terms": (C.c_int, [_vp, _vp, _vp]),
+    "mnk_tape_grad": (C.c_int, [_vp, _vp, _vp]),
+    "mnk_tape_cons": (C.c_int, [_vp, _vp, _vp]),
+    "mnk_tape_jac_coord": (C.c_int, [_vp, _vp, _vp]),
+    "mnk_tape_hess_coord": (C.c_int, [_vp, _vp, _vp, C.c_double, _vp]),
     "mnk_sc_set_aug_RR": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double]),
     "mnk_dc_set_aug_RR": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double]),
     "mnk_ls_bk_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, _vp]),

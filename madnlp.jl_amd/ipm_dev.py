@@ -7,11 +7,12 @@ nothing of its control flow except the first trial of the inertia correction.  T
   * `mnk_ipm_*`:      the reductions and elementwise pieces of reference `src/IPM/kernels.jl`, and the loop's plain vector
                       work (`mnk_ipm_vec_*`, `mnk_ipm_get_dot`, `mnk_ipm_gemv`)
   * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
+  * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
 
 Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as the reference's preset does) and
 `DenseCondensedKKTSystem` (equalities allowed), with models whose callbacks can be evaluated on the device: the AC-OPF NLP
-(`DeviceOPFCallbacks`), the sparse QP through the KKT handle's own SpMV on the compressed Jacobian / Hessian, the dense QP
+(`DeviceOPFCallbacks`), any `TapeModel` on the sparse condensed system (`DeviceTapeCallbacks`), the sparse QP through the KKT handle's own SpMV on the compressed Jacobian / Hessian, the dense QP
 through `mnk_ipm_gemv` on device copies of P and A.  Initialization runs once on the host (the base class) and is uploaded.
 
 With `hessian_approximation = "bfgs" / "damped_bfgs"` (dense systems) the Hessian approximation lives in the KKT handle's
@@ -212,8 +213,98 @@ class DeviceOPFCallbacks:
             pass
 
 
+class DeviceTapeCallbacks:
+    """Callbacks of ANY model written as patterns (`tape_model.TapeModel`) on the device (`mnk_tape_*`, csrc/tape_eval.hip): the
+    model's expression tapes are handed to the library once; objective terms, gradient, constraints, Jacobian and
+    Lagrangian-Hessian COO values are then interpreted from the device iterate, in the model's own COO order (the KKT handle is
+    created from the model's `jac_I .. hess_J`).  Same method set as `DeviceOPFCallbacks`."""
+
+    def __init__(self, nlp, kkt, dev, K):
+        nlp.finalize()
+        self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
+        lib = L.lib()
+        self._h = C.c_void_p()
+        L.check(lib.mnk_tape_create(K.ctx.handle, nlp.n, nlp.m, C.byref(self._h)), "mnk_tape_create")
+        try:
+            for p in nlp.patterns:
+                args = []
+                for t in p.tapes:
+                    args += [len(t.code), t.code.ctypes.data, len(t.consts), t.consts.ctypes.data, t.nout, t.out_operand.ctypes.data,
+                             t.out_j.ctypes.data, t.out_l.ctypes.data, t.nslot]
+                L.check(lib.mnk_tape_add_pattern(self._h, p.kind, p.R, p.k, p.q, p.var_index.ctypes.data, p.params.ctypes.data,
+                                                 p.rows.ctypes.data if p.kind == 1 else None, *args), "mnk_tape_add_pattern")
+            L.check(lib.mnk_tape_finalize(self._h), "mnk_tape_finalize")
+            sz = [C.c_int64() for _ in range(5)]
+            L.check(lib.mnk_tape_sizes(self._h, *[C.byref(v) for v in sz]), "mnk_tape_sizes")
+            nnzj, nnzh = len(nlp.jac_I), len(nlp.hess_I)
+            if tuple(v.value for v in sz) != (nlp.n, nlp.m, nlp.nterms, nnzj, nnzh):
+                raise RuntimeError(f"mnk_tape_sizes {tuple(v.value for v in sz)} differs from the host model's "
+                                   f"{(nlp.n, nlp.m, nlp.nterms, nnzj, nnzh)}")
+            st = [np.zeros(max(k, 1), dtype=np.int32) for k in (nnzj, nnzj, nnzh, nnzh)]
+            L.check(lib.mnk_tape_get_structure(self._h, *[a.ctypes.data for a in st]), "mnk_tape_get_structure")
+            for name, a, b in zip(("jac_I", "jac_J", "hess_I", "hess_J"), st, (nlp.jac_I, nlp.jac_J, nlp.hess_I, nlp.hess_J)):
+                if not np.array_equal(a[:len(b)], b):   # (values would land in the wrong KKT entries)
+                    raise RuntimeError(f"the library's COO structure ({name}) differs from the host model's")
+        except Exception:
+            self.close()
+            raise
+        E = lambda k: torch.empty(max(k, 1), dtype=torch.float64, device=dev)[:k]  # noqa: E731
+        self.jv, self.hv, self.hv0, self.terms = E(nnzj), E(nnzh), E(nnzh), E(nlp.nterms)
+        if nnzh:
+            K.vec_fill(self.hv0, 0.0)
+
+    def obj_terms(self, x):
+        L.check(L.lib().mnk_tape_obj_terms(self._h, x.data_ptr(), self.terms.data_ptr()), "mnk_tape_obj_terms")
+        return self.terms
+
+    def obj(self, x):
+        return self.K.get_sum(self.obj_terms(x)) if len(self.terms) else 0.0
+
+    def grad(self, g, x):
+        L.check(L.lib().mnk_tape_grad(self._h, x.data_ptr(), g.data_ptr()), "mnk_tape_grad")
+
+    def cons(self, c, x):
+        L.check(L.lib().mnk_tape_cons(self._h, x.data_ptr(), c.data_ptr()), "mnk_tape_cons")
+
+    def jac_coord(self, x):
+        L.check(L.lib().mnk_tape_jac_coord(self._h, x.data_ptr(), self.jv.data_ptr()), "mnk_tape_jac_coord")
+        return self.jv
+
+    def hess_coord(self, x, y, sigma=1.0):
+        L.check(L.lib().mnk_tape_hess_coord(self._h, x.data_ptr(), y.data_ptr(), float(sigma), self.hv.data_ptr()),
+                "mnk_tape_hess_coord")
+        return self.hv
+
+    def jtprod_x(self, out_x, y):
+        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
+
+    def load_jac(self, x):
+        self.kkt.compress_jacobian(self.jac_coord(x))
+
+    def load_hess(self, x, y, sigma=1.0):
+        self.kkt.compress_hessian(self.hess_coord(x, y, sigma))
+
+    def zero_hess(self):
+        self.kkt.compress_hessian(self.hv0)
+
+    def close(self):
+        if self._h:
+            L.lib().mnk_tape_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceMadNLPSolver(MadNLPSolver):
     def __init__(self, nlp, kkt_factory, opt: IPMOptions | None = None, device="cuda", sparse=True):
+        if getattr(nlp, "is_tape_model", False) and not sparse:
+            raise NotImplementedError("DeviceMadNLPSolver evaluates a TapeModel for the sparse condensed KKT handle only "
+                                      "(DeviceTapeCallbacks feed COO values to its compressors): use sparse=True with "
+                                      "relax_equality, or MadNLPSolver with host callbacks")
         super().__init__(nlp, kkt_factory, opt, sparse=sparse)
         if self.inertia_correction_method != "inertia_based":
             if hasattr(self.kkt, "close"):
@@ -236,7 +327,9 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self.K = IPMDeviceKernels(nt, self.ind_lb, self.ind_ub, ctx=ctx)
         self.K.set_perturbation_sets(self.ind_llb, self.ind_uub)
         self.d, self.p, self._w1, self._w4 = (self._new_vec(self._lw) for _ in range(4))   # flat device KKT vectors
-        if hasattr(self.nlp, "arc_coef"):
+        if getattr(self.nlp, "is_tape_model", False):
+            cls = DeviceTapeCallbacks
+        elif hasattr(self.nlp, "arc_coef"):
             assert self.sparse, "the AC-OPF callbacks feed the sparse condensed handle"
             cls = DeviceOPFCallbacks
         else:
