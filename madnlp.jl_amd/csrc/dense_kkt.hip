@@ -234,11 +234,8 @@ using namespace mnk;
 struct mnk_dc_extra {
     DevBuf<int32_t> ineq_slot;   // constraint -> inequality slot or -1
     DevBuf<int32_t> eq_slot;     // constraint -> equality slot or -1
-    // device-side solve_kkt! / mul!
-    int64_t nlb = 0, nub = 0;
-    DevBuf<int64_t> ind_lb, ind_ub;
-    DevBuf<double> reg, l_diag, u_diag, l_lower, u_lower, buffer, pd, wdev, xdev, feed;
-    bool have_bounds = false, have_terms = false, have_diag = false;
+    KktVecState st;              // bound structure, barrier terms, work vectors (kkt_vec.h)
+    DevBuf<double> buffer, pd;   // m, order: device-side solve_kkt! of the condensed system
 };
 static mnk_dc_extra* extra_of(mnk_dc* dc) { return static_cast<mnk_dc_extra*>(dc->extra); }
 
@@ -345,8 +342,7 @@ int mnk_dc_build(mnk_dc* dc, const double* pr_diag, const double* du_diag, int l
     hipStream_t s = dc->ctx->stream;
     if (pr_diag == nullptr && du_diag == nullptr) {
         // the diagonals the handle keeps itself (mnk_dc_set_aug_diagonal / mnk_dc_regularize_diagonal)
-        mnk_dc_extra* ex0 = extra_of(dc);
-        MNK_REQUIRE(ex0 != nullptr && ex0->have_diag, "mnk_dc_build: no diagonals given and mnk_dc_set_aug_diagonal was not called");
+        MNK_REQUIRE(extra_of(dc)->st.have_diag, "mnk_dc_build: no diagonals given and mnk_dc_set_aug_diagonal was not called");
     } else {
         MNK_REQUIRE(pr_diag && (du_diag || dc->m == 0), "mnk_dc_build: NULL argument");
         if (loc == MNK_DEVICE) {
@@ -407,62 +403,37 @@ int mnk_dc_get_aug(mnk_dc* dc, double* out, int loc) {
 }
 
 
-// ---- device-side solve_kkt! / mul! -------------------------------------------------------------------
+// ---- device-side solve_kkt! / mul!: the bound / barrier state and the frames are kkt_vec.h's, the matrix part is below ----
 int mnk_dc_set_bounds(mnk_dc* dc, int64_t nlb, const int64_t* ind_lb, int64_t nub, const int64_t* ind_ub, int index_base) {
-    MNK_REQUIRE(dc && nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub), "mnk_dc_set_bounds: bad argument");
-    MNK_HIP(hipSetDevice(dc->ctx->device));
-    mnk_dc_extra* ex = extra_of(dc);
-    MNK_REQUIRE(ex != nullptr, "mnk_dc_set_bounds: unknown handle");
-    const int64_t np = dc->n + dc->ns;
-    std::vector<int64_t> lb(nlb), ub(nub);
-    for (int64_t i = 0; i < nlb; ++i) {
-        lb[i] = ind_lb[i] - index_base;
-        MNK_REQUIRE(lb[i] >= 0 && lb[i] < np, "mnk_dc_set_bounds: lower-bound index out of range");
-    }
-    for (int64_t i = 0; i < nub; ++i) {
-        ub[i] = ind_ub[i] - index_base;
-        MNK_REQUIRE(ub[i] >= 0 && ub[i] < np, "mnk_dc_set_bounds: upper-bound index out of range");
-    }
-    hipStream_t s = dc->ctx->stream;
-    const size_t lw = (size_t)(np + dc->m + nlb + nub);
-    int rc = ex->ind_lb.upload(lb, s);
-    rc |= ex->ind_ub.upload(ub, s);
-    rc |= ex->reg.alloc(np);
-    rc |= ex->l_diag.alloc(nlb);
-    rc |= ex->l_lower.alloc(nlb);
-    rc |= ex->u_diag.alloc(nub);
-    rc |= ex->u_lower.alloc(nub);
-    rc |= ex->buffer.alloc(dc->m);
-    rc |= ex->pd.alloc(dc->order);
-    rc |= ex->wdev.alloc(lw);
-    rc |= ex->xdev.alloc(lw);
+    int rc = kkt_enter(dc, nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub), "mnk_dc_set_bounds",
+                       "bad argument");
     if (rc) return rc;
-    ex->nlb = nlb;
-    ex->nub = nub;
-    ex->have_bounds = true;
-    return 0;
+    mnk_dc_extra* ex = extra_of(dc);
+    rc = ex->buffer.alloc(dc->m) | ex->pd.alloc(dc->order);
+    if (rc) return rc;
+    return kkt_set_bounds(ex->st, dc->ctx, "mnk_dc_set_bounds", dc->n + dc->ns, dc->n + dc->ns + dc->m, nlb, ind_lb, nub, ind_ub,
+                          index_base);
+}
+
+int mnk_dc_set_barrier_terms(mnk_dc* dc, const double* reg, const double* l_diag, const double* u_diag,
+                             const double* l_lower, const double* u_lower, int loc) {
+    int rc = kkt_enter(dc, true, "mnk_dc_set_barrier_terms", "NULL argument");
+    if (rc) return rc;
+    return kkt_set_barrier_terms(extra_of(dc)->st, dc->ctx, "mnk_dc_set_barrier_terms", dc->n + dc->ns, reg, l_diag, u_diag,
+                                 l_lower, u_lower, loc);
 }
 
 static int dc_diag_view(mnk_dc* dc, AugDiagView& v, const char* who) {
-    if (!dc) { set_error("%s: NULL argument", who); return -1; }
-    MNK_HIP(hipSetDevice(dc->ctx->device));
-    mnk_dc_extra* ex = extra_of(dc);
-    if (!(ex != nullptr && ex->have_bounds)) { set_error("%s: call mnk_dc_set_bounds first", who); return -1; }
-    v = AugDiagView{dc->ctx, dc->n + dc->ns, dc->m, ex->nlb, ex->nub, ex->reg.p, dc->pr_diag.p, dc->du_diag.p, ex->l_diag.p,
-                    ex->u_diag.p, ex->l_lower.p, ex->u_lower.p, ex->ind_lb.p, ex->ind_ub.p, &ex->feed};
-    return 0;
+    int rc = kkt_enter(dc, true, who, "NULL argument");
+    if (rc) return rc;
+    return kkt_diag_view(v, extra_of(dc)->st, dc->ctx, who, dc->n + dc->ns, dc->m, dc->pr_diag.p, dc->du_diag.p);
 }
 
 int mnk_dc_set_aug_diagonal(mnk_dc* dc, const double* x, const double* xl, const double* xu, const double* zl,
                             const double* zu, double primal_reg, double dual_reg, int loc) {
     AugDiagView v;
     int rc = dc_diag_view(dc, v, "mnk_dc_set_aug_diagonal");
-    if (rc) return rc;
-    MNK_REQUIRE(x && xl && xu && zl && zu, "mnk_dc_set_aug_diagonal: NULL vector");
-    rc = kkt_set_aug_diagonal(v, x, xl, xu, zl, zu, primal_reg, dual_reg, loc);
-    if (rc) return rc;
-    extra_of(dc)->have_terms = extra_of(dc)->have_diag = true;
-    return 0;
+    return rc ? rc : kkt_set_aug_diagonal(v, "mnk_dc_set_aug_diagonal", x, xl, xu, zl, zu, primal_reg, dual_reg, loc);
 }
 
 // set_aug_RR!(kkt, solver, RR) (reference src/IPM/kernels.jl:72-87): device-resident vectors only
@@ -471,153 +442,77 @@ int mnk_dc_set_aug_RR(mnk_dc* dc, const double* x, const double* xl, const doubl
                       double primal_reg, double dual_reg) {
     AugDiagView v;
     int rc = dc_diag_view(dc, v, "mnk_dc_set_aug_RR");
-    if (rc) return rc;
-    MNK_REQUIRE(x && xl && xu && zl && zu && D_R && (v.ndu == 0 || (pp && zp && nn && zn)), "mnk_dc_set_aug_RR: NULL vector");
-    rc = kkt_set_aug_RR(v, x, xl, xu, zl, zu, D_R, pp, zp, nn, zn, zeta, primal_reg, dual_reg);
-    if (rc) return rc;
-    extra_of(dc)->have_terms = extra_of(dc)->have_diag = true;
-    return 0;
+    return rc ? rc : kkt_set_aug_RR(v, "mnk_dc_set_aug_RR", x, xl, xu, zl, zu, D_R, pp, zp, nn, zn, zeta, primal_reg, dual_reg);
 }
 
 int mnk_dc_regularize_diagonal(mnk_dc* dc, double primal, double dual) {
     AugDiagView v;
     int rc = dc_diag_view(dc, v, "mnk_dc_regularize_diagonal");
-    if (rc) return rc;
-    MNK_REQUIRE(extra_of(dc)->have_diag, "mnk_dc_regularize_diagonal: call mnk_dc_set_aug_diagonal first");
-    return kkt_regularize_diagonal(v, primal, dual);
+    return rc ? rc : kkt_regularize_diagonal(v, "mnk_dc_regularize_diagonal", primal, dual);
 }
 
 int mnk_dc_get_diagonals(mnk_dc* dc, double* pr_diag, double* du_diag, double* reg, double* l_diag, double* u_diag,
                          double* l_lower, double* u_lower) {
     AugDiagView v;
     int rc = dc_diag_view(dc, v, "mnk_dc_get_diagonals");
-    if (rc) return rc;
-    return kkt_get_diagonals(v, pr_diag, du_diag, reg, l_diag, u_diag, l_lower, u_lower);
-}
-
-int mnk_dc_set_barrier_terms(mnk_dc* dc, const double* reg, const double* l_diag, const double* u_diag,
-                             const double* l_lower, const double* u_lower, int loc) {
-    MNK_REQUIRE(dc, "mnk_dc_set_barrier_terms: NULL argument");
-    MNK_HIP(hipSetDevice(dc->ctx->device));
-    mnk_dc_extra* ex = extra_of(dc);
-    MNK_REQUIRE(ex != nullptr && ex->have_bounds, "mnk_dc_set_barrier_terms: call mnk_dc_set_bounds first");
-    hipStream_t s = dc->ctx->stream;
-    auto put = [&](double* dst, const double* src, int64_t cnt) -> int {
-        if (cnt <= 0) return 0;
-        MNK_REQUIRE(src != nullptr, "mnk_dc_set_barrier_terms: NULL vector");
-        if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
-        else MNK_HIP(mnk::h2d_copy(dst, src, cnt * sizeof(double), s));
-        return 0;
-    };
-    int rc = put(ex->reg.p, reg, dc->n + dc->ns);
-    rc |= put(ex->l_diag.p, l_diag, ex->nlb);
-    rc |= put(ex->u_diag.p, u_diag, ex->nub);
-    rc |= put(ex->l_lower.p, l_lower, ex->nlb);
-    rc |= put(ex->u_lower.p, u_lower, ex->nub);
-    if (rc) return rc;
-    if (loc != MNK_DEVICE) MNK_HIP(mnk::stream_wait(s));
-    ex->have_terms = true;
-    return 0;
+    return rc ? rc : kkt_get_diagonals(v, pr_diag, du_diag, reg, l_diag, u_diag, l_lower, u_lower);
 }
 
 #define MNK_GRID(cnt) dim3((unsigned)(((cnt) + 255) / 256)), dim3(256), 0, s
 
 int mnk_dc_solve_kkt(mnk_dc* dc, mnk_ls* ls, double* w, int loc) {
-    MNK_REQUIRE(dc && ls && w, "mnk_dc_solve_kkt: NULL argument");
+    int rc = kkt_enter(dc, ls && w, "mnk_dc_solve_kkt", "NULL argument");
+    if (rc) return rc;
     MNK_REQUIRE(ls->ctx == dc->ctx && ls->N == dc->order, "mnk_dc_solve_kkt: the solver does not belong to this system");
-    MNK_HIP(hipSetDevice(dc->ctx->device));
     mnk_dc_extra* ex = extra_of(dc);
-    MNK_REQUIRE(ex != nullptr && ex->have_bounds && ex->have_terms,
-                "mnk_dc_solve_kkt: call mnk_dc_set_bounds / mnk_dc_set_barrier_terms / mnk_dc_build first");
     hipStream_t s = dc->ctx->stream;
-    const int64_t n = dc->n, ns = dc->ns, m = dc->m, n_eq = dc->n_eq, nlb = ex->nlb, nub = ex->nub;
-    const int64_t lw = n + ns + m + nlb + nub;
-    // see mnk_sc_solve_kkt: an aborted persistent solve is detected before the copy-back and redone stepwise
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        double* d = w;
-        if (loc != MNK_DEVICE) {
-            d = ex->wdev.p;
-            MNK_HIP(mnk::h2d_copy(d, w, lw * sizeof(double), s));
-        }
-        double *ws = d + n, *dual = d + n + ns, *wl = dual + m, *wu = wl + nlb;
-        if (nlb > 0) hipLaunchKernelGGL(reduce_rhs_kernel, MNK_GRID(nlb), d, ex->ind_lb.p, wl, ex->l_diag.p, nlb);
-        if (nub > 0) hipLaunchKernelGGL(reduce_rhs_kernel, MNK_GRID(nub), d, ex->ind_ub.p, wu, ex->u_diag.p, nub);
-        int rc = 0;
-        if (!dc->condensed) {
-            // reduced solve (reference src/IPM/factorization.jl:41-46): the solver acts on primal_dual(w) in place
-            rc = mnk_ls_solve(ls, d, 1, dc->order, MNK_DEVICE);
-            if (rc) return rc;
+    const int64_t n = dc->n, ns = dc->ns, m = dc->m, n_eq = dc->n_eq;
+    return kkt_solve_kkt(ex->st, dc->ctx, "mnk_dc_solve_kkt", ls, n + ns + m, w, loc, [&](double* d) -> int {
+        // reduced solve (reference src/IPM/factorization.jl:41-46): the solver acts on primal_dual(w) in place
+        if (!dc->condensed) return mnk_ls_solve(ls, d, 1, dc->order, MNK_DEVICE);
+        double *ws = d + n, *dual = d + n + ns;
+        const double* Ss = dc->pr_diag.p + n;
+        if (m > 0) {
+            hipLaunchKernelGGL(dc_condense_rhs_kernel, MNK_GRID(m), ex->buffer.p, dual, ws, dc->diag_buffer.p, Ss,
+                               ex->ineq_slot.p, m);
+            hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, ex->pd.p, dc->jac.p, m,
+                               ex->buffer.p, m, n, 1.0, 0.0);  // xx = jac' * buffer
         } else {
-            const double* Ss = dc->pr_diag.p + n;
-            if (m > 0) {
-                hipLaunchKernelGGL(dc_condense_rhs_kernel, MNK_GRID(m), ex->buffer.p, dual, ws, dc->diag_buffer.p, Ss,
-                                   ex->ineq_slot.p, m);
-                hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, ex->pd.p, dc->jac.p, m,
-                                   ex->buffer.p, m, n, 1.0, 0.0);  // xx = jac' * buffer
-            } else {
-                MNK_HIP(hipMemsetAsync(ex->pd.p, 0, n * sizeof(double), s));
-            }
-            hipLaunchKernelGGL(dc_pack_kernel, MNK_GRID(n + n_eq), ex->pd.p, d, dual, dc->d_ind_eq.p, n, n_eq);
-            rc = mnk_ls_solve(ls, ex->pd.p, 1, dc->order, MNK_DEVICE);
-            if (rc) return rc;
-            MNK_HIP(hipMemcpyAsync(d, ex->pd.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));  // wx = xx
-            if (m > 0) {
-                hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, s, dual, dc->jac.p, m, d, m, n,
-                                   1.0, 0.0);  // dual(w) = jac * wx
-                hipLaunchKernelGGL(dc_expand_kernel, MNK_GRID(m), dual, ws, ex->buffer.p, dc->diag_buffer.p, Ss,
-                                   ex->ineq_slot.p, ex->eq_slot.p, ex->pd.p + n, m);
-            }
+            MNK_HIP(hipMemsetAsync(ex->pd.p, 0, n * sizeof(double), s));
         }
-        if (nlb > 0) hipLaunchKernelGGL(finish_aug_kernel, MNK_GRID(nlb), wl, d, ex->ind_lb.p, ex->l_lower.p, ex->l_diag.p, nlb, 0);
-        if (nub > 0) hipLaunchKernelGGL(finish_aug_kernel, MNK_GRID(nub), wu, d, ex->ind_ub.p, ex->u_lower.p, ex->u_diag.p, nub, 1);
-        MNK_HIP(hipGetLastError());
-        if (loc == MNK_DEVICE) break;
-        MNK_HIP(mnk::stream_wait(s));
-        if (attempt == 0 && mnk_ls_take_solve_abort(ls)) continue;
-        MNK_HIP(mnk::d2h_copy(w, d, lw * sizeof(double), s));
-        break;
-    }
-    return 0;
+        hipLaunchKernelGGL(dc_pack_kernel, MNK_GRID(n + n_eq), ex->pd.p, d, dual, dc->d_ind_eq.p, n, n_eq);
+        int rc = mnk_ls_solve(ls, ex->pd.p, 1, dc->order, MNK_DEVICE);
+        if (rc) return rc;
+        MNK_HIP(hipMemcpyAsync(d, ex->pd.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));  // wx = xx
+        if (m > 0) {
+            hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, s, dual, dc->jac.p, m, d, m, n,
+                               1.0, 0.0);  // dual(w) = jac * wx
+            hipLaunchKernelGGL(dc_expand_kernel, MNK_GRID(m), dual, ws, ex->buffer.p, dc->diag_buffer.p, Ss,
+                               ex->ineq_slot.p, ex->eq_slot.p, ex->pd.p + n, m);
+        }
+        return 0;
+    });
 }
 
 int mnk_dc_mul(mnk_dc* dc, double* w, const double* x, double alpha, double beta, int loc) {
-    MNK_REQUIRE(dc && w && x, "mnk_dc_mul: NULL argument");
-    MNK_HIP(hipSetDevice(dc->ctx->device));
+    int rc = kkt_enter(dc, w && x, "mnk_dc_mul", "NULL argument");
+    if (rc) return rc;
     mnk_dc_extra* ex = extra_of(dc);
-    MNK_REQUIRE(ex != nullptr && ex->have_bounds && ex->have_terms,
-                "mnk_dc_mul: call mnk_dc_set_bounds / mnk_dc_set_barrier_terms first");
     hipStream_t s = dc->ctx->stream;
-    const int64_t n = dc->n, ns = dc->ns, m = dc->m, nlb = ex->nlb, nub = ex->nub;
-    const int64_t lw = n + ns + m + nlb + nub;
-    double* dw = w;
-    const double* dx = x;
-    if (loc != MNK_DEVICE) {
-        dw = ex->wdev.p;
-        MNK_HIP(mnk::h2d_copy(ex->wdev.p, w, lw * sizeof(double), s));
-        MNK_HIP(mnk::h2d_copy(ex->xdev.p, x, lw * sizeof(double), s));
-        dx = ex->xdev.p;
-    }
-    // wx = alpha Sym(H) xx + beta wx ; wx += alpha jac' dual(x) ; dual(w) = alpha jac xx + beta dual(w)
-    hipLaunchKernelGGL(symv_l_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dw, dc->hess.p, n, dx, alpha, beta);
-    if (m > 0) {
-        hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dw, dc->jac.p, m, dx + n + ns, m, n,
-                           alpha, 1.0);
-        hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, s, dw + n + ns, dc->jac.p, m, dx, m,
-                           n, alpha, beta);
-    }
-    hipLaunchKernelGGL(dc_kktmul_diag_kernel, MNK_GRID(n + ns + m), dw, dx, ex->reg.p, dc->du_diag.p, dc->d_ind_ineq.p,
-                       ex->ineq_slot.p, alpha, beta, n, ns, m);
-    if (nlb > 0)
-        hipLaunchKernelGGL(kktmul_bound_kernel, MNK_GRID(nlb), dw, dw + n + ns + m, dx, dx + n + ns + m, ex->ind_lb.p,
-                           ex->l_lower.p, ex->l_diag.p, alpha, beta, nlb, 0);
-    if (nub > 0)
-        hipLaunchKernelGGL(kktmul_bound_kernel, MNK_GRID(nub), dw, dw + n + ns + m + nlb, dx, dx + n + ns + m + nlb,
-                           ex->ind_ub.p, ex->u_lower.p, ex->u_diag.p, alpha, beta, nub, 1);
-    MNK_HIP(hipGetLastError());
-    if (loc != MNK_DEVICE) {
-        MNK_HIP(mnk::d2h_copy(w, dw, lw * sizeof(double), s));
-    }
-    return 0;
+    const int64_t n = dc->n, ns = dc->ns, m = dc->m;
+    return kkt_mul(ex->st, dc->ctx, "mnk_dc_mul", n + ns + m, w, x, alpha, beta, loc, [&](double* dw, const double* dx) -> int {
+        // wx = alpha Sym(H) xx + beta wx ; wx += alpha jac' dual(x) ; dual(w) = alpha jac xx + beta dual(w)
+        hipLaunchKernelGGL(symv_l_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dw, dc->hess.p, n, dx, alpha, beta);
+        if (m > 0) {
+            hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dw, dc->jac.p, m, dx + n + ns, m, n,
+                               alpha, 1.0);
+            hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)((m + 63) / 64)), dim3(256), 0, s, dw + n + ns, dc->jac.p, m, dx, m,
+                               n, alpha, beta);
+        }
+        hipLaunchKernelGGL(dc_kktmul_diag_kernel, MNK_GRID(n + ns + m), dw, dx, ex->st.reg.p, dc->du_diag.p, dc->d_ind_ineq.p,
+                           ex->ineq_slot.p, alpha, beta, n, ns, m);
+        return 0;
+    });
 }
 #undef MNK_GRID
 

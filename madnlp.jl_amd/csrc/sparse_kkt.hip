@@ -165,21 +165,15 @@ static std::vector<int32_t> col_index(const std::vector<int32_t>& colptr) {
 
 using namespace mnk;
 
-// extra device structures for spmv (kept out of ls.h: only this unit uses them)
-struct mnk_sc_spmv_data {
+// the handle's device structures that only this unit uses (kept out of ls.h)
+struct mnk_sc_extra {
     DevBuf<int32_t> jtr_ptr, jtr_idx, jtr_perm;   // CSR of Jt (rows = variables)
     DevBuf<int32_t> hs_ptr, hs_idx, hs_perm;      // rows of Symmetric(hess_com, :L)
-    // device-side solve_kkt! / mul!: bound structure, barrier terms, work vectors
-    int64_t nlb = 0, nub = 0;
-    DevBuf<int64_t> ind_lb, ind_ub;               // positions in the primal block [0, n+m)
-    DevBuf<double> reg, l_diag, u_diag, l_lower, u_lower;
-    DevBuf<double> buffer, buffer2, wdev, xdev;   // m, m, len(w), len(w)
-    DevBuf<double> feed;                          // staging of host iterates for mnk_sc_set_aug_diagonal
-    bool have_bounds = false, have_terms = false, have_diag = false;
-    DevBuf<double> saved_diag;                    // reg | pr_diag | du_diag of mnk_sc_save_diagonals
-    bool have_saved_diag = false;
+    KktVecState st;                               // bound structure, barrier terms, work vectors (kkt_vec.h)
+    DevBuf<double> buffer, buffer2;               // m, m: device-side solve_kkt!
 };
-static mnk_sc_spmv_data* spmv_of(mnk_sc* sc) { return static_cast<mnk_sc_spmv_data*>(sc->extra); }
+static mnk_sc_extra* extra_of(mnk_sc* sc) { return static_cast<mnk_sc_extra*>(sc->extra); }
+static const char* const SC_NULL = "NULL argument or host-only handle";
 
 extern "C" {
 
@@ -301,7 +295,7 @@ int mnk_sc_create(mnk_ctx* ctx, int64_t n, int64_t m, int64_t nnzj, const int32_
     rc |= sc->diag_buffer.alloc(m); rc |= sc->pr_diag.alloc(n + m); rc |= sc->du_diag.alloc(m);
 
     // spmv structures: CSR of Jt and the row lists of Symmetric(hess_com, :L)
-    mnk_sc_spmv_data* sp = new mnk_sc_spmv_data();
+    mnk_sc_extra* sp = new mnk_sc_extra();
     {
         std::vector<int32_t> rp(n + 1, 0), ri(sc->nnz_jt), rperm(sc->nnz_jt);
         for (int32_t r : jt.rowval) rp[r + 1]++;
@@ -347,7 +341,7 @@ int mnk_sc_destroy(mnk_sc* sc) {
         (void)hipSetDevice(sc->ctx->device);
         (void)mnk::stream_wait(sc->ctx->stream);
     }
-    delete spmv_of(sc);
+    delete extra_of(sc);
     sc->extra = nullptr;
     mnk_ctx* ctx = sc->ctx;
     delete sc;
@@ -442,8 +436,7 @@ int mnk_sc_build(mnk_sc* sc, const double* pr_diag, const double* du_diag, int l
     hipStream_t s = sc->ctx->stream;
     if (pr_diag == nullptr && du_diag == nullptr) {
         // the diagonals the handle keeps itself (mnk_sc_set_aug_diagonal / mnk_sc_regularize_diagonal)
-        mnk_sc_spmv_data* sp0 = spmv_of(sc);
-        MNK_REQUIRE(sp0 != nullptr && sp0->have_diag, "mnk_sc_build: no diagonals given and mnk_sc_set_aug_diagonal was not called");
+        MNK_REQUIRE(extra_of(sc)->st.have_diag, "mnk_sc_build: no diagonals given and mnk_sc_set_aug_diagonal was not called");
         pr_diag = sc->pr_diag.p;
         du_diag = sc->du_diag.p;
         loc = MNK_DEVICE;
@@ -484,7 +477,7 @@ int mnk_sc_get_values(mnk_sc* sc, int which, double* out, int loc) {
 int mnk_sc_spmv(mnk_sc* sc, int which, int trans, double alpha, const double* x, double beta, double* y) {
     MNK_REQUIRE(sc && sc->ctx && x && y, "mnk_sc_spmv: NULL argument or host-only handle");
     MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
+    mnk_sc_extra* sp = extra_of(sc);
     MNK_REQUIRE(sp != nullptr, "mnk_sc_spmv: unknown handle");
     hipStream_t s = sc->ctx->stream;
     if (which == MNK_SC_JT && trans == 0) {
@@ -506,88 +499,37 @@ int mnk_sc_spmv(mnk_sc* sc, int which, int trans, double alpha, const double* x,
     return 0;
 }
 
-// ---- device-side solve_kkt! / mul! ------------------------------------------------------------------
+// ---- device-side solve_kkt! / mul!: the bound / barrier state and the frames are kkt_vec.h's, the matrix part is below ----
 int mnk_sc_set_bounds(mnk_sc* sc, int64_t nlb, const int64_t* ind_lb, int64_t nub, const int64_t* ind_ub, int index_base) {
-    MNK_REQUIRE(sc && sc->ctx && nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub),
-                "mnk_sc_set_bounds: bad argument or host-only handle");
-    MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp != nullptr, "mnk_sc_set_bounds: unknown handle");
-    const int64_t np = sc->n + sc->m;
-    std::vector<int64_t> lb(nlb), ub(nub);
-    for (int64_t i = 0; i < nlb; ++i) {
-        lb[i] = ind_lb[i] - index_base;
-        MNK_REQUIRE(lb[i] >= 0 && lb[i] < np, "mnk_sc_set_bounds: lower-bound index out of range");
-    }
-    for (int64_t i = 0; i < nub; ++i) {
-        ub[i] = ind_ub[i] - index_base;
-        MNK_REQUIRE(ub[i] >= 0 && ub[i] < np, "mnk_sc_set_bounds: upper-bound index out of range");
-    }
-    hipStream_t s = sc->ctx->stream;
-    int rc = sp->ind_lb.upload(lb, s);
-    rc |= sp->ind_ub.upload(ub, s);
-    rc |= sp->reg.alloc(np);
-    rc |= sp->l_diag.alloc(nlb);
-    rc |= sp->l_lower.alloc(nlb);
-    rc |= sp->u_diag.alloc(nub);
-    rc |= sp->u_lower.alloc(nub);
-    rc |= sp->buffer.alloc(sc->m);
-    rc |= sp->buffer2.alloc(sc->m);
-    const size_t lw = (size_t)(sc->n + 2 * sc->m + nlb + nub);
-    rc |= sp->wdev.alloc(lw);
-    rc |= sp->xdev.alloc(lw);
+    int rc = kkt_enter(sc, nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub), "mnk_sc_set_bounds",
+                       "bad argument or host-only handle");
     if (rc) return rc;
-    sp->nlb = nlb;
-    sp->nub = nub;
-    sp->have_bounds = true;
-    return 0;
-}
-
-static int copy_in(mnk_ctx* ctx, double* dst, const double* src, int64_t n, int loc) {
-    if (n <= 0) return 0;
-    MNK_REQUIRE(src != nullptr, "NULL vector");
-    if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    else MNK_HIP(mnk::h2d_copy(dst, src, n * sizeof(double), ctx->stream));
-    return 0;
+    mnk_sc_extra* sp = extra_of(sc);
+    rc = sp->buffer.alloc(sc->m) | sp->buffer2.alloc(sc->m);
+    if (rc) return rc;
+    return kkt_set_bounds(sp->st, sc->ctx, "mnk_sc_set_bounds", sc->n + sc->m, sc->n + 2 * sc->m, nlb, ind_lb, nub, ind_ub,
+                          index_base);
 }
 
 int mnk_sc_set_barrier_terms(mnk_sc* sc, const double* reg, const double* l_diag, const double* u_diag,
                              const double* l_lower, const double* u_lower, int loc) {
-    MNK_REQUIRE(sc && sc->ctx, "mnk_sc_set_barrier_terms: NULL argument or host-only handle");
-    MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp != nullptr && sp->have_bounds, "mnk_sc_set_barrier_terms: call mnk_sc_set_bounds first");
-    int rc = copy_in(sc->ctx, sp->reg.p, reg, sc->n + sc->m, loc);
-    rc |= copy_in(sc->ctx, sp->l_diag.p, l_diag, sp->nlb, loc);
-    rc |= copy_in(sc->ctx, sp->u_diag.p, u_diag, sp->nub, loc);
-    rc |= copy_in(sc->ctx, sp->l_lower.p, l_lower, sp->nlb, loc);
-    rc |= copy_in(sc->ctx, sp->u_lower.p, u_lower, sp->nub, loc);
+    int rc = kkt_enter(sc, true, "mnk_sc_set_barrier_terms", SC_NULL);
     if (rc) return rc;
-    if (loc != MNK_DEVICE) MNK_HIP(mnk::stream_wait(sc->ctx->stream));  // the host arrays may change after return
-    sp->have_terms = true;
-    return 0;
+    return kkt_set_barrier_terms(extra_of(sc)->st, sc->ctx, "mnk_sc_set_barrier_terms", sc->n + sc->m, reg, l_diag, u_diag,
+                                 l_lower, u_lower, loc);
 }
 
 static int sc_diag_view(mnk_sc* sc, AugDiagView& v, const char* who) {
-    if (!(sc && sc->ctx)) { set_error("%s: NULL argument or host-only handle", who); return -1; }
-    MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    if (!(sp != nullptr && sp->have_bounds)) { set_error("%s: call mnk_sc_set_bounds first", who); return -1; }
-    v = AugDiagView{sc->ctx, sc->n + sc->m, sc->m, sp->nlb, sp->nub, sp->reg.p, sc->pr_diag.p, sc->du_diag.p, sp->l_diag.p,
-                    sp->u_diag.p, sp->l_lower.p, sp->u_lower.p, sp->ind_lb.p, sp->ind_ub.p, &sp->feed};
-    return 0;
+    int rc = kkt_enter(sc, true, who, SC_NULL);
+    if (rc) return rc;
+    return kkt_diag_view(v, extra_of(sc)->st, sc->ctx, who, sc->n + sc->m, sc->m, sc->pr_diag.p, sc->du_diag.p);
 }
 
 int mnk_sc_set_aug_diagonal(mnk_sc* sc, const double* x, const double* xl, const double* xu, const double* zl,
                             const double* zu, double primal_reg, double dual_reg, int loc) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_set_aug_diagonal");
-    if (rc) return rc;
-    MNK_REQUIRE(x && xl && xu && zl && zu, "mnk_sc_set_aug_diagonal: NULL vector");
-    rc = kkt_set_aug_diagonal(v, x, xl, xu, zl, zu, primal_reg, dual_reg, loc);
-    if (rc) return rc;
-    spmv_of(sc)->have_terms = spmv_of(sc)->have_diag = true;
-    return 0;
+    return rc ? rc : kkt_set_aug_diagonal(v, "mnk_sc_set_aug_diagonal", x, xl, xu, zl, zu, primal_reg, dual_reg, loc);
 }
 
 // set_aug_RR!(kkt, solver, RR) (reference src/IPM/kernels.jl:72-87): device-resident vectors only
@@ -596,92 +538,47 @@ int mnk_sc_set_aug_RR(mnk_sc* sc, const double* x, const double* xl, const doubl
                       double primal_reg, double dual_reg) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_set_aug_RR");
-    if (rc) return rc;
-    MNK_REQUIRE(x && xl && xu && zl && zu && D_R && (v.ndu == 0 || (pp && zp && nn && zn)), "mnk_sc_set_aug_RR: NULL vector");
-    rc = kkt_set_aug_RR(v, x, xl, xu, zl, zu, D_R, pp, zp, nn, zn, zeta, primal_reg, dual_reg);
-    if (rc) return rc;
-    spmv_of(sc)->have_terms = spmv_of(sc)->have_diag = true;
-    return 0;
+    return rc ? rc : kkt_set_aug_RR(v, "mnk_sc_set_aug_RR", x, xl, xu, zl, zu, D_R, pp, zp, nn, zn, zeta, primal_reg, dual_reg);
 }
 
 int mnk_sc_regularize_diagonal(mnk_sc* sc, double primal, double dual) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_regularize_diagonal");
-    if (rc) return rc;
-    MNK_REQUIRE(spmv_of(sc)->have_diag, "mnk_sc_regularize_diagonal: call mnk_sc_set_aug_diagonal first");
-    return kkt_regularize_diagonal(v, primal, dual);
+    return rc ? rc : kkt_regularize_diagonal(v, "mnk_sc_regularize_diagonal", primal, dual);
 }
 
-// reg, pr_diag and du_diag as they are, into a buffer of the handle / back from it (device copies on the handle's stream): the
-// bracket of a SPECULATIVE trial of inertia_correction! (madnlp_jl_amd.ipm_dev: the trial with the next perturbation is factorized
-// together with the unperturbed one; when the unperturbed matrix is accepted after all, the diagonals return to the bits they had
-// -- pr_diag + dw - dw would not)
+// the bracket of a SPECULATIVE trial of inertia_correction!: kkt_save_diagonals / kkt_restore_diagonals (kkt_vec.h)
 int mnk_sc_save_diagonals(mnk_sc* sc) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_save_diagonals");
-    if (rc) return rc;
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp->have_diag, "mnk_sc_save_diagonals: call mnk_sc_set_aug_diagonal first");
-    const size_t npr = (size_t)v.npr, ndu = (size_t)v.ndu;
-    if (sp->saved_diag.n < 2 * npr + ndu && sp->saved_diag.alloc(2 * npr + ndu)) {
-        const std::string why = mnk_last_error_string();   // (the allocation's own message: which hipMalloc failed and why)
-        set_error("mnk_sc_save_diagonals: no device memory for the saved diagonals: %s", why.c_str());
-        return -1;
-    }
-    hipStream_t s = sc->ctx->stream;
-    MNK_HIP(hipMemcpyAsync(sp->saved_diag.p, v.reg, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
-    MNK_HIP(hipMemcpyAsync(sp->saved_diag.p + npr, v.pr_diag, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (ndu > 0) MNK_HIP(hipMemcpyAsync(sp->saved_diag.p + 2 * npr, v.du_diag, ndu * sizeof(double), hipMemcpyDeviceToDevice, s));
-    sp->have_saved_diag = true;
-    return 0;
+    return rc ? rc : kkt_save_diagonals(v, "mnk_sc_save_diagonals");
 }
 
 int mnk_sc_restore_diagonals(mnk_sc* sc) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_restore_diagonals");
-    if (rc) return rc;
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp->have_saved_diag, "mnk_sc_restore_diagonals: nothing saved (mnk_sc_save_diagonals)");
-    const size_t npr = (size_t)v.npr, ndu = (size_t)v.ndu;
-    hipStream_t s = sc->ctx->stream;
-    MNK_HIP(hipMemcpyAsync(v.reg, sp->saved_diag.p, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
-    MNK_HIP(hipMemcpyAsync(v.pr_diag, sp->saved_diag.p + npr, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (ndu > 0) MNK_HIP(hipMemcpyAsync(v.du_diag, sp->saved_diag.p + 2 * npr, ndu * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return 0;
+    return rc ? rc : kkt_restore_diagonals(v, "mnk_sc_restore_diagonals");
 }
 
 int mnk_sc_get_diagonals(mnk_sc* sc, double* pr_diag, double* du_diag, double* reg, double* l_diag, double* u_diag,
                          double* l_lower, double* u_lower) {
     AugDiagView v;
     int rc = sc_diag_view(sc, v, "mnk_sc_get_diagonals");
-    if (rc) return rc;
-    return kkt_get_diagonals(v, pr_diag, du_diag, reg, l_diag, u_diag, l_lower, u_lower);
+    return rc ? rc : kkt_get_diagonals(v, pr_diag, du_diag, reg, l_diag, u_diag, l_lower, u_lower);
 }
 
 #define MNK_GRID(cnt) dim3((unsigned)(((cnt) + 255) / 256)), dim3(256), 0, s
 
 int mnk_sc_solve_kkt(mnk_sc* sc, mnk_ls* ls, double* w, int loc) {
-    MNK_REQUIRE(sc && sc->ctx && ls && w, "mnk_sc_solve_kkt: NULL argument or host-only handle");
+    int rc = kkt_enter(sc, ls && w, "mnk_sc_solve_kkt", SC_NULL);
+    if (rc) return rc;
     MNK_REQUIRE(ls->ctx == sc->ctx && ls->N == sc->n, "mnk_sc_solve_kkt: the solver does not belong to this system");
-    MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp != nullptr && sp->have_bounds && sp->have_terms,
-                "mnk_sc_solve_kkt: call mnk_sc_set_bounds / mnk_sc_set_barrier_terms / mnk_sc_build first");
+    mnk_sc_extra* sp = extra_of(sc);
     hipStream_t s = sc->ctx->stream;
-    const int64_t n = sc->n, m = sc->m, nlb = sp->nlb, nub = sp->nub, lw = n + 2 * m + nlb + nub;
-    // Host-resident caller: the host still owns `w` until the final copy-back, so a persistent solve that gave
-    // up (abort word raised, solve.hip) is detected HERE, after the stream synchronization and before anything
-    // is copied back, and the whole solve_kkt! is redone once with the stepwise solve.
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        double* d = w;
-        if (loc != MNK_DEVICE) {
-            d = sp->wdev.p;
-            MNK_HIP(mnk::h2d_copy(d, w, lw * sizeof(double), s));
-        }
-        double *ws = d + n, *wz = d + n + m, *wl = d + n + 2 * m, *wu = wl + nlb;
+    const int64_t n = sc->n, m = sc->m;
+    return kkt_solve_kkt(sp->st, sc->ctx, "mnk_sc_solve_kkt", ls, n + 2 * m, w, loc, [&](double* d) -> int {
+        double *ws = d + n, *wz = d + n + m;
         const double* Ss = sc->pr_diag.p + n;
-        if (nlb > 0) hipLaunchKernelGGL(reduce_rhs_kernel, MNK_GRID(nlb), d, sp->ind_lb.p, wl, sp->l_diag.p, nlb);
-        if (nub > 0) hipLaunchKernelGGL(reduce_rhs_kernel, MNK_GRID(nub), d, sp->ind_ub.p, wu, sp->u_diag.p, nub);
         if (m > 0) {
             hipLaunchKernelGGL(condense_rhs_kernel, MNK_GRID(m), sp->buffer.p, sc->diag_buffer.p, ws, wz, Ss, m);
             int rc = mnk_sc_spmv(sc, MNK_SC_JT, 0, 1.0, sp->buffer.p, 1.0, d);  // wx += Jt * buffer
@@ -694,55 +591,29 @@ int mnk_sc_solve_kkt(mnk_sc* sc, mnk_ls* ls, double* w, int loc) {
             if (rc) return rc;
             hipLaunchKernelGGL(expand_sol_kernel, MNK_GRID(m), ws, wz, sp->buffer.p, sp->buffer2.p, sc->diag_buffer.p, Ss, m);
         }
-        if (nlb > 0) hipLaunchKernelGGL(finish_aug_kernel, MNK_GRID(nlb), wl, d, sp->ind_lb.p, sp->l_lower.p, sp->l_diag.p, nlb, 0);
-        if (nub > 0) hipLaunchKernelGGL(finish_aug_kernel, MNK_GRID(nub), wu, d, sp->ind_ub.p, sp->u_lower.p, sp->u_diag.p, nub, 1);
-        MNK_HIP(hipGetLastError());
-        if (loc == MNK_DEVICE) break;  // device-resident caller: mnk_ls_check_solve() reports an abort
-        MNK_HIP(mnk::stream_wait(s));
-        if (attempt == 0 && mnk_ls_take_solve_abort(ls)) continue;  // redo with the stepwise solve
-        MNK_HIP(mnk::d2h_copy(w, d, lw * sizeof(double), s));
-        break;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 int mnk_sc_mul(mnk_sc* sc, double* w, const double* x, double alpha, double beta, int loc) {
-    MNK_REQUIRE(sc && sc->ctx && w && x, "mnk_sc_mul: NULL argument or host-only handle");
-    MNK_HIP(hipSetDevice(sc->ctx->device));
-    mnk_sc_spmv_data* sp = spmv_of(sc);
-    MNK_REQUIRE(sp != nullptr && sp->have_bounds && sp->have_terms,
-                "mnk_sc_mul: call mnk_sc_set_bounds / mnk_sc_set_barrier_terms first");
-    hipStream_t s = sc->ctx->stream;
-    const int64_t n = sc->n, m = sc->m, nlb = sp->nlb, nub = sp->nub, lw = n + 2 * m + nlb + nub;
-    double* dw = w;
-    const double* dx = x;
-    if (loc != MNK_DEVICE) {
-        dw = sp->wdev.p;
-        MNK_HIP(mnk::h2d_copy(sp->wdev.p, w, lw * sizeof(double), s));
-        MNK_HIP(mnk::h2d_copy(sp->xdev.p, x, lw * sizeof(double), s));
-        dx = sp->xdev.p;
-    }
-    // wx = alpha Sym(H) xx + beta wx ; wx += alpha Jt xz ; wz = alpha Jt' xx + beta wz
-    int rc = mnk_sc_spmv(sc, MNK_SC_HESS, 0, alpha, dx, beta, dw);
+    int rc = kkt_enter(sc, w && x, "mnk_sc_mul", SC_NULL);
     if (rc) return rc;
-    if (m > 0) {
-        rc = mnk_sc_spmv(sc, MNK_SC_JT, 0, alpha, dx + n + m, 1.0, dw);
+    mnk_sc_extra* sp = extra_of(sc);
+    hipStream_t s = sc->ctx->stream;
+    const int64_t n = sc->n, m = sc->m;
+    return kkt_mul(sp->st, sc->ctx, "mnk_sc_mul", n + 2 * m, w, x, alpha, beta, loc, [&](double* dw, const double* dx) -> int {
+        // wx = alpha Sym(H) xx + beta wx ; wx += alpha Jt xz ; wz = alpha Jt' xx + beta wz
+        int rc = mnk_sc_spmv(sc, MNK_SC_HESS, 0, alpha, dx, beta, dw);
         if (rc) return rc;
-        rc = mnk_sc_spmv(sc, MNK_SC_JT, 1, alpha, dx, beta, dw + n + m);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kktmul_diag_kernel, MNK_GRID(n + 2 * m), dw, dx, sp->reg.p, sc->du_diag.p, alpha, beta, n, m);
-    if (nlb > 0)
-        hipLaunchKernelGGL(kktmul_bound_kernel, MNK_GRID(nlb), dw, dw + n + 2 * m, dx, dx + n + 2 * m, sp->ind_lb.p,
-                           sp->l_lower.p, sp->l_diag.p, alpha, beta, nlb, 0);
-    if (nub > 0)
-        hipLaunchKernelGGL(kktmul_bound_kernel, MNK_GRID(nub), dw, dw + n + 2 * m + nlb, dx, dx + n + 2 * m + nlb,
-                           sp->ind_ub.p, sp->u_lower.p, sp->u_diag.p, alpha, beta, nub, 1);
-    MNK_HIP(hipGetLastError());
-    if (loc != MNK_DEVICE) {
-        MNK_HIP(mnk::d2h_copy(w, dw, lw * sizeof(double), s));
-    }
-    return 0;
+        if (m > 0) {
+            rc = mnk_sc_spmv(sc, MNK_SC_JT, 0, alpha, dx + n + m, 1.0, dw);
+            if (rc) return rc;
+            rc = mnk_sc_spmv(sc, MNK_SC_JT, 1, alpha, dx, beta, dw + n + m);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(kktmul_diag_kernel, MNK_GRID(n + 2 * m), dw, dx, sp->st.reg.p, sc->du_diag.p, alpha, beta, n, m);
+        return 0;
+    });
 }
 #undef MNK_GRID
 

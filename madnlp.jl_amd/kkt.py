@@ -84,16 +84,47 @@ class _KKTCommon:
         self.pr_diag[self.ind_lb] -= self.l_lower / self.l_diag
         self.pr_diag[self.ind_ub] -= self.u_lower / self.u_diag
 
-    # ---- device-side feeders (SURVEY 8(a)11 on the device; `_PFX` = "mnk_sc" / "mnk_dc")
+    # ---- the handle's bound / barrier state and device-side solve_kkt! / mul! (`_PFX` = "mnk_sc" / "mnk_dc")
+    def _call(self, name, *args):
+        L.check(getattr(L.lib(), self._PFX + name)(self._h, *args), self._PFX + name)
+
+    def _set_bounds(self):
+        """Upload the bound structure (`ind_lb`, `ind_ub`, 0-based) once."""
+        self._call("_set_bounds", len(self.ind_lb), self.ind_lb.ctypes.data, len(self.ind_ub), self.ind_ub.ctypes.data, 0)
+
+    def upload_barrier_terms(self):
+        """reg, l_diag, u_diag, l_lower, u_lower of the current iterate -> device (for the device-side
+        `solve_kkt!` / `mul!`)."""
+        self._call("_set_barrier_terms", self.reg.ctypes.data, self.l_diag.ctypes.data, self.u_diag.ctypes.data,
+                   self.l_lower.ctypes.data, self.u_lower.ctypes.data, L.MNK_HOST)
+
+    def solve_kkt_device(self, w):
+        """`solve_kkt!` on the device (reference `src/IPM/factorization.jl:143-167` sparse condensed, `:190-229` dense
+        condensed, `:41-46` dense); `w` is an UnreducedKKTVector (host values) or a device tensor holding its values."""
+        p, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
+        rc = getattr(L.lib(), self._PFX + "_solve_kkt")(self._h, self.linear_solver._h, p, loc)
+        if rc:
+            from .linear_solver import SolveException
+            raise SolveException(L.lib().mnk_last_error_string().decode())
+        return w
+
+    def mul_device(self, w, x, alpha=1.0, beta=0.0):
+        """`mul!(w, kkt, x, alpha, beta)` on the device (reference `src/IPM/factorization.jl:289-308` sparse condensed,
+        `:310-330` dense)."""
+        pw, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
+        px, loc2 = _ptr(x.values if isinstance(x, UnreducedKKTVector) else x)
+        assert loc == loc2
+        self._call("_mul", pw, px, float(alpha), float(beta), loc)
+        return w
+
+    # ---- device-side feeders (SURVEY 8(a)11 on the device)
     def set_aug_diagonal_device(self, x, xl, xu, zl, zu, primal_reg=0.0, dual_reg=0.0):
         """`set_aug_diagonal!(kkt, solver)` (reference `src/IPM/kernels.jl:4-27`) inside the handle: `x, xl, xu, zl, zu`
         are the full primal-length vectors of the iterate (host arrays or device tensors); reg, du_diag, l_diag,
         u_diag, l_lower, u_lower and pr_diag are computed and kept on the device (no host vector involved)."""
         ptrs = [_ptr(v) for v in (x, xl, xu, zl, zu)]
         assert len({loc for _, loc in ptrs}) == 1, "all five vectors must live on the same side"
-        fn = getattr(L.lib(), self._PFX + "_set_aug_diagonal")
-        L.check(fn(self._h, *[p for p, _ in ptrs], float(primal_reg), float(dual_reg), ptrs[0][1]),
-                self._PFX + "_set_aug_diagonal")
+        self._call("_set_aug_diagonal", *[p for p, _ in ptrs], float(primal_reg), float(dual_reg), ptrs[0][1])
 
     def set_aug_RR_device(self, x, xl, xu, zl, zu, D_R, pp, zp, nn, zn, zeta, primal_reg, dual_reg):
         """`set_aug_RR!(kkt, solver, RR)` (reference `src/IPM/kernels.jl:72-87`) inside the handle, from device tensors:
@@ -101,19 +132,16 @@ class _KKTCommon:
         `set_aug_diagonal!`."""
         ptrs = [_ptr(v) for v in (x, xl, xu, zl, zu, D_R, pp, zp, nn, zn)]
         assert all(loc == L.MNK_DEVICE for _, loc in ptrs), "set_aug_RR_device takes device tensors"
-        fn = getattr(L.lib(), self._PFX + "_set_aug_RR")
-        L.check(fn(self._h, *[p for p, _ in ptrs], float(zeta), float(primal_reg), float(dual_reg)), self._PFX + "_set_aug_RR")
+        self._call("_set_aug_RR", *[p for p, _ in ptrs], float(zeta), float(primal_reg), float(dual_reg))
 
     def regularize_diagonal_device(self, primal, dual):
         """`regularize_diagonal!(kkt, primal, dual)` (reference `src/KKT/KKTsystem.jl:222-226`) on the handle's own
         reg / pr_diag / du_diag."""
-        fn = getattr(L.lib(), self._PFX + "_regularize_diagonal")
-        L.check(fn(self._h, float(primal), float(dual)), self._PFX + "_regularize_diagonal")
+        self._call("_regularize_diagonal", float(primal), float(dual))
 
     def build_kkt_device(self):
         """`build_kkt!` from the diagonals the handle keeps itself (after `set_aug_diagonal_device`)."""
-        fn = getattr(L.lib(), self._PFX + "_build")
-        L.check(fn(self._h, None, None, L.MNK_DEVICE), self._PFX + "_build")
+        self._call("_build", None, None, L.MNK_DEVICE)
         self._diag_buffer = None
 
     def get_diagonals_device(self):
@@ -121,9 +149,8 @@ class _KKTCommon:
         out = {"pr_diag": np.zeros_like(self.pr_diag), "du_diag": np.zeros_like(self.du_diag),
                "reg": np.zeros_like(self.reg), "l_diag": np.zeros_like(self.l_diag), "u_diag": np.zeros_like(self.u_diag),
                "l_lower": np.zeros_like(self.l_lower), "u_lower": np.zeros_like(self.u_lower)}
-        fn = getattr(L.lib(), self._PFX + "_get_diagonals")
-        L.check(fn(self._h, *[out[k].ctypes.data for k in ("pr_diag", "du_diag", "reg", "l_diag", "u_diag", "l_lower",
-                                                            "u_lower")]), self._PFX + "_get_diagonals")
+        self._call("_get_diagonals", *[out[k].ctypes.data for k in ("pr_diag", "du_diag", "reg", "l_diag", "u_diag", "l_lower",
+                                                                      "u_lower")])
         return out
 
     def factorize_kkt(self):
@@ -232,8 +259,7 @@ class SparseCondensedKKTSystem(_KKTCommon):
             # definite or not" is ever read from the inertia of this system: the factorization of a matrix that is not may stop
             # at its first non-positive pivot (as dpotrf does) instead of running to the end (as dsytrf does)
             self.linear_solver.set_option("early_reject", 1 if early_reject else 0)
-        L.check(lib.mnk_sc_set_bounds(self._h, nlb, self.ind_lb.ctypes.data, nub, self.ind_ub.ctypes.data, 0),
-                "mnk_sc_set_bounds")
+        self._set_bounds()
         self._spare_args = (linear_solver, opt_linear_solver, early_reject)
         self.spare_solver = None
         _LIVE_OBJECTS.add(self)
@@ -359,31 +385,6 @@ class SparseCondensedKKTSystem(_KKTCommon):
         if self.device_kkt_ops:
             self.upload_barrier_terms()
 
-    def upload_barrier_terms(self):
-        """reg, l_diag, u_diag, l_lower, u_lower of the current iterate -> device (for the device-side
-        `solve_kkt!` / `mul!`)."""
-        L.check(L.lib().mnk_sc_set_barrier_terms(self._h, self.reg.ctypes.data, self.l_diag.ctypes.data,
-                                                 self.u_diag.ctypes.data, self.l_lower.ctypes.data,
-                                                 self.u_lower.ctypes.data, L.MNK_HOST), "mnk_sc_set_barrier_terms")
-
-    def solve_kkt_device(self, w):
-        """`solve_kkt!` on the device (reference `src/IPM/factorization.jl:143-167`); `w` is an
-        UnreducedKKTVector (host values) or a device tensor holding its values."""
-        p, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
-        rc = L.lib().mnk_sc_solve_kkt(self._h, self.linear_solver._h, p, loc)
-        if rc:
-            from .linear_solver import SolveException
-            raise SolveException(L.lib().mnk_last_error_string().decode())
-        return w
-
-    def mul_device(self, w, x, alpha=1.0, beta=0.0):
-        """`mul!(w, kkt, x, alpha, beta)` on the device (reference `src/IPM/factorization.jl:289-308`)."""
-        pw, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
-        px, loc2 = _ptr(x.values if isinstance(x, UnreducedKKTVector) else x)
-        assert loc == loc2
-        L.check(L.lib().mnk_sc_mul(self._h, pw, px, float(alpha), float(beta), loc), "mnk_sc_mul")
-        return w
-
     def spmv_device(self, which, trans, alpha, x, beta, y):
         """y = alpha op(A) x + beta y on device vectors with A = jt_csc (`MNK_SC_JT`; trans 0: n <- m, 1: m <- n) or
         Symmetric(hess_com, :L) (`MNK_SC_HESS`), the compressed values the handle holds (`mnk_sc_spmv`)."""
@@ -495,28 +496,7 @@ class _DenseBase(_KKTCommon):
         """Upload the bound structure once; with `device_kkt_ops` `solve_kkt!` / `mul!` run on the device
         (`mnk_dc_solve_kkt`, `mnk_dc_mul`)."""
         self.device_kkt_ops = bool(device_kkt_ops)
-        L.check(L.lib().mnk_dc_set_bounds(self._h, len(self.ind_lb), self.ind_lb.ctypes.data, len(self.ind_ub),
-                                          self.ind_ub.ctypes.data, 0), "mnk_dc_set_bounds")
-
-    def upload_barrier_terms(self):
-        L.check(L.lib().mnk_dc_set_barrier_terms(self._h, self.reg.ctypes.data, self.l_diag.ctypes.data,
-                                                 self.u_diag.ctypes.data, self.l_lower.ctypes.data,
-                                                 self.u_lower.ctypes.data, L.MNK_HOST), "mnk_dc_set_barrier_terms")
-
-    def solve_kkt_device(self, w):
-        p, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
-        rc = L.lib().mnk_dc_solve_kkt(self._h, self.linear_solver._h, p, loc)
-        if rc:
-            from .linear_solver import SolveException
-            raise SolveException(L.lib().mnk_last_error_string().decode())
-        return w
-
-    def mul_device(self, w, x, alpha=1.0, beta=0.0):
-        pw, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
-        px, loc2 = _ptr(x.values if isinstance(x, UnreducedKKTVector) else x)
-        assert loc == loc2
-        L.check(L.lib().mnk_dc_mul(self._h, pw, px, float(alpha), float(beta), loc), "mnk_dc_mul")
-        return w
+        self._set_bounds()
 
     def _upload(self):
         lib = L.lib()

@@ -3,6 +3,7 @@
   python tools/ipm_trajectory_dump.py --out A.json                       host driver (MadNLPSolver) on the CPU oracle back-end
   python tools/ipm_trajectory_dump.py --device --out A.json              DeviceMadNLPSolver on the HIP KKT systems (needs a GPU)
   python tools/ipm_trajectory_dump.py --device --time 3 --out T.json     wall clock of the two runs bench.py's `ipm_loop` times
+  python tools/ipm_trajectory_dump.py --device --handles --out H.json    the KKT handles' own entry points, host and device vectors
   python tools/ipm_trajectory_dump.py --compare A.json B.json            identical, or per field the largest relative difference
   ... --package DIR                                                      take the package from DIR (a copy of another commit's
                                                                          `madnlp.jl_amd/`; with MNK_LIBPATH the same built library)
@@ -329,6 +330,84 @@ def time_device(args, mj):
     ctx.close()
 
 
+# ------------------------------------------------------------------------------------------------ device: the KKT handles alone
+def handle_cases(mj, ctx):
+    """(name, system) on a 3-variable, 2-constraint problem: sparse condensed (two inequalities), dense augmented and dense
+    condensed (one equality, one inequality); variable 2 carries both bounds; one bound side empty; dense without constraints."""
+    n, hess, jac = 3, np.array([[4.0, 0, 0], [1.0, 3.0, 0], [0.5, -1.0, 5.0]]), np.array([[1.0, 2.0, -1.0], [0.5, -1.0, 3.0]])
+    for kind in ("sparse_condensed", "dense", "dense_condensed"):
+        for variant in ("both", "nlb0", "nub0") + (() if kind == "sparse_condensed" else ("m0",)):
+            m = 0 if variant == "m0" else 2
+            ineq, eq = (np.arange(m), []) if kind == "sparse_condensed" else (np.arange(1, m), np.arange(min(m, 1)))
+            npr = n + len(ineq)
+            lb = [] if variant == "nlb0" else [0, 2, npr - 1]
+            ub = [] if variant == "nub0" else [1, 2]
+            if kind == "sparse_condensed":
+                jI, jJ = np.divmod(np.arange(m * n), n)
+                hI, hJ = np.tril_indices(n)
+                k = mj.SparseCondensedKKTSystem(n, m, jI, jJ, hI, hJ, ineq, lb, ub, ctx=ctx,
+                                                opt_linear_solver=mj.HipSolverOptions(lapack_algorithm=mj.CHOLESKY))
+                k.jac[:], k.hess[:] = jac[jI, jJ], hess[hI, hJ]
+                k.compress_jacobian()
+                k.compress_hessian()
+            else:
+                k = (mj.DenseCondensedKKTSystem(n, m, ineq, eq, lb, ub, ctx=ctx) if kind == "dense_condensed" else
+                     mj.DenseKKTSystem(n, m, ineq, lb, ub, ctx=ctx))
+                k.hess[...], k.jac[...] = hess, jac[:m]
+                k._upload()
+            yield f"{kind}-{variant}", k
+
+
+def run_handles(args, mj):
+    """The handles' entry points on their own, which the IPM runs reach with device vectors only: the diagonals after
+    set_aug_diagonal, after regularize_diagonal and (sparse) after save -> regularize -> restore; mul! for three (alpha, beta);
+    solve_kkt! -- each vector once as a host array and once as a device tensor."""
+    import torch
+    assert torch.cuda.is_available(), "--device needs a GPU"
+    ctx = mj.HipContext(0)
+    dev = lambda a: torch.from_numpy(np.array(a)).cuda()  # noqa: E731
+    out = {}
+    for name, k in handle_cases(mj, ctx):
+        rng = np.random.default_rng(3)
+        npr, nlb, nub = len(k.pr_diag), len(k.ind_lb), len(k.ind_ub)
+        lw = npr + len(k.du_diag) + nlb + nub
+        x, xl, xu, zl, zu = rng.uniform(-0.4, 0.4, npr), np.full(npr, -1e300), np.full(npr, 1e300), np.zeros(npr), np.zeros(npr)
+        xl[k.ind_lb], xu[k.ind_ub] = -rng.uniform(0.5, 2.0, nlb), rng.uniform(0.5, 2.0, nub)
+        zl[k.ind_lb], zu[k.ind_ub] = 10.0 ** rng.uniform(-8, 2, nlb), 10.0 ** rng.uniform(-8, 2, nub)
+        rec = {}
+
+        def diagonals(key):
+            rec[key] = {f: hexes(v) for f, v in sorted(k.get_diagonals_device().items())}
+        for where, put in (("host", np.array), ("device", dev)):
+            k.set_aug_diagonal_device(*[put(v) for v in (x, xl, xu, zl, zu)], primal_reg=0.5, dual_reg=1e-8)
+            diagonals(f"set_aug_diagonal-{where}")
+        if hasattr(k, "save_diagonals_device"):
+            k.save_diagonals_device()
+        k.regularize_diagonal_device(1e-4, 1e-8)
+        diagonals("regularize_diagonal")
+        if hasattr(k, "save_diagonals_device"):
+            k.restore_diagonals_device()
+            diagonals("save-regularize-restore")
+        k.build_kkt_device()
+        k.linear_solver.factorize()
+        rec["inertia"] = list(k.linear_solver.inertia())
+        xv, wv, bv = rng.standard_normal(lw), rng.standard_normal(lw), rng.standard_normal(lw)
+        for where, put in (("host", np.array), ("device", dev)):
+            for alpha, beta in ((1.0, 0.0), (-1.0, 1.0), (0.75, -0.5)):
+                w = k.mul_device(put(wv), put(xv), alpha, beta)
+                ctx.synchronize()
+                rec[f"mul-{alpha}-{beta}-{where}"] = hexes(w if where == "host" else w.cpu().numpy())
+            w = k.solve_kkt_device(put(bv))
+            ctx.synchronize()
+            rec[f"solve_kkt-{where}"] = hexes(w if where == "host" else w.cpu().numpy())
+        out[name] = rec
+        print(f"{name}: inertia {rec['inertia']}, host == device: "
+              f"{all(rec[f] == rec[f[:-4] + 'device'] for f in rec if f.endswith('-host'))}", flush=True)
+        k.close()
+    print(f"sha256 {finish(out, args.out, {'cases': sorted(out)})}  {len(out)} handles")
+    ctx.close()
+
+
 # ------------------------------------------------------------------------------------------------ compare two dumps
 def compare(a_path, b_path):
     """Exit status 0: every integer, status, phase and branch / launch count equal.  Prints `identical` when the floats are too,
@@ -376,6 +455,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--package", help="directory to load as madnlp_jl_amd instead of the repository's madnlp.jl_amd/")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--handles", action="store_true", help="with --device: the KKT handles' entry points instead of IPM runs")
     ap.add_argument("--time", type=int, default=0, help="with --device: timed runs per problem (after one warm-up run)")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
     args = ap.parse_args()
@@ -386,6 +466,8 @@ def main():
     mj = load_package(args.package)
     if args.device and args.time:
         time_device(args, mj)
+    elif args.device and args.handles:
+        run_handles(args, mj)
     elif args.device:
         run_device(args, mj)
     else:
