@@ -40,19 +40,17 @@
 
 namespace mnk {
 
-// What a bulk task needs to know about the factorization it belongs to.  One launch may serve SEVERAL independent
-// factorizations of the same order (mnk_factorize_batch_*: the task lists of the instances are merged into one queue, each
-// task carries its instance index), so these live in a per-instance record instead of the kernel's argument block.
 // Diagonal tiles are accumulated in SUBTRACT order (gemm_tile.h: gemm_nt_load_neg_lower): C - t_1 - t_2 ... with the tile in
 // the accumulators from the first chunk on, instead of a sum of products that grows from zero and is subtracted at the end.
 // Both are backward stable; the difference shows on condensed KKT matrices whose pivots are the difference of numbers of
 // size 1e13 that agree to 15 digits (AC-OPF case1354): the pivot chain saw -0.031 where the exact
 // value is +0.0195, the interior-point run needed 10 Richardson steps per solve and left LAPACK's trajectory at iteration 9;
 // with the subtract order it follows it to three digits through all 20 iterations (47 -> 30 back-solves).  Cost: a tile's
-// chunks run one after the other (+0.5 % at N = 11 192, tools/diag_sub_ab.sh).  0 = the old order (A/B builds).
-#ifndef MNK_DAG_DIAG_SUB
-#define MNK_DAG_DIAG_SUB 1
-#endif
+// chunks run one after the other (+0.5 % at N = 11 192 against the old order: profiles/r05_diag_subtract_order_ab.txt).
+
+// What a bulk task needs to know about the factorization it belongs to.  One launch may serve SEVERAL independent
+// factorizations of the same order (mnk_factorize_batch_*: the task lists of the instances are merged into one queue, each
+// task carries its instance index), so these live in a per-instance record instead of the kernel's argument block.
 struct DagInst {
     double* F;
     int64_t ld;
@@ -88,15 +86,12 @@ struct DagArgs {       // (the batch kernel's; a single factorization: DagArgs1 
     int fake_share;             // DIAGNOSTIC (env MNK_DAG_FAKE_SHARE, wrong results): every chunk reads the operand rows of tile rows 0..n-1
 };
 
-#ifndef MNK_DIAG_BULK_DBG
-#define MNK_DIAG_BULK_DBG 0   // DIAGNOSTIC build (tools/stall_hunt.py): every workgroup of dag_bulk_kernel1 records its task and its long waits
-#endif
 constexpr int DAG_BANDACC = 1, DAG_FINAL = 2, DAG_FIRST = 4, DAG_FILL = 8;  // task flags
 
 // Wave 0 waits until min(front[s0..s3]) > c and returns that minimum (clamped to kend): tile columns [c, ret) are final
 // for all four strips.  -1: the factorization failed elsewhere or the wait expired.  Ends with an acquire + barrier.
 template <class IP>
-__device__ __forceinline__ int dag_wait_front(IP a, long spin_limit, int s0, int s1, int s2, int s3, int c, int kend, int* s_val, int* d8 = nullptr) {
+__device__ __forceinline__ int dag_wait_front(IP a, long spin_limit, int s0, int s1, int s2, int s3, int c, int kend, int* s_val) {
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
         const int idx = lane == 0 ? s0 : (lane == 1 ? s1 : (lane == 2 ? s2 : s3));
@@ -104,25 +99,13 @@ __device__ __forceinline__ int dag_wait_front(IP a, long spin_limit, int s0, int
         int r;
         for (;;) {
             int f = lane < 4 ? __hip_atomic_load(a->front + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : INT_MAX;
-#if MNK_DIAG_BULK_DBG
-            const int f_raw = f;
-#endif
             f = min(f, __shfl_xor(f, 1));
             f = min(f, __shfl_xor(f, 2));
             r = __builtin_amdgcn_readfirstlane(f);
             if (r > c) break;
             __builtin_amdgcn_s_sleep(4);
             if ((++spins & 255) == 0) {
-#if MNK_DIAG_BULK_DBG
-                if (d8 != nullptr && (spins & 0x3ffff) == 0) {
-                    if (lane < 4) d8[8 + lane] = f_raw;   // (the four words as this workgroup sees them)
-                    if (lane == 0) { d8[1] = 2; d8[2] = s0 | (s2 << 16); d8[3] = c; d8[4] = r; d8[5] = (int)(spins >> 18); }
-                }
-#endif
                 if (__hip_atomic_load(a->info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-#if MNK_DIAG_BULK_DBG
-                    if (d8 != nullptr && lane == 0) { const unsigned long long now = wall_clock64(); d8[1] |= 16; d8[14] = (int)(unsigned)now; d8[15] = (int)(unsigned)(now >> 32); }
-#endif
                     r = -1;
                     break;
                 }
@@ -145,7 +128,7 @@ __device__ __forceinline__ int dag_wait_front(IP a, long spin_limit, int s0, int
 
 // Wave 0 waits until *w0 >= t0 and *w1 >= t1 (progress words of the pivot chain); false: failed / expired.  Acquire + barrier.
 template <class IP>
-__device__ __forceinline__ bool dag_wait_words(IP a, long spin_limit, const int* w0, int t0, const int* w1, int t1, int* s_val, int* d8 = nullptr) {
+__device__ __forceinline__ bool dag_wait_words(IP a, long spin_limit, const int* w0, int t0, const int* w1, int t1, int* s_val) {
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
         long spins = 0;
@@ -155,13 +138,7 @@ __device__ __forceinline__ bool dag_wait_words(IP a, long spin_limit, const int*
             if (__all(v >= (lane == 0 ? t0 : (lane == 1 ? t1 : INT_MIN)))) break;
             __builtin_amdgcn_s_sleep(2);
             if ((++spins & 255) == 0) {
-#if MNK_DIAG_BULK_DBG
-                if (d8 != nullptr && (spins & 0x3ffff) == 0 && lane == 0) { d8[1] = 3; d8[2] = 0; d8[3] = t0; d8[4] = v; d8[5] = (int)(spins >> 18); }
-#endif
                 if (__hip_atomic_load(a->info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-#if MNK_DIAG_BULK_DBG
-                    if (d8 != nullptr && lane == 0) { const unsigned long long now = wall_clock64(); d8[1] |= 16; d8[14] = (int)(unsigned)now; d8[15] = (int)(unsigned)(now >> 32); }
-#endif
                     ok = 0;
                     break;
                 }
@@ -517,7 +494,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             if (tr) { tr[4] = wall_clock64(); s_stat[1] += tr[4] - tr[3]; }
             dag_finalize_tile<LDL>(in, row0, col0, 2 * J, smem_raw, tid, X, tr);
             if (tr) s_stat[3] += wall_clock64() - tr[4];
-        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > k0)) {
+        } else if (!(I == J && kend > k0)) {
             v4f64 acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -609,17 +586,7 @@ struct DagArgs1 {
     const int* qoff;
     int* qheads;
     int nq;
-#if MNK_DIAG_BULK_DBG
-    int* bdbg;                 // 16 words per workgroup: {task, stage, words, target, value, spins >> 18, tasks done, -, the 4 front words seen}
-#endif
 };
-
-#if MNK_DIAG_BULK_DBG
-#define MNK_BDBG(a) ((a).bdbg != nullptr ? (a).bdbg + 16 * blockIdx.x : nullptr)
-int* g_diag_bdbg = nullptr;   // (set by the host side before a launch; diagnostic builds only)
-#else
-#define MNK_BDBG(a) nullptr
-#endif
 
 // The next task of a workgroup (one thread) with per-XCD queues: the head of the queue of its own XCD (sq[0] >= 0: that queue;
 // -1 - queue once it was found empty), and only when that one is exhausted the head of the queue with the most tasks left.  Own
@@ -688,16 +655,6 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             return;
         }
         if (a.wgstat != nullptr && tid == 0) { if (s_stat[0] == 0) s_stat[0] = wall_clock64(); ++s_stat[2]; }
-#if MNK_DIAG_BULK_DBG
-        if (a.bdbg != nullptr && tid == 0) {
-            int* d8 = a.bdbg + 16 * blockIdx.x;
-            d8[0] = t; d8[1] = 1; d8[6] += 1;
-            // where the workgroup runs (HW_ID: cu [11:8], sh [12], se [15:13]; XCC_ID [3:0]) and when it took the task (100 MHz)
-            d8[7] = (int)((__builtin_amdgcn_s_getreg(63492) & 0xffffu) | ((__builtin_amdgcn_s_getreg(63508) & 15u) << 16));
-            const unsigned long long now = wall_clock64();
-            d8[12] = (int)(unsigned)now; d8[13] = (int)(unsigned)(now >> 32);
-        }
-#endif
         const int4 tk = a.tasks[t];
         const int flags = __builtin_amdgcn_readfirstlane(tk.x) & 255, q = __builtin_amdgcn_readfirstlane(tk.x) >> 8;
         const int I = __builtin_amdgcn_readfirstlane(tk.y), J = __builtin_amdgcn_readfirstlane(tk.z) & 0xfff;
@@ -726,7 +683,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
         int limit = 0;
         auto gate_at = [&](int kc) -> int {   // tile columns [kc, return value) final for all four strips
             const unsigned long long w0 = tr ? wall_clock64() : 0;
-            const int r = dag_wait_front(&a, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kc, kend, &s_val, MNK_BDBG(a));
+            const int r = dag_wait_front(&a, a.spin_limit, 2 * I, 2 * I + 1, 2 * J, 2 * J + 1, kc, kend, &s_val);
             if (tr) { const unsigned long long w1 = wall_clock64(); tr[2] = w1; tr[6] += 1; tr[7] += w1 - w0; s_stat[1] += w1 - w0; }
             return r;
         };
@@ -743,7 +700,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             if (flags & DAG_FIRST) return true;
             const int* word = a.tprog + (int64_t)I * a.ntile + J;
             const unsigned long long w0 = tr ? wall_clock64() : 0;
-            if (!dag_wait_words(&a, a.spin_limit, word, q, word, q, &s_val, MNK_BDBG(a))) return false;
+            if (!dag_wait_words(&a, a.spin_limit, word, q, word, q, &s_val)) return false;
             if (tr) s_stat[1] += wall_clock64() - w0;
             return true;
         };
@@ -784,11 +741,11 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             for (int i = 0; i < 8; ++i) { asm volatile("" : "+v"(X[i][0])); asm volatile("" : "+v"(X[i][1])); }
             if (tr) tr[1] = tr[3] = wall_clock64();  // K-loop done = tile applied
             // the diagonal blocks of tile column J and L(2J + 1, 2J)
-            if (dag_wait_front(&a, a.spin_limit, 2 * J, 2 * J + 1, 2 * J, 2 * J + 1, J, J + 1, &s_val, MNK_BDBG(a)) < 0) return;
+            if (dag_wait_front(&a, a.spin_limit, 2 * J, 2 * J + 1, 2 * J, 2 * J + 1, J, J + 1, &s_val) < 0) return;
             if (tr) { tr[4] = wall_clock64(); s_stat[1] += tr[4] - tr[3]; }
             dag_finalize_tile<LDL>(&a, row0, col0, 2 * J, smem_raw, tid, X, tr);
             if (tr) s_stat[3] += wall_clock64() - tr[4];
-        } else if (!(MNK_DAG_DIAG_SUB && I == J && kend > k0)) {
+        } else if (!(I == J && kend > k0)) {
             v4f64 acc[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -835,13 +792,6 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
                 __hip_atomic_store(a.af + (int64_t)I * a.ntile + J, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (tr) tr[5] = wall_clock64();
-#if MNK_DIAG_BULK_DBG
-            if (a.bdbg != nullptr) {   // published, and when
-                int* d8 = a.bdbg + 16 * blockIdx.x;
-                const unsigned long long now = wall_clock64();
-                d8[1] = 4; d8[14] = (int)(unsigned)now; d8[15] = (int)(unsigned)(now >> 32);
-            }
-#endif
         }
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();  // (s_val and the LDS tiles are reused by the next task)
@@ -1062,9 +1012,6 @@ static int launch_dag_bulk(hipStream_t s, bool ldl, const DagInst& one, const Da
         DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
                    one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate,
                    qoff, qheads, nq};
-#if MNK_DIAG_BULK_DBG
-        a.bdbg = g_diag_bdbg;
-#endif
         return ldl ? launch_bulk1_t<true>(s, a, nwg) : launch_bulk1_t<false>(s, a, nwg);
     }
     DagArgs a{insts, reinterpret_cast<const int4*>(tasks), ntasks, ntile, qctr, spin_limit, trace, wgstat, fake};
@@ -1297,9 +1244,6 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         if (rc) return rc;
         // (more than three workgroups per CU -- to fill slots a shader-engine-imbalanced mask might leave empty -- measured
         // no difference: 4 / 5 / 6 per CU 9.63-9.67 vs 9.64-9.68 ms)
-#if MNK_DIAG_BULK_DBG
-        mnk::g_diag_bdbg = ls->dag_debug && ls->dag_dbg.p ? ls->dag_dbg.p + 8 * 128 : nullptr;
-#endif
         const int ph = (int)(counter - qctr), nq = ls->dag_nq[ph];
         // (per-XCD queues: every queue needs workgroups of its own XCD -- the grid the list was dealt for, see mnk_ls_dag_prepare)
         MNK_REQUIRE(nq == 0 || (ntask >= mnk_ctx_bulk_wgs(ctx, chain_cus, 3) && bulk_xcds(ctx, chain_cus) == nq),

@@ -142,10 +142,6 @@ __global__ __launch_bounds__(256) void trsm64_mfma_batch_kernel(const TrsmBatchR
                              rec.info, nullptr);
 }
 
-#ifndef MNK_LEAF_V
-#define MNK_LEAF_V 1   // the pivot leaf: 1 = potrf64v_core (round 6: indicator sums, pivot tests behind the chain, 4x4x4 block solves, third-order
-                       // reciprocals), 0 = potrf64w_core (rounds 2-5) -- A/B builds (tools/leaf_ab.sh)
-#endif
 template <bool LDL>
 __device__ __forceinline__ void potrf64w_body(const double* __restrict__ F, int64_t ld, int64_t j0,
                                               double* __restrict__ Dout, double* __restrict__ inv16,
@@ -165,11 +161,7 @@ __device__ __forceinline__ void potrf64w_body(const double* __restrict__ F, int6
                 // 'L' storage: the strict upper triangle of the block may hold anything (NaN included)
                 Lt[cb][b][r] = (cb == b && l15 < l4 + 4 * r) ? 0.0 : v;
             }
-#if MNK_LEAF_V
     potrf64v_core<LDL>(Lt, j0, Dout, inv16, dvec, dinv, info, pivot_tol, Lsh, Ish, vmax);
-#else
-    potrf64w_core<LDL>(Lt, j0, Dout, inv16, dvec, dinv, info, pivot_tol, Lsh, Ish, vmax);
-#endif
 }
 
 template <bool LDL>
@@ -186,7 +178,7 @@ __global__ __launch_bounds__(64) void potrf64w_kernel(const double* __restrict__
 // Persistent panel kernel (panel_algo = 4): ONE launch factors nb <= NB 64-column blocks of a panel, every row of it.
 // Workgroup t owns the 64-row strip t of the panel (wave w: 16 rows, its nb x 4 column blocks of 16 stay in
 // registers, C^T layout as in trsm64_mfma_kernel).  The strips 0..nb-1 hold the diagonal blocks.  Right-looking, per
-// column block j:   strip j: wave 0 factors the diagonal block (potrf64w_core) and publishes it;
+// column block j:   strip j: wave 0 factors the diagonal block (potrf64v_core) and publishes it;
 //                   strip t > j: waits for it, X = T L_jj^-T, stores V / L, then T[t, c] -= V[t, j] L[c, j]^T for the
 //                   later column blocks c <= t, where L[c, j] is what strip c published in ITS step j.
 // prog[c] = 16 * epoch + (number of column blocks strip c has completed and published); release/acquire at agent scope
@@ -197,37 +189,19 @@ __global__ __launch_bounds__(64) void potrf64w_kernel(const double* __restrict__
 // update of its diagonal block from LDS, exchange to wave 0 -> potrf: no kernel boundaries and no idle launches.
 // ---------------------------------------------------------------------------------------
 constexpr long PP_SPIN_LIMIT = 1L << 20;  // ~0.5 s
-#ifndef MNK_LEAF_WAVES
-#define MNK_LEAF_WAVES 1   // waves that factor a 64x64 diagonal block of the pivot chain.  1: potrf64w_core on wave 0 (the shipped leaf).  4: potrf64q_core,
-                           // every wave its own block row -- built and measured in round 5: the same bits, 0.89 vs 0.86 ms at N = 2048 (tools/leaf_ab.sh,
-                           // profiles/r05_leaf_lab.txt): the scalar 4x4 factorizations, 57 % of the leaf, are repeated by every wave and the
-                           // exchanges through LDS cost what the split of the MFMAs saves.  Diagnostic builds only.
-#endif
-#ifndef MNK_DIAG_RACY_PUB
-#define MNK_DIAG_RACY_PUB 0
-#endif
-#ifndef MNK_DIAG_STEP_TRACE
-#define MNK_DIAG_STEP_TRACE 0
-#endif
-#ifndef MNK_DIAG_NO_EARLY
-#define MNK_DIAG_NO_EARLY 0   // (-DMNK_DIAG_NO_EARLY=1: a diagnostic build without the chain's early diagonal update)
-#endif
-#ifndef MNK_TILE_DMA
-#define MNK_TILE_DMA 1   // (0: the staging tiles of the chain strips go through registers, rounds 2-5)
-#endif
 // A staging tile that arrives by LDS-DMA lies k-column-major: request g' = 2 g + odd of 32 (one global_load_lds_dwordx4 = 64 lanes x 16
 // bytes = rows 0..63 of the k-columns 4 g + odd and 4 g + odd + 2) at byte 2176 g + 1152 odd -- the two k-columns a ds_read_b64 lane group
 // (lanes 0-31: l4 = 0, 1; lanes 32-63: l4 = 2, 3) reads are 1152 = 128 (mod 256) bytes apart: different bank halves.
 constexpr int KT_G = 2176, KT_ODD = 1152, KT_BYTES = 16 * KT_G;
 constexpr int KT_NULL = 2 * KT_BYTES;   // 1 KB per wave behind the staging tiles: where a step that has no next tile sends its requests (no branch in the loop)
-constexpr int PP_STAGE_BYTES = MNK_TILE_DMA ? 2 * KT_BYTES + 4096 : 2 * 4096 * 8;
+constexpr int PP_STAGE_BYTES = 2 * KT_BYTES + 4096;   // two staging tiles + the null region
 constexpr int PP_LDS_BYTES = PP_STAGE_BYTES + 4096 * 8;  // two staging tiles (the first doubles as the exchange buffer) + own tile
 constexpr int PC_LDS_BYTES = PP_STAGE_BYTES + 2 * 4096 * 8;  // pivot-chain kernels: + the strip's NEXT diagonal block (see pp_strip, EARLY)
 
 // acc[cb2] += sum over ib, s of tile[(4 cb2 + ib) * 64 + lane][s] * B[ib][s] for the 16x16 blocks cb2 < ncb2 (wave-uniform) of one 64x64 tile
 // in LDS (the chain strips' tile step: 64 products per wave).  The callers negate the B operand once per block column instead of
 // every A operand on its way from LDS (round 5: two v_xor per LDS read), and the read of block q + 1 is requested before the products
-// of block q.  Measured in the schedule (tools/chain_steps2.py, profiles/r06_chain_steps.txt): 1.79 us per tile step against the matrix
+// of block q.  Measured in the schedule (a per-step trace build, removed; record in profiles/r06_chain_steps.txt): 1.79 us per tile step against the matrix
 // pipe's 1.71; the same loop as ONE inline-assembly block with every A operand requested six products ahead (ds_read_b64 into a ring
 // of eight registers) was 1.85 -- the LDS latency is not what a tile step waits for; its other 0.7 us are the 16 global loads of the
 // next tile (0.38), the arrival of this one + its way into LDS (0.26) and the barrier (0.05).
@@ -246,11 +220,6 @@ __device__ __forceinline__ void tile_mac(const v4d* __restrict__ tile, const int
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);   // ... then this block's four products
         a = an;
     }
-}
-// (a diagonal strip's own block: lower triangle only -- the 16x16 blocks cb2 <= w)
-__device__ __forceinline__ void tile_mac(const v4d* __restrict__ tile, const int lane, const bool own_block, const int w, const v4d* __restrict__ B, v4d* __restrict__ acc) {
-    if (own_block) tile_mac<false>(tile, lane, w + 1, B, acc);
-    else tile_mac<true>(tile, lane, 4, B, acc);
 }
 // The same sum (same products, same order, same bits) over a staging tile in the LDS-DMA layout; `next(q)`, q = 0..7, issues this wave's
 // q-th request of the NEXT tile -- spread over the products, so that the texture addresser works under the matrix pipe and the
@@ -359,7 +328,7 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
     const int xn_state = EARLY && xn_have != nullptr ? *xn_have : 0;   // (rewritten behind the barrier below)
     const bool use_xn = xn_state != 0;
     // ... and whether this strip does the same for the next strip-column
-    const bool make_xn = EARLY && !MNK_DIAG_NO_EARLY && xn_have != nullptr && dag.front != nullptr && t >= 4 && t < 8 && nb == 4 && R < Np && t != dbg_missing;
+    const bool make_xn = EARLY && xn_have != nullptr && dag.front != nullptr && t >= 4 && t < 8 && nb == 4 && R < Np && t != dbg_missing;
     if (tid == 0) *s_go = (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) ? 1 : 0;
     __syncthreads();
     const int go_bits = *s_go;
@@ -382,18 +351,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
     const int tabs = (int)(p0 >> 6) + t;  // this strip's 64-row block
     unsigned long long* ptr_tr = dag.trace != nullptr && tid == 0 ? dag.trace + 8 * t : nullptr;
     if (ptr_tr) ptr_tr[0] = wall_clock64();
-#if MNK_DIAG_STEP_TRACE   // (diagnostic build: 16 more stamps per strip -- per step: block seen / substitution done / rows published / updates done;
-                          // second half of the chain's trace region, single-phase schedules of <= 64 strip-columns; tools/chain_steps2.py)
-    unsigned long long* tr2 = ptr_tr != nullptr && (p0 >> 8) < 64 ? ptr_tr + 2048 * 8 + ((p0 >> 8) * 8 * (int64_t)gridDim.x + 8 * t) : nullptr;
-#define MNK_TR2(slot) do { if (tr2) tr2[slot] = wall_clock64(); } while (0)
-    // ... and eight sums over the prologue's tile steps, in shader cycles: {steps, wait for the tile's loads + LDS write, barrier, issue of the
-    // next loads, the 64 products, total}
-    unsigned long long* tr3 = ptr_tr != nullptr && (p0 >> 8) < 64 ? ptr_tr + 3072 * 8 : nullptr;
-    unsigned long long pr_n = 0, pr_vm = 0, pr_bar = 0, pr_ld = 0, pr_mac = 0;
-#define MNK_PCLK() __builtin_readcyclecounter()
-#else
-#define MNK_TR2(slot) do { } while (0)
-#endif
     if (EARLY && make_xn) {
 #pragma unroll
         for (int cb2 = 0; cb2 < 4; ++cb2)
@@ -458,7 +415,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
     const int ncb_pro = use_xn ? t : jmax + 1;   // (use_xn: the strip's own diagonal block -- column block t -- needs no prologue)
     if (Kp > 0 && ncb_pro > 0) {
         const int nch = Kp >> 6, ncb = ncb_pro;
-#if MNK_TILE_DMA
         v4d Bv[4], Bn[4];
         // this wave's eight requests of a tile: k-columns 16 w + 4 (q >> 1) + (q & 1) + 2 (lane >> 5), rows 2 (lane & 31), + 1
         const double* dsrc = F + (p0 + 2 * (lane & 31)) + (p0 - Kp + 16 * w + 2 * (lane >> 5)) * ld;
@@ -489,17 +445,8 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 if (c >= ncb) break;
                 const int buf = it & 1;
                 ++it;
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k0 = MNK_PCLK();
-#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part of the tile is in LDS ...
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k1 = MNK_PCLK();
-#endif
                 __syncthreads();                                    // ... and everybody's; the other buffer is free
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k2c = MNK_PCLK();
-#endif
                 // the next k-chunk's V behind the barrier: a step away from the wait above, and from the one that takes it
                 if (c == 0 && kc + 1 < nch) b_load(kc + 1, Bn);
                 int c2 = c + 1, k2 = kc;
@@ -507,76 +454,11 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 const bool more = k2 < nch;
                 if (!more) { k2 = kc; c2 = c; }   // (the last step asks for its own tile again, into the null region)
                 auto next = [&](int q) { tile_dma(k2, c2, buf ^ 1, q, more); };
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k3 = MNK_PCLK();
-#endif
                 if (c == t) tile_mac_k<false>(pp_smem + buf * KT_BYTES, l15, l4, w + 1, Bv, &X[4 * c], next);
                 else tile_mac_k<true>(pp_smem + buf * KT_BYTES, l15, l4, 4, Bv, &X[4 * c], next);
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k4 = MNK_PCLK();
-                pr_n += 1; pr_vm += k1 - k0; pr_bar += k2c - k1; pr_ld += k3 - k2c; pr_mac += k4 - k3;
-#endif
             }
         }
         __syncthreads();
-#else
-        v4d pre[4], Bv[4], Bn[4];
-        auto tile_load = [&](int kc, int c) {
-            const double* src = F + (p0 + 64 * (int64_t)c + lane) + (p0 - Kp + 64 * (int64_t)kc + w) * ld;
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) pre[ib][s] = src[(16 * ib + 4 * s) * ld];
-        };
-        auto b_load = [&](int kc, v4d (&B)[4]) {
-            const double* src = Vp + (r0 + l15) + (64 * (int64_t)kc + l4) * ldv;
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) B[ib][s] = src[(16 * ib + 4 * s) * ldv];
-        };
-        int it = 0;
-        tile_load(0, 0);
-        b_load(0, Bn);
-        for (int kc = 0; kc < nch; ++kc) {
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib) { Bv[ib] = -Bn[ib]; pin(Bv[ib]); }   // (T -= V L^T: the sign goes into the operand that is copied anyway)
-            if (kc + 1 < nch) b_load(kc + 1, Bn);
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                if (c >= ncb) break;
-                v4d* tile = stage + (it & 1) * 1024;
-                ++it;
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k0 = MNK_PCLK();
-#endif
-#pragma unroll
-                for (int ib = 0; ib < 4; ++ib) tile[((lane >> 4) * 4 + ib) * 64 + (lane & 15) + 16 * w] = pre[ib];
-#if MNK_DIAG_STEP_TRACE
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const unsigned long long k1 = MNK_PCLK();
-#endif
-                __syncthreads();
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k2c = MNK_PCLK();
-#endif
-                {
-                    int c2 = c + 1, k2 = kc;
-                    if (c2 >= ncb) { c2 = 0; k2 = kc + 1; }
-                    if (k2 < nch) tile_load(k2, c2);
-                }
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k3 = MNK_PCLK();
-#endif
-                tile_mac(tile, lane, c == t, w, Bv, &X[4 * c]);
-#if MNK_DIAG_STEP_TRACE
-                const unsigned long long k4 = MNK_PCLK();
-                pr_n += 1; pr_vm += k1 - k0; pr_bar += k2c - k1; pr_ld += k3 - k2c; pr_mac += k4 - k3;
-#endif
-            }
-        }
-        __syncthreads();
-#endif
     }
     if (EARLY && use_xn) {
 #pragma unroll
@@ -592,9 +474,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
             }
     }
     if (ptr_tr) ptr_tr[4] = wall_clock64();
-#if MNK_DIAG_STEP_TRACE
-    if (tr3) { tr3[0] = pr_n; tr3[1] = pr_vm; tr3[2] = pr_bar; tr3[3] = pr_ld; tr3[4] = pr_mac; }
-#endif
 
     // One step per column block.  `j` is a compile-time constant (generic lambda over integral_constant), so every
     // index into X is static from the start and the strip stays in registers; returns true when the strip is done.
@@ -628,33 +507,9 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                     }
             }
         } else if (j > 0) __syncthreads();  // the LDS tiles of the previous step are free
-        if (j == t && MNK_LEAF_WAVES == 4) {
-            // ---- diagonal step, four waves: every wave factors its own block row of the 64x64 block (potrf64q_core); the
-            // stores of all four are complete before one lane publishes the block
-            const int64_t jb = (p0 >> 6) + j;
-            v4d Lq[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Lq[b][r] = (b == w && l15 < l4 + 4 * r) ? 0.0 : X[4 * j + b][r];
-            potrf64q_core<LDL, WT>(Lq, w, p0 + 64 * j, dblk0 + jb * 4096, inv0 + jb * 1024, dvec, dinv, info, pivot_tol,
-                                   reinterpret_cast<double*>(stage), dag.vmax);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                if (!WT) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(prog + j, epoch16 + j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // (its last step: the strip's rows are final through the tile column of block j)
-                if (dag.front != nullptr)
-                    __hip_atomic_store(dag.front + tabs, (int)(p0 >> 7) + (j >> 1) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (dag.trace != nullptr) dag.trace[8 * t + 2] = wall_clock64();
-            }
-            return true;
-        }
         if (j == t) {
-            // ---- diagonal step, one wave (MNK_LEAF_WAVES = 1: rounds 2-4): hand the updated 64x64 block to wave 0 (same
-            // lane mapping), factor, publish
+            // ---- diagonal step: hand the updated 64x64 block to wave 0 (same lane mapping), which factors it (the one-wave
+            // leaf, potrf64v_core) and publishes it
 #pragma unroll
             for (int b = 0; b < 4; ++b)
                 if (b <= w) stage[(w * (w + 1) / 2 + b) * 64 + lane] = X[4 * j + b];
@@ -671,13 +526,8 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 }
             const int64_t jb = (p0 >> 6) + j;
             if (ptr_tr) ptr_tr[7] = wall_clock64();   // (trace: the leaf starts)
-#if MNK_LEAF_V
             potrf64v_core<LDL, WT>(Lt, p0 + 64 * j, dblk0 + jb * 4096, inv0 + jb * 1024, dvec, dinv, info, pivot_tol, nullptr,
                                    nullptr, dag.vmax);
-#else
-            potrf64w_core<LDL, WT>(Lt, p0 + 64 * j, dblk0 + jb * 4096, inv0 + jb * 1024, dvec, dinv, info, pivot_tol, nullptr,
-                                   nullptr, dag.vmax);
-#endif
             if (!WT) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) {
@@ -692,7 +542,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
         // ---- wait for the diagonal block j, X = T L_jj^-T
         pp_wait<NB, LDL>(prog, j, nb, epoch16 + j + 1, seen, info, pp_limit, dag.dbg != nullptr ? dag.dbg + 8 * t : nullptr, (int)(p0 >> 8), t);
         if (ptr_tr && j == t - 1) ptr_tr[6] = wall_clock64();   // (trace, tools/chain_steps.py: the block in front of this strip's own seen)
-        MNK_TR2(4 * j + 0);
         const int64_t jb = (p0 >> 6) + j;
         const double* Dblk = dblk0 + jb * 4096;
         const double* Iv16 = inv0 + jb * 1024;
@@ -734,7 +583,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 X[4 * j + cb] = x;
             }
         }
-        MNK_TR2(4 * j + 1);
         // ---- store V (LDL: to the W panel) and L; a diagonal strip also keeps its L rows in LDS and publishes
         double vm = 0.0;
 #pragma unroll
@@ -760,14 +608,8 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
         // task-DAG schedule: the strip's rows are final through a whole tile column after every second block
         const bool pub_front = dag.front != nullptr && ((j & 1) != 0 || j == jmax);
         if (diag_strip || pub_front) {
-#if MNK_DIAG_RACY_PUB   // (timing only, results void: what the stores' completion in front of the publication costs the chain)
-            if (!diag_strip) {
-#endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-#if MNK_DIAG_RACY_PUB
-            }
-#endif
             if (tid == 0) {
                 if (!WT) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -777,9 +619,7 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 if (pub_front && dag.trace != nullptr) dag.trace[8 * t + (j == jmax ? 2 : 3)] = wall_clock64();
             }
         }
-        MNK_TR2(4 * j + 2);
         // ---- T[t, c] -= V[t, j] L[c, j]^T for the later column blocks (software-pipelined through LDS)
-#if MNK_TILE_DMA
         // (the tile of column block c -- rows of the diagonal strip c, k-columns of block j -- goes straight into the staging tile c & 1: the
         // first one at once, the following ones under the products of the one before)
         const double* dsrc = F + (p0 + 2 * (lane & 31)) + (p0 + 64 * j + 16 * w + 2 * (lane >> 5)) * ld;
@@ -816,35 +656,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
             if (c == t) tile_mac<false>(own, lane, w + 1, Bj, &X[4 * c]);   // (the block behind a strip's own one is past jmax: no next tile)
             else tile_mac_k<true>(pp_smem + (c & 1) * KT_BYTES, l15, l4, 4, Bj, &X[4 * c], next);
         }
-#else
-        v4d pre[4];
-        auto prefetch = [&](int c) {
-            pp_wait<NB, LDL>(prog, c, nb, epoch16 + j + 1, seen, info, pp_limit, dag.dbg != nullptr ? dag.dbg + 8 * t : nullptr, (int)(p0 >> 8), t);
-            const double* src = F + (p0 + 64 * (int64_t)c + lane) + (p0 + 64 * j + w) * ld;
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) pre[ib][s] = src[(16 * ib + 4 * s) * ld];
-        };
-        if (j + 1 <= jmax && j + 1 != t) prefetch(j + 1 < NB ? j + 1 : 0);
-        // the block column's V (stored above, final) is the B operand of every product below: its sign is flipped once, in place
-        // (X[4 j ..] is not read again as what it was: later steps and strip-columns take the stored values)
-        v4d* const Bj = &X[4 * j];
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) { Bj[ib] = -Bj[ib]; pin(Bj[ib]); }
-#pragma unroll
-        for (int c = j + 1; c < NB; ++c) {
-            if (c > jmax) break;
-            v4d* tile = c == t ? own : stage + (c & 1) * 1024;
-            if (c != t) {
-#pragma unroll
-                for (int ib = 0; ib < 4; ++ib) tile[((lane >> 4) * 4 + ib) * 64 + (lane & 15) + 16 * w] = pre[ib];
-            }
-            __syncthreads();
-            if (c + 1 < NB && c + 1 <= jmax && c + 1 != t) prefetch(c + 1 < NB ? c + 1 : 0);
-            tile_mac(tile, lane, c == t, w, Bj, &X[4 * c]);
-        }
-#endif
         if (EARLY && make_xn) {
             // ---- the same product for the strip's diagonal block of the NEXT strip-column (its k-chunk j)
             __syncthreads();   // `own` is complete
@@ -861,7 +672,6 @@ __device__ __forceinline__ void pp_strip(const int t, double* __restrict__ F, in
                 }
             if (tn_now && tid == 0) *xn_have = 2;
         }
-        MNK_TR2(4 * j + 3);
         return false;
     };
     if (step(std::integral_constant<int, 0>{})) return;

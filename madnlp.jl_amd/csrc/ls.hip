@@ -311,8 +311,8 @@ std::vector<int> ctx_bits(const mnk_ctx* c) {
 // inside an XCD shader engine by shader engine (mask bit b is CU b / 8 of XCD b % 8, shader engine (b / 8) % 4) -- whatever
 // the mask left of an engine, so the engine with the fewest CUs bounds what is resident at once: 16 chain CUs take one CU
 // from engines 0 and 1 of every XCD, which then hold 7 x 3 = 21 workgroups each, and of a grid of 3 x 240 = 720 exactly
-// 32 x 21 = 672 start (tools/stall_hunt.py on a diagnostic build: 21 / 21 / 22 / 21-22 workgroups per engine, 35 CUs of
-// engines 2 and 3 holding two).  The others are placed LATER, in mid-kernel, when the hardware finds room -- and a workgroup
+// 32 x 21 = 672 start (seen in round 4 with a build whose bulk workgroups recorded their CU -- removed, record in
+// profiles/r04_stall_captures.md: 21 / 21 / 22 / 21-22 workgroups per engine, 35 CUs of engines 2 and 3 holding two).  The others are placed LATER, in mid-kernel, when the hardware finds room -- and a workgroup
 // placed in mid-kernel is what the one-in-~3000 time-out of the task-DAG schedule was: in both captured
 // events 6 resp. 12 workgroups with block ids 672..686 had all just been started, within 0.2 ms of each other, took a task
 // each, and then did nothing for the ~965 ms until the time-out sent the others home -- at which point each ran its whole
@@ -813,7 +813,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     if (!strcmp(key, "dag_debug")) {
         ls->dag_debug = value != 0.0;
         if (ls->dag_debug && !ls->dag_dbg.p) {
-            // (8 words per chain strip, then -- diagnostic builds with MNK_DIAG_BULK_DBG -- 16 words per bulk workgroup)
+            // (8 words per chain strip; the 16 words per bulk workgroup behind them were a removed diagnostic build's and stay zero)
             if (ls->dag_dbg.alloc(8 * 128 + 16 * 1024)) return -2;
             MNK_HIP(hipMemset(ls->dag_dbg.p, 0, (8 * 128 + 16 * 1024) * sizeof(int)));
         }

@@ -334,9 +334,7 @@ __global__ __launch_bounds__(256) void bwd_panel_kernel(const double* __restrict
 // ================================================================================================
 constexpr int PS_MAXOWN = 12;            // owned blocks per workgroup: Np <= 12 * 64 * G
 constexpr int PS_NEAR = 3;               // blocks within this many steps of the front poll eagerly
-#ifndef PS_DAHEAD
-#define PS_DAHEAD 3                      // steps between the request of a block's inverse slice and its diagonal role (1: rounds 2-5)
-#endif
+constexpr int PS_DAHEAD = 3;             // steps between the request of a block's inverse slice and its diagonal role
 
 __device__ __forceinline__ void ps_publish(double* p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v),
@@ -478,7 +476,7 @@ __device__ __forceinline__ void persistent_solve_body(
     // right before it: a workgroup's requests go through ONE texture addresser at ~14 cycles per wave instruction, so the 128 KB of L for
     // the last update (256 wave instructions) plus up to 128 KB of the inverse took 2.5 (first block of a step) to 4.4 us (fourth) to
     // arrive -- longer than the step's y took to get there: the gather's barrier waited for the slices, not for the hop (round 6,
-    // tools/solve_trace.py on a build with -DMNK_DIAG_SOLVE_PREFETCH).  Same arithmetic, same bits.
+    // tools/solve_trace.py; one step ahead, as in rounds 2-5: profiles/r06_solve_two_step_ab.txt).  Same arithmetic, same bits.
     for (int k = 0; k < nsteps && m0 < nown; ++k) {
         const int b0 = 4 * k, nbk = nb - b0 < 4 ? nb - b0 : 4;
         int i = g + m0 * G;

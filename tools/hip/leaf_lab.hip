@@ -1,4 +1,4 @@
-// Leaf laboratory: the 64x64 diagonal-block factorization of the pivot chain (csrc/leaf64.h) on its own -- one workgroup, the
+// Leaf laboratory: the 64x64 diagonal-block factorization of the pivot chain (csrc/leaf64.h; its predecessors: leaf_variants.h) on its own -- one workgroup, the
 // block in registers, repeated; shader-clock cycles per factorization for the one-wave leaf (potrf64w_core) and the four-wave
 // leaf (potrf64q_core), LDL^T and Cholesky, and for timing-only variants with pieces left out (results void) that say where
 // the cycles go.  build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I madnlp.jl_amd/csrc tools/hip/leaf_lab.hip -o tools/hip/leaf_lab
@@ -6,7 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "leaf64.h"
+#include "leaf_variants.h"   // the superseded leaves (potrf64w/s/q_core); brings csrc/leaf64.h
 namespace mnk { void set_error(const char*, ...) {} }
 using namespace mnk;
 

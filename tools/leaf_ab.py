@@ -1,5 +1,7 @@
 """A/B of two builds of the library on the task-DAG schedule: factorize! time and a hash of the factor's bits per order /
-algorithm (the four-wave leaf of round 5 against the one-wave leaf: MNK_LIBPATH=madnlp.jl_amd/lib/libmadnlp_hip_leaf1.so).
+algorithm.  Run it once as it is (this tree's library) and once with MNK_LIBPATH=<libmadnlp_hip.so built from the parent
+commit, same ABI>, alternating on one box.  (Records: the round-5 / round-6 leaves and the LDS-DMA tiles against their
+predecessors, profiles/r05_leaf_four_wave_ab.txt, r06_leaf_ab.txt, r06_tile_dma_ab.txt.)
 usage: [MNK_LIBPATH=...] python tools/leaf_ab.py [N ...]"""
 import hashlib
 import os

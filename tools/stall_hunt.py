@@ -1,7 +1,8 @@
 """Hunt for the rare stall of the task-DAG schedule: rounds of 16 back-to-back factorizations of
 case1354pegase-shaped systems on one context, option dag_debug = 1 (and dag_fill = 0: the task list is then the one
 tools/dag_tasks.py mirrors), until one of them runs into its bounded wait; the progress words the time-out left and what the
-chain's strips were waiting for go to gpurun_out/stall/state_<k>.json for offline analysis (tools/stall_analyze.py).
+chain's strips were waiting for go to stall/state_<k>.json under the output directory (`out_dir` below; the captures of
+round 4: profiles/r04_stall_captures.md).
 usage: python tools/stall_hunt.py [max_rounds] [events]"""
 import ctypes as C
 import json
@@ -60,11 +61,7 @@ with torch.cuda.stream(st):
                 L.check(L.lib().mnk_ls_debug_dag_state(M._h, flags.ctypes.data, nflags, chain.ctypes.data, chain.size, C.byref(have)), "state")
                 rec = {"round": rnd, "instance": idx, "N": P.n, "Np": Np, "ntile": ntile, "site": M.get_stat("timeout_site"),
                        "have": have.value, "inertia": inertia, "dag_ntasks": M.get_stat("dag_ntasks"),
-                       "flags": flags.tolist(), "chain": chain[:128].reshape(-1, 8).tolist(),
-                       # (a diagnostic build -DMNK_DIAG_BULK_DBG=1 only, zeros otherwise: 16 words per bulk workgroup --
-                       # task, stage (1 grabbed / 2 waiting for rows / 3 waiting for the chunk order / 4 published), the waited
-                       # words, target, value seen, polls >> 18, tasks grabbed, -, the four front words as seen)
-                       "bulk": chain[8 * 128:].reshape(-1, 16).tolist()}
+                       "flags": flags.tolist(), "chain": chain[:128].reshape(-1, 8).tolist()}
                 path = os.path.join(out_dir, f"state_{events}.json")
                 json.dump(rec, open(path, "w"))
                 print(f"round {rnd} instance {idx}: time-out at site {rec['site']}, state -> {path}; chain strips waiting: "
