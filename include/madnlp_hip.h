@@ -513,6 +513,21 @@ int mnk_ipm_bound_dual_fill(mnk_ipm* ipm, double* zl, double* zu, double v);
 int mnk_ipm_gemv(mnk_ipm* ipm, int trans, int64_t m, int64_t n, double alpha, const double* A, int64_t lda, const double* x,
                  double beta, double* y);
 
+/* ---- NLP scaling and objective sense around a model's raw callback values (csrc/nlp_scale.hip) -------------------------
+ * The factors the reference's callback wrappers apply (src/Callbacks/nlpmodels.jl:771-906, src/IPM/callbacks.jl:28-49), on
+ * device vectors, asynchronous on the context's stream, one launch each; a length of 0 launches nothing.  Every product and
+ * difference is rounded on its own (no FMA).
+ *   mnk_ipm_vec_mul     out[i] = a[i] * b[i], i < n; out may alias a or b
+ *   mnk_ipm_scale_cons  eval_cons_wrapper! after the model's cons!: c[i] = c[i] * con_scale[i], minus the slack of row i,
+ *                       minus rhs[i], in this order.  con_scale = NULL: ones.  slack has ns entries; slack_pos (device, m
+ *                       entries, 0-based) holds for every row the position of its slack in `slack`, negative for an
+ *                       equality row -- the inverse of the solver's ind_ineq; NULL: the identity (ns == m), or unused (ns == 0)
+ *   mnk_ipm_scale_grad  f[0 .. n) *= factor (obj_sign * obj_scale), f[n .. ntot) = 0: the slack part of the gradient */
+int mnk_ipm_vec_mul(mnk_ipm* ipm, double* out, const double* a, const double* b, int64_t n);
+int mnk_ipm_scale_cons(mnk_ipm* ipm, double* c, const double* con_scale, const double* slack, const int64_t* slack_pos,
+                       int64_t ns, const double* rhs, int64_t m);
+int mnk_ipm_scale_grad(mnk_ipm* ipm, double* f, int64_t n, int64_t ntot, double factor);
+
 /* ---- device evaluation of an NLP model's callbacks: polar AC optimal power flow (callback half) --------
  * What eval_f_wrapper / eval_grad_f_wrapper! / eval_cons_wrapper! / eval_jac_wrapper! / eval_lag_hess_wrapper!
  * (reference src/IPM/callbacks.jl:1-96) obtain from the model through NLPModels.obj / grad! / cons! / jac_coord! /

@@ -11,24 +11,9 @@
 #include <utility>
 
 #include "common.h"
+#include "ipm_handle.h"
 
 using namespace mnk;
-
-struct mnk_ipm {
-    mnk_ctx* ctx = nullptr;
-    int64_t ntot = 0, nlb = 0, nub = 0;
-    int64_t nllb = 0, nuub = 0;
-    DevBuf<int64_t> ind_lb, ind_ub, ind_llb, ind_uub;
-    DevBuf<double> gemv_part;   // column-slab partial sums of mnk_ipm_gemv (grown on demand)
-    DevBuf<double> part;   // IPM_SLOTS x IPM_BLOCKS partials
-    double* pin = nullptr;     // IPM_SLOTS pinned, device-mapped host words: the final reduction stores its result here
-    double* pin_dev = nullptr;
-    // batch mode (mnk_ipm_batch_begin / _end): the get_* calls only enqueue their reductions into successive slots and
-    // leave a finalizer behind; ONE synchronization at batch_end, then every deferred `out` receives its value
-    bool batching = false;
-    int next_slot = 0;
-    std::vector<std::pair<int, std::function<void(const double*)>>> pending;  // (first slot, finalizer)
-};
 
 namespace {
 

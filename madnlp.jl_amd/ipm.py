@@ -18,9 +18,10 @@ reference closely enough that iteration counts and residual histories are meanin
   robust!                src/IPM/solver.jl:413-545, src/IPM/restoration.jl:39-76, filter_line_search_RR!
                          src/IPM/line_search.jl:128-222, _update_monotone_RR! src/IPM/barrier.jl:39-84
 
-Not implemented: NLP
-scaling (problems used here have gradients below nlp_scaling_max_gradient, so the reference's
-scaling factors are 1).  Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems):
+NLP scaling (`nlp_scaling`, off by default) and the objective sense (a model's `minimize` attribute): `set_scaling!`
+src/IPM/solver.jl:37-49 with the factor functions of src/Callbacks/nlpmodels.jl:222-264, the callback wrappers :771-906 and
+src/IPM/callbacks.jl:9,28-30,82, un-scaled results (`solution()`) nlpmodels.jl:649-661.
+Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems):
 `quasi_newton.py` and `eval_lag_hess` below (src/IPM/callbacks.jl:145-190).
 
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
@@ -106,6 +107,10 @@ class IPMOptions:
     # options.jl `hessian_approximation`: "exact" (ExactHessian), "bfgs" (BFGS), "damped_bfgs" (DampedBFGS); the last two on
     # the dense KKT systems only (the reference has no dense BFGS for sparse systems, and CompactLBFGS is not part of this project)
     hessian_approximation: str = "exact"
+    # options.jl:164-165.  The reference's default is `true`; here it is False because every recorded trajectory, golden file
+    # and profile of this project was made without scaling -- switching the default is a change of its own
+    nlp_scaling: bool = False
+    nlp_scaling_max_gradient: float = 100.0
 
     @property
     def mu_min(self):
@@ -217,6 +222,46 @@ def _initialize_variables(x, xl, xu, bound_push, bound_fac):
             x[i] = min(u - bound_push * max(1, abs(u)), x[i])
 
 
+def set_obj_scale(grad, max_gradient):
+    """`set_obj_scale!` nlpmodels.jl:225-227: min(1, max_gradient / norm(grad, Inf)); a zero gradient gives 1 (Julia: 100 / 0
+    = Inf)."""
+    g = float(np.abs(grad).max(initial=0.0))
+    return 1.0 if g == 0.0 else min(1.0, max_gradient / g)
+
+
+def set_con_scale_sparse(m, jac_I, jac, max_gradient):
+    """`set_con_scale_sparse!` nlpmodels.jl:229-244: per row min(1, max_gradient / max(1, max |jac entry|)) over the COO
+    entries as they are (duplicates are not summed)."""
+    row_max = np.ones(m)
+    np.maximum.at(row_max, np.asarray(jac_I, dtype=np.int64), np.abs(np.asarray(jac, dtype=float)))
+    return np.minimum(1.0, max_gradient / row_max)
+
+
+def set_con_scale_dense(jac, max_gradient):
+    """`set_con_scale_dense!` nlpmodels.jl:254-264: the same from the rows of a dense Jacobian (init = 1)."""
+    jac = np.asarray(jac, dtype=float)
+    return np.minimum(1.0, max_gradient / np.abs(jac).max(axis=1, initial=1.0))
+
+
+@dataclass
+class Solution:
+    """What the reference hands back in `MadNLPExecutionStats`, un-scaled (nlpmodels.jl:649-661).  `constraints` is left out."""
+    status: str
+    iterations: int
+    solution: np.ndarray
+    objective: float
+    multipliers: np.ndarray
+    multipliers_L: np.ndarray
+    multipliers_U: np.ndarray
+
+
+def unpack_solution(solver, x, y, zl, zu):
+    """`unpack_obj`, `unpack_x!`, `unpack_y!`, `unpack_z!` on host copies of the iterate."""
+    n, s = solver.n, solver.obj_scale
+    return Solution(solver.status, solver.cnt.k, np.array(x[:n]), solver.obj_sign * solver.obj_val / s,
+                    (y * solver.con_scale) * (solver.obj_sign / s), zl[:n] / s, zu[:n] / s)
+
+
 # What a back-end of `MadNLPSolver` supplies: the methods that touch vectors.  The host class implements them with numpy; a
 # subclass that keeps its vectors elsewhere (`ipm_dev.DeviceMadNLPSolver`) overrides ALL of them -- none may fall back to numpy
 # on its vectors (tests/test_ipm_driver_structure.py).  The inertia-free corrector's kernels (`_set_g_ifr`, `_set_aug_rhs_ifr`,
@@ -230,6 +275,7 @@ BACKEND_PRIMITIVES = (
     "_rel_search_norm", "_line_search_scalars", "_trial_scalars",
     "_rr_init_vectors", "_rr_obj_val", "_rr_theta", "_rr_inf_pr", "_rr_inf_du", "_rr_inf_compl", "_rr_varphi", "_rr_varphi_d",
     "_rr_alpha_max", "_rr_alpha_z", "_rr_set_aug", "_rr_set_rhs", "_rr_finish", "_rr_set_f", "_rr_reset_slack_duals",
+    "solution",
 )
 
 
@@ -275,43 +321,55 @@ class MadNLPSolver:
         self.alpha = self.alpha_z = 0.0
         self.mu = self.tau = 0.0
         self.obj_val = 0.0
+        # NLP scaling (all ones until `initialize` sets them) and the objective sense (callbacks.jl:9)
+        self.obj_scale = 1.0
+        self.obj_sign = 1.0 if getattr(nlp, "minimize", True) else -1.0
+        self.con_scale = np.ones(m)
+        self.jac_scale = np.ones(len(nlp.jac_I)) if sparse else None     # con_scale[jac_I]
         self.status = "INITIAL"
 
     # ------------------------------------------------------------------ callbacks (src/IPM/callbacks.jl)
+    # The model's raw values take the scaling factors and the sense here (nlpmodels.jl:771-906); with the factors at one every
+    # product below is exact.
     def eval_f(self, x):
-        return self.nlp.obj(x[:self.n])
+        return self.obj_sign * (self.nlp.obj(x[:self.n]) * self.obj_scale)
 
     def eval_grad(self, x):
         self.f[:self.n] = self.nlp.grad(x[:self.n])
+        self.f[:self.n] *= self.obj_scale
+        if self.obj_sign != 1.0:
+            self.f[:self.n] *= self.obj_sign
         self.f[self.n:] = 0.0
         self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
         c[:] = self.nlp.cons(x[:self.n])
+        c *= self.con_scale
         c[self.ind_ineq] -= x[self.n:]
         c -= self.rhs
 
     def eval_jac(self, x):
         if self.sparse:
-            self.kkt.get_jacobian()[:] = self.nlp.jac_coord(x[:self.n])
+            self.kkt.get_jacobian()[:] = self.nlp.jac_coord(x[:self.n]) * self.jac_scale
         else:
-            self.kkt.get_jacobian()[...] = self.nlp.jac_dense(x[:self.n])
+            self.kkt.get_jacobian()[...] = self.nlp.jac_dense(x[:self.n]) * self.con_scale[:, None]
         self.kkt.compress_jacobian()
 
     def eval_lag_hess(self, x, y, is_resto=False):
         """`eval_lag_hess_wrapper!` callbacks.jl:77-95: objective weight 0 in the robust restoration phase."""
         if self.qn is not None:
             return self._eval_lag_hess_qn(x, y)
-        w = 0.0 if is_resto else 1.0
+        w = (0.0 if is_resto else 1.0) * self.obj_sign * self.obj_scale
         if self.sparse:
-            self.kkt.get_hessian()[:] = self.nlp.hess_coord(x[:self.n], y, w)
+            self.kkt.get_hessian()[:] = self.nlp.hess_coord(x[:self.n], y * self.con_scale, w)
         else:
-            self.kkt.get_hessian()[...] = self.nlp.hess_dense(x[:self.n], y, w)
+            self.kkt.get_hessian()[...] = self.nlp.hess_dense(x[:self.n], y * self.con_scale, w)
         self.kkt.compress_hessian()
         self.cnt.lag_hess_cnt += 1
 
     def _model_jtprod(self, x, l):
-        """`_eval_jtprod_wrapper!`: J(x)' l through the model's `jtprod` where it has one."""
+        """`_eval_jtprod_wrapper!` nlpmodels.jl:791-801: J(x)' (l .* con_scale) through the model's `jtprod` where it has one."""
+        l = l * self.con_scale
         if hasattr(self.nlp, "jtprod"):
             return np.asarray(self.nlp.jtprod(x, l), dtype=float)
         return self.nlp.jac_dense(x).T @ l
@@ -378,6 +436,21 @@ class MadNLPSolver:
         self.jacl[:] = 0.0
         self.zl[self.ind_lb] = 1.0
         self.zu[self.ind_ub] = 1.0
+        if o.nlp_scaling:
+            # set_scaling! (solver.jl:37-49, nlpmodels.jl:693-765): the factors from the model's raw Jacobian and gradient at the
+            # pushed starting point (this gradient is not one of `cnt.obj_grad_cnt`), then y0, rhs and the slacks with their bounds
+            if self.sparse:
+                self.con_scale[:] = set_con_scale_sparse(self.m, nlp.jac_I, nlp.jac_coord(x0), o.nlp_scaling_max_gradient)
+                self.jac_scale[:] = self.con_scale[np.asarray(nlp.jac_I, dtype=np.int64)]
+            else:
+                self.con_scale[:] = set_con_scale_dense(nlp.jac_dense(x0), o.nlp_scaling_max_gradient)
+            self.obj_scale = set_obj_scale(nlp.grad(x0), o.nlp_scaling_max_gradient)
+            con_scale_slk = self.con_scale[self.ind_ineq]
+            self.y /= self.con_scale
+            self.rhs *= self.con_scale
+            self.x[n:] *= con_scale_slk
+            self.xl[n:] *= con_scale_slk
+            self.xu[n:] *= con_scale_slk
         self.kkt.initialize()
         self.eval_jac(self.x)
         self.eval_grad(self.x)
@@ -790,9 +863,14 @@ class MadNLPSolver:
 
     def _kkt_initialize(self): self.kkt.initialize()
 
+    def solution(self):
+        """The result as the reference reports it: un-scaled, in the model's own sense."""
+        return unpack_solution(self, self.x, self.y, self.zl, self.zu)
+
     def _record(self, phase=""):
-        self.history.append(IterRecord(self.cnt.k, self.obj_val, self.inf_pr, self.inf_du, self.inf_compl_v, self.mu,
-                                       self.del_w, self.alpha, self.cnt.l, phase))
+        # (the un-scaled objective, as `print_iter` shows it: IPM/utils.jl:162-179)
+        self.history.append(IterRecord(self.cnt.k, self.obj_val / self.obj_scale, self.inf_pr, self.inf_du, self.inf_compl_v,
+                                       self.mu, self.del_w, self.alpha, self.cnt.l, phase))
 
     # robust restorer pieces
     def _rr_init_vectors(self, RR, mu_R, rho):

@@ -6,6 +6,8 @@ nothing of its control flow except the first trial of the inertia correction.  T
   * the KKT handle:   `set_aug_diagonal!`, `regularize_diagonal!`, `build_kkt!`, `factorize!`, `solve_kkt!`, `mul!`, SpMV
   * `mnk_ipm_*`:      the reductions and elementwise pieces of reference `src/IPM/kernels.jl`, and the loop's plain vector
                       work (`mnk_ipm_vec_*`, `mnk_ipm_get_dot`, `mnk_ipm_gemv`)
+  * `mnk_ipm_vec_mul`, `mnk_ipm_scale_cons`, `mnk_ipm_scale_grad` (csrc/nlp_scale.hip): NLP scaling and the objective sense
+                      around the callbacks' raw values, only when `nlp_scaling` is set or the model maximizes
   * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
   * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
@@ -26,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .ipm import IPMOptions, MadNLPSolver
+from .ipm import IPMOptions, MadNLPSolver, unpack_solution
 from .ipm_device import IPMDeviceKernels
 
 
@@ -35,13 +37,21 @@ def _up(a, dev, dtype=np.float64):
 
 
 class DeviceQPCallbacks:
-    """f = 0.5 x'Hx + q'x, c = Jx with H = Symmetric(hess_com, :L) and J = jt_csc' held by the KKT handle."""
+    """f = 0.5 x'Hx + q'x, c = Jx with H = Symmetric(hess_com, :L) and J = jt_csc' held by the KKT handle.  The data ARE the
+    handle's, so NLP scaling and the sense go into them once, on the host (`prescaled`): H and q times `obj_factor` = obj_sign
+    obj_scale, the rows of J times `con_scale`; the solver applies no factor to what these callbacks return."""
+    prescaled = True
 
-    def __init__(self, nlp, kkt, dev, K):
+    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None):
         self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
-        self.q = _up(nlp.q, dev)
-        self.jv = _up(nlp.jac_coord(None), dev)
-        self.hv = _up(nlp.hess_coord(None, None, 1.0), dev)
+        q, jv, hv = np.asarray(nlp.q, float), np.asarray(nlp.jac_coord(None), float), np.asarray(nlp.hess_coord(None, None, 1.0), float)
+        if obj_factor != 1.0:
+            q, hv = q * obj_factor, hv * obj_factor
+        if con_scale is not None:
+            jv = jv * con_scale[np.asarray(nlp.jac_I, dtype=np.int64)]
+        self.q = _up(q, dev)
+        self.jv = _up(jv, dev)
+        self.hv = _up(hv, dev)
         self.hv0 = torch.empty_like(self.hv)
         K.vec_fill(self.hv0, 0.0)
         self.handle_has_H = True
@@ -90,14 +100,21 @@ class DeviceQPCallbacks:
 
 class DeviceDenseQPCallbacks:
     """f = 0.5 x'Px + q'x, c = Ax with dense P, A on the device (`DenseQPModel`); Hessian / Jacobian of the KKT handle are
-    loaded from these device copies (`mnk_dc_set_hess` / `mnk_dc_set_jac` with device pointers)."""
+    loaded from these device copies (`mnk_dc_set_hess` / `mnk_dc_set_jac` with device pointers).  `prescaled` as
+    `DeviceQPCallbacks`: P and q are uploaded times `obj_factor`, the rows of A times `con_scale`."""
+    prescaled = True
 
-    def __init__(self, nlp, kkt, dev, K):
+    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None):
         self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
+        P, A, q = np.asarray(nlp.P, float), np.asarray(nlp.A, float), np.asarray(nlp.q, float)
+        if obj_factor != 1.0:
+            P, q = P * obj_factor, q * obj_factor
+        if con_scale is not None:
+            A = A * con_scale[:, None]
         # column-major device images (a row-major upload of the transpose IS the column-major matrix)
-        self.P_cm = _up(np.asarray(nlp.P).T, dev)
-        self.A_cm = _up(np.asarray(nlp.A).T, dev)        # (n, m) row-major == (m, n) column-major
-        self.q = _up(nlp.q, dev)
+        self.P_cm = _up(P.T, dev)
+        self.A_cm = _up(A.T, dev)        # (n, m) row-major == (m, n) column-major
+        self.q = _up(q, dev)
         self.P0_cm = torch.empty_like(self.P_cm)
         K.vec_fill(self.P0_cm, 0.0)
         self.handle_has_H = True
@@ -153,7 +170,9 @@ class DeviceDenseQPCallbacks:
 class DeviceOPFCallbacks:
     """Callbacks of `problems.ACOPFModel` on the device (`mnk_opf_*`, csrc/opf_eval.hip): objective, gradient, constraints,
     Jacobian and Lagrangian-Hessian COO values are computed from the device iterate and handed to the KKT handle's
-    compressors without leaving HBM (reference `eval_*_wrapper!`, src/IPM/callbacks.jl:1-96, with a device model)."""
+    compressors without leaving HBM (reference `eval_*_wrapper!`, src/IPM/callbacks.jl:1-96, with a device model).  The values
+    are the model's raw ones (`prescaled = False`): the solver's `eval_*` apply NLP scaling and the sense around them."""
+    prescaled = False
 
     def __init__(self, nlp, kkt, dev, K):
         self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
@@ -217,7 +236,8 @@ class DeviceTapeCallbacks:
     """Callbacks of ANY model written as patterns (`tape_model.TapeModel`) on the device (`mnk_tape_*`, csrc/tape_eval.hip): the
     model's expression tapes are handed to the library once; objective terms, gradient, constraints, Jacobian and
     Lagrangian-Hessian COO values are then interpreted from the device iterate, in the model's own COO order (the KKT handle is
-    created from the model's `jac_I .. hess_J`).  Same method set as `DeviceOPFCallbacks`."""
+    created from the model's `jac_I .. hess_J`).  Same method set as `DeviceOPFCallbacks`, raw values too."""
+    prescaled = False
 
     def __init__(self, nlp, kkt, dev, K):
         nlp.finalize()
@@ -334,8 +354,23 @@ class DeviceMadNLPSolver(MadNLPSolver):
             cls = DeviceOPFCallbacks
         else:
             cls = DeviceQPCallbacks if self.sparse else DeviceDenseQPCallbacks
-        self.cb = cls(self.nlp, self.kkt, self.dev, self.K)
+        # NLP scaling / the sense: the scaled launches replace the plain ones only when there is something to apply
+        self._scaled = bool(self.opt.nlp_scaling) or self.obj_sign != 1.0
+        if cls.prescaled:
+            scaled_data = dict(obj_factor=self.obj_sign * self.obj_scale, con_scale=self.con_scale) if self._scaled else {}
+            self.cb = cls(self.nlp, self.kkt, self.dev, self.K, **scaled_data)
+        else:
+            self.cb = cls(self.nlp, self.kkt, self.dev, self.K)
         self.ind_ineq_t = _up(self.ind_ineq, self.dev, np.int64)
+        if self._scaled:
+            self.con_scale_t = None if cls.prescaled else _up(self.con_scale, self.dev)
+            self.jac_scale_t = _up(self.jac_scale, self.dev) if self.sparse and not cls.prescaled else None
+            self.ybuf = self._new_vec(m)          # y .* con_scale, what the model's Hessian / J' product is given
+            self.slack_pos_t = None
+            if 0 < self.ns < m:                   # the inverse of ind_ineq: a row's slack, -1 for an equality row
+                pos = np.full(m, -1, dtype=np.int64)
+                pos[self.ind_ineq] = np.arange(self.ns)
+                self.slack_pos_t = _up(pos, self.dev, np.int64)
         self.kkt.device_kkt_ops = True
         if not self.sparse:          # the dense handle reads Hessian / Jacobian from its own device copies
             self.cb.load_jac()
@@ -356,19 +391,26 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_f(self, x):
         if not self._on_device:
             return super().eval_f(x)
-        return self.cb.obj(x[:self.n])
+        if self.cb.prescaled:
+            return self.cb.obj(x[:self.n])
+        return self.obj_sign * (self.cb.obj(x[:self.n]) * self.obj_scale)
 
     def eval_grad(self, x):
         if not self._on_device:
             return super().eval_grad(x)
         self.cb.grad(self.f[:self.n], x[:self.n])
-        self.K.vec_fill(self.f[self.n:], 0.0)
+        if self._scaled and not self.cb.prescaled:     # the factor and the zero slack part in one launch
+            self.K.scale_grad(self.f, self.n, self.obj_sign * self.obj_scale)
+        else:
+            self.K.vec_fill(self.f[self.n:], 0.0)
         self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
         if not self._on_device:
             return super().eval_cons(c, x)
         self.cb.cons(c, x[:self.n])
+        if self._scaled:                               # c .* con_scale - slack - rhs in one launch
+            return self.K.scale_cons(c, self.con_scale_t, x[self.n:], self.slack_pos_t, self.rhs)
         if self.ns == self.m:
             self.K.vec_axpby(c, 1.0, c, -1.0, x[self.n:])      # ind_ineq = all constraints, in order
         else:
@@ -378,6 +420,10 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_jac(self, x):
         if not self._on_device:
             return super().eval_jac(x)
+        if self._scaled and not self.cb.prescaled:
+            jv = self.cb.jac_coord(x[:self.n])
+            self.K.vec_mul(jv, jv, self.jac_scale_t)
+            return self.kkt.compress_jacobian(jv)
         self.cb.load_jac(x[:self.n])
 
     def eval_lag_hess(self, x, y, is_resto=False):
@@ -385,7 +431,12 @@ class DeviceMadNLPSolver(MadNLPSolver):
             return super().eval_lag_hess(x, y, is_resto)
         if self.qn is not None:
             return self._eval_lag_hess_qn_device(x, y)
-        self.cb.load_hess(x[:self.n], y, 0.0 if is_resto else 1.0)   # objective weight 0 in robust!
+        w = 0.0 if is_resto else 1.0                                 # objective weight 0 in robust!
+        if self._scaled and not self.cb.prescaled:
+            self.K.vec_mul(self.ybuf, y, self.con_scale_t)
+            self.kkt.compress_hessian(self.cb.hess_coord(x[:self.n], self.ybuf, w * self.obj_sign * self.obj_scale))
+        else:
+            self.cb.load_hess(x[:self.n], y, w)
         self.cnt.lag_hess_cnt += 1
 
     # ------------------------------------------------------------------ quasi-Newton Hessian in the handle's device buffer
@@ -410,6 +461,9 @@ class DeviceMadNLPSolver(MadNLPSolver):
         jl = jv = None
         if self.m > 0:
             jl = self.jacl[:n]                                      # J(x+)' l+ (current: see the host mirror)
+            if self._scaled and not self.cb.prescaled:              # J(x)' (l .* con_scale), nlpmodels.jl:791-801
+                self.K.vec_mul(self.ybuf, y, self.con_scale_t)
+                y = self.ybuf
             self.cb.jtprod_at(d.last_x, y, d.last_jv)
             jv = d.last_jv
         self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
@@ -755,6 +809,10 @@ class DeviceMadNLPSolver(MadNLPSolver):
             self.initialize()          # host (numpy), once
             self._upload()
         return super().solve()
+
+    def solution(self):
+        """`MadNLPSolver.solution` from a download of the iterate."""
+        return unpack_solution(self, *self.host_state())
 
     def host_state(self):
         """x, y, zl, zu on the host (tests, reporting)."""

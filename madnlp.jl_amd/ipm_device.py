@@ -236,6 +236,25 @@ class IPMDeviceKernels:
         if out.numel():
             self._void("mnk_ipm_vec_gather", _dev(out), float(a), _dev(x), idx.data_ptr(), int(out.numel()))
 
+    # ---- NLP scaling and objective sense around the callbacks' raw values (csrc/nlp_scale.hip)
+    def vec_mul(self, out, a, b):
+        """out = a .* b; out may alias a or b."""
+        assert out.numel() == a.numel() == b.numel()
+        self._void("mnk_ipm_vec_mul", _dev(out), _dev(a), _dev(b), int(out.numel()))
+
+    def scale_cons(self, c, con_scale, slack, slack_pos, rhs):
+        """c = c .* con_scale (None: ones), minus every row's slack, minus rhs, in one launch.  `slack_pos` (int64 device
+        tensor, one entry per row): the position of the row's slack, negative for an equality row; None: row i owns slack i."""
+        ns = int(slack.numel())
+        assert rhs.numel() == c.numel() and (con_scale is None or con_scale.numel() == c.numel())
+        assert slack_pos is None or slack_pos.numel() == c.numel()
+        self._void("mnk_ipm_scale_cons", _dev(c), None if con_scale is None else _dev(con_scale), _dev(slack) if ns else None,
+                   None if slack_pos is None else slack_pos.data_ptr(), ns, _dev(rhs), int(c.numel()))
+
+    def scale_grad(self, f, n, factor):
+        """f[:n] *= factor, f[n:] = 0."""
+        self._void("mnk_ipm_scale_grad", _dev(f), int(n), int(f.numel()), float(factor))
+
     def bound_dual_axpy(self, zl, zu, a, dzl, dzu):
         self._void("mnk_ipm_bound_dual_axpy", _dev(zl), _dev(zu), float(a), _dev(dzl), _dev(dzu))
 

@@ -461,6 +461,46 @@ class LootsmaModel:
         return np.asfortranarray(np.diag(self.hess_coord(x, y, w)))
 
 
+class SimplexLPModel:
+    """The LP of the reference's `test_scaling` and `test_max_problem` (lib/MadNLPTests/src/MadNLPTests.jl:334-379):
+    min / max  big (x1 + 2 x2 + 3 x3)  s.t.  big (x1 + x2 + x3) = big,  x >= 0,  x0 = 0.  `test_scaling` is `big = 1e6`,
+    minimized (answer x = (1, 0, 0), multiplier -1, bound multipliers (0, big, 2 big)); `test_max_problem` is `big = 1`,
+    maximized (`minimize = False`: objective 3 at (0, 0, 1), multiplier -3, bound multipliers (2, 1, 0))."""
+    n, m = 3, 1
+    jac_I = np.array([0, 0, 0])
+    jac_J = np.array([0, 1, 2])
+    hess_I = np.zeros(0, dtype=np.int64)
+    hess_J = np.zeros(0, dtype=np.int64)
+
+    def __init__(self, big=1.0, minimize=True):
+        self.big, self.minimize = float(big), bool(minimize)
+        self.cost = self.big * np.array([1.0, 2.0, 3.0])
+        self.x0, self.y0 = np.zeros(3), np.zeros(1)
+        self.lvar, self.uvar = np.zeros(3), np.full(3, np.inf)
+        self.lcon, self.ucon = np.array([self.big]), np.array([self.big])
+
+    def obj(self, x):
+        return float(self.cost @ x)
+
+    def grad(self, x):
+        return self.cost.copy()
+
+    def cons(self, x):
+        return np.array([self.big * (x[0] + x[1] + x[2])])
+
+    def jac_coord(self, x):
+        return np.full(3, self.big)
+
+    def jac_dense(self, x):
+        return np.full((1, 3), self.big, order="F")
+
+    def hess_coord(self, x, y, w=1.0):
+        return np.zeros(0)
+
+    def hess_dense(self, x, y, w=1.0):
+        return np.zeros((3, 3), order="F")
+
+
 class DenseQPModel:
     """min 0.5 x'Px + q'x  s.t. 0 <= x <= 1, gl <= Ax <= gu -- the reference's DenseDummyQP
     (lib/MadNLPTests/src/Instances/dummy_qp.jl) with our own seeded RNG."""

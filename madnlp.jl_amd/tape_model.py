@@ -332,8 +332,9 @@ class TapeModel:
     lvar, uvar, lcon, ucon, jac_I, jac_J, hess_I, hess_J, obj, grad, cons, jac_coord, hess_coord(x, y, w)`)."""
     is_tape_model = True      # what `DeviceMadNLPSolver` selects `DeviceTapeCallbacks` by
 
-    def __init__(self, n, m, x0, lvar, uvar, lcon, ucon, name="tape"):
+    def __init__(self, n, m, x0, lvar, uvar, lcon, ucon, name="tape", minimize=True):
         self.n, self.m, self.name = int(n), int(m), name
+        self.minimize = bool(minimize)      # the objective sense (False: the drivers maximize)
         f = lambda a, k: np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (k,)))  # noqa: E731
         self.x0, self.lvar, self.uvar = f(x0, self.n), f(lvar, self.n), f(uvar, self.n)
         self.lcon, self.ucon = f(lcon, self.m), f(ucon, self.m)
@@ -522,4 +523,16 @@ def lootsma_tape_model():
     xyz = np.array([[0, 1, 2]])
     M.add_constraint(-sqrt(V(0)) - sqrt(V(1)) + sqrt(V(2)), np.array([0]), xyz)
     M.add_constraint(sqrt(V(0)) + sqrt(V(1)) + sqrt(V(2)), np.array([1]), xyz)
+    return M.finalize()
+
+
+def simplex_lp_tape_model(big=1.0, minimize=True):
+    """`problems.SimplexLPModel` as patterns (the LP of the reference's `test_scaling` / `test_max_problem`); it has no
+    second derivatives, so its Hessian pattern is empty."""
+    from .problems import SimplexLPModel
+    A = SimplexLPModel(big, minimize)
+    M = TapeModel(3, 1, A.x0, A.lvar, A.uvar, A.lcon, A.ucon, name="tape_simplex_lp", minimize=minimize)
+    xs = np.array([[0], [1], [2]])
+    M.add_objective(P(0) * V(0), xs, A.cost[:, None])
+    M.add_constraint(P(0) * V(0), np.zeros(3, dtype=np.int64), xs, np.full((3, 1), A.big))
     return M.finalize()
