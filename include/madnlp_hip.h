@@ -553,7 +553,10 @@ int mnk_opf_hess_coord(mnk_opf* opf, const double* x, const double* y, double ob
  * row, rows fed by none evaluate to 0).  `madnlp_jl_amd.tape_model` compiles an expression to the three tapes a pattern is
  * added with -- 0 value (one output), 1 first derivatives (out_j[o] = local variable), 2 second derivatives (out_j[o] >=
  * out_l[o] = local pair) -- and is the host mirror.  A tape is straight-line code: `code` holds (op, dst_slot, a, b) per
- * instruction, op 0 add 1 sub 2 mul 3 div 4 neg 5 sin 6 cos 7 exp 8 log 9 sqrt (4 .. 9 read `a` only); an operand is
+ * instruction, op 0 add 1 sub 2 mul 3 div 4 neg 5 sin 6 cos 7 exp 8 log 9 sqrt 16 pow 17 tan 18 atan 19 tanh 20 abs
+ * 21 sign 22 step 23 min 24 max (10 .. 15 are unassigned and refused; 0 .. 3, 16, 23 and 24 read `a` and `b`, the others
+ * `a` only); min = (b < a) ? b : a, max = (b > a) ? b : a, step = (a >= 0) ? 1 : 0, sign = (a > 0) ? 1 : (a < 0) ? -1 : 0
+ * as written, abs clears the sign bit.  An operand is
  * kind << 24 | index with kind 0 slot (< nslot <= 32), 1 local variable (< k <= 8), 2 parameter column (< q <= 8),
  * 3 constant (< nconst).  var_index is R x k and params R x q, row-major; all index arrays are host, 0-based; a row of
  * var_index names k distinct variables.  mnk_tape_add_pattern checks everything a kernel will index with and returns
@@ -579,6 +582,9 @@ int mnk_tape_add_pattern(void* tape, int kind /* 0 objective, 1 constraint */, i
                          const int32_t* out_operand2, const int32_t* out_j2, const int32_t* out_l2, int nslot2);
 int mnk_tape_finalize(void* tape);
 int mnk_tape_sizes(void* tape, int64_t* n, int64_t* m, int64_t* nterms, int64_t* nnzj, int64_t* nnzh);
+/* which callback launches have a tape with an opcode from 16 on and therefore run the larger of the two interpreter
+ * kernels: the sum of obj 1, grad 2, cons 4, jac 8, hess 16 (0: every launch runs the kernel that knows 0 .. 9 only) */
+int mnk_tape_extended(void* tape, int* mask);
 int mnk_tape_get_structure(void* tape, int32_t* jac_I, int32_t* jac_J, int32_t* hess_I, int32_t* hess_J);
 int mnk_tape_obj_terms(void* tape, const double* x, double* terms /* nterms; obj = sum(terms) */);
 int mnk_tape_grad(void* tape, const double* x, double* g);

@@ -203,6 +203,7 @@ SIGNATURES = {
                              + [C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int] * 3),
     "mnk_tape_finalize": (C.c_int, [_vp]),
     "mnk_tape_sizes": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mnk_tape_extended": (C.c_int, [_vp, _vp]),
     "mnk_tape_get_structure": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mnk_tape_obj_terms": (C.c_int, [_vp, _vp, _vp]),
     "mnk_tape_grad": (C.c_int, [_vp, _vp, _vp]),

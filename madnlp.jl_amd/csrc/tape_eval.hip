@@ -3,10 +3,16 @@
 // each one scalar expression applied to R rows of index and parameter data; `madnlp_jl_amd.tape_model` compiles every pattern to
 // three straight-line tapes (value | first derivatives | second derivatives of the local pairs j >= l) and is the host mirror of
 // this file: the same instructions in the same order, so everything built from + - * / and negation is bit-identical
-// (no FMA contraction); sin / cos / exp / log come from another math library.
+// (no FMA contraction), and so are abs / sign / step / min / max, which are comparisons and a sign-bit mask on both sides;
+// sin / cos / exp / log / pow / tan / atan / tanh come from another math library.
 //
 //   instruction   (op, dst, a, b), 4 x int32; operand = kind << 24 | index: 0 slot, 1 local variable, 2 parameter column,
-//                 3 constant pool; unary operations read `a` only
+//                 3 constant pool; unary operations read `a` only.  Opcodes 0 .. 9 and 16 .. 24 (10 .. 15 are unassigned).
+//   two kernels   ONE body, instantiated twice: tape_kernel<false> knows opcodes 0 .. 9 and is, instruction for instruction,
+//                 the kernel from before opcodes 16 .. 24 existed (the registers of pow / tan / atan / tanh would halve the
+//                 occupancy of every model that never calls them, and any further branch lengthens the path of every
+//                 interpreted instruction); tape_kernel<true> knows 16 .. 24 as well.  mnk_tape_finalize picks per callback
+//                 launch (does any tape of it hold an opcode >= 16?); a launch stays one launch over all patterns.
 //   outputs       tape output o of row r is stored at out[base + o * R + r]; Hessian outputs are multiplied by y[rows[r]]
 //                 (constraint pattern) or obj_weight (objective pattern) on the way out
 //   kernel        one thread per pattern row, one launch per callback through a block -> (tape, first row) table; the instruction
@@ -32,7 +38,8 @@ constexpr int TAPE_SLOT_MAX = 32;   // LDS: (32 + 8 + 8) columns x 128 lanes x 8
 constexpr int TAPE_K_MAX = 8;
 constexpr int TAPE_Q_MAX = 8;
 constexpr int TAPE_BS = 128;
-constexpr int TAPE_NOPS = 10;       // add sub mul div neg sin cos exp log sqrt
+constexpr int TAPE_NOPS = 10;       // 0 .. 9: add sub mul div neg sin cos exp log sqrt
+enum { OP_POW = 16, OP_TAN, OP_ATAN, OP_TANH, OP_ABS, OP_SIGN, OP_STEP, OP_MIN, OP_MAX, OP_END };
 constexpr int64_t TAPE_COUNT_MAX = (1LL << 31) - 2 * TAPE_BS;
 
 enum { G_OBJ = 0, G_GRAD, G_CONS, G_JAC, G_HESS, G_COUNT };
@@ -44,6 +51,7 @@ struct TapeDesc {      // one tape of one pattern as the kernel sees it
 
 struct HostTape {
     int nslot = 0;
+    bool extended = false;          // has an instruction with an opcode >= 16
     std::vector<int32_t> code;      // 4 per instruction; operands already LDS columns (>= 0) or ~constant index (< 0)
     std::vector<int32_t> outs;
     std::vector<double> consts;
@@ -69,6 +77,9 @@ __device__ __forceinline__ double tape_fetch(const double* col, const double* __
     return consts[~o];
 }
 
+// EXT: the instantiation that knows opcodes 16 .. 24.  The selection operations are comparisons, not fmin / fmax /
+// copysign: min = (b < a) ? b : a, max = (b > a) ? b : a, step = (a >= 0), sign = (a > 0) - (a < 0), abs clears the sign bit.
+template <bool EXT>
 __global__ __launch_bounds__(TAPE_BS) void tape_kernel(const TapeDesc* __restrict__ descs, const int2* __restrict__ blocks,
                                                         const int32_t* __restrict__ vi, const double* __restrict__ par,
                                                         const int32_t* __restrict__ rows, const int4* __restrict__ code,
@@ -93,6 +104,19 @@ __global__ __launch_bounds__(TAPE_BS) void tape_kernel(const TapeDesc* __restric
         if (op < 4) {
             const double b = tape_fetch(col, cp, __builtin_amdgcn_readfirstlane(ins.w));
             v = op == 0 ? a + b : op == 1 ? a - b : op == 2 ? a * b : a / b;
+        } else if (EXT && op >= OP_POW) {
+            const double b = tape_fetch(col, cp, __builtin_amdgcn_readfirstlane(ins.w));      // (the unary ones carry `a` twice)
+            switch (op) {
+                case OP_POW: v = pow(a, b); break;
+                case OP_TAN: v = tan(a); break;
+                case OP_ATAN: v = atan(a); break;
+                case OP_TANH: v = tanh(a); break;
+                case OP_ABS: v = __longlong_as_double(__double_as_longlong(a) & 0x7FFFFFFFFFFFFFFFLL); break;
+                case OP_SIGN: v = a > 0.0 ? 1.0 : a < 0.0 ? -1.0 : 0.0; break;
+                case OP_STEP: v = a >= 0.0 ? 1.0 : 0.0; break;
+                case OP_MIN: v = b < a ? b : a; break;
+                default: v = b > a ? b : a; break;
+            }
         } else {
             switch (op) {
                 case 4: v = -a; break;
@@ -165,18 +189,21 @@ int check_tape(const char* what, int k, int q, int64_t ninstr, const int32_t* co
         return 0;
     };
     T.nslot = nslot;
+    T.extended = false;
     T.code.resize(4 * ninstr);
     for (int64_t i = 0; i < ninstr; ++i) {
         const int32_t op = code[4 * i], dst = code[4 * i + 1];
-        if (op < 0 || op >= TAPE_NOPS) TAPE_FAIL("mnk_tape_add_pattern: %s tape, instruction %lld: bad opcode %d (0 .. %d)", what, (long long)i, op, TAPE_NOPS - 1);
+        if (op < 0 || (op >= TAPE_NOPS && op < OP_POW) || op >= OP_END)
+            TAPE_FAIL("mnk_tape_add_pattern: %s tape, instruction %lld: bad opcode %d (0 .. %d, %d .. %d)", what, (long long)i, op, TAPE_NOPS - 1, (int)OP_POW, OP_END - 1);
         if (dst < 0 || dst >= nslot) TAPE_FAIL("mnk_tape_add_pattern: %s tape, instruction %lld: destination slot %d is out of range (nslot = %d)", what, (long long)i, dst, nslot);
         int32_t ca = 0, cb = 0;
         if (column(code[4 * i + 2], i, "instruction", &ca)) return -1;
-        if (op < 4) {
+        if (op < 4 || op == OP_POW || op == OP_MIN || op == OP_MAX) {
             if (column(code[4 * i + 3], i, "instruction", &cb)) return -1;
         } else {
             cb = ca;
         }
+        T.extended |= op >= OP_POW;
         written[dst] = true;
         T.code[4 * i] = op; T.code[4 * i + 1] = dst; T.code[4 * i + 2] = ca; T.code[4 * i + 3] = cb;
     }
@@ -218,6 +245,7 @@ struct mnk_tape {
     DevBuf<int2> blocks[G_COUNT];
     int64_t nblocks[G_COUNT] = {};
     size_t lds_bytes[G_COUNT] = {};
+    bool extended[G_COUNT] = {};    // the launch has a tape with an opcode >= 16: tape_kernel<true>
     DevBuf<int32_t> vi, rows, code, outs, g_ptr, g_idx, c_ptr, c_idx;
     DevBuf<double> par, consts, gterm, cterm;
 };
@@ -354,6 +382,7 @@ int mnk_tape_finalize(void* tape) {
             if (d.nout > 0) {
                 for (int64_t r0 = 0; r0 < p.R; r0 += TAPE_BS) blocks[group].push_back(int2{(int)descs.size(), (int)r0});
                 maxcol[group] = std::max(maxcol[group], t.nslot + p.k + p.q);
+                h->extended[group] |= t.extended;
             }
             descs.push_back(d);
         }
@@ -388,6 +417,15 @@ int mnk_tape_sizes(void* tape, int64_t* n, int64_t* m, int64_t* nterms, int64_t*
     return 0;
 }
 
+// which callback launches run the extended kernel: obj = 1, grad = 2, cons = 4, jac = 8, hess = 16
+int mnk_tape_extended(void* tape, int* mask) {
+    mnk_tape* h = static_cast<mnk_tape*>(tape);
+    MNK_REQUIRE(h != nullptr && mask != nullptr && h->finalized, "mnk_tape_extended: NULL argument or unfinalized handle");
+    *mask = 0;
+    for (int g = 0; g < G_COUNT; ++g) *mask |= (int)h->extended[g] << g;
+    return 0;
+}
+
 int mnk_tape_get_structure(void* tape, int32_t* jac_I, int32_t* jac_J, int32_t* hess_I, int32_t* hess_J) {
     mnk_tape* h = static_cast<mnk_tape*>(tape);
     MNK_REQUIRE(h != nullptr && h->finalized, "mnk_tape_get_structure: NULL or unfinalized handle");
@@ -400,7 +438,7 @@ int mnk_tape_get_structure(void* tape, int32_t* jac_I, int32_t* jac_J, int32_t* 
 
 static int tape_launch(mnk_tape* h, int g, const double* x, const double* y, double w, double* out) {
     if (h->nblocks[g] == 0) return 0;
-    hipLaunchKernelGGL(tape_kernel, dim3((unsigned)h->nblocks[g]), dim3(TAPE_BS), h->lds_bytes[g], h->ctx->stream, h->descs.p,
+    hipLaunchKernelGGL(h->extended[g] ? tape_kernel<true> : tape_kernel<false>, dim3((unsigned)h->nblocks[g]), dim3(TAPE_BS), h->lds_bytes[g], h->ctx->stream, h->descs.p,
                        h->blocks[g].p, h->vi.p, h->par.p, h->rows.p, (const int4*)h->code.p, h->consts.p, h->outs.p, x, y, w, out);
     MNK_HIP(hipGetLastError());
     return 0;

@@ -273,6 +273,15 @@ class DeviceTapeCallbacks:
         if nnzh:
             K.vec_fill(self.hv0, 0.0)
 
+    EXT_OBJ, EXT_GRAD, EXT_CONS, EXT_JAC, EXT_HESS = 1, 2, 4, 8, 16
+
+    def extended(self):
+        """Which callback launches run the interpreter kernel that knows the opcodes from 16 on -- pow tan atan tanh abs sign step
+        min max -- (`mnk_tape_extended`): the sum of EXT_OBJ .. EXT_HESS; 0 for a model that uses none of them."""
+        mask = C.c_int(-1)
+        L.check(L.lib().mnk_tape_extended(self._h, C.byref(mask)), "mnk_tape_extended")
+        return mask.value
+
     def obj_terms(self, x):
         L.check(L.lib().mnk_tape_obj_terms(self._h, x.data_ptr(), self.terms.data_ptr()), "mnk_tape_obj_terms")
         return self.terms

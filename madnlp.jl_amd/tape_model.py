@@ -3,8 +3,9 @@ index and parameter data (the way ExaModels compiles the models of the reference
 expression TAPES that one interpreter evaluates -- here in numpy (the host mirror and oracle), in `csrc/tape_eval.hip` on the
 device (`mnk_tape_*`, `ipm_dev.DeviceTapeCallbacks`).  DESIGN.md section 14 documents the format.
 
-  expression   V(j) local variable j of the row, P(c) parameter column c, float constants; + - * / unary minus, non-negative
-               integer powers (expanded to products), sin cos exp log sqrt
+  expression   V(j) local variable j of the row, P(c) parameter column c, float constants; + - * / unary minus, powers (integer
+               exponents expanded to products, 0.5 a square root, anything else `pow_`), sin cos exp log sqrt tan atan tanh, and
+               the piecewise abs_ sign step minimum maximum (defined by comparisons, see `minimum`)
   pattern      objective:  f   += sum_r expr(x[var_index[r, :]], params[r, :])
                constraint: c[rows[r]] += expr(x[var_index[r, :]], params[r, :])      (several patterns may feed one row)
   tapes        per pattern three: value | first derivatives per local variable | second derivatives per local pair j >= l;
@@ -28,11 +29,32 @@ SLOT_MAX = 32    # slots of one tape (its live intermediate values); the device 
 K_MAX = 8        # local variables of a pattern
 Q_MAX = 8        # parameter columns of a pattern
 OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_SIN, OP_COS, OP_EXP, OP_LOG, OP_SQRT = range(10)
-OP_NAMES = ("add", "sub", "mul", "div", "neg", "sin", "cos", "exp", "log", "sqrt")
+OP_POW, OP_TAN, OP_ATAN, OP_TANH, OP_ABS, OP_SIGN, OP_STEP, OP_MIN, OP_MAX = range(16, 25)      # 10 .. 15 are unassigned
+OP_NAMES = ("add", "sub", "mul", "div", "neg", "sin", "cos", "exp", "log", "sqrt") + (None,) * 6 + \
+           ("pow", "tan", "atan", "tanh", "abs", "sign", "step", "min", "max")
+OP_EXTENDED = frozenset(range(OP_POW, OP_MAX + 1))      # what the device keeps in the second instantiation of its kernel
 KIND_SLOT, KIND_VAR, KIND_PAR, KIND_CONST = range(4)
-_UNARY = {OP_NEG: np.negative, OP_SIN: np.sin, OP_COS: np.cos, OP_EXP: np.exp, OP_LOG: np.log, OP_SQRT: np.sqrt}
-_BINARY = {OP_ADD: np.add, OP_SUB: np.subtract, OP_MUL: np.multiply, OP_DIV: np.divide}
-_FOLD = {OP_SIN: math.sin, OP_COS: math.cos, OP_EXP: math.exp, OP_LOG: math.log, OP_SQRT: math.sqrt}
+
+
+# The selection operations are these comparisons on both interpreters (not fmin / fmax / copysign, whose NaN and signed-zero
+# rules differ between libraries): a NaN in `b` returns `a`, sign(NaN) = 0, a tie returns `a`.
+def _np_min(a, b): return np.where(np.less(b, a), b, a)
+def _np_max(a, b): return np.where(np.greater(b, a), b, a)
+def _np_step(a): return np.where(np.greater_equal(a, 0.0), 1.0, 0.0)
+def _np_sign(a): return np.where(np.greater(a, 0.0), 1.0, np.where(np.less(a, 0.0), -1.0, 0.0))
+def _py_min(a, b): return b if b < a else a
+def _py_max(a, b): return b if b > a else a
+def _py_step(a): return 1.0 if a >= 0.0 else 0.0
+def _py_sign(a): return 1.0 if a > 0.0 else -1.0 if a < 0.0 else 0.0
+
+
+_UNARY = {OP_NEG: np.negative, OP_SIN: np.sin, OP_COS: np.cos, OP_EXP: np.exp, OP_LOG: np.log, OP_SQRT: np.sqrt,
+          OP_TAN: np.tan, OP_ATAN: np.arctan, OP_TANH: np.tanh, OP_ABS: np.abs, OP_SIGN: _np_sign, OP_STEP: _np_step}
+_BINARY = {OP_ADD: np.add, OP_SUB: np.subtract, OP_MUL: np.multiply, OP_DIV: np.divide,
+           OP_POW: np.power, OP_MIN: _np_min, OP_MAX: _np_max}
+_FOLD = {OP_SIN: math.sin, OP_COS: math.cos, OP_EXP: math.exp, OP_LOG: math.log, OP_SQRT: math.sqrt,
+         OP_TAN: math.tan, OP_ATAN: math.atan, OP_TANH: math.tanh, OP_ABS: abs, OP_SIGN: _py_sign, OP_STEP: _py_step}
+_FOLD2 = {OP_POW: math.pow, OP_MIN: _py_min, OP_MAX: _py_max}
 
 
 class Expr:
@@ -69,15 +91,8 @@ class Expr:
     def __neg__(self): return _neg(self)
     def __pos__(self): return self
 
-    def __pow__(self, p):
-        if not isinstance(p, (int, np.integer)) or p < 0:
-            raise TypeError("tape expressions take non-negative integer powers only")
-        if p == 0:
-            return const(1.0)
-        e = self
-        for _ in range(int(p) - 1):
-            e = e * self
-        return e
+    def __pow__(self, p): return pow_(self, p)
+    def __rpow__(self, o): return pow_(o, self)
 
 
 def const(v):
@@ -184,6 +199,63 @@ def cos(a): return _fun(OP_COS, a)
 def exp(a): return _fun(OP_EXP, a)
 def log(a): return _fun(OP_LOG, a)
 def sqrt(a): return _fun(OP_SQRT, a)
+def tan(a): return _fun(OP_TAN, a)
+def atan(a): return _fun(OP_ATAN, a)
+def tanh(a): return _fun(OP_TANH, a)
+
+
+def abs_(a):
+    """|a|: the sign bit cleared; its derivative is sign(a), 0 at the kink"""
+    return _fun(OP_ABS, a)
+
+
+def sign(a):
+    """(a > 0) ? 1 : (a < 0) ? -1 : 0 -- 0 for +-0 and for NaN; its derivative is the structural zero"""
+    return _fun(OP_SIGN, a)
+
+
+def step(a):
+    """(a >= 0) ? 1 : 0 -- 1 for +-0, 0 for NaN; its derivative is the structural zero"""
+    return _fun(OP_STEP, a)
+
+
+def _fun2(op, a, b):
+    a, b = _wrap(a), _wrap(b)
+    if a.is_const and b.is_const:
+        try:
+            return const(_FOLD2[op](a.value, b.value))
+        except (ValueError, OverflowError, ZeroDivisionError):     # a negative base with a real exponent, 0 ** -1: run time
+            pass
+    return _node(op, a, b)
+
+
+def minimum(a, b):
+    """(b < a) ? b : a -- a tie and a NaN in `b` return `a`; the derivative follows the same choice: db + step(b - a) (da - db)"""
+    return _fun2(OP_MIN, a, b)
+
+
+def maximum(a, b):
+    """(b > a) ? b : a -- a tie and a NaN in `b` return `a`; the derivative follows the same choice: db + step(a - b) (da - db)"""
+    return _fun2(OP_MAX, a, b)
+
+
+def pow_(a, b):
+    """a ** b.  A constant exponent with an integer value is expanded to products (a negative one to 1 / products, 0 to the
+    constant 1), 0.5 is sqrt(a); every other exponent is the pow instruction.  With a constant exponent c the derivative is
+    c pow(a, c - 1) da and holds wherever pow does; with an exponent that is an expression it is
+    pow(a, b) (db log a + b da / a), which needs a > 0."""
+    a, b = _wrap(a), _wrap(b)
+    if b.is_const and abs(b.value) < 2.0 ** 31 and b.value == math.floor(b.value):     # (NaN and inf fail the bound)
+        k = int(b.value)
+        if k == 0:
+            return const(1.0)
+        e = a
+        for _ in range(abs(k) - 1):
+            e = _mul(e, a)
+        return e if k > 0 else _div(const(1.0), e)
+    if _is(b, 0.5):
+        return sqrt(a)
+    return _fun2(OP_POW, a, b)
 
 
 def diff(e, j):
@@ -202,6 +274,8 @@ def _diff(e, j):
         return const(0.0)
     if op == "var":
         return const(1.0 if e.value == j else 0.0)
+    if op in (OP_SIGN, OP_STEP):              # piecewise constant: a structural zero (the jump is not differentiated)
+        return const(0.0)
     da = diff(e.a, j)
     if op == OP_ADD:
         return _add(da, diff(e.b, j))
@@ -226,6 +300,22 @@ def _diff(e, j):
         return _div(da, e.a)
     if op == OP_SQRT:
         return _div(da, _mul(const(2.0), e))
+    if op == OP_POW:
+        if e.b.is_const:
+            return _mul(_mul(e.b, pow_(e.a, e.b.value - 1.0)), da)
+        return _mul(e, _add(_mul(diff(e.b, j), log(e.a)), _div(_mul(e.b, da), e.a)))
+    if op == OP_TAN:
+        return _mul(_add(const(1.0), _mul(e, e)), da)
+    if op == OP_ATAN:
+        return _div(da, _add(const(1.0), _mul(e.a, e.a)))
+    if op == OP_TANH:
+        return _mul(_sub(const(1.0), _mul(e, e)), da)
+    if op == OP_ABS:
+        return _mul(sign(e.a), da)
+    if op in (OP_MAX, OP_MIN):                # the derivative of the operand the value rule selects (`a` at a tie)
+        db = diff(e.b, j)
+        pick_a = step(_sub(e.a, e.b) if op == OP_MAX else _sub(e.b, e.a))
+        return _add(db, _mul(pick_a, _sub(da, db)))
     raise AssertionError(op)
 
 
