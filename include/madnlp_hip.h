@@ -694,6 +694,16 @@ int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2, int taper0
 int mnk_sc_debug_tile_env(mnk_sc* sc, int64_t order, int32_t* out, int cap);
 /* ... and the one mnk_ls_factorize_csc derives from a lower CSC matrix of order n. */
 int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap);
+/* The same per 64-row HALF of a tile row, in 64-column units (option "envelope_half" of a linear solver, default 1, ignored with
+ * "envelope" = 0: the waves of a bulk chunk skip the k-tiles left of the envelopes of their own halves and the upper quadrant of a
+ * diagonal tile): two entries per tile row, envh[2I] and envh[2I + 1]; tile_env[I] = min(envh[2I], envh[2I + 1]) / 2.  Returns the
+ * number of halves, 2 * ((order + 127) / 128). */
+int mnk_sc_debug_tile_envh(mnk_sc* sc, int64_t order, int32_t* out, int cap);
+int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap);
+/* The statistics "envh_ksteps" (count[0]) and "envh_ksteps_skipped" (count[1]) of mnk_ls_get_stat for the task list of `ntile`
+ * tiles: half-tile k-steps (a 64 x 64 quadrant of a tile over 64 columns) that the tile envelope `env` leaves of the bulk tasks /
+ * of them skipped with the half-tile envelope `envh` (NULL: none).  Returns the number of tasks. */
+int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int taper0, const int* env, const int* envh, int64_t* count);
 
 /* Diagnostics (tools/microbench_update.py): time `reps` lower-tile trailing updates C -= A*A^T under the
  * schedules the factorization uses (static tiling / tile queue; context, update, update+panel streams). */

@@ -287,5 +287,7 @@ constexpr int DAG_QHEAD_STRIDE = 32;  // ints between two queue heads (128 bytes
 constexpr int DAG_QHEAD_WORDS = (DAG_NQ + 1) * DAG_QHEAD_STRIDE;   // the heads of one launch and, behind them, its count of stolen tasks
 void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
                     std::vector<int>& off);
+// half-tile k-steps of a task list under the tile envelope `env` (NULL: none) / of them skipped with the half-tile envelope `envh` (NULL: none)
+void dag_envh_count(const std::vector<int>& tasks, const int* env, const int* envh, int nenv, int64_t* count);
 
 }  // namespace mnk

@@ -67,6 +67,7 @@ struct DagInst {
     int64_t N;            // order of the matrix (rows / columns N .. Np - 1 are padding: unit diagonal)
     const int* env;       // envelope per tile row (mnk_sc::tile_env): L(I, k) = 0 for tile columns k < env[I]; NULL: dense
     const int* envgate;   // != 0: a NaN / Inf entry was transferred, the envelope is off for this factorization (mnk_ls::env_word)
+    const int* envh;      // envelope per 64-row half of a tile row in 64-column units (mnk_sc::tile_envh; only dag_bulk_kernel1 reads it); NULL: none
 };
 
 // (read through the constant address space: the fields are uniform and never written while a bulk kernel runs, so every use
@@ -580,6 +581,7 @@ struct DagArgs1 {
     int64_t N;
     const int* env;             // (as in DagInst)
     const int* envgate;
+    const int* envh;
     // per-XCD queues (dag_deal_tasks): nq > 0: `tasks` is the dealt copy of the list, queue x = tasks [qoff[x], qoff[x + 1]), its head
     // qheads[x * DAG_QHEAD_STRIDE]; a task's position in the LIST (the index of its trace record) rides in the third word above
     // the tile column.  nq == 0: one queue, the list as built, popped through `qctr`.
@@ -634,6 +636,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
     if (threadIdx.x < 4) s_stat[threadIdx.x] = 0;
     // the envelope of this factorization (NULL: dense -- no envelope, or a NaN / Inf entry)
     const int* __restrict__ env = a.env != nullptr && __builtin_amdgcn_readfirstlane(*a.envgate) == 0 ? a.env : nullptr;
+    const int* __restrict__ envh = env != nullptr ? a.envh : nullptr;   // (the same gate)
     __syncthreads();
     for (;;) {
         int tid = threadIdx.x;
@@ -678,6 +681,21 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             eI = __builtin_amdgcn_readfirstlane(env[I]);
             k0 = min(kend, max(kbeg, max(eI, __builtin_amdgcn_readfirstlane(env[J]))));
         }
+        // Half-tile envelope (chunks): wave w of the chunks' K-loop owns the quadrant (rows 64 (w & 1) ..,
+        // columns 64 (w >> 1) ..) of the tile, its operands are the 64-row halves 2I + (w & 1) of L and 2J + (w >> 1) of V.  Left
+        // of the later of the two halves' envelopes one factor of every product is an exact zero: the wave multiplies from
+        // k-tile kf on (k-tiles of 8 columns, counted from k0; <= 0: all).  The upper quadrant of a diagonal tile (w == 2) is
+        // neither stored nor read by anybody: never multiplied.  The k-tiles in front of EVERY wave's first one (ks: 0 or 8 --
+        // the tile envelope is the earlier half's, in whole tiles) are not even staged: the chunk's K-loop starts behind them.
+        int kf = 0, ks = 0;
+        if (envh != nullptr && (!(flags & DAG_FINAL) || (flags & DAG_BANDACC))) {
+            const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int hI0 = __builtin_amdgcn_readfirstlane(envh[2 * I]), hI1 = __builtin_amdgcn_readfirstlane(envh[2 * I + 1]);
+            const int hJ0 = __builtin_amdgcn_readfirstlane(envh[2 * J]), hJ1 = __builtin_amdgcn_readfirstlane(envh[2 * J + 1]);
+            ks = min(max(8 * max(min(hI0, hI1), min(hJ0, hJ1)) - 16 * k0, 0), 16 * (kend - k0));
+            kf = (I == J && w == 2) ? INT_MAX : 8 * max((w & 1) ? hI1 : hI0, (w >> 1) ? hJ1 : hJ0) - 16 * k0 - ks;
+        }
+        const int nk = 16 * (kend - k0) - ks;   // k-tiles of a chunk's K-loop
         // k-tiles [0, limit) of this chunk have final operands; the gate blocks at the first k-tile of a tile column that is
         // not final yet (a rare event: the queue is sorted by readiness)
         int limit = 0;
@@ -689,13 +707,13 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
         };
         auto gate = [&](int kt) -> bool {
             if (kt < limit) return true;
-            const int r = gate_at(k0 + (kt >> 4));
+            const int r = gate_at(k0 + ((kt + ks) >> 4));
             if (r < 0) return false;
-            limit = (__builtin_amdgcn_readfirstlane(r) - k0) * 16;
+            limit = (__builtin_amdgcn_readfirstlane(r) - k0) * 16 - ks;
             return true;
         };
-        const double* Ak = a.F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)128 * k0 * a.ld;
-        const double* Bk = (LDL ? a.V : a.F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)128 * k0 * a.ld;
+        const double* Ak = a.F + (a.fake_share > 0 ? (int64_t)128 * (kend + I % a.fake_share) : row0) + (int64_t)(128 * k0 + 8 * ks) * a.ld;
+        const double* Bk = (LDL ? a.V : a.F) + (a.fake_share > 0 ? (int64_t)128 * (kend + J % a.fake_share) : col0) + (int64_t)(128 * k0 + 8 * ks) * a.ld;
         auto wait_chunk_order = [&]() -> bool {   // the chunks of one tile are applied in order
             if (flags & DAG_FIRST) return true;
             const int* word = a.tprog + (int64_t)I * a.ntile + J;
@@ -754,11 +772,11 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             // the last chunk of a band tile is on the critical path of the chain: it issues first
             if (flags & DAG_FINAL) __builtin_amdgcn_s_setprio(3);
             // (the two-buffer loop: the three-buffer one is ~10 % slower at three workgroups per CU -- tools/hip/time_kstep.hip)
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - k0) * 16, smem_raw, tid, gate)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             if (!wait_chunk_order()) return;
-            // C(I, J) -= acc
-            if (kend > k0)
+            // C(I, J) -= acc (a wave that multiplied nothing has nothing to subtract)
+            if (kend > k0 && kf < nk)
                 gemm_nt_epilogue<2, 2, 4, 2, false, true>(acc, row0, col0, (int64_t)1 << 40, (int64_t)1 << 40, a.F, a.ld, nullptr, nullptr, 0, tid);
             if (tr) tr[3] = wall_clock64();
         } else {
@@ -772,7 +790,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             __builtin_amdgcn_s_setprio(3);   // (every chunk: the next one of the tile -- in the end the chain -- waits for it)
             if (!wait_chunk_order()) return;
             gemm_nt_load_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, (kend - k0) * 16, smem_raw, tid, gate)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             gemm_nt_store_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
             if (tr) tr[3] = wall_clock64();
@@ -932,6 +950,8 @@ void dag_merge_tasks(const std::vector<int>& tasks, const std::vector<int>& read
 //   * a gang goes whole to the queue with the fewest k-steps dealt so far (ties: round-robin), so the queues carry equal work at
 //     every position of the list: the heaviest and the lightest differ by at most one gang.
 // The envelope is ignored (gang-mates whose K-loops start later join the shared stream later): one deal serves every matrix of an order.
+// (Balancing the queues by the K-loop lengths under the envelope, kend - max(kbeg, env[I], env[J]), was measured on C3 and is not
+// built: 9.101 against 9.080 ms per step)
 void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
                     std::vector<int>& off) {
     nq = std::max(nq, 1);
@@ -967,6 +987,29 @@ void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready
     for (int q = 0; q < nq; ++q) {
         order.insert(order.end(), qs[q].begin(), qs[q].end());
         off.push_back((int)order.size());
+    }
+}
+
+// Statistics (envh_ksteps / envh_ksteps_skipped): the bulk tasks of a list in half-tile k-steps -- one 64 x 64 quadrant of a tile
+// over 64 columns, 8 per 128-column k-step of a tile.  count[0]: what the tile envelope `env` leaves (NULL: everything);
+// count[1]: of that, what the waves of dag_bulk_kernel1 skip with the half-tile envelope `envh` (NULL: nothing) -- in a chunk's
+// K-loop the quadrant (r, c) of tile (I, J) starts at max(envh[2I + r], envh[2J + c]), and the upper quadrant of a diagonal
+// tile is never multiplied.  Tile-closing tasks skip nothing by halves.
+void dag_envh_count(const std::vector<int>& tasks, const int* env, const int* envh, int nenv, int64_t* count) {
+    count[0] = count[1] = 0;
+    for (size_t t = 0; t + 3 < tasks.size(); t += 4) {
+        const int flags = tasks[t] & 255, I = tasks[t + 1] & 0xffff, J = tasks[t + 2] & 0xfff, kb = tasks[t + 3] & 0xffff, ke = tasks[t + 3] >> 16;
+        if (flags & DAG_FILL) continue;
+        const bool in = env != nullptr && I < nenv && J < nenv;
+        const int k0 = in ? std::min(ke, std::max(kb, std::max(env[I], env[J]))) : kb;
+        if (in && (flags & DAG_FINAL) && !(flags & DAG_BANDACC) && J < env[I]) continue;   // (a structurally zero tile is closed without its K-step)
+        count[0] += 8 * (int64_t)(ke - k0);
+        if (!in || envh == nullptr || ((flags & DAG_FINAL) && !(flags & DAG_BANDACC))) continue;
+        for (int r = 0; r < 2; ++r)
+            for (int c = 0; c < 2; ++c) {
+                const int h0 = (I == J && r == 0 && c == 1) ? 2 * ke : std::max(envh[2 * I + r], envh[2 * J + c]);
+                count[1] += std::min(2 * ke, std::max(2 * k0, h0)) - 2 * k0;
+            }
     }
 }
 
@@ -1010,7 +1053,7 @@ static int launch_dag_bulk(hipStream_t s, bool ldl, const DagInst& one, const Da
     static const int fake = getenv("MNK_DAG_FAKE_SHARE") ? atoi(getenv("MNK_DAG_FAKE_SHARE")) : 0;
     if (insts == nullptr) {
         DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
-                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate,
+                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate, one.envh,
                    qoff, qheads, nq};
         return ldl ? launch_bulk1_t<true>(s, a, nwg) : launch_bulk1_t<false>(s, a, nwg);
     }
@@ -1097,7 +1140,7 @@ static mnk::DagInst dag_instance(mnk_ls* ls) {
     const bool env = ls->envelope && ls->env_dev != nullptr && ls->env_word.p != nullptr;
     return mnk::DagInst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
                         front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N, env ? ls->env_dev : nullptr,
-                        env ? ls->env_word.p + 1 : nullptr};
+                        env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->envh_dev : nullptr};
 }
 
 // Buffers of the task-DAG schedule: the task list (built once per matrix order and option set), the progress words and,
@@ -1211,6 +1254,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
     const mnk::DagInst inst = dag_instance(ls);
     ls->dag_filled = inst.zfill != nullptr;
     ls->env_used = inst.env != nullptr;
+    ls->envh_used = inst.envh != nullptr;
     hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, s,
                        ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
                        ls->env_word.p, ls->dag_qheads.p, ls->dag_qheads.p ? 2 * mnk::DAG_QHEAD_WORDS : 0);
@@ -1390,6 +1434,7 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
             hin.push_back(dag_instance(ls));
             ls->dag_filled = hin.back().zfill != nullptr;
             ls->env_used = hin.back().env != nullptr;
+            ls->envh_used = false;   // (the merged kernel of a batch skips by tiles only)
             // (the instance's record for the bulk kernel rides along with the reset of its progress words)
             hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, h,
                                ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1),
@@ -1543,7 +1588,9 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
                 ls->dag_filled = hin.back().zfill != nullptr;
                 hin.back().env = nullptr;   // (batches of small systems run dense: their bulk tasks only accumulate band tiles)
                 hin.back().envgate = nullptr;
+                hin.back().envh = nullptr;
                 ls->env_used = false;
+                ls->envh_used = false;
                 fronts.push_back(hin.back().front);
                 afs.push_back(hin.back().af);
                 st_inst[i] = hin.back();
@@ -1754,4 +1801,14 @@ extern "C" int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2,
     if (tasks_out != nullptr)
         for (int i = 0; i < std::min(n, cap) * 4; ++i) tasks_out[i] = h[i];
     return n;
+}
+
+// Diagnostics / tests: the statistics envh_ksteps (count[0]) and envh_ksteps_skipped (count[1]) of the task list of `ntile` tiles
+// under the tile envelope `env` (ntile entries) and the half-tile envelope `envh` (2 ntile entries; NULL: nothing skipped).  Host only.
+extern "C" int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int taper0, const int* env, const int* envh, int64_t* count) {
+    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0 || count == nullptr) return -1;
+    std::vector<int> h;
+    (void)mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, nullptr);
+    mnk::dag_envh_count(h, env, envh, ntile, count);
+    return (int)(h.size() / 4);
 }

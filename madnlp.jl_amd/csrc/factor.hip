@@ -1216,6 +1216,7 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     // persistent schedule is tried again 16, then 64, 256, ... factorizations later.
     ls->algo_now = ls->panel_algo;
     ls->env_used = false;   // (the task-DAG schedule sets it when it launches with an envelope)
+    ls->envh_used = false;
     // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag.hip)
     const int64_t min_rows = mnk_batch_active() ? std::min<int64_t>(ls->dag_min_rows, 256) : ls->dag_min_rows;
     if (ls->algo_now == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) ls->algo_now = 4;

@@ -61,13 +61,16 @@ __device__ __forceinline__ void decode_tile(int logical, int ntm, int nc, int sw
 // call it with the same arguments; it ends with a workgroup barrier (the LDS tiles are free on return).
 // GATE: `gate(kt)` is called (by every thread, uniformly) before the loads of k-tile kt are issued and may block until
 // the operands of that k-tile exist (dag.hip: the factor's columns become final while the loop runs); false = give up.
+// `kfirst` (uniform over a WAVE, may differ between the waves): the first k-tile whose products this wave needs -- the wave
+// stages its share of every k-tile and takes every barrier, but reads no fragments and issues no MFMA for the k-tiles in front
+// of it (dag.hip: the operand rows of the wave's 64 x 64 quadrant are structurally zero there, or nobody reads the quadrant).
 struct GemmNoGate {
     __device__ __forceinline__ bool operator()(int) const { return true; }
 };
 template <int WM, int WN, int WT, int DBG, int BKT, class GATE = GemmNoGate>
 __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const double* __restrict__ Ag, int64_t lda,
                                                  const double* __restrict__ Bg, int64_t ldb, int nk, char* smem_raw,
-                                                 int tid, GATE gate = GATE()) {
+                                                 int tid, GATE gate = GATE(), int kfirst = 0) {
     constexpr int NT = 64 * WM * WN;
     constexpr int WS = 16 * WT;  // wave tile edge (WT x WT MFMA 16x16 tiles per wave)
     constexpr int BM = WS * WM, BN = WS * WN;
@@ -158,19 +161,21 @@ __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const dou
         }
         const double* as = As + cur * BKT * LDA_S + wm * WS + l15;
         const double* bs = Bs + cur * BKT * LDB_S + wn * WS + l15;
+        if (kt >= kfirst) {
 #pragma unroll
-        for (int kk = 0; kk < BKT / 4; ++kk) {
-            double af[WT], bf[WT];
+            for (int kk = 0; kk < BKT / 4; ++kk) {
+                double af[WT], bf[WT];
 #pragma unroll
-            for (int i = 0; i < WT; ++i) {
-                af[i] = as[(kk * 4 + l4) * LDA_S + i * 16];
-                bf[i] = bs[(kk * 4 + l4) * LDB_S + i * 16];
+                for (int i = 0; i < WT; ++i) {
+                    af[i] = as[(kk * 4 + l4) * LDA_S + i * 16];
+                    bf[i] = bs[(kk * 4 + l4) * LDB_S + i * 16];
+                }
+#pragma unroll
+                for (int ni = 0; ni < WT; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < WT; ++mi)
+                        acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[ni], af[mi], acc[ni][mi], 0, 0, 0);
             }
-#pragma unroll
-            for (int ni = 0; ni < WT; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < WT; ++mi)
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[ni], af[mi], acc[ni][mi], 0, 0, 0);
         }
         if (DMA) {
             // the DMA writes are ordered for the readers by this wave's vmcnt followed by the barrier

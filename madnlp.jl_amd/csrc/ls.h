@@ -19,6 +19,10 @@ struct mnk_sc {
     // first nonzero, so the tiles L(I, J), J < tile_env[I], are exact zeros (the task-DAG bulk kernel skips them, dag.hip)
     std::vector<int32_t> tile_env;
     mnk::DevBuf<int32_t> d_tile_env;
+    // the same per 64-row HALF of a tile row, in 64-column units (mnk_tile_envelope_half): tile_envh[2I], tile_envh[2I + 1];
+    // tile_env[I] = min of the two / 2.  The bulk kernel's waves skip the k-tiles left of their own half (option "envelope_half")
+    std::vector<int32_t> tile_envh;
+    mnk::DevBuf<int32_t> d_tile_envh;
     std::vector<int64_t> jt_map, h_map;
     std::vector<int32_t> d_dst, d_src, hp_dst, hp_src, j_dst, j_c, j_k, j_l;
     // device: COO -> CSC segmented transfer (sources grouped by destination slot)
@@ -52,6 +56,23 @@ inline std::vector<int32_t> mnk_tile_envelope(int64_t n, const int32_t* row, con
         env[I] = f / 128;
     }
     return env;
+}
+
+// tile_envh (see mnk_sc) of the same pattern: two entries per 128-row tile of the padded order, the first nonzero column over the
+// rows of each 64-row half / 64 (a padding row is its own first nonzero: a half of padding rows points at its own diagonal).
+inline std::vector<int32_t> mnk_tile_envelope_half(int64_t n, const int32_t* row, const int32_t* col, int64_t nnz) {
+    std::vector<int32_t> fnz(n);
+    for (int64_t i = 0; i < n; ++i) fnz[i] = (int32_t)i;
+    for (int64_t k = 0; k < nnz; ++k)
+        if (row[k] >= 0 && row[k] < n && col[k] < fnz[row[k]]) fnz[row[k]] = col[k];
+    const int64_t nhalf = 2 * ((n + 127) / 128);
+    std::vector<int32_t> envh(nhalf);
+    for (int64_t h = 0; h < nhalf; ++h) {
+        int32_t f = (int32_t)(64 * h);
+        for (int64_t i = 64 * h; i < std::min<int64_t>(n, 64 * h + 64); ++i) f = std::min(f, fnz[i]);
+        envh[h] = f / 64;
+    }
+    return envh;
 }
 
 struct mnk_dc {
@@ -146,6 +167,12 @@ struct mnk_ls {
     const int32_t* env_dev = nullptr;
     std::vector<int32_t> env_host;   // its host copy (statistics)
     mnk::DevBuf<int32_t> env_own;
+    // ... and per 64-row half in 64-column units (option "envelope_half", ignored with envelope = 0; mnk_sc::tile_envh)
+    int envelope_half = 1;
+    const int32_t* envh_dev = nullptr;
+    std::vector<int32_t> envh_host;
+    mnk::DevBuf<int32_t> envh_own;
+    bool envh_used = false;          // the last task-DAG factorization was launched with the half-tile envelope (statistics)
     // [0] set by a transfer that met a NaN / Inf entry, [1] that verdict for the factorization being run: dag_reset_kernel moves
     // [0] into [1] and clears [0]; the bulk kernel skips nothing when [1] != 0 (a NaN spreads through 0 * NaN in the dense order)
     mnk::DevBuf<int> env_word;

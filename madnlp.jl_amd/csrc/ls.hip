@@ -719,6 +719,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
             return 0;
         }
     if (!strcmp(key, "pivot_tol")) { ls->pivot_tol = value; return 0; }
+    if (!strcmp(key, "envelope_half")) { ls->envelope_half = value != 0.0; return 0; }   // 0: the waves of a bulk chunk multiply the k-tiles left of their own 64-row halves' envelopes and the upper quadrant of a diagonal tile too (ignored with envelope = 0)
     if (!strcmp(key, "envelope")) { ls->envelope = value != 0.0; return 0; }   // 0: the task-DAG bulk kernel multiplies the structurally zero tiles of sparse sources too
     if (!strcmp(key, "split_a")) { ls->split_a = (int)value; return 0; }
     if (!strcmp(key, "tail_rows")) { ls->tail_rows = (int64_t)value; return 0; }
@@ -945,8 +946,10 @@ extern "C" {
 // The envelope of a sparse source for the factorization that follows (mnk_ls::env_dev; nullptr: none), and the word its
 // transfer marks when it meets a NaN / Inf entry.  `env_host`: the envelope of the source's order, truncated to this solver's
 // tiles (a leading principal block of the source has the leading part of its envelope).
-static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host) {
+static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host, const int32_t* envh_dev,
+                         const std::vector<int32_t>& envh_host) {
     ls->env_dev = nullptr;
+    ls->envh_dev = nullptr;
     if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR || ls->algo == MNK_LU || ls->algo == MNK_EVD) return nullptr;
     if (!ls->env_word.p) {
         if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
@@ -961,6 +964,11 @@ static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<i
     ls->env_armed = true;
     ls->env_dev = env_dev;
     ls->env_host.assign(env_host.begin(), env_host.begin() + std::min<size_t>(env_host.size(), (size_t)(ls->Np / 128)));
+    // the half-tile envelope rides on the tile envelope: the same source, the same gate
+    if (ls->envelope_half && envh_dev != nullptr && envh_host.size() == 2 * env_host.size()) {
+        ls->envh_dev = envh_dev;
+        ls->envh_host.assign(envh_host.begin(), envh_host.begin() + 2 * ls->env_host.size());
+    }
     return ls->env_word.p;
 }
 
@@ -968,7 +976,7 @@ static int transfer_sc(mnk_ls* ls, mnk_sc* sc) {
     int rc = prepare_fill(ls);
     if (rc) return rc;
     const int64_t nnz = sc->nnz_aug;
-    int* nonfinite = set_envelope(ls, sc->d_tile_env.p, sc->tile_env);
+    int* nonfinite = set_envelope(ls, sc->d_tile_env.p, sc->tile_env, sc->d_tile_envh.p, sc->tile_envh);
     hipLaunchKernelGGL(scatter_csc_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ls->ctx->stream,
                        ls->fact.p, ls->ld, sc->aug_row.p, sc->aug_col.p, sc->aug_nz.p, nnz, amax_word(ls),
                        ls->N < sc->n ? (int32_t)ls->N : INT32_MAX, nonfinite);
@@ -1006,6 +1014,7 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
     // since then would otherwise count a small positive pivot of the block as zero and reject what the parent accepts)
     c->pivot_tol = ls->pivot_tol;
     c->envelope = ls->envelope;
+    c->envelope_half = ls->envelope_half;
     if (c->dag_xcd_queues != ls->dag_xcd_queues || c->dag_gang != ls->dag_gang) {
         c->dag_xcd_queues = ls->dag_xcd_queues;
         c->dag_gang = ls->dag_gang;
@@ -1178,14 +1187,16 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
     rc |= dnz.upload(nzv, ls->ctx->stream);
     // the envelope of this pattern (only the task-DAG schedule reads it)
     const std::vector<int32_t> env = ls->envelope ? mnk_tile_envelope(N, row.data(), col.data(), nnz) : std::vector<int32_t>();
+    const std::vector<int32_t> envh = ls->envelope && ls->envelope_half ? mnk_tile_envelope_half(N, row.data(), col.data(), nnz) : std::vector<int32_t>();
     if (ls->envelope) rc |= ls->env_own.upload(env, ls->ctx->stream);
+    if (!envh.empty()) rc |= ls->envh_own.upload(envh, ls->ctx->stream);
     if (rc) return -2;
     rc = ensure_wbuf(ls);
     if (rc) return rc;
-    auto transfer = [ls, nnz, &drow, &dcol, &dnz, &env]() -> int {
+    auto transfer = [ls, nnz, &drow, &dcol, &dnz, &env, &envh]() -> int {
         int r = prepare_fill(ls);
         if (r) return r;
-        int* nonfinite = set_envelope(ls, env.empty() ? nullptr : ls->env_own.p, env);
+        int* nonfinite = set_envelope(ls, env.empty() ? nullptr : ls->env_own.p, env, envh.empty() ? nullptr : ls->envh_own.p, envh);
         if (nnz > 0)
             hipLaunchKernelGGL(scatter_csc_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ls->ctx->stream,
                                ls->fact.p, ls->ld, drow.p, dcol.p, dnz.p, nnz, amax_word(ls), INT32_MAX, nonfinite);
@@ -1215,6 +1226,18 @@ int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowv
     if (out != nullptr)
         for (int I = 0; I < std::min((int)env.size(), cap); ++I) out[I] = env[I];
     return (int)env.size();
+}
+
+int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap) {
+    if (n <= 0 || colptr == nullptr || rowval == nullptr || cap < 0) return -1;
+    const int64_t nnz = colptr[n] - index_base;
+    std::vector<int32_t> row(nnz), col(nnz);
+    for (int64_t c = 0; c < n; ++c)
+        for (int64_t k = colptr[c] - index_base; k < colptr[c + 1] - index_base; ++k) { row[k] = rowval[k] - index_base; col[k] = (int32_t)c; }
+    const std::vector<int32_t> envh = mnk_tile_envelope_half(n, row.data(), col.data(), nnz);
+    if (out != nullptr)
+        for (int h = 0; h < std::min((int)envh.size(), cap); ++h) out[h] = envh[h];
+    return (int)envh.size();
 }
 
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
@@ -1466,6 +1489,19 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
             skipped += std::min(ke, std::max(kb, e)) - kb;
         }
         *value = (double)(!strcmp(key, "env_ksteps") ? total : skipped);
+        return 0;
+    }
+    if (!strcmp(key, "envh_ksteps") || !strcmp(key, "envh_ksteps_skipped")) {
+        // the same in HALF-tile k-steps (one 64 x 64 quadrant of a tile over 64 columns: 1 / 8 of a k-step): what the tile envelope
+        // leaves of the bulk tasks / of that, what the waves of the last factorization skipped by the envelopes of their 64-row
+        // halves and as upper quadrants of diagonal tiles (0 with envelope_half = 0, without an envelope or when the gate closed it)
+        int gate = 1;
+        if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
+        const bool on = ls->env_used && gate == 0;
+        int64_t cnt[2] = {0, 0};
+        mnk::dag_envh_count(ls->dag_host_tasks, on ? ls->env_host.data() : nullptr, on && ls->envh_used ? ls->envh_host.data() : nullptr,
+                            (int)ls->env_host.size(), cnt);
+        *value = (double)(!strcmp(key, "envh_ksteps") ? cnt[0] : cnt[1]);
         return 0;
     }
     set_error("mnk_ls_get_stat: unknown key '%s'", key);

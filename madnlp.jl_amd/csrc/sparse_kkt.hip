@@ -272,6 +272,7 @@ int mnk_sc_create(mnk_ctx* ctx, int64_t n, int64_t m, int64_t nnzj, const int32_
     sc->nnz_aug = slot + 1;
     sc->len_jptr = L;
     sc->tile_env = mnk_tile_envelope(n, a_row.data(), a_col.data(), sc->nnz_aug);
+    sc->tile_envh = mnk_tile_envelope_half(n, a_row.data(), a_col.data(), sc->nnz_aug);
 
     if (!ctx) { *out = sc; return 0; }
     // ---- upload ----
@@ -288,6 +289,7 @@ int mnk_sc_create(mnk_ctx* ctx, int64_t n, int64_t m, int64_t nnzj, const int32_
     rc |= sc->aug_jk.upload(a_jk, s); rc |= sc->aug_jl.upload(a_jl, s);
     rc |= sc->aug_row.upload(a_row, s); rc |= sc->aug_col.upload(a_col, s);
     rc |= sc->d_tile_env.upload(sc->tile_env, s);
+    rc |= sc->d_tile_envh.upload(sc->tile_envh, s);
     rc |= sc->d_jt_colptr.upload(sc->jt_colptr, s); rc |= sc->d_jt_rowval.upload(sc->jt_rowval, s);
     rc |= sc->d_h_colptr.upload(sc->h_colptr, s); rc |= sc->d_h_rowval.upload(sc->h_rowval, s);
     rc |= sc->jac_coo.alloc(nnzj); rc |= sc->hess_coo.alloc(nnzh);
@@ -363,6 +365,14 @@ int mnk_sc_debug_tile_env(mnk_sc* sc, int64_t order, int32_t* out, int cap) {
     const int n = (int)((order + 127) / 128);
     if (out != nullptr)
         for (int I = 0; I < std::min(n, cap); ++I) out[I] = sc->tile_env[I];
+    return n;
+}
+
+int mnk_sc_debug_tile_envh(mnk_sc* sc, int64_t order, int32_t* out, int cap) {
+    if (sc == nullptr || order <= 0 || order > sc->n || cap < 0) return -1;
+    const int n = 2 * (int)((order + 127) / 128);
+    if (out != nullptr)
+        for (int h = 0; h < std::min(n, cap); ++h) out[h] = sc->tile_envh[h];
     return n;
 }
 
