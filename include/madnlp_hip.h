@@ -705,11 +705,6 @@ int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* row
  * of them skipped with the half-tile envelope `envh` (NULL: none).  Returns the number of tasks. */
 int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int taper0, const int* env, const int* envh, int64_t* count);
 
-/* Diagnostics (tools/microbench_update.py): time `reps` lower-tile trailing updates C -= A*A^T under the
- * schedules the factorization uses (static tiling / tile queue; context, update, update+panel streams). */
-int mnk_debug_update(mnk_ctx* ctx, int variant, int64_t M, int64_t K, const double* A, int64_t lda,
-                     double* C, double* C2, int64_t ldc, int reps, double* ms);
-
 #ifdef __cplusplus
 }
 #endif

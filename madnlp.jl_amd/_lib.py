@@ -260,8 +260,6 @@ SIGNATURES = {
     "mnk_sc_step_batch": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "mnk_ls_inertia_batch": (C.c_int, [C.c_int, _vp, _i64p, _i64p, _i64p]),
     "mnk_ls_solve_batch": (C.c_int, [C.c_int, _vp, _vp, C.c_int]),
-    "mnk_debug_update": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int,
-                                   C.POINTER(C.c_double)]),
     "mnk_gemm_nt": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
                               C.c_int64, _vp, C.c_int64]),
 }

@@ -739,7 +739,7 @@ __global__ __launch_bounds__(256, 3) void bkp_update_kernel(double* __restrict__
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = v4f64{0.0, 0.0, 0.0, 0.0};
-    (void)gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, LW + (int64_t)128 * tm, ldw, W + (int64_t)128 * tn, ldw, BK_NBW / 8, smem_raw, tid);
+    (void)gemm_nt_mainloop<2, 2, 4, 8>(acc, LW + (int64_t)128 * tm, ldw, W + (int64_t)128 * tn, ldw, BK_NBW / 8, smem_raw, tid);
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1, l15 = lane & 15, l4 = lane >> 4;
 #pragma unroll

@@ -43,23 +43,11 @@ constexpr int SLACK = 256;
 // max|a_ij| of a transfer is folded into AMAX_SLOTS words 128 bytes apart behind the four result words (ls.h: amax_dev)
 constexpr int AMAX_SLOT0 = 16, AMAX_STRIDE = 16, AMAX_SLOTS = 64, AMAX_WORDS = AMAX_SLOT0 + AMAX_STRIDE * AMAX_SLOTS;
 
-// Host-side wait for a stream: hipStreamSynchronize (short spin, then an interrupt-driven sleep) by default; with
-// MNK_SPIN_WAIT=1 the stream is polled instead (one host core busy for the duration of every wait).  Round 2 chased
+// Host-side wait for a stream: hipStreamSynchronize (short spin, then an interrupt-driven sleep).  Round 2 chased
 // 40-80 ms stalls of the inertia fetch down to the HOST being frozen by its cgroup CPU quota (BLAS / OpenMP pools sized
-// after 256 visible cpus on a 16-CPU quota), not to this wait: both forms measure the same once the pools are bounded
-// (bench.py: _cpu_quota).
-inline hipError_t stream_wait(hipStream_t s) {
-    static const bool spin = []() {
-        const char* e = getenv("MNK_SPIN_WAIT");
-        return e != nullptr && atoi(e) != 0;
-    }();
-    if (!spin) return hipStreamSynchronize(s);
-    for (;;) {
-        const hipError_t e = hipStreamQuery(s);
-        if (e != hipErrorNotReady) return e;
-        __builtin_ia32_pause();
-    }
-}
+// after 256 visible cpus on a 16-CPU quota), not to this wait: polling the stream instead (hipStreamQuery, one host core
+// busy for the duration of every wait) measures the same once the pools are bounded (bench.py: _cpu_quota).
+inline hipError_t stream_wait(hipStream_t s) { return hipStreamSynchronize(s); }
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -264,11 +252,6 @@ int launch_gemm_nt_batch(hipStream_t s, int64_t M, int64_t N, int64_t K, const G
 int launch_gemm_nt_lower_small(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                                const double* B, int64_t ldb, double* C, int64_t ldc, const int* info_flag);
 int gemm_nt_lower_tiles(int64_t M, int64_t N);
-int launch_gemm_nt_dbg(hipStream_t s, int shared_ab, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double* C, int64_t ldc);
-int launch_gemm_nt_lower_range(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                               const double* B, int64_t ldb, double* C, int64_t ldc, const int* info_flag,
-                               int tile_begin, int tile_count);
 int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                          const double* B, int64_t ldb, double* C, int64_t ldc, int* counter, int cus,
                          const int* info_flag);

@@ -302,25 +302,6 @@ __device__ __forceinline__ void dag_finalize_tile(IP a, int64_t row0, int64_t co
     }
 }
 
-// Gate on the bulk stream of a small system (every row a strip of the chain): returns when `*word >= target` -- the chain's
-// last diagonal strip has published its rows -- so that the inverses queued behind it start within microseconds of the
-// chain's end instead of after the event hand-over between the streams (45 us of a 1 ms factorize! at N = 2048; with a
-// shallow band the bulk stream is busy until the end and the same gate measured slower).  Bounded like every device-side
-// wait; a failed factorization opens it at once.
-__global__ void dag_gate_kernel(const int* __restrict__ word, int target, int* __restrict__ info, long spin_limit) {
-    long spins = 0;
-    while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(8);
-        if ((++spins & 255) == 0) {
-            if (__hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-            if (spins > spin_limit) {
-                if (atomicCAS(info, 0, -7) == 0) info[1] = 3;   // (site 3: a gate on the bulk stream)
-                break;
-            }
-        }
-    }
-}
-
 // (`envw`: the solver's mnk_ls::env_word -- the verdict of the transfer on its finiteness becomes this factorization's, and the word
 // the next transfer marks is cleared)
 __global__ __launch_bounds__(256) void dag_reset_kernel(int* __restrict__ flags, int64_t n, int* __restrict__ info, DagInst rec,
@@ -504,7 +485,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             // the last chunk of a band tile is on the critical path of the chain: it issues first
             if (flags & DAG_FINAL) __builtin_amdgcn_s_setprio(3);
             // (the two-buffer loop: the three-buffer one is ~10 % slower at three workgroups per CU -- tools/hip/time_kstep.hip)
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
+            if (!gemm_nt_mainloop<2, 2, 4, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             if (!wait_chunk_order()) return false;
             // C(I, J) -= acc
@@ -522,7 +503,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel(DagArgs a) {
             __builtin_amdgcn_s_setprio(3);   // (every chunk: the next one of the tile -- in the end the chain -- waits for it)
             if (!wait_chunk_order()) return false;
             gemm_nt_load_neg_lower<2, 2, 4>(acc, row0, col0, in->F, in->ld, tid);
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
+            if (!gemm_nt_mainloop<2, 2, 4, 8>(acc, Ak, in->ld, Bk, in->ld, (kend - k0) * 16, smem_raw, tid, gate)) return false;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             gemm_nt_store_neg_lower<2, 2, 4>(acc, row0, col0, in->F, in->ld, tid);
             if (tr) tr[3] = wall_clock64();
@@ -772,7 +753,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             // the last chunk of a band tile is on the critical path of the chain: it issues first
             if (flags & DAG_FINAL) __builtin_amdgcn_s_setprio(3);
             // (the two-buffer loop: the three-buffer one is ~10 % slower at three workgroups per CU -- tools/hip/time_kstep.hip)
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             if (!wait_chunk_order()) return;
             // C(I, J) -= acc (a wave that multiplied nothing has nothing to subtract)
@@ -790,7 +771,7 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
             __builtin_amdgcn_s_setprio(3);   // (every chunk: the next one of the tile -- in the end the chain -- waits for it)
             if (!wait_chunk_order()) return;
             gemm_nt_load_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
-            if (!gemm_nt_mainloop<2, 2, 4, 0, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
+            if (!gemm_nt_mainloop<2, 2, 4, 8>(acc, Ak, a.ld, Bk, a.ld, nk, smem_raw, tid, gate, kf)) return;
             if (tr) tr[1] = wall_clock64();  // K-loop done
             gemm_nt_store_neg_lower<2, 2, 4>(acc, row0, col0, a.F, a.ld, tid);
             if (tr) tr[3] = wall_clock64();
@@ -1182,7 +1163,7 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         std::vector<int>& h = ls->dag_host_tasks;   // (kept on the host: a batch merges the lists of its instances)
         ls->dag_ntasks1 = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->dag_js2, h, ls->dag_taper0, &ls->dag_host_ready);
         // zero-fill of the next factorization's buffer as tasks of the queue (sparse sources; see dag_fill_tile)
-        ls->dag_has_fill = ls->dag_fill && ls->prefill && Np <= ls->prefill_max_rows;
+        ls->dag_has_fill = ls->dag_fill && ls->prefill && Np <= mnk_ls::PREFILL_MAX_ROWS;
         if (ls->dag_has_fill && h.empty()) ls->dag_has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
         if (ls->dag_has_fill) ls->dag_ntasks1 = mnk::dag_add_fill_tasks(ntile, h, ls->dag_host_ready, ls->dag_ntasks1);
         ls->dag_ntasks = (int)(h.size() / 4);
@@ -1276,7 +1257,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         // of the first diagonal block, no join behind the last one, and the inverses simply follow the chain.  Its workgroups
         // are dispatched before the bulk kernel's (which waits for the event) and need a CU each to themselves (registers);
         // the CUs outside the bulk stream's mask -- at least as many as there are strips -- cannot be taken from them.
-        const bool small = js_begin == 0 && js_end == nsc && js2 == 0 && ls->dag_chain_inline;
+        const bool small = js_begin == 0 && js_end == nsc && js2 == 0;
         if (small) sp = s;
         MNK_HIP(hipEventRecord(ctx->ev_a, s));
         if (!small) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
@@ -1313,11 +1294,6 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         }
         if (small) {
             rc = mnk_ls_invert_blocks(ls, s, 0, nsc);
-            if (rc) return rc;
-            ls->inv_done = nsc;
-        } else if (js_begin == 0 && js_end == nsc && js2 == 0) {
-            hipLaunchKernelGGL(mnk::dag_gate_kernel, dim3(1), dim3(1), 0, su, front + (nblk - 1), ntile, ls->info_dev.p, spin_limit);
-            rc = mnk_ls_invert_blocks(ls, su, 0, nsc);
             if (rc) return rc;
             ls->inv_done = nsc;
         }
@@ -1414,7 +1390,7 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
     if (rc) return rc;
     auto body = [&]() -> int {
         BatchBuffers& B = g_batch[c0->device & 63];
-        const int period = std::max((ntile + 1) / 2, l0->batch_period > 0 ? l0->batch_period : 0);
+        const int period = (ntile + 1) / 2;   // shift between consecutive instances in the merged queue, in tile columns of chain position: half the matrix, the minimum
         if (B.ntile != ntile || B.ninst != ninst || B.period != period || B.chunk != l0->dag_chunk || B.taper0 != l0->dag_taper0 ||
             B.band != l0->dag_band || B.fill != l0->dag_has_fill || !B.tasks.p) {
             std::vector<int> merged;

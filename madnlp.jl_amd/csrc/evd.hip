@@ -553,10 +553,6 @@ int mnk_evd_factor(mnk_ls* ls) {
         // (a NaN / Inf entry, or one above 1e154, makes the norm non-finite for good: no sweep can help)
         if (!std::isfinite(all2)) { info = 1; break; }
         const double off = std::sqrt(off2), nrm = std::sqrt(all2);
-        {   // diagnostics: the convergence history, one line per sweep
-            static const bool trace = getenv("MNK_EVD_TRACE") != nullptr;
-            if (trace) fprintf(stderr, "evd: N = %lld, after %d sweeps off(A) / |A|_F = %.3e\n", (long long)N, sweeps, off / nrm);
-        }
         if (off <= DBL_EPSILON * nrm) break;
         if (off <= (double)N * DBL_EPSILON * nrm) {
             if (near) break;

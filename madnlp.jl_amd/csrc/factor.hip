@@ -942,6 +942,9 @@ unsigned long long* mnk_ls_growth_word(mnk_ls* ls) {
     return (ls->algo == MNK_LDL && ls->bk_requested && ls->bk_fallback && ls->amax_dev.p) ? ls->amax_dev.p + 1 : nullptr;
 }
 
+// middle-level updates (inside an outer panel) with fewer 128x128 tiles than this use 64x64 workgroup tiles
+constexpr int SMALL_TILES_MID = 1000;
+
 // panel_algo = 4: persistent panel launches (ppanel_kernel) of 4 blocks, recursive updates between them
 static int factor_outer_panel_pp(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t kend, double* wbase,
                                  hipEvent_t rest_ready, int64_t rest_from, const double* Vfirst, int64_t ldvfirst,
@@ -1004,7 +1007,7 @@ static int factor_outer_panel_pp(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t 
         }
         const double* Wp = ldl ? wbase + p1 + (pb - ko) * ls->ldw : F + p1 + pb * ld;
         int rc;
-        if (gemm_nt_lower_tiles(Np - p1, ncols) < ls->small_tiles_mid)
+        if (gemm_nt_lower_tiles(Np - p1, ncols) < SMALL_TILES_MID)
             rc = launch_gemm_nt_lower_small(s, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + pb * ld, ld,
                                             F + p1 + p1 * ld, ld, ls->info_dev.p);
         else
@@ -1060,7 +1063,7 @@ static int factor_outer_panel(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t ken
         }
         const double* Wp = ldl ? wbase + p1 + (p0 - ko) * ls->ldw : F + p1 + p0 * ld;
         int rc;
-        if (gemm_nt_lower_tiles(Np - p1, ncols) < ls->small_tiles_mid)
+        if (gemm_nt_lower_tiles(Np - p1, ncols) < SMALL_TILES_MID)
             rc = launch_gemm_nt_lower_small(s, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + p0 * ld, ld,
                                             F + p1 + p1 * ld, ld, ls->info_dev.p);
         else
@@ -1259,12 +1262,15 @@ static int run_factorization_body(mnk_ls* ls) {
     const int64_t NBO = mnk_ls_effective_nbo(ls);
     if (ls->algo_now != 5) MNK_HIP(hipMemsetAsync(ls->info_dev.p, 0, 2 * sizeof(int), s));   // (the task-DAG driver resets it with its flags)
     // Outer panel boundaries.  Once the remaining matrix is small the factorization is bound by the panel
-    // chain, not by the update: narrower outer panels (tail_nbo) then drop the middle-level update and halve
+    // chain, not by the update: narrower outer panels (TAIL_NBO) then drop the middle-level update and halve
     // the depth of the (a) piece the chain waits for (measured: 355 -> ~300 us per 512 columns of the tail).
+    // The outer panels are TAIL_NBO wide once TAIL_ROWS rows (or fewer) remain: one persistent launch per panel with the
+    // fused prologue, no inner update (C3: 11.80 -> 11.71 ms).
+    constexpr int64_t TAIL_ROWS = 4096, TAIL_NBO = 256;
     std::vector<int64_t> bnd{0};
     for (int64_t pos = 0; pos < Np;) {
-        const bool tail = ls->lookahead && NBO < Np && ls->tail_rows > 0 && Np - pos <= ls->tail_rows && ls->tail_nbo < NBO;
-        pos = std::min<int64_t>(pos + (tail ? ls->tail_nbo : NBO), Np);
+        const bool tail = ls->lookahead && NBO < Np && Np - pos <= TAIL_ROWS && TAIL_NBO < NBO;
+        pos = std::min<int64_t>(pos + (tail ? TAIL_NBO : NBO), Np);
         bnd.push_back(pos);
     }
     const int64_t npanel = (int64_t)bnd.size() - 1;
@@ -1323,14 +1329,11 @@ static int run_factorization_body(mnk_ls* ls) {
         }
         // Panel 0 has nothing to overlap with: it runs on the caller's stream, i.e. on the whole chip (its
         // triangular solves and inner updates are throughput-bound at this height), before the fork.
-        int rc = 0;
-        if (ls->panel0_whole) rc = factor_outer_panel(ls, s, 0, bnd[1], ls->wbuf[0].p);
+        int rc = factor_outer_panel(ls, s, 0, bnd[1], ls->wbuf[0].p);
         if (rc) return rc;
         MNK_HIP(hipEventRecord(ctx->ev_a, s));
         MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
         MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
-        if (!ls->panel0_whole) rc = factor_outer_panel(ls, sp, 0, bnd[1], ls->wbuf[0].p);
-        if (rc) return rc;
         MNK_HIP(hipEventRecord(ctx->ev_panel[0], sp));
         for (int64_t k = 0; k + 1 < npanel; ++k) {
             const int64_t ko = bnd[k], kend = bnd[k + 1];
@@ -1343,9 +1346,8 @@ static int run_factorization_body(mnk_ls* ls) {
             const int64_t Kw = kend - ko;
             // ev_panel[k] is recorded after panel k and after the panel stream's share of (b)_{k-1}
             MNK_HIP(hipStreamWaitEvent(su, ctx->ev_panel[k], 0));
-            // (a) columns of the next outer panel, delivered in two pieces: its first 256-column middle
-            // panel (the panel stream starts on it at once), then the remaining columns (needed only when
-            // that middle panel is finished)
+            // (a) columns of the next outer panel, delivered in two pieces: the columns the panel stream starts on
+            // at once, then the remaining ones (needed only when those are finished)
             auto update_a = [&](hipStream_t st, int64_t c0, int64_t c1) -> int {
                 const int64_t Mp = Mt - c0, Nn = c1 - c0;
                 double* Cp = F + (kend + c0) + (kend + c0) * ld;
@@ -1355,18 +1357,17 @@ static int run_factorization_body(mnk_ls* ls) {
                 return launch_gemm_nt(st, 2, Mp, Nn, Kw, Wsrc + c0, ldws, F + kend + c0 + ko * ld, ld, Cp, ld, nullptr,
                                       nullptr, 0, ls->info_dev.p);
             };
-            // split_a == 2: the first 64 columns of the next panel are updated on the PANEL stream itself, right
-            // behind panel k (no cross-stream hand-over before the next pivot block starts); the update stream
-            // delivers the other columns while that block is being factored.  split_a == 1: first 256 columns
-            // on the update stream, then the rest.
-            // (the 256-column panel step needs the first 256 columns at once: they come from the update stream)
+            // The first OWN_COLS columns of the next panel are updated on the PANEL stream itself, right behind
+            // panel k (no cross-stream hand-over before the next pivot block starts); the update stream delivers
+            // the other columns while they are being factored.
             // Few rows left (the pivot chain is the critical path): the first persistent launch of the next panel applies
             // panel k to its own 256 columns itself (ppanel_kernel's prologue) -- no (a) kernel and no cross-stream
             // hand-over in front of the chain; the update stream delivers the other columns of the panel meanwhile.
             const bool fuse_a = ls->algo_now == 4 && ls->pp_fuse_rows > 0 && Mt <= ls->pp_fuse_rows && Kw <= 512;
-            const bool own_first = !fuse_a && ls->split_a == 2 && nnext > NBI;
-            const int64_t n1 = own_first ? std::min<int64_t>(ls->own_cols, nnext - NBI) : std::min<int64_t>(256, nnext);
-            const bool split_a = (ls->split_a || fuse_a) && nnext > n1;
+            constexpr int64_t OWN_COLS = 128;
+            const bool own_first = !fuse_a && nnext > NBI;
+            const int64_t n1 = own_first ? std::min<int64_t>(OWN_COLS, nnext - NBI) : std::min<int64_t>(256, nnext);
+            const bool split_a = nnext > n1;
             if (fuse_a) {
                 if (k > 0) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_bdone[k - 1], 0));  // (b)_{k-1} touched these columns
                 if (split_a) {
@@ -1381,15 +1382,10 @@ static int run_factorization_body(mnk_ls* ls) {
                 rc = update_a(su, n1, nnext);
                 if (rc) return rc;
                 MNK_HIP(hipEventRecord(ctx->ev_next2[k], su));
-            } else {
-                rc = update_a(su, 0, split_a ? n1 : nnext);
+            } else {   // (a next panel of one 64-column block: nothing to split)
+                rc = update_a(su, 0, nnext);
                 if (rc) return rc;
                 MNK_HIP(hipEventRecord(ctx->ev_next[k], su));
-                if (split_a) {
-                    rc = update_a(su, n1, nnext);
-                    if (rc) return rc;
-                    MNK_HIP(hipEventRecord(ctx->ev_next2[k], su));
-                }
             }
             // (b) the rest of the trailing matrix
             const int64_t Mb = Mt - nnext;

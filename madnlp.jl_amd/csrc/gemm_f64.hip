@@ -44,20 +44,8 @@ __global__ __launch_bounds__(64 * WM * WN, tile_occ(WM, WN, WT)) void gemm_nt_ke
     int logical = tile_off + ((per > 0 && bid < per * 8) ? (bid & 7) * per + (bid >> 3) : bid);
     int tm, tn;
     decode_tile<MODE>(logical, ntm, nc, sw, tm, tn);
-    gemm_nt_tile<WM, WN, WT, MODE, LDL_EPI, 0, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, A, lda, B, ldb, C, ldc, colscale,
+    gemm_nt_tile<WM, WN, WT, MODE, LDL_EPI, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, A, lda, B, ldb, C, ldc, colscale,
                                                                        C2, ldc2, smem_raw);
-}
-
-template <int WM, int WN, int WT, int MODE, int DBG>
-__global__ __launch_bounds__(64 * WM * WN, DBG == 6 ? 2 : tile_occ(WM, WN, WT)) void gemm_nt_dbg_kernel(
-    int64_t M, int64_t N, int64_t K, const double* __restrict__ A, int64_t lda,
-    const double* __restrict__ B, int64_t ldb, double* C, int64_t ldc, int ntm) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    int nblk = gridDim.x, bid = blockIdx.x, per = nblk >> 3;
-    int logical = (per > 0 && bid < per * 8) ? (bid & 7) * per + (bid >> 3) : bid;
-    int tm, tn;
-    decode_tile<MODE>(logical, ntm, ntm, 1, tm, tn);
-    gemm_nt_tile<WM, WN, WT, MODE, false, DBG == 6 ? 0 : DBG, DBG == 6 ? 16 : tile_bk(WM, WN, WT)>(tm, tn, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, smem_raw);
 }
 
 // Work-queue variant: the workgroups of one or more launches (possibly on different streams with
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(64 * WM * WN, tile_occ(WM, WN, WT)) void gemm_nt_qu
         if (logical >= hi) { ++probe; continue; }
         int tm, tn;
         decode_tile<MODE>(logical, ntm, nc, sw, tm, tn);
-        gemm_nt_tile<WM, WN, WT, MODE, false, 0, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, A, lda, B, ldb, C, ldc, nullptr,
+        gemm_nt_tile<WM, WN, WT, MODE, false, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, A, lda, B, ldb, C, ldc, nullptr,
                                                                           nullptr, 0, smem_raw);
         __syncthreads();  // LDS tiles are reused by the next round
     }
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(64 * WM * WN, tile_occ(WM, WN, WT)) void gemm_nt_ba
     if (rec.info != nullptr && *rec.info != 0) return;
     int tm, tn;
     decode_tile<MODE>((int)blockIdx.x, ntm, nc, sw, tm, tn);
-    gemm_nt_tile<WM, WN, WT, MODE, false, 0, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, rec.A, lda, rec.B, ldb, rec.C, ldc, nullptr,
+    gemm_nt_tile<WM, WN, WT, MODE, false, tile_bk(WM, WN, WT)>(tm, tn, M, N, K, rec.A, lda, rec.B, ldb, rec.C, ldc, nullptr,
                                                                       nullptr, 0, smem_raw);
 }
 
@@ -147,7 +135,7 @@ static int tile_super_width() {
 template <int WM, int WN, int WT, int MODE, bool LDL_EPI>
 static int launch_t(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                     const double* B, int64_t ldb, double* C, int64_t ldc, const double* colscale,
-                    double* C2, int64_t ldc2, const int* info_flag, int tile_begin = 0, int tile_count = -1) {
+                    double* C2, int64_t ldc2, const int* info_flag) {
     constexpr int BM = 16 * WT * WM, BN = 16 * WT * WN;
     const int ntm = (int)((M + BM - 1) / BM), ntn = (int)((N + BN - 1) / BN);
     int ntiles = ntm * ntn;
@@ -166,10 +154,9 @@ static int launch_t(hipStream_t s, int64_t M, int64_t N, int64_t K, const double
         MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
     }
-    if (tile_count >= 0) ntiles = std::min(ntiles - tile_begin, tile_count);
     if (ntiles <= 0) return 0;
     hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64 * WM * WN), smem, s, M, N, K, A, lda, B, ldb, C,
-                       ldc, colscale, C2, ldc2, ntm, info_flag, tile_begin, nc, tile_super_width());
+                       ldc, colscale, C2, ldc2, ntm, info_flag, /*tile_off=*/0, nc, tile_super_width());
     MNK_HIP(hipGetLastError());
     return 0;
 }
@@ -221,41 +208,6 @@ int launch_gemm_nt_lower_small(hipStream_t s, int64_t M, int64_t N, int64_t K, c
     if (M <= 0 || N <= 0) return 0;
     MNK_REQUIRE(M % 64 == 0 && N % 64 == 0 && K % BK == 0 && K > 0, "gemm_nt: M,N must be multiples of 64, K of 16");
     return launch_t<2, 2, 2, 2, false>(s, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, info_flag);
-}
-
-// a contiguous range of the lower tiles of the 128x128 tiling (mode 2), for chunked launches
-int launch_gemm_nt_lower_range(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                               const double* B, int64_t ldb, double* C, int64_t ldc, const int* info_flag,
-                               int tile_begin, int tile_count) {
-    if (M <= 0 || N <= 0) return 0;
-    MNK_REQUIRE(M % 64 == 0 && N % 64 == 0 && K % BK == 0 && K > 0, "gemm_nt: M,N must be multiples of 64, K of 16");
-    return launch_t<2, 2, 4, 2, false>(s, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, info_flag, tile_begin,
-                                       tile_count);
-}
-
-int gemm_nt_lower_tiles(int64_t M, int64_t N);
-int launch_gemm_nt_dbg(hipStream_t s, int shared_ab, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double* C, int64_t ldc) {
-    const int ntm = (int)((M + 127) / 128);
-    const int ntiles = gemm_nt_lower_tiles(M, N);
-    const size_t smem = 2 * tile_bk(2, 2, 4) * ((128 + 16) + (128 + 16)) * sizeof(double);
-#define MNK_DBG_LAUNCH(D)                                                                                        \
-    do {                                                                                                         \
-        auto kern = gemm_nt_dbg_kernel<2, 2, 4, 2, D>;                                                           \
-        const size_t smem_d = D == 6 ? smem * 2 : smem; /* variant 6 runs BK = 16 */                             \
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_d)); \
-        hipLaunchKernelGGL(kern, dim3(ntiles), dim3(256), smem_d, s, M, N, K, A, lda, B, ldb, C, ldc, ntm);      \
-    } while (0)
-    if (shared_ab == 1) MNK_DBG_LAUNCH(1);
-    else if (shared_ab == 2) MNK_DBG_LAUNCH(2);
-    else if (shared_ab == 3) MNK_DBG_LAUNCH(3);
-    else if (shared_ab == 4) MNK_DBG_LAUNCH(4);
-    else if (shared_ab == 5) MNK_DBG_LAUNCH(5);
-    else if (shared_ab == 6) MNK_DBG_LAUNCH(6);  // BK = 16, two workgroups per CU (the earlier configuration)
-    else MNK_DBG_LAUNCH(0);
-#undef MNK_DBG_LAUNCH
-    MNK_HIP(hipGetLastError());
-    return 0;
 }
 
 int gemm_nt_lower_tiles(int64_t M, int64_t N) {

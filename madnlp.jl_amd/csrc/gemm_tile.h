@@ -67,7 +67,7 @@ __device__ __forceinline__ void decode_tile(int logical, int ntm, int nc, int sw
 struct GemmNoGate {
     __device__ __forceinline__ bool operator()(int) const { return true; }
 };
-template <int WM, int WN, int WT, int DBG, int BKT, class GATE = GemmNoGate>
+template <int WM, int WN, int WT, int BKT, class GATE = GemmNoGate>
 __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const double* __restrict__ Ag, int64_t lda,
                                                  const double* __restrict__ Bg, int64_t ldb, int nk, char* smem_raw,
                                                  int tid, GATE gate = GATE(), int kfirst = 0) {
@@ -124,8 +124,8 @@ __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const dou
     // 128x128 tiles stage through the LDS-DMA path (global_load_lds_dwordx4: one wave instruction moves one
     // 128-row k-column, 1 KiB, straight into its LDS row; no staging registers, no ds_write pass):
     // measured +3 % (192 CUs) / +5 % (256 CUs) on the trailing update, bit-identical results.
-    // DBG == 5 (diagnostics) forces the register-staged path for A/B runs.
-    constexpr bool DMA = BM == 128 && BN == 128 && (DBG == 0 || DBG == 1 || DBG == 4);
+    // The other shapes (the 64x64 tiles) stage through registers.
+    constexpr bool DMA = BM == 128 && BN == 128;
     constexpr int NW = NT / 64;
     auto gl_lds = [&](int kt, int buf) {
         const int64_t k0 = (int64_t)kt * BKT;
@@ -156,7 +156,7 @@ __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const dou
         if (kt + 1 < nk && !gate(kt + 1)) return false;
         if (DMA) {
             if (kt + 1 < nk) gl_lds(kt + 1, cur ^ 1);
-        } else if (DBG != 3 && kt + 1 < nk) {
+        } else if (kt + 1 < nk) {
             gload(kt + 1);
         }
         const double* as = As + cur * BKT * LDA_S + wm * WS + l15;
@@ -182,8 +182,8 @@ __device__ __forceinline__ bool gemm_nt_mainloop(v4f64 (&acc)[WT][WT], const dou
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         } else {
-            if (DBG != 3 && kt + 1 < nk) sstore(cur ^ 1);
-            if (DBG != 2 && DBG != 3) __syncthreads();
+            if (kt + 1 < nk) sstore(cur ^ 1);
+            __syncthreads();
         }
     }
     return true;
@@ -391,7 +391,7 @@ __device__ __forceinline__ void gemm_nt_store_neg_lower(const v4f64 (&acc)[WT][W
 }
 
 // One workgroup tile of C.  Every thread of the workgroup must call it with the same (tm, tn).
-template <int WM, int WN, int WT, int MODE, bool LDL_EPI, int DBG = 0, int BKT = BK>
+template <int WM, int WN, int WT, int MODE, bool LDL_EPI, int BKT = BK>
 __device__ __forceinline__ void gemm_nt_tile(
     int tm, int tn, int64_t M, int64_t N, int64_t K, const double* __restrict__ A, int64_t lda,
     const double* __restrict__ B, int64_t ldb, double* C, int64_t ldc,
@@ -404,17 +404,14 @@ __device__ __forceinline__ void gemm_nt_tile(
     // Opaque to the optimizer: inside the work-queue loop everything derived from the thread id would be
     // hoisted out of the loop and then spilled (168-VGPR budget); recomputing it per tile costs a few VALU ops.
     asm volatile("" : "+v"(tid));
-    // DBG (diagnostics only, results are wrong for DBG >= 2): 1 = every tile reads the same two operand
-    // blocks (perfect cache reuse: separates the memory-side cost from the MFMA/LDS cost); 2 = no barrier in
-    // the k-loop; 3 = no global loads / LDS stores in the k-loop (MFMA + LDS-read loop alone)
-    const double* Ag = A + (DBG == 1 ? (int64_t)(tm & 1) * BM : row0);
-    const double* Bg = B + (DBG == 1 ? (int64_t)(tn & 1) * BN : col0);
+    const double* Ag = A + row0;
+    const double* Bg = B + col0;
     v4f64 acc[WT][WT];  // [ni][mi]
 #pragma unroll
     for (int i = 0; i < WT; ++i)
 #pragma unroll
         for (int j = 0; j < WT; ++j) acc[i][j] = v4f64{0.0, 0.0, 0.0, 0.0};
-    (void)gemm_nt_mainloop<WM, WN, WT, DBG, BKT>(acc, Ag, lda, Bg, ldb, (int)(K / BKT), smem_raw, tid);
+    (void)gemm_nt_mainloop<WM, WN, WT, BKT>(acc, Ag, lda, Bg, ldb, (int)(K / BKT), smem_raw, tid);
     gemm_nt_epilogue<WM, WN, WT, MODE, LDL_EPI>(acc, row0, col0, M, N, C, ldc, colscale, C2, ldc2, tid);
 }
 

@@ -102,25 +102,20 @@ struct mnk_ls {
     int lookahead = 1;
     int share = 1;         // look-ahead only: the panel stream's CUs join the trailing update through a tile queue
     int small_tiles = 400;  // (a)-updates with fewer 128x128 tiles than this use 64x64 workgroup tiles
-    int split_a = 2;          // 1: next panel delivered in two pieces by the update stream; 2: its first 64 columns by the panel stream itself
     int64_t single_rows = 2560;  // systems up to this (padded) order are factored as ONE outer panel on the whole chip (with the fused tail panels the look-ahead schedule wins from N = 3072 on: 2.12 vs 2.34 ms at 4096)
-    int64_t tail_rows = 4096; // outer panels are tail_nbo wide once this many rows (or fewer) remain: one persistent launch per panel with the fused prologue, no inner update (C3: 11.80 -> 11.71 ms; 0 disables)
-    int64_t tail_nbo = 256;
-    int small_tiles_mid = 1000;  // same for the middle-level update inside an outer panel
     mnk::DevBuf<int> tile_ctr;  // one work-queue counter per outer step
     mnk::DevBuf<double> fact, wbuf[2], linv, dblk, inv16, linv256, linv256t, dvec, dinv, xwork;
     // Sparse sources are scattered into a ZEROED dense buffer (8 Np^2 / 2 bytes of zeros per factorization: 116 us at C3,
     // HBM-bound).  With `prefill` the zeros are written in the background into a second buffer while the current
     // factorization / its solves run; the next factorize! swaps the two (costs a second factor buffer, so only up to
-    // prefill_max_rows).
+    // PREFILL_MAX_ROWS).
     mnk::DevBuf<double> fact_spare;
     hipEvent_t ev_spare = nullptr, ev_free = nullptr;
     bool spare_zeroed = false, spare_pending = false;
     int prefill = 1;
-    int64_t prefill_max_rows = 24576;
+    static constexpr int64_t PREFILL_MAX_ROWS = 24576;
     int epoch = 0;    // value the hand-off flags of the current factorization carry
     mnk::DevBuf<int> flag_p;
-    int panel0_whole = 1;  // look-ahead: the first outer panel is factored on the whole chip before the streams fork
     int algo_now = 1;    // the panel algorithm of the current factorization (panel_algo, or 1 where 4 is not safe)
     bool pp_blocked = false;
     int64_t fact_count = 0, pp_retry_at = 0, pp_backoff = 16;   // a schedule that timed out is tried again after 16, 64, 256, ... factorizations
@@ -129,7 +124,6 @@ struct mnk_ls {
     double stall_ms_total = 0.0; // host time between the launch of a factorization whose bounded wait expired and the moment the expiry was seen: what the fall-backs of this solver have cost (get_stat "stall_ms_total"; "stall_ms_process": all solvers)
     double t_fact_launch_ms = 0.0;   // host clock (ms) when the current factorization was enqueued
     int64_t pp_fuse_rows = 4096; // > 0: once this many rows (or fewer) remain, persistent panel launches apply the columns in front of them themselves
-    int64_t own_cols = 128;   // split_a = 2: columns of the next panel that the panel stream updates itself
     // task-DAG schedule (panel_algo = 5, dag.hip)
     mnk::DevBuf<int> dag_tasks;   // 4 ints per task, built once per order
     int dag_ntasks = 0, dag_ntasks1 = 0, dag_js2 = 0;  // all tasks / tasks of the first phase / first strip-column of the second
@@ -137,7 +131,6 @@ struct mnk_ls {
     int dag_fill = 1;             // option: the zero-fill of the spare factor buffer (sparse sources) runs as DAG_FILL tasks of the bulk queue instead of on a side stream beside the solves
     bool dag_has_fill = false;    // the current task list contains them
     bool dag_filled = false;      // the factorization that was just queued zeroes the spare buffer itself (mnk_ls_prefill_spare has nothing to launch)
-    int batch_period = 0;         // option: shift between consecutive instances of a batch in the merged queue, in tile columns of chain position (0: half the matrix, the minimum)
     hipEvent_t ev_info = nullptr;    // recorded behind finish_info_kernel: what mnk_ls_fetch_info waits for
     bool ev_info_recorded = false;
     hipEvent_t ev_defer = nullptr;   // batch: "matrix transferred" on this solver's stream / "batch done"
@@ -181,9 +174,7 @@ struct mnk_ls {
     int64_t dag_max_rows = 30720; // larger ones too: their trailing updates already run at the update kernel's rate (round 6, LDL, schedule 4 / this one: N = 24 576 87.4 / 81.7 ms, 28 672 133.6 / 128.6, 32 768 188.2 / 190.2; rounds 3-5: 24 576)
     int panel_algo = 5;  // 5: task-DAG schedule (dag.hip: persistent pivot chain + persistent left-looking bulk kernel); 4: persistent panel kernel per 256 columns + one trailing update per outer panel (also what 5 uses outside [dag_min_rows, dag_max_rows]); 1: one launch per piece, the fallback of 4 and 5
     int persistent_solve = 1;  // both sweeps of a solve in one launch (solve.hip); 0: one launch per step
-    int solve512 = 0;          // 1: the one-launch solve steps over 512 columns (32-row blocks, 512x512 explicit inverses) from solve512_min_rows on.  C3: solve! 0.46 -> 0.33 ms, but the extra inverses cost factorize! +0.37 ms (they finish 0.3 ms after the chain): worth it from ~4 solves per factorization
-    int64_t solve512_min_rows = 4096;
-    int dag_chain_inline = 1;  // task-DAG schedule, small systems: the pivot chain runs on the caller's stream (no fork / join around it)
+    int solve512 = 0;          // 1: the one-launch solve steps over 512 columns (32-row blocks, 512x512 explicit inverses) from 4096 rows on.  C3: solve! 0.46 -> 0.33 ms, but the extra inverses cost factorize! +0.37 ms (they finish 0.3 ms after the chain): worth it from ~4 solves per factorization
     std::vector<std::string> env_keys;   // options fixed by MNK_OPTIONS for this process
     int dag_js2_override = -1;
     int linv_mfma = 1;         // 256x256 explicit inverses on the matrix cores (0: the scalar LDS kernel, ~70 us per workgroup)

@@ -721,11 +721,6 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     if (!strcmp(key, "pivot_tol")) { ls->pivot_tol = value; return 0; }
     if (!strcmp(key, "envelope_half")) { ls->envelope_half = value != 0.0; return 0; }   // 0: the waves of a bulk chunk multiply the k-tiles left of their own 64-row halves' envelopes and the upper quadrant of a diagonal tile too (ignored with envelope = 0)
     if (!strcmp(key, "envelope")) { ls->envelope = value != 0.0; return 0; }   // 0: the task-DAG bulk kernel multiplies the structurally zero tiles of sparse sources too
-    if (!strcmp(key, "split_a")) { ls->split_a = (int)value; return 0; }
-    if (!strcmp(key, "tail_rows")) { ls->tail_rows = (int64_t)value; return 0; }
-    if (!strcmp(key, "tail_nbo")) { ls->tail_nbo = (int64_t)value; return 0; }
-    if (!strcmp(key, "own_cols")) { ls->own_cols = std::max<long>(64, (long)value / 64 * 64); return 0; }
-    if (!strcmp(key, "panel0_whole")) { ls->panel0_whole = (int)value; return 0; }
     if (!strcmp(key, "dag_js2")) { ls->dag_js2_override = (int)value; return 0; }   // experiments: strip-column at which every row joins the band (-1: by size)
     if (!strcmp(key, "outer_block")) {
         int64_t v = (int64_t)value;
@@ -737,11 +732,8 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         return 0;
     }
     if (!strcmp(key, "solve512")) { ls->solve512 = value != 0; return 0; }   // 512-column steps of the one-launch solve
-    if (!strcmp(key, "solve512_min_rows")) { ls->solve512_min_rows = (int64_t)value; return 0; }
     if (!strcmp(key, "linv_mfma")) { ls->linv_mfma = value != 0.0; return 0; }
-    if (!strcmp(key, "dag_chain_inline")) { ls->dag_chain_inline = value != 0.0; return 0; }
     if (!strcmp(key, "prefill")) { ls->prefill = value != 0; return 0; }   // background zero-fill into a second factor buffer
-    if (!strcmp(key, "prefill_max_rows")) { ls->prefill_max_rows = (int64_t)value; return 0; }
     if (!strcmp(key, "single_rows")) {  // systems up to this order: one outer panel, no look-ahead (0: never)
         ls->single_rows = (int64_t)value;
         ls->wbuf[0].release();
@@ -753,7 +745,6 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     // 2: always (used by the schedule tests)
     if (!strcmp(key, "share")) { ls->share = (int)value; return 0; }
     if (!strcmp(key, "small_tiles")) { ls->small_tiles = (int)value; return 0; }
-    if (!strcmp(key, "small_tiles_mid")) { ls->small_tiles_mid = (int)value; return 0; }
     // 5: task-DAG schedule (persistent left-looking bulk kernel beside the pivot chain, dag.hip); 4: persistent panel
     // kernel per 256 columns + one trailing update per outer panel; 1: one launch per piece (the fallback of 4 and 5)
     if (!strcmp(key, "panel_algo")) {
@@ -795,7 +786,6 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         ls->dag_tasks.release();
         return 0;
     }
-    if (!strcmp(key, "batch_period")) { ls->batch_period = (int)value; return 0; }
     if (!strcmp(key, "dag_trace")) { ls->dag_trace_on = value != 0.0; return 0; }  // diagnostics: tools/dag_timeline.py
     if (!strcmp(key, "dag_max_rows")) { ls->dag_max_rows = (int64_t)value; return 0; }
     if (!strcmp(key, "dag_deep_rows")) { ls->dag_deep_rows = (int64_t)value; ls->dag_tasks.release(); return 0; }   // largest order with every row in the chain's band
@@ -886,7 +876,7 @@ static int prepare_fill(mnk_ls* ls) {
     mnk_ctx* ctx = ls->ctx;
     hipStream_t s = ctx->stream;
     dim3 grid((unsigned)ls->Np, (unsigned)((ls->Np / 2 + 255) / 256));
-    bool pre = ls->prefill && ls->Np <= ls->prefill_max_rows;
+    bool pre = ls->prefill && ls->Np <= mnk_ls::PREFILL_MAX_ROWS;
     if (pre && !ls->fact_spare.p) {
         // second factor buffer, events, side stream; if any of it cannot be had the fill stays in line
         if (ls->fact_spare.alloc(ls->fact.n) != 0) { (void)hipGetLastError(); ls->prefill = 0; pre = false; }
@@ -1443,7 +1433,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     }
     if (!strcmp(key, "panel_algo")) { *value = ls->algo_now; return 0; }
     if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp_fallbacks; return 0; }
-    // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 3 gate on the bulk stream, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
+    // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
     if (!strcmp(key, "timeout_site")) { *value = ls->last_timeout_site; return 0; }
     if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe_hits; return 0; }       // matrices rejected by the leading-block probe alone
     if (!strcmp(key, "probe_misses")) { *value = (double)ls->probe_misses; return 0; }   // probes that passed (the full factorization followed)
@@ -1531,103 +1521,6 @@ int mnk_gemm_nt(mnk_ctx* ctx, int mode, int64_t M, int64_t N, int64_t K, const d
     MNK_REQUIRE(ctx && A && B && C, "mnk_gemm_nt: NULL argument");
     MNK_HIP(hipSetDevice(ctx->device));
     return launch_gemm_nt(ctx->stream, mode, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, nullptr);
-}
-
-// Clock probe: one wave runs a fixed dependent chain of fp64 FMAs and reports the elapsed constant-rate
-// (100 MHz) timer ticks; run beside a load, the ratio to the idle value is the shader-clock ratio.
-__global__ void clock_probe_kernel(unsigned long long* out, int iters, double a, double b) {
-    double x = (double)threadIdx.x;
-    const unsigned long long t0 = wall_clock64();
-    for (int i = 0; i < iters; ++i) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x = __builtin_fma(x, a, b);
-    }
-    const unsigned long long t1 = wall_clock64();
-    if (threadIdx.x == 0) out[0] = t1 - t0;
-    if (x == 1.2345) out[1] = 1;
-}
-
-// Diagnostics: time `reps` lower-tile updates C -= A*A^T (M x M, depth K) under one of the
-// schedules the factorization uses.  variant 0: static tiling on the context stream (all CUs);
-// 1: tile queue on the context stream; 2: static on the update stream (its CU mask); 3: queue on the
-// update stream; 4: queue drained by update + panel streams together; 5: static on the update
-// stream while the panel stream runs the same product on a second matrix C2 (interference probe);
-// 6-8: static in chunks of 512/1024/256 tiles; 9/10: every tile reads the same operand blocks
-// (context / update stream); 20: clock probe alone, 21: clock probe beside an update (ms <- ticks).
-int mnk_debug_update(mnk_ctx* ctx, int variant, int64_t M, int64_t K, const double* A, int64_t lda, double* C,
-                     double* C2, int64_t ldc, int reps, double* ms) {
-    MNK_REQUIRE(ctx && A && C && ms, "mnk_debug_update: NULL argument");
-    MNK_HIP(hipSetDevice(ctx->device));
-    { int rc_s = mnk_ctx_ensure_panel_streams(ctx); if (rc_s) return rc_s; }
-    hipStream_t s = ctx->stream, su = ctx->su, sp = ctx->sp;
-    MNK_REQUIRE(su && sp, "mnk_debug_update: no look-ahead streams");
-    DevBuf<int> ctr;
-    int rc = ctr.alloc(8 * (size_t)reps);
-    if (rc) return rc;
-    MNK_HIP(hipMemsetAsync(ctr.p, 0, 8 * (size_t)reps * sizeof(int), s));
-    hipEvent_t e0, e1;
-    MNK_HIP(hipEventCreate(&e0));
-    MNK_HIP(hipEventCreate(&e1));
-    const int pcus = ctx->panel_cus, ucus = ctx->num_cu - pcus;
-    MNK_HIP(hipEventRecord(e0, s));
-    MNK_HIP(hipEventRecord(ctx->ev_a, s));
-    MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
-    MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
-    for (int r = 0; r < reps && !rc; ++r) {
-        switch (variant) {
-        case 0: rc = launch_gemm_nt(s, 2, M, M, K, A, lda, A, lda, C, ldc, nullptr, nullptr, 0, nullptr); break;
-        case 1: rc = launch_gemm_nt_queue(s, M, M, K, A, lda, A, lda, C, ldc, ctr.p + 8 * r, ctx->num_cu, nullptr); break;
-        case 2: rc = launch_gemm_nt(su, 2, M, M, K, A, lda, A, lda, C, ldc, nullptr, nullptr, 0, nullptr); break;
-        case 3: rc = launch_gemm_nt_queue(su, M, M, K, A, lda, A, lda, C, ldc, ctr.p + 8 * r, ucus, nullptr); break;
-        case 4:
-            rc = launch_gemm_nt_queue(su, M, M, K, A, lda, A, lda, C, ldc, ctr.p + 8 * r, ucus, nullptr);
-            if (!rc) rc = launch_gemm_nt_queue(sp, M, M, K, A, lda, A, lda, C, ldc, ctr.p + 8 * r, pcus, nullptr);
-            break;
-        case 20: break;  // probe only
-        case 21: rc = launch_gemm_nt(su, 2, M, M, K, A, lda, A, lda, C, ldc, nullptr, nullptr, 0, nullptr); break;
-        case 9: rc = launch_gemm_nt_dbg(s, 1, M, M, K, A, lda, A, lda, C, ldc); break;
-        case 10: rc = launch_gemm_nt_dbg(su, 1, M, M, K, A, lda, A, lda, C, ldc); break;
-        case 11: rc = launch_gemm_nt_dbg(su, 2, M, M, K, A, lda, A, lda, C, ldc); break;  // no k-loop barrier
-        case 12: rc = launch_gemm_nt_dbg(su, 3, M, M, K, A, lda, A, lda, C, ldc); break;  // MFMA + LDS reads only
-        case 13: rc = launch_gemm_nt_dbg(su, 5, M, M, K, A, lda, A, lda, C, ldc); break;  // register staging
-        case 14: rc = launch_gemm_nt_dbg(s, 5, M, M, K, A, lda, A, lda, C, ldc); break;
-        case 15: rc = launch_gemm_nt_dbg(su, 6, M, M, K, A, lda, A, lda, C, ldc); break;  // BK = 16, 2 workgroups/CU
-        case 16: rc = launch_gemm_nt_dbg(s, 6, M, M, K, A, lda, A, lda, C, ldc); break;
-        case 6: case 7: case 8: {  // static tiling on the context stream, one launch per `chunk` tiles
-            const int chunk = variant == 6 ? 2 * ctx->num_cu : variant == 7 ? 4 * ctx->num_cu : ctx->num_cu;
-            const int nt = gemm_nt_lower_tiles(M, M);
-            for (int t = 0; t < nt && !rc; t += chunk)
-                rc = launch_gemm_nt_lower_range(s, M, M, K, A, lda, A, lda, C, ldc, nullptr, t, chunk);
-            break;
-        }
-        default:
-            rc = launch_gemm_nt(su, 2, M, M, K, A, lda, A, lda, C, ldc, nullptr, nullptr, 0, nullptr);
-            if (!rc && C2) rc = launch_gemm_nt(sp, 2, M / 2, M / 2, K, A, lda, A, lda, C2, ldc, nullptr, nullptr, 0, nullptr);
-            break;
-        }
-    }
-    DevBuf<unsigned long long> probe;
-    if (variant == 20 || variant == 21) {
-        rc |= probe.alloc(2);
-        if (!rc) hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, sp, probe.p, 12000, 0.999999, 1e-9);
-    }
-    MNK_HIP(hipEventRecord(ctx->ev_a, sp));
-    MNK_HIP(hipEventRecord(ctx->ev_b, su));
-    MNK_HIP(hipStreamWaitEvent(s, ctx->ev_a, 0));
-    MNK_HIP(hipStreamWaitEvent(s, ctx->ev_b, 0));
-    MNK_HIP(hipEventRecord(e1, s));
-    MNK_HIP(mnk::stream_wait(s));
-    float t = 0.f;
-    MNK_HIP(hipEventElapsedTime(&t, e0, e1));
-    *ms = (double)t;
-    if (variant == 20 || variant == 21) {  // report the probe's ticks (10 ns each) instead
-        unsigned long long h = 0;
-        { mnk::H2DGuard guard; MNK_HIP(hipMemcpy(&h, probe.p, sizeof(h), hipMemcpyDeviceToHost)); }
-        *ms = (double)h;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
 }
 
 }  // extern "C"

@@ -950,11 +950,11 @@ __global__ __launch_bounds__(256, 3) void inv512_gemm_kernel(const double* __res
     double* T = Tt + t * 65536;
     if (STAGE == 1) {
         const double* C = F + (512 * t + 256) + (512 * t) * ld;
-        gemm_nt_tile<2, 2, 4, 1, false, 0, 8>(tm, tn, 256, 256, 256, IA_t, 256, C, ld, T, 256, nullptr, nullptr, 0, smem_raw);
+        gemm_nt_tile<2, 2, 4, 1, false, 8>(tm, tn, 256, 256, 256, IA_t, 256, C, ld, T, 256, nullptr, nullptr, 0, smem_raw);
     } else if (blockIdx.z == 0) {
-        gemm_nt_tile<2, 2, 4, 0, false, 0, 8>(tm, tn, 256, 256, 256, ID, 256, T, 256, Inv512 + t * 262144 + 256, 512, nullptr, nullptr, 0, smem_raw);
+        gemm_nt_tile<2, 2, 4, 0, false, 8>(tm, tn, 256, 256, 256, ID, 256, T, 256, Inv512 + t * 262144 + 256, 512, nullptr, nullptr, 0, smem_raw);
     } else {
-        gemm_nt_tile<2, 2, 4, 0, false, 0, 8>(tm, tn, 256, 256, 256, T, 256, ID, 256, InvT512 + t * 262144 + (int64_t)256 * 512, 512, nullptr, nullptr, 0, smem_raw);
+        gemm_nt_tile<2, 2, 4, 0, false, 8>(tm, tn, 256, 256, 256, T, 256, ID, 256, InvT512 + t * 262144 + (int64_t)256 * 512, 512, nullptr, nullptr, 0, smem_raw);
     }
 }
 
@@ -977,7 +977,8 @@ int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
     //   inv [A 0; C D] = [A^-1 0; -D^-1 C A^-1  D^-1],   T' = A^-T C' (stage 1),  X = -D^-1 T,  X' = -T' D^-T (stage 2)
     // (a 512 x 512 triangle inverted block by block with the scalar kernel above costs 35 dependent 64x64x16 products:
     // +0.63 ms on factorize! at C3, measured).
-    if (ls->solve512 && ls->Np >= ls->solve512_min_rows && ls->Np % 512 != 384 && !ls->linv512.p) {
+    constexpr int64_t SOLVE512_MIN_ROWS = 4096;
+    if (ls->solve512 && ls->Np >= SOLVE512_MIN_ROWS && ls->Np % 512 != 384 && !ls->linv512.p) {
         const size_t ntri = (size_t)((ls->Np + 511) / 512);
         if (ls->linv512.alloc(ntri * 512 * 512) || ls->linv512t.alloc(ntri * 512 * 512) || ls->linv512tmp.alloc(ntri * 256 * 256)) {
             (void)hipGetLastError();
@@ -1255,13 +1256,12 @@ static int solve_batch_flush() {
     pend.swap(t_sbatch.pend);
     // systems per launch: four for large systems (measured at N = 11 192: 2 -> 104.0, 4 -> 107.4, 8 -> 106.2 it/s of the C5
     // step), as many as the CUs hold for small ones (a 512-row block has 8 blocks of 64 rows: 32 of them per launch)
-    static const int envq = []() { const char* e = getenv("MNK_SOLVE_BATCH_Q"); return e ? std::max(1, std::min(PS_BATCH_MAXQ, atoi(e))) : 0; }();
     int rc_all = 0;
     while (!pend.empty()) {
         mnk_ls* l0 = pend.front().ls;
         const int64_t nb64 = l0->Np / 64;
         const int g4 = (int)std::max<int64_t>(1, std::min<int64_t>(nb64, l0->ctx->num_cu / 4));   // workgroups of a system when four share the chip
-        const int maxq = envq > 0 ? envq : std::max(1, std::min(PS_BATCH_MAXQ, l0->ctx->num_cu / g4));
+        const int maxq = std::max(1, std::min(PS_BATCH_MAXQ, l0->ctx->num_cu / g4));
         std::vector<SolveReq> g, rest;
         for (const SolveReq& r : pend) {
             bool take = (int)g.size() < maxq && r.ls->ctx->device == l0->ctx->device && r.ls->Np == l0->Np && r.ls->algo == l0->algo;

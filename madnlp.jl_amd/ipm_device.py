@@ -4,7 +4,6 @@ Python float.  Same names as the reference; the `_r` views are taken inside the 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -19,22 +18,17 @@ def _dev(v):
 
 
 class _Batch:
-    """MNK_IPM_NO_BATCH=1 (A/B): the calls of the block synchronize one by one, as outside a batch."""
-    _off = os.environ.get("MNK_IPM_NO_BATCH", "0") not in ("", "0")
-
     def __init__(self, K):
         self.K = K
 
     def __enter__(self):
-        if not self._off:
-            L.check(L.lib().mnk_ipm_batch_begin(self.K._h), "mnk_ipm_batch_begin")
+        L.check(L.lib().mnk_ipm_batch_begin(self.K._h), "mnk_ipm_batch_begin")
         self.K._batching, self.K._keep = True, []
         return self.K
 
     def __exit__(self, *exc):
         self.K._batching = False
-        if not self._off:
-            L.check(L.lib().mnk_ipm_batch_end(self.K._h), "mnk_ipm_batch_end")
+        L.check(L.lib().mnk_ipm_batch_end(self.K._h), "mnk_ipm_batch_end")
         self.K._keep = []
         return False
 

@@ -781,3 +781,32 @@ def test_environment_overrides_win_over_set_option(ctx, monkeypatch, capfd):
     ls.factorize()
     assert ls.get_stat("panel_algo") == 5.0
     ls.close()
+
+
+def test_deployment_shorthands_pin_the_non_persistent_schedules(ctx, monkeypatch):
+    """MNK_PANEL_ALGO / MNK_PERSISTENT_SOLVE, the two shorthands INTEGRATION.md gives a deployment that shares a GPU between
+    processes: read at mnk_ls_create like MNK_OPTIONS, pinned against later set_option calls; the factorization then runs one
+    launch per piece and the stepwise solve still solves."""
+    rng = np.random.default_rng(4)
+    N = 1700
+    R = rng.standard_normal((N, 32))
+    A = R @ R.T + np.eye(N) * 5.0
+    monkeypatch.setenv("MNK_PANEL_ALGO", "1")
+    monkeypatch.setenv("MNK_PERSISTENT_SOLVE", "0")
+    ls = mj.HipLinearSolver(np.asfortranarray(A), ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm="CHOLESKY", panel_algo=5))
+    ls.set_option("persistent_solve", 1)   # ignored: pinned
+    ls.factorize()
+    assert ls.inertia() == (N, 0, 0)
+    assert ls.get_stat("panel_algo") == 1.0
+    assert ls.get_stat("pinned:panel_algo") == 1.0 and ls.get_stat("pinned:persistent_solve") == 1.0
+    b = rng.standard_normal(N)
+    x = b.copy()
+    ls.solve_linear_system(x)
+    res = np.abs(A @ x - b).max() / (np.abs(A).sum(axis=1).max() * np.abs(x).max() + np.abs(b).max())
+    assert res <= 1e-14, res
+    ls.close()
+    monkeypatch.delenv("MNK_PANEL_ALGO")
+    monkeypatch.delenv("MNK_PERSISTENT_SOLVE")
+    ls = mj.HipLinearSolver(np.asfortranarray(A), ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm="CHOLESKY", panel_algo=5))
+    assert ls.get_stat("pinned:panel_algo") == 0.0 and ls.get_stat("pinned:persistent_solve") == 0.0
+    ls.close()
