@@ -37,7 +37,7 @@
 
 namespace mnk {
 
-constexpr int EB = EVD_BLOCK;      // block width
+constexpr int EB = 32;            // block width: columns per block of the block Jacobi (a pivot block is 64 x 64: twice in LDS)
 constexpr int EP = 2 * EB;         // order of a pivot block
 static_assert(EB == 32, "the kernels of evd.hip are written for 32-column blocks");
 constexpr int ELD = EP + 1;        // leading dimension of the pair kernel's LDS matrices
@@ -486,139 +486,138 @@ __global__ __launch_bounds__(256) void evd_sum_kernel(const double* __restrict__
     x[i] = acc;
 }
 
+struct EvdSolver final : mnk_ls_alt {
+    // the work matrix (full, Np x Np) that the block Jacobi sweeps diagonalize and the accumulated eigenvectors, the transposed
+    // 64 x 64 rotations of a round's block pairs and their "identity" marks, per-column sums of squares of the stop test, the
+    // unsorted eigenvalues and their ranks, the 64-column partial sums of x = Q t
+    DevBuf<double> evd_a, evd_v, evd_rt, evd_colsum, evd_lam, evd_part;
+    DevBuf<int> evd_ident, evd_rank;
+    int evd_sweep_cap = 60;      // sweeps after which factorize! gives up (info = 1).  Measured: 5-13 on random matrices, 17 and 23 on
+                                 // the bench's matrices, whose off-norm falls 2-4 x per sweep through a long linear phase before the
+                                 // quadratic end; 60 still serves a rate of 1.7 x per sweep
+    int evd_sweeps = 0;          // sweeps of the last factorization (get_stat "evd_sweeps")
+
+    int alloc(mnk_ls* ls) override {
+        const size_t Np = (size_t)ls->Np;
+        int rc = evd_a.alloc(Np * Np + SLACK);
+        rc |= evd_v.alloc(Np * Np + SLACK);
+        rc |= evd_rt.alloc((Np / EP) * (EP * EP));
+        rc |= evd_ident.alloc(Np / EP);
+        rc |= evd_colsum.alloc(2 * Np);
+        rc |= evd_lam.alloc(Np);
+        rc |= evd_rank.alloc(Np);
+        rc |= evd_part.alloc((Np / 64) * Np);
+        return rc;
+    }
+
+    // off(A)^2 and |A|_F^2 of the work matrix, through the pinned words (waits for the stream)
+    int norms(mnk_ls* ls, double* off2, double* all2) {
+        hipStream_t s = ls->ctx->stream;
+        hipLaunchKernelGGL(evd_colnorm_kernel, dim3((unsigned)ls->N), dim3(256), 0, s, evd_a.p, ls->Np, ls->N, evd_colsum.p);
+        hipLaunchKernelGGL(evd_norm_kernel, dim3(1), dim3(256), 0, s, evd_colsum.p, ls->N, ls->pin_dev);
+        MNK_HIP(hipGetLastError());
+        MNK_HIP(stream_wait(s));
+        volatile unsigned long long* pw = ls->pin;
+        const unsigned long long wo = pw[4], wa = pw[5];
+        memcpy(off2, &wo, sizeof wo);
+        memcpy(all2, &wa, sizeof wa);
+        return 0;
+    }
+
+    // factorize! of an EVD solver: the matrix has been transferred (lower triangle); see the top.  Runs to its end before it
+    // returns (one host synchronization per sweep), so the *_async entry points are synchronous for EVD.
+    int factor(mnk_ls* ls) override {
+        hipStream_t s = ls->ctx->stream;
+        const int64_t N = ls->N, Np = ls->Np;
+        const int nb = (int)(Np / EB), npairs = nb / 2;
+        double *A = evd_a.p, *V = evd_v.p;
+        {   // the pair kernel's LDS is above the static limit: once per (kernel, device) pair of this process
+            static std::atomic<uint64_t> attr_devs{0};
+            int dev = 0;
+            MNK_HIP(hipGetDevice(&dev));
+            if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
+                MNK_HIP(hipFuncSetAttribute((const void*)evd_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EVD_PAIR_LDS));
+                attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+            }
+        }
+        hipLaunchKernelGGL(evd_init_kernel, dim3((unsigned)Np), dim3(256), 0, s, ls->fact.p, ls->ld, N, Np, A, V);
+        MNK_HIP(hipGetLastError());
+        int info = 0, sweeps = 0;
+        // Stop rule: off(A) <= N eps |A|_F, the Frobenius test, leaves a residual |A Q - Q L|_1 of up to sqrt(N) times that
+        // (measured at N = 2100: scaled residuals of 5 .. 95 where the other ratios are below 1).  Convergence is quadratic, so
+        // one sweep more takes off(A) to rounding level: the sweeps end when off <= eps |A|_F, or when the Frobenius test had
+        // already held before the last sweep.
+        bool near = false;
+        for (;;) {
+            double off2 = 0.0, all2 = 0.0;
+            int rc = norms(ls, &off2, &all2);
+            if (rc) return rc;
+            // (a NaN / Inf entry, or one above 1e154, makes the norm non-finite for good: no sweep can help)
+            if (!std::isfinite(all2)) { info = 1; break; }
+            const double off = std::sqrt(off2), nrm = std::sqrt(all2);
+            if (off <= DBL_EPSILON * nrm) break;
+            if (off <= (double)N * DBL_EPSILON * nrm) {
+                if (near) break;
+                near = true;
+            }
+            if (sweeps >= evd_sweep_cap) { info = near ? 0 : 1; break; }
+            for (int round = 0; round < nb - 1; ++round) {
+                hipLaunchKernelGGL(evd_pair_kernel, dim3(npairs), dim3(256), EVD_PAIR_LDS, s, A, Np, N, nb, round, evd_rt.p,
+                                   evd_ident.p);
+                hipLaunchKernelGGL(evd_update_kernel<true>, dim3((unsigned)(npairs * (npairs + 1) / 2)), dim3(256), 0, s, A, Np,
+                                   nb, round, evd_rt.p, evd_ident.p);
+                hipLaunchKernelGGL(evd_update_kernel<false>, dim3((unsigned)(Np / EP), (unsigned)npairs), dim3(256), 0, s, V, Np,
+                                   nb, round, evd_rt.p, evd_ident.p);
+            }
+            MNK_HIP(hipGetLastError());
+            ++sweeps;
+        }
+        evd_sweeps = sweeps;
+        const unsigned g = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(evd_diag_kernel, dim3(g), dim3(256), 0, s, A, Np, N, evd_lam.p);
+        hipLaunchKernelGGL(evd_rank_kernel, dim3(g), dim3(256), 0, s, evd_lam.p, N, evd_rank.p);
+        hipLaunchKernelGGL(evd_permute_kernel, dim3((unsigned)N), dim3(256), 0, s, V, Np, N, evd_rank.p, evd_lam.p, ls->fact.p,
+                           ls->ld, ls->dvec.p);
+        hipLaunchKernelGGL(evd_inertia_kernel, dim3(1), dim3(256), 0, s, evd_lam.p, N, info, ls->pin_dev);
+        MNK_HIP(hipGetLastError());
+        ls->info = info;
+        return 0;
+    }
+
+    // info (0, or 1 at the sweep cap) and the inertia (the signs of lambda) of the factorization queued last, from the pinned
+    // words (waits for it)
+    int fetch_info(mnk_ls* ls) override {
+        MNK_HIP(stream_wait(ls->ctx->stream));
+        volatile unsigned long long* pw = ls->pin;
+        ls->npos = (int64_t)pw[0];
+        ls->nzero = (int64_t)pw[1];
+        ls->nneg = (int64_t)pw[2];
+        ls->info = (int)(long long)pw[3];
+        ls->info_valid = true;
+        return 0;
+    }
+
+    // solve_linear_system! of an EVD solver (reference src/LinearSolvers/lapack.jl:229-234).  The division is IEEE's: a zero
+    // eigenvalue gives Inf / NaN.
+    int solve_vec(mnk_ls* ls, const double* b, double* x) override {
+        hipStream_t s = ls->ctx->stream;
+        const int64_t N = ls->N, Np = ls->Np, ld = ls->ld;
+        const double* Q = ls->fact.p;
+        double* t = ls->xwork.p + Np;
+        const int nchunk = (int)((N + 63) / 64);
+        const unsigned g = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(evd_qtx_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, Q, ld, N, ls->dvec.p, b, t);
+        hipLaunchKernelGGL(evd_qt_kernel, dim3(g, (unsigned)nchunk), dim3(256), 0, s, Q, ld, N, Np, t, evd_part.p);
+        hipLaunchKernelGGL(evd_sum_kernel, dim3(g), dim3(256), 0, s, evd_part.p, N, Np, nchunk, x);
+        MNK_HIP(hipGetLastError());
+        return 0;
+    }
+
+    double stat(const char* key) override { return !strcmp(key, "evd_sweeps") ? (double)evd_sweeps : 0.0; }
+};
+
 }  // namespace mnk
 
 using namespace mnk;
 
-int mnk_evd_alloc(mnk_ls* ls) {
-    const size_t Np = (size_t)ls->Np;
-    int rc = ls->evd_a.alloc(Np * Np + SLACK);
-    rc |= ls->evd_v.alloc(Np * Np + SLACK);
-    rc |= ls->evd_rt.alloc((Np / EP) * (EP * EP));
-    rc |= ls->evd_ident.alloc(Np / EP);
-    rc |= ls->evd_colsum.alloc(2 * Np);
-    rc |= ls->evd_lam.alloc(Np);
-    rc |= ls->evd_rank.alloc(Np);
-    rc |= ls->evd_part.alloc((Np / 64) * Np);
-    return rc;
-}
-
-// off(A)^2 and |A|_F^2 of the work matrix, through the pinned words (waits for the stream)
-static int evd_norms(mnk_ls* ls, double* off2, double* all2) {
-    hipStream_t s = ls->ctx->stream;
-    hipLaunchKernelGGL(evd_colnorm_kernel, dim3((unsigned)ls->N), dim3(256), 0, s, ls->evd_a.p, ls->Np, ls->N, ls->evd_colsum.p);
-    hipLaunchKernelGGL(evd_norm_kernel, dim3(1), dim3(256), 0, s, ls->evd_colsum.p, ls->N, ls->pin_dev);
-    MNK_HIP(hipGetLastError());
-    MNK_HIP(stream_wait(s));
-    volatile unsigned long long* pw = ls->pin;
-    const unsigned long long wo = pw[4], wa = pw[5];
-    memcpy(off2, &wo, sizeof wo);
-    memcpy(all2, &wa, sizeof wa);
-    return 0;
-}
-
-// factorize! of an EVD solver: the matrix has been transferred (lower triangle); see the top.  Runs to its end before it
-// returns (one host synchronization per sweep), so the *_async entry points are synchronous for EVD.
-int mnk_evd_factor(mnk_ls* ls) {
-    hipStream_t s = ls->ctx->stream;
-    const int64_t N = ls->N, Np = ls->Np;
-    const int nb = (int)(Np / EB), npairs = nb / 2;
-    ++ls->fact_count;
-    ls->factor_invalid = false;
-    ls->bk_active = false;
-    ls->t_fact_launch_ms = mnk_host_ms();
-    double* A = ls->evd_a.p;
-    double* V = ls->evd_v.p;
-    {   // the pair kernel's LDS is above the static limit: once per (kernel, device) pair of this process
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        MNK_HIP(hipGetDevice(&dev));
-        if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-            MNK_HIP(hipFuncSetAttribute((const void*)evd_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EVD_PAIR_LDS));
-            attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
-    }
-    hipLaunchKernelGGL(evd_init_kernel, dim3((unsigned)Np), dim3(256), 0, s, ls->fact.p, ls->ld, N, Np, A, V);
-    MNK_HIP(hipGetLastError());
-    int info = 0, sweeps = 0;
-    // Stop rule: off(A) <= N eps |A|_F, the Frobenius test, leaves a residual |A Q - Q L|_1 of up to sqrt(N) times that (measured
-    // at N = 2100: scaled residuals of 5 .. 95 where the other ratios are below 1).  Convergence is quadratic, so one sweep
-    // more takes off(A) to rounding level: the sweeps end when off <= eps |A|_F, or when the Frobenius test had already held
-    // before the last sweep.
-    bool near = false;
-    for (;;) {
-        double off2 = 0.0, all2 = 0.0;
-        int rc = evd_norms(ls, &off2, &all2);
-        if (rc) return rc;
-        // (a NaN / Inf entry, or one above 1e154, makes the norm non-finite for good: no sweep can help)
-        if (!std::isfinite(all2)) { info = 1; break; }
-        const double off = std::sqrt(off2), nrm = std::sqrt(all2);
-        if (off <= DBL_EPSILON * nrm) break;
-        if (off <= (double)N * DBL_EPSILON * nrm) {
-            if (near) break;
-            near = true;
-        }
-        if (sweeps >= ls->evd_sweep_cap) { info = near ? 0 : 1; break; }
-        for (int round = 0; round < nb - 1; ++round) {
-            hipLaunchKernelGGL(evd_pair_kernel, dim3(npairs), dim3(256), EVD_PAIR_LDS, s, A, Np, N, nb, round, ls->evd_rt.p,
-                               ls->evd_ident.p);
-            hipLaunchKernelGGL(evd_update_kernel<true>, dim3((unsigned)(npairs * (npairs + 1) / 2)), dim3(256), 0, s, A, Np, nb,
-                               round, ls->evd_rt.p, ls->evd_ident.p);
-            hipLaunchKernelGGL(evd_update_kernel<false>, dim3((unsigned)(Np / EP), (unsigned)npairs), dim3(256), 0, s, V, Np, nb,
-                               round, ls->evd_rt.p, ls->evd_ident.p);
-        }
-        MNK_HIP(hipGetLastError());
-        ++sweeps;
-    }
-    ls->evd_sweeps = sweeps;
-    const unsigned g = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(evd_diag_kernel, dim3(g), dim3(256), 0, s, A, Np, N, ls->evd_lam.p);
-    hipLaunchKernelGGL(evd_rank_kernel, dim3(g), dim3(256), 0, s, ls->evd_lam.p, N, ls->evd_rank.p);
-    hipLaunchKernelGGL(evd_permute_kernel, dim3((unsigned)N), dim3(256), 0, s, V, Np, N, ls->evd_rank.p, ls->evd_lam.p, ls->fact.p,
-                       ls->ld, ls->dvec.p);
-    hipLaunchKernelGGL(evd_inertia_kernel, dim3(1), dim3(256), 0, s, ls->evd_lam.p, N, info, ls->pin_dev);
-    MNK_HIP(hipGetLastError());
-    ls->info = info;
-    ls->npos = ls->nzero = ls->nneg = 0;
-    ls->factorized = true;
-    ls->info_valid = false;
-    return 0;
-}
-
-// info and the inertia of the factorization queued last, from the pinned words (waits for it)
-int mnk_evd_fetch_info(mnk_ls* ls) {
-    MNK_HIP(stream_wait(ls->ctx->stream));
-    volatile unsigned long long* pw = ls->pin;
-    ls->npos = (int64_t)pw[0];
-    ls->nzero = (int64_t)pw[1];
-    ls->nneg = (int64_t)pw[2];
-    ls->info = (int)(long long)pw[3];
-    ls->info_valid = true;
-    return 0;
-}
-
-// solve_linear_system! of an EVD solver (reference src/LinearSolvers/lapack.jl:229-234): nrhs columns of x (leading
-// dimension ldx, host or device), in place.  The division is IEEE's: a zero eigenvalue gives Inf / NaN.
-int mnk_evd_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
-    hipStream_t s = ls->ctx->stream;
-    const int64_t N = ls->N, Np = ls->Np, ld = ls->ld;
-    const double* Q = ls->fact.p;
-    double* stage = ls->xwork.p;
-    double* t = ls->xwork.p + Np;
-    const int nchunk = (int)((N + 63) / 64);
-    const unsigned g = (unsigned)((N + 255) / 256);
-    for (int64_t k = 0; k < nrhs; ++k) {
-        double* xk = x + k * ldx;
-        double* xd = xk;
-        if (loc != MNK_DEVICE) {
-            MNK_HIP(h2d_copy(stage, xk, N * sizeof(double), s));
-            xd = stage;
-        }
-        hipLaunchKernelGGL(evd_qtx_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, Q, ld, N, ls->dvec.p, xd, t);
-        hipLaunchKernelGGL(evd_qt_kernel, dim3(g, (unsigned)nchunk), dim3(256), 0, s, Q, ld, N, Np, t, ls->evd_part.p);
-        hipLaunchKernelGGL(evd_sum_kernel, dim3(g), dim3(256), 0, s, ls->evd_part.p, N, Np, nchunk, xd);
-        MNK_HIP(hipGetLastError());
-        if (loc != MNK_DEVICE) MNK_HIP(d2h_copy(xk, stage, N * sizeof(double), s));
-    }
-    return 0;
-}
+std::unique_ptr<mnk_ls_alt> mnk_evd_new() { return std::make_unique<EvdSolver>(); }

@@ -1188,9 +1188,7 @@ int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t
 }
 
 int mnk_ls_run_factorization(mnk_ls* ls) {
-    if (ls->algo == MNK_QR) return mnk_qr_factor(ls);   // (not merged into a factorization batch: runs when called)
-    if (ls->algo == MNK_LU) return mnk_lu_factor(ls);   // (likewise)
-    if (ls->algo == MNK_EVD) return mnk_evd_factor(ls);   // (likewise; it also runs to its end before it returns)
+    if (ls->alt) return mnk_ls_alt_factorize(ls);   // (not merged into a factorization batch: runs when called)
     mnk_ctx* ctx = ls->ctx;
     hipStream_t s = ctx->stream;
     const int64_t Np = ls->Np;
@@ -1532,14 +1530,7 @@ static int bk_fallback(mnk_ls* ls) {
 int mnk_ls_fetch_info(mnk_ls* ls) {
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
     if (ls->info_valid) return 0;
-    if (ls->algo == MNK_QR) {   // geqrf's info is always 0; a singular matrix shows up in the solve
-        MNK_HIP(mnk::stream_wait(ls->ctx->stream));
-        ls->info = 0;
-        ls->info_valid = true;
-        return 0;
-    }
-    if (ls->algo == MNK_LU) return mnk_lu_fetch_info(ls);   // getrf's info: the first exactly zero pivot (1-based), 0 if none
-    if (ls->algo == MNK_EVD) return mnk_evd_fetch_info(ls);   // 0, or 1 at the sweep cap; the inertia is the signs of lambda
+    if (ls->alt) return ls->alt->fetch_info(ls);
     hipStream_t s = ls->ctx->stream;
     if (ls->bk_active) {
         MNK_HIP(hipMemsetAsync(ls->inertia_dev.p, 0, 3 * sizeof(unsigned long long), s));

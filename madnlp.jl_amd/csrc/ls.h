@@ -1,4 +1,4 @@
-// Internal layout of the opaque handles (shared by factor.hip, solve.hip, ls.hip, kkt units).
+// Internal layout of the opaque handles (shared by factor.hip, solve.hip, ls.hip, kkt units).  mnk_ls is the tiled Cholesky / LDL^T solver; QR, LU and EVD live behind mnk_ls_alt and keep their state in their own units.
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -91,7 +91,23 @@ struct mnk_dc {
 };
 void mnk_dc_qn_release(mnk_dc* dc);   // qn.hip: frees mnk_dc::qn
 
-constexpr int EVD_BLOCK = 32;   // evd.hip: columns per block of the block Jacobi (a pivot block is 64 x 64: twice in LDS)
+struct mnk_ls;
+
+// An algorithm that factors the transferred matrix by something other than the tiled Cholesky / LDL^T: QR (qr.hip), LU (lu.hip),
+// EVD (evd.hip).  It owns its buffers; the matrix, the factor buffer, dvec, xwork and the pinned words are the solver's.
+// ls_alt.hip maps an algorithm to its factory and holds what the three share (the bookkeeping around factor, the loop over
+// right-hand sides); the entry points of the tiled path hand over to it with one `if (ls->alt)` each.
+struct mnk_ls_alt {
+    virtual ~mnk_ls_alt() = default;
+    virtual int alloc(mnk_ls* ls) = 0;
+    virtual int factor(mnk_ls* ls) = 0;       // enqueues the factorization of the transferred lower triangle and sets ls->info (0, or what is known by then)
+    virtual int fetch_info(mnk_ls* ls) = 0;   // waits for it; fills info, info_valid and (where the algorithm reveals it) the inertia
+    // One right-hand side of N entries on the device, b -> x (x may be b).  Workspace: the solver's xwork BEHIND its first Np
+    // entries, which are the staging slot of host-resident right-hand sides (mnk_ls_alt_solve).
+    virtual int solve_vec(mnk_ls* ls, const double* b, double* x) = 0;
+    virtual const char* no_inertia_message() const { return nullptr; }   // mnk_ls_inertia's refusal; nullptr: fetch_info fills the inertia
+    virtual double stat(const char* key) { (void)key; return 0.0; }      // mnk_ls_get_stat keys that belong to one algorithm
+};
 
 struct mnk_ls {
     mnk_ctx* ctx = nullptr;
@@ -247,39 +263,18 @@ struct mnk_ls {
                                  // only happened if that factorization ran to its end (info == 0)
     int info = 0;
     int64_t npos = 0, nzero = 0, nneg = 0;
-    // QR (qr.hip): V of the current panel, the T of every panel (kept for the solves), split-K partials of W^T = A2^T V and
-    // W^T T, partial sums of the panel / solve kernels
-    mnk::DevBuf<double> qr_v, qr_t, qr_w, qr_p;
-    // LU (lu.hip): U12^T of the current panel (B operand of the trailing update), the panel's pivot candidates (64 entries and
-    // the row per 256-row block, two sets used alternately) and the row the next pivot replaces; the pivots (0-based), the
-    // row permutation they compose to (what the solves gather with) and getrf's info
-    mnk::DevBuf<double> lu_ut, lu_p;
-    mnk::DevBuf<int> lu_cand, lu_ipiv, lu_perm, lu_info;
-    // EVD (evd.hip): the work matrix (full, Np x Np) that the block Jacobi sweeps diagonalize and the accumulated eigenvectors,
-    // the transposed 64 x 64 rotations of a round's block pairs and their "identity" marks, per-column sums of squares of the
-    // stop test, the unsorted eigenvalues and their ranks, the 64-column partial sums of x = Q t
-    mnk::DevBuf<double> evd_a, evd_v, evd_rt, evd_colsum, evd_lam, evd_part;
-    mnk::DevBuf<int> evd_ident, evd_rank;
-    int evd_sweep_cap = 60;      // sweeps after which factorize! gives up (info = 1).  Measured: 5-13 on random matrices, 17 and 23 on
-                                 // the bench's matrices, whose off-norm falls 2-4 x per sweep through a long linear phase before the
-                                 // quadratic end; 60 still serves a rate of 1.7 x per sweep
-    int evd_sweeps = 0;          // sweeps of the last factorization (get_stat "evd_sweeps")
+    std::unique_ptr<mnk_ls_alt> alt;   // QR / LU / EVD: the algorithm that factors and solves instead of the tiled path (null for CHOLESKY / LDL)
 };
 
 int64_t mnk_ls_effective_nbo(const mnk_ls* ls);
-int mnk_qr_alloc(mnk_ls* ls);    // qr.hip: the QR solver's buffers
-int mnk_qr_factor(mnk_ls* ls);   // qr.hip: tril_to_full! + blocked Householder QR of the transferred matrix (enqueued only)
-int mnk_qr_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // qr.hip: x <- R^-1 Q^T x
+std::unique_ptr<mnk_ls_alt> mnk_qr_new();    // qr.hip: blocked Householder QR (dgeqrf / ormqr / trsv)
+std::unique_ptr<mnk_ls_alt> mnk_lu_new();    // lu.hip: blocked LU with partial pivoting (dgetrf / dgetrs)
+std::unique_ptr<mnk_ls_alt> mnk_evd_new();   // evd.hip: block Jacobi eigendecomposition (dsyevd)
 int mnk_launch_tril_to_full(hipStream_t s, double* F, int64_t ld, int64_t N, int64_t Np);   // qr.hip: upper(F) = lower(F)^T
 int mnk_launch_upper_bsolve(hipStream_t s, const double* F, int64_t ld, int64_t Np, double* y, double* x);   // qr.hip: x = U^-1 y (y is overwritten)
-int mnk_lu_alloc(mnk_ls* ls);    // lu.hip: the LU solver's buffers
-int mnk_lu_factor(mnk_ls* ls);   // lu.hip: tril_to_full! + blocked LU with partial pivoting of the transferred matrix (enqueued only)
-int mnk_lu_fetch_info(mnk_ls* ls);   // lu.hip: getrf's info of the last factorization (waits for it)
-int mnk_lu_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // lu.hip: x <- U^-1 L^-1 P x
-int mnk_evd_alloc(mnk_ls* ls);    // evd.hip: the EVD solver's buffers
-int mnk_evd_factor(mnk_ls* ls);   // evd.hip: block Jacobi eigendecomposition of the transferred matrix (runs to its end: one host synchronization per sweep)
-int mnk_evd_fetch_info(mnk_ls* ls);   // evd.hip: info (0 / 1: sweep cap) and the spectral inertia of the last factorization
-int mnk_evd_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // evd.hip: x <- Q diag(1 / lambda) Q^T x
+std::unique_ptr<mnk_ls_alt> mnk_ls_alt_new(int algo);   // ls_alt.hip: the algorithm's mnk_ls_alt (null for CHOLESKY / LDL)
+int mnk_ls_alt_factorize(mnk_ls* ls);   // ls_alt.hip: factorize! of a solver with ls->alt (the matrix has been transferred)
+int mnk_ls_alt_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);   // ls_alt.hip: solve! of a solver with ls->alt
 int mnk_ls_run_factorization(mnk_ls* ls);
 int mnk_ls_run_factorization_now(mnk_ls* ls);      // factor.hip: the launch part (the schedule has been chosen; batches call it for leftovers)
 int mnk_ls_launch_finish_info(mnk_ls* ls, hipStream_t s);   // factor.hip: inertia / growth words / info -> pinned host words

@@ -657,17 +657,10 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     }
     rc |= ls->info_dev.alloc(4);   // info | which bounded device-side wait expired (info = -7) / last valid pivot (info = -9) | early-rejection switch | -
     rc |= ls->inertia_dev.alloc(3);
-    if (algo == MNK_QR) {
-        rc |= mnk_qr_alloc(ls);
-        ls->prefill = 0;   // (qr.hip overwrites the whole factor buffer's upper triangle: no background zero-fill)
-    }
-    if (algo == MNK_LU) {
-        rc |= mnk_lu_alloc(ls);
-        ls->prefill = 0;   // (lu.hip, likewise)
-    }
-    if (algo == MNK_EVD) {
-        rc |= mnk_evd_alloc(ls);
-        ls->prefill = 0;   // (evd.hip writes Q over the whole factor buffer)
+    ls->alt = mnk_ls_alt_new(algo);
+    if (ls->alt) {
+        rc |= ls->alt->alloc(ls);
+        ls->prefill = 0;   // (they write the whole factor buffer, the upper triangle included: no background zero-fill)
     }
     if (rc) { delete ls; return -2; }
     MNK_HIP(hipMemsetAsync(ls->fact.p, 0, ((size_t)ls->ld * ls->Np + SLACK) * sizeof(double), ctx->stream));
@@ -940,7 +933,7 @@ static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<i
                          const std::vector<int32_t>& envh_host) {
     ls->env_dev = nullptr;
     ls->envh_dev = nullptr;
-    if (!ls->envelope || env_dev == nullptr || ls->algo == MNK_QR || ls->algo == MNK_LU || ls->algo == MNK_EVD) return nullptr;
+    if (!ls->envelope || env_dev == nullptr || ls->alt) return nullptr;
     if (!ls->env_word.p) {
         if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
             (void)hipGetLastError();   // (no envelope then)
@@ -1232,8 +1225,7 @@ int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* row
 
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
     MNK_REQUIRE(ls, "mnk_ls_inertia: NULL argument");
-    MNK_REQUIRE(ls->algo != MNK_QR, "mnk_ls_inertia: a QR factorization reveals no inertia (is_inertia is false for QR)");
-    MNK_REQUIRE(ls->algo != MNK_LU, "mnk_ls_inertia: an LU factorization reveals no inertia (is_inertia is false for LU)");
+    if (ls->alt) { const char* refusal = ls->alt->no_inertia_message(); MNK_REQUIRE(refusal == nullptr, refusal); }
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
     MNK_REQUIRE(ls->factorized, "mnk_ls_inertia: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
@@ -1291,9 +1283,7 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
     { int rc_f = ensure_complete_factor(ls, "mnk_ls_solve"); if (rc_f) return rc_f; }
     MNK_REQUIRE(nrhs >= 1 && ldx >= ls->N, "mnk_ls_solve: bad nrhs/ldx");
     MNK_HIP(hipSetDevice(ls->ctx->device));
-    if (ls->algo == MNK_QR) return mnk_qr_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
-    if (ls->algo == MNK_LU) return mnk_lu_solve(ls, x, nrhs, ldx, loc);   // (likewise)
-    if (ls->algo == MNK_EVD) return mnk_evd_solve(ls, x, nrhs, ldx, loc);   // (likewise)
+    if (ls->alt) return mnk_ls_alt_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
     if (ls->solve_abort && *ls->solve_abort != 0) {
         // a previous solve on device-resident vectors gave up (its result is invalid): fail loudly now and use
         // the stepwise solve from here on
@@ -1445,7 +1435,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "growth")) { *value = ls->last_growth; return 0; }  // BUNCHKAUFMAN: max|d_k| / max|a_ij| of the static-pivot tier
     if (!strcmp(key, "sign_changes")) { *value = (double)ls->last_sign_changes; return 0; }  // ... and sign changes along its pivots
     if (!strcmp(key, "bk_count")) { *value = ls->bk_count; return 0; }
-    if (!strcmp(key, "evd_sweeps")) { *value = ls->evd_sweeps; return 0; }   // EVD: block Jacobi sweeps of the last factorization
+    if (!strcmp(key, "evd_sweeps")) { *value = ls->alt ? ls->alt->stat(key) : 0.0; return 0; }   // EVD: block Jacobi sweeps of the last factorization
     if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk_multi_last ? 1.0 : 0.0; return 0; }
     if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk_mw_fallbacks; return 0; }
     if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain

@@ -321,116 +321,102 @@ __global__ __launch_bounds__(256) void lu_pivots_out_kernel(const int* __restric
 
 static int lu_nblk(int64_t Np) { return (int)((Np + LU_RB - 1) / LU_RB); }
 
+struct LuSolver final : mnk_ls_alt {
+    // U12^T of the current panel (B operand of the trailing update), the panel's pivot candidates (64 entries and the row per
+    // 256-row block, two sets used alternately) and the row the next pivot replaces; the pivots (0-based), the row permutation
+    // they compose to (what the solves gather with) and getrf's info
+    DevBuf<double> lu_ut, lu_p;
+    DevBuf<int> lu_cand, lu_ipiv, lu_perm, lu_info;
+
+    int alloc(mnk_ls* ls) override {
+        const int64_t Np = ls->Np;
+        const int nblk = lu_nblk(Np);
+        int rc = lu_ut.alloc((size_t)Np * LB + SLACK * LB);
+        rc |= lu_p.alloc((size_t)2 * nblk * 64 + 2 * 64);
+        rc |= lu_cand.alloc((size_t)2 * nblk);
+        rc |= lu_ipiv.alloc((size_t)Np);
+        rc |= lu_perm.alloc((size_t)Np);
+        rc |= lu_info.alloc(1);
+        return rc;
+    }
+
+    // factorize! of an LU solver: the matrix has been transferred (lower triangle); mirror it and factor it (see the top).
+    int factor(mnk_ls* ls) override {
+        hipStream_t s = ls->ctx->stream;
+        double* F = ls->fact.p;
+        const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
+        const int np = (int)(Np / LB), nblk = lu_nblk(Np);
+        int rc = mnk_launch_tril_to_full(s, F, ld, N, Np);
+        if (rc) return rc;
+        double* P[2] = {lu_p.p, lu_p.p + (int64_t)nblk * 64};
+        double* R[2] = {lu_p.p + (int64_t)2 * nblk * 64, lu_p.p + (int64_t)2 * nblk * 64 + 64};
+        int* I[2] = {lu_cand.p, lu_cand.p + nblk};
+        int *ipiv = lu_ipiv.p, *perm = lu_perm.p, *info = lu_info.p;
+        double* Ut = lu_ut.p;
+        hipLaunchKernelGGL(lu_init_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, ipiv, perm, Np, info);
+        for (int p = 0; p < np; ++p) {
+            const int64_t j0 = (int64_t)p * LB, m = Np - j0, n2 = m - LB;
+            const int nb = (int)((m + LU_RB - 1) / LU_RB);
+            hipLaunchKernelGGL(lu_panel_kernel<false>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, -1, nullptr, nullptr, nullptr,
+                               P[0], I[0], R[0], ipiv, ls->dvec.p, info, nb);
+            for (int c = 0; c < LB; ++c)
+                hipLaunchKernelGGL(lu_panel_kernel<true>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, c, P[c & 1], I[c & 1],
+                                   R[c & 1], P[(c + 1) & 1], I[(c + 1) & 1], R[(c + 1) & 1], ipiv, ls->dvec.p, info, nb);
+            const unsigned gs = (unsigned)std::max<int64_t>(1, (Np - LB + 15) / 16);
+            hipLaunchKernelGGL(lu_laswp_kernel, dim3(gs), dim3(256), 0, s, F, ld, j0, Np, ipiv, perm);
+            if (n2 > 0) {
+                hipLaunchKernelGGL(lu_trsm_kernel, dim3((unsigned)(n2 / 64)), dim3(64), 0, s, F, ld, j0, Ut, Np);
+                MNK_HIP(hipGetLastError());
+                rc = launch_gemm_nt(s, 0, n2, n2, LB, F + j0 + LB + j0 * ld, ld, Ut, Np, F + j0 + LB + (j0 + LB) * ld, ld,
+                                    nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+            }
+        }
+        MNK_HIP(hipGetLastError());
+        ls->info = 0;
+        return 0;
+    }
+
+    // getrf's info of the factorization queued last (waits for it): the first exactly zero pivot (1-based), 0 if none
+    int fetch_info(mnk_ls* ls) override {
+        int info = 0;
+        MNK_HIP(d2h_copy(&info, lu_info.p, sizeof(int), ls->ctx->stream));
+        ls->info = info;
+        ls->info_valid = true;
+        return 0;
+    }
+
+    // solve_lu! (reference src/LinearSolvers/lapack.jl:183-187): P b, then L^-1, then U^-1 on the padded vectors y, z, xo; the
+    // first N entries of xo go to x.
+    int solve_vec(mnk_ls* ls, const double* b, double* x) override {
+        hipStream_t s = ls->ctx->stream;
+        const double* F = ls->fact.p;
+        const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
+        const int np = (int)(Np / LB);
+        double* y = ls->xwork.p + Np;
+        double* z = ls->xwork.p + 2 * Np;
+        double* xo = ls->xwork.p + 3 * Np;
+        hipLaunchKernelGGL(lu_gather_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, b, N, Np, lu_perm.p, y);
+        for (int q = 0; q < np; ++q) {
+            const int64_t below = Np - (int64_t)(q + 1) * LB;
+            const unsigned g = (unsigned)std::max<int64_t>(1, (below + LU_RB - 1) / LU_RB);
+            hipLaunchKernelGGL(lu_lsolve_kernel, dim3(g), dim3(256), 0, s, F, ld, Np, q, y, z);
+        }
+        MNK_HIP(hipGetLastError());
+        int rc = mnk_launch_upper_bsolve(s, F, ld, Np, z, xo);
+        if (rc) return rc;
+        MNK_HIP(hipMemcpyAsync(x, xo, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+
+    const char* no_inertia_message() const override { return "mnk_ls_inertia: an LU factorization reveals no inertia (is_inertia is false for LU)"; }
+};
+
 }  // namespace mnk
 
 using namespace mnk;
 
-int mnk_lu_alloc(mnk_ls* ls) {
-    const int64_t Np = ls->Np;
-    const int nblk = lu_nblk(Np);
-    int rc = ls->lu_ut.alloc((size_t)Np * LB + SLACK * LB);
-    rc |= ls->lu_p.alloc((size_t)2 * nblk * 64 + 2 * 64);
-    rc |= ls->lu_cand.alloc((size_t)2 * nblk);
-    rc |= ls->lu_ipiv.alloc((size_t)Np);
-    rc |= ls->lu_perm.alloc((size_t)Np);
-    rc |= ls->lu_info.alloc(1);
-    return rc;
-}
-
-// factorize! of an LU solver: the matrix has been transferred (lower triangle); mirror it and factor it (see the top).
-int mnk_lu_factor(mnk_ls* ls) {
-    hipStream_t s = ls->ctx->stream;
-    double* F = ls->fact.p;
-    const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
-    const int np = (int)(Np / LB), nblk = lu_nblk(Np);
-    ++ls->fact_count;
-    ls->factor_invalid = false;
-    ls->bk_active = false;
-    ls->t_fact_launch_ms = mnk_host_ms();
-    int rc = mnk_launch_tril_to_full(s, F, ld, N, Np);
-    if (rc) return rc;
-    double* P[2] = {ls->lu_p.p, ls->lu_p.p + (int64_t)nblk * 64};
-    double* R[2] = {ls->lu_p.p + (int64_t)2 * nblk * 64, ls->lu_p.p + (int64_t)2 * nblk * 64 + 64};
-    int* I[2] = {ls->lu_cand.p, ls->lu_cand.p + nblk};
-    int* ipiv = ls->lu_ipiv.p;
-    int* perm = ls->lu_perm.p;
-    int* info = ls->lu_info.p;
-    double* Ut = ls->lu_ut.p;
-    hipLaunchKernelGGL(lu_init_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, ipiv, perm, Np, info);
-    for (int p = 0; p < np; ++p) {
-        const int64_t j0 = (int64_t)p * LB, m = Np - j0, n2 = m - LB;
-        const int nb = (int)((m + LU_RB - 1) / LU_RB);
-        hipLaunchKernelGGL(lu_panel_kernel<false>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, -1, nullptr, nullptr, nullptr,
-                           P[0], I[0], R[0], ipiv, ls->dvec.p, info, nb);
-        for (int c = 0; c < LB; ++c)
-            hipLaunchKernelGGL(lu_panel_kernel<true>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, c, P[c & 1], I[c & 1], R[c & 1],
-                               P[(c + 1) & 1], I[(c + 1) & 1], R[(c + 1) & 1], ipiv, ls->dvec.p, info, nb);
-        const unsigned gs = (unsigned)std::max<int64_t>(1, (Np - LB + 15) / 16);
-        hipLaunchKernelGGL(lu_laswp_kernel, dim3(gs), dim3(256), 0, s, F, ld, j0, Np, ipiv, perm);
-        if (n2 > 0) {
-            hipLaunchKernelGGL(lu_trsm_kernel, dim3((unsigned)(n2 / 64)), dim3(64), 0, s, F, ld, j0, Ut, Np);
-            MNK_HIP(hipGetLastError());
-            rc = launch_gemm_nt(s, 0, n2, n2, LB, F + j0 + LB + j0 * ld, ld, Ut, Np, F + j0 + LB + (j0 + LB) * ld, ld, nullptr,
-                                nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-    }
-    MNK_HIP(hipGetLastError());
-    ls->info = 0;
-    ls->npos = ls->nzero = ls->nneg = 0;
-    ls->factorized = true;
-    ls->info_valid = false;
-    return 0;
-}
-
-// getrf's info of the factorization queued last (waits for it)
-int mnk_lu_fetch_info(mnk_ls* ls) {
-    int info = 0;
-    MNK_HIP(d2h_copy(&info, ls->lu_info.p, sizeof(int), ls->ctx->stream));
-    ls->info = info;
-    ls->info_valid = true;
-    return 0;
-}
-
-// P b, then L^-1, then U^-1 on the padded vectors (device): b (N entries) -> x (Np entries); y, z: Np entries of workspace
-static int lu_solve_vec(mnk_ls* ls, const double* b, double* y, double* z, double* x) {
-    hipStream_t s = ls->ctx->stream;
-    const double* F = ls->fact.p;
-    const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
-    const int np = (int)(Np / LB);
-    hipLaunchKernelGGL(lu_gather_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, b, N, Np, ls->lu_perm.p, y);
-    for (int q = 0; q < np; ++q) {
-        const int64_t below = Np - (int64_t)(q + 1) * LB;
-        const unsigned g = (unsigned)std::max<int64_t>(1, (below + LU_RB - 1) / LU_RB);
-        hipLaunchKernelGGL(lu_lsolve_kernel, dim3(g), dim3(256), 0, s, F, ld, Np, q, y, z);
-    }
-    MNK_HIP(hipGetLastError());
-    return mnk_launch_upper_bsolve(s, F, ld, Np, z, x);
-}
-
-// solve_linear_system! of an LU solver (solve_lu!, reference src/LinearSolvers/lapack.jl:183-187): nrhs columns of x
-// (leading dimension ldx, host or device), in place.
-int mnk_lu_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
-    hipStream_t s = ls->ctx->stream;
-    const int64_t N = ls->N, Np = ls->Np;
-    double* stage = ls->xwork.p;
-    double* y = ls->xwork.p + Np;
-    double* z = ls->xwork.p + 2 * Np;
-    double* xo = ls->xwork.p + 3 * Np;
-    for (int64_t k = 0; k < nrhs; ++k) {
-        double* xk = x + k * ldx;
-        const double* b = xk;
-        if (loc != MNK_DEVICE) {
-            MNK_HIP(h2d_copy(stage, xk, N * sizeof(double), s));
-            b = stage;
-        }
-        int rc = lu_solve_vec(ls, b, y, z, xo);
-        if (rc) return rc;
-        if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(xk, xo, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        else MNK_HIP(d2h_copy(xk, xo, N * sizeof(double), s));
-    }
-    return 0;
-}
+std::unique_ptr<mnk_ls_alt> mnk_lu_new() { return std::make_unique<LuSolver>(); }
 
 extern "C" {
 
@@ -442,14 +428,15 @@ int mnk_ls_get_pivots(mnk_ls* ls, int64_t* ipiv, int loc) {
     MNK_HIP(hipSetDevice(ls->ctx->device));
     hipStream_t s = ls->ctx->stream;
     const int64_t N = ls->N;
+    const int* lu_ipiv = static_cast<const LuSolver*>(ls->alt.get())->lu_ipiv.p;   // (checked above: the alt is this unit's)
     if (loc == MNK_DEVICE) {
-        hipLaunchKernelGGL(lu_pivots_out_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, ls->lu_ipiv.p, N, ipiv);
+        hipLaunchKernelGGL(lu_pivots_out_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, lu_ipiv, N, ipiv);
         MNK_HIP(hipGetLastError());
         MNK_HIP(stream_wait(s));
         return 0;
     }
     std::vector<int> h((size_t)N);
-    MNK_HIP(d2h_copy(h.data(), ls->lu_ipiv.p, N * sizeof(int), s));
+    MNK_HIP(d2h_copy(h.data(), lu_ipiv, N * sizeof(int), s));
     for (int64_t i = 0; i < N; ++i) ipiv[i] = (int64_t)h[i] + 1;
     return 0;
 }

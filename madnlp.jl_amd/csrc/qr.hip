@@ -404,18 +404,98 @@ static int launch_tn(hipStream_t s, const double* A, int64_t lda, const double* 
     return 0;
 }
 
+struct QrSolver final : mnk_ls_alt {
+    // V of the current panel, the T of every panel (kept for the solves), split-K partials of W^T = A2^T V and W^T T, partial
+    // sums of the panel / solve kernels
+    DevBuf<double> qr_v, qr_t, qr_w, qr_p;
+
+    int alloc(mnk_ls* ls) override {
+        const int64_t Np = ls->Np;
+        int rc = qr_v.alloc((size_t)Np * QB + SLACK * QB);
+        rc |= qr_t.alloc((size_t)(Np / QB) * QB * QB);
+        rc |= qr_w.alloc((size_t)(QR_SMAX + 1) * Np * QB + SLACK * QB);
+        rc |= qr_p.alloc((size_t)2 * qr_nblk(Np) * 64 + 2 * 64);
+        return rc;
+    }
+
+    // factorize! of a QR solver: the matrix has been transferred (lower triangle); mirror it and factor it (see the top).
+    int factor(mnk_ls* ls) override {
+        hipStream_t s = ls->ctx->stream;
+        double* F = ls->fact.p;
+        const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
+        const int np = (int)(Np / QB), nblk = qr_nblk(Np);
+        int rc = mnk_launch_tril_to_full(s, F, ld, N, Np);
+        if (rc) return rc;
+        double* P[2] = {qr_p.p, qr_p.p + (int64_t)nblk * 64};
+        double* R[2] = {qr_p.p + (int64_t)2 * nblk * 64, qr_p.p + (int64_t)2 * nblk * 64 + 64};
+        double *V = qr_v.p, *Wp = qr_w.p;
+        const int64_t ldw = Np, wstride = Np * QB;
+        double* Wt = Wp + (int64_t)QR_SMAX * wstride;
+        for (int p = 0; p < np; ++p) {
+            const int64_t j0 = (int64_t)p * QB, m = Np - j0, n2 = m - QB;
+            const int nb = (int)((m + QR_RB - 1) / QR_RB);
+            hipLaunchKernelGGL(qr_panel_kernel<false>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, -1, nullptr, nullptr, P[0], R[0],
+                               ls->dvec.p, nb);
+            for (int c = 0; c < QB; ++c)
+                hipLaunchKernelGGL(qr_panel_kernel<true>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, c, P[c & 1], R[c & 1],
+                                   P[(c + 1) & 1], R[(c + 1) & 1], ls->dvec.p, nb);
+            hipLaunchKernelGGL(qr_extract_v_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, F, ld, j0, m, V, Np);
+            int S;
+            launch_tn(s, V, Np, V, Np, m, QB, Wp, ldw, wstride, &S);
+            double* T = qr_t.p + (int64_t)p * QB * QB;
+            hipLaunchKernelGGL(qr_form_t_kernel, dim3(1), dim3(256), 0, s, Wp, ldw, wstride, S, ls->dvec.p + j0, T);
+            if (n2 > 0) {
+                double* A2 = F + j0 + (j0 + QB) * ld;
+                launch_tn(s, A2, ld, V, Np, m, n2, Wp, ldw, wstride, &S);
+                hipLaunchKernelGGL(qr_wt_kernel, dim3((unsigned)(n2 / 64)), dim3(256), 0, s, Wp, ldw, wstride, S, T, Wt);
+                MNK_HIP(hipGetLastError());
+                rc = launch_gemm_nt(s, 0, m, n2, QB, V, Np, Wt, ldw, A2, ld, nullptr, nullptr, 0, nullptr);
+                if (rc) return rc;
+            }
+        }
+        MNK_HIP(hipGetLastError());
+        ls->info = 0;
+        return 0;
+    }
+
+    // geqrf's info is always 0 (factor set it); a singular matrix shows up in the solve
+    int fetch_info(mnk_ls* ls) override {
+        MNK_HIP(stream_wait(ls->ctx->stream));
+        ls->info_valid = true;
+        return 0;
+    }
+
+    // solve_qr! (reference src/LinearSolvers/lapack.jl:205-209): Q^T then R^-1 on the zero-padded copy y of b; the solution
+    // (Np entries) goes to xo and its first N entries to x.
+    int solve_vec(mnk_ls* ls, const double* b, double* x) override {
+        hipStream_t s = ls->ctx->stream;
+        const double* F = ls->fact.p;
+        const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
+        const int np = (int)(Np / QB), nblk = qr_nblk(Np);
+        double* y = ls->xwork.p + Np;
+        double* xo = ls->xwork.p + 2 * Np;
+        double* P[2] = {qr_p.p, qr_p.p + (int64_t)nblk * 64};
+        MNK_HIP(hipMemsetAsync(y, 0, Np * sizeof(double), s));
+        MNK_HIP(hipMemcpyAsync(y, b, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(qr_qt_kernel<false>, dim3(nblk), dim3(256), 0, s, F, ld, Np, -1, np, y, qr_t.p, nullptr, P[0], nblk);
+        for (int p = 0; p < np; ++p) {
+            const int b0 = (int)((int64_t)p * QB / QR_RB);
+            hipLaunchKernelGGL(qr_qt_kernel<true>, dim3(nblk - b0), dim3(256), 0, s, F, ld, Np, p, np, y, qr_t.p, P[p & 1],
+                               P[(p + 1) & 1], nblk);
+        }
+        MNK_HIP(hipGetLastError());
+        int rc = mnk_launch_upper_bsolve(s, F, ld, Np, y, xo);
+        if (rc) return rc;
+        MNK_HIP(hipMemcpyAsync(x, xo, N * sizeof(double), hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+
+    const char* no_inertia_message() const override { return "mnk_ls_inertia: a QR factorization reveals no inertia (is_inertia is false for QR)"; }
+};
+
 }  // namespace mnk
 
 using namespace mnk;
-
-int mnk_qr_alloc(mnk_ls* ls) {
-    const int64_t Np = ls->Np;
-    int rc = ls->qr_v.alloc((size_t)Np * QB + SLACK * QB);
-    rc |= ls->qr_t.alloc((size_t)(Np / QB) * QB * QB);
-    rc |= ls->qr_w.alloc((size_t)(QR_SMAX + 1) * Np * QB + SLACK * QB);
-    rc |= ls->qr_p.alloc((size_t)2 * qr_nblk(Np) * 64 + 2 * 64);
-    return rc;
-}
 
 // (lu.hip) the same mirror and the same block back substitution for the LU solver
 int mnk_launch_tril_to_full(hipStream_t s, double* F, int64_t ld, int64_t N, int64_t Np) {
@@ -434,91 +514,4 @@ int mnk_launch_upper_bsolve(hipStream_t s, const double* F, int64_t ld, int64_t 
     return 0;
 }
 
-// factorize! of a QR solver: the matrix has been transferred (lower triangle); mirror it and factor it (see the top).
-int mnk_qr_factor(mnk_ls* ls) {
-    hipStream_t s = ls->ctx->stream;
-    double* F = ls->fact.p;
-    const int64_t ld = ls->ld, N = ls->N, Np = ls->Np;
-    const int np = (int)(Np / QB), nblk = qr_nblk(Np);
-    ++ls->fact_count;
-    ls->factor_invalid = false;
-    ls->bk_active = false;
-    ls->t_fact_launch_ms = mnk_host_ms();
-    hipLaunchKernelGGL(qr_mirror_kernel, dim3((unsigned)(Np / 32), (unsigned)(Np / 32)), dim3(256), 0, s, F, ld, N);
-    double* P[2] = {ls->qr_p.p, ls->qr_p.p + (int64_t)nblk * 64};
-    double* R[2] = {ls->qr_p.p + (int64_t)2 * nblk * 64, ls->qr_p.p + (int64_t)2 * nblk * 64 + 64};
-    double* V = ls->qr_v.p;
-    double* Wp = ls->qr_w.p;
-    const int64_t ldw = Np, wstride = Np * QB;
-    double* Wt = Wp + (int64_t)QR_SMAX * wstride;
-    for (int p = 0; p < np; ++p) {
-        const int64_t j0 = (int64_t)p * QB, m = Np - j0, n2 = m - QB;
-        const int nb = (int)((m + QR_RB - 1) / QR_RB);
-        hipLaunchKernelGGL(qr_panel_kernel<false>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, -1, nullptr, nullptr, P[0], R[0],
-                           ls->dvec.p, nb);
-        for (int c = 0; c < QB; ++c)
-            hipLaunchKernelGGL(qr_panel_kernel<true>, dim3(nb), dim3(256), 0, s, F, ld, j0, Np, c, P[c & 1], R[c & 1],
-                               P[(c + 1) & 1], R[(c + 1) & 1], ls->dvec.p, nb);
-        hipLaunchKernelGGL(qr_extract_v_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, F, ld, j0, m, V, Np);
-        int S;
-        launch_tn(s, V, Np, V, Np, m, QB, Wp, ldw, wstride, &S);
-        double* T = ls->qr_t.p + (int64_t)p * QB * QB;
-        hipLaunchKernelGGL(qr_form_t_kernel, dim3(1), dim3(256), 0, s, Wp, ldw, wstride, S, ls->dvec.p + j0, T);
-        if (n2 > 0) {
-            double* A2 = F + j0 + (j0 + QB) * ld;
-            launch_tn(s, A2, ld, V, Np, m, n2, Wp, ldw, wstride, &S);
-            hipLaunchKernelGGL(qr_wt_kernel, dim3((unsigned)(n2 / 64)), dim3(256), 0, s, Wp, ldw, wstride, S, T, Wt);
-            MNK_HIP(hipGetLastError());
-            int rc = launch_gemm_nt(s, 0, m, n2, QB, V, Np, Wt, ldw, A2, ld, nullptr, nullptr, 0, nullptr);
-            if (rc) return rc;
-        }
-    }
-    MNK_HIP(hipGetLastError());
-    ls->info = 0;
-    ls->npos = ls->nzero = ls->nneg = 0;
-    ls->factorized = true;
-    ls->info_valid = false;
-    return 0;
-}
-
-// Q^T then R^-1 on the padded vector y (Np entries, device); the solution goes to x (Np entries, device).
-static int qr_solve_vec(mnk_ls* ls, double* y, double* x) {
-    hipStream_t s = ls->ctx->stream;
-    const double* F = ls->fact.p;
-    const int64_t ld = ls->ld, Np = ls->Np;
-    const int np = (int)(Np / QB), nblk = qr_nblk(Np);
-    double* P[2] = {ls->qr_p.p, ls->qr_p.p + (int64_t)nblk * 64};
-    hipLaunchKernelGGL(qr_qt_kernel<false>, dim3(nblk), dim3(256), 0, s, F, ld, Np, -1, np, y, ls->qr_t.p, nullptr, P[0], nblk);
-    for (int p = 0; p < np; ++p) {
-        const int b0 = (int)((int64_t)p * QB / QR_RB);
-        hipLaunchKernelGGL(qr_qt_kernel<true>, dim3(nblk - b0), dim3(256), 0, s, F, ld, Np, p, np, y, ls->qr_t.p, P[p & 1],
-                           P[(p + 1) & 1], nblk);
-    }
-    for (int q = np - 1; q >= 0; --q) {
-        const int64_t d0 = (int64_t)q * QB;
-        const unsigned g = (unsigned)std::max<int64_t>(1, (d0 + QR_RB - 1) / QR_RB);
-        hipLaunchKernelGGL(qr_rsolve_kernel, dim3(g), dim3(256), 0, s, F, ld, q, y, x);
-    }
-    MNK_HIP(hipGetLastError());
-    return 0;
-}
-
-// solve_linear_system! of a QR solver (solve_qr!, reference src/LinearSolvers/lapack.jl:205-209): nrhs columns of x
-// (leading dimension ldx, host or device), in place.
-int mnk_qr_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
-    hipStream_t s = ls->ctx->stream;
-    const int64_t N = ls->N, Np = ls->Np;
-    double* y = ls->xwork.p;
-    double* xo = ls->xwork.p + Np;
-    for (int64_t k = 0; k < nrhs; ++k) {
-        double* xk = x + k * ldx;
-        MNK_HIP(hipMemsetAsync(y, 0, Np * sizeof(double), s));
-        if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(y, xk, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        else MNK_HIP(h2d_copy(y, xk, N * sizeof(double), s));
-        int rc = qr_solve_vec(ls, y, xo);
-        if (rc) return rc;
-        if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(xk, xo, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        else MNK_HIP(d2h_copy(xk, xo, N * sizeof(double), s));
-    }
-    return 0;
-}
+std::unique_ptr<mnk_ls_alt> mnk_qr_new() { return std::make_unique<QrSolver>(); }

@@ -23,7 +23,7 @@ from tests.evd_cases import (DIAG_SIZES, EPS, KINDS, SIZES, backward_error, diag
 pytestmark = pytest.mark.gpu
 
 FACTOR = 20.0        # device ratio <= FACTOR * max(1, dsyevd's ratio on the same matrix)
-SWEEP_CAP = 60        # evd_sweep_cap of csrc/ls.h
+SWEEP_CAP = 60        # evd_sweep_cap of csrc/evd.hip
 OPT = mj.HipSolverOptions(lapack_algorithm=mj.EVD)
 _measured = {}
 
