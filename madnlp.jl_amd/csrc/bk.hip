@@ -953,8 +953,8 @@ int mnk_ls_run_bunchkaufman(mnk_ls* ls) {
     // and stay there)
     ++ls->bk_mw_fallbacks;
     ls->bk_mw_blocked = true;
-    MNK_REQUIRE((bool)ls->retransfer, "Bunch-Kaufman tier: a panel hand-off timed out and the matrix cannot be transferred again");
-    rc = ls->retransfer();
+    MNK_REQUIRE((bool)ls->src.retransfer, "Bunch-Kaufman tier: a panel hand-off timed out and the matrix cannot be transferred again");
+    rc = ls->src.retransfer();
     if (rc) return rc;
     return run_bunchkaufman(ls, false);
 }

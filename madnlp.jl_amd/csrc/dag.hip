@@ -1109,19 +1109,27 @@ static int bulk_xcds(const mnk_ctx* c, int first) {
     return n;
 }
 
+// ---- DagPlan (ls.h): the sizes of its device words ----
+size_t DagPlan::progress_words(int64_t Np) {   // two queue counters | front | af | tprog
+    const int64_t ntile = Np / 128;
+    return (size_t)2 + (size_t)(Np / NBI) + 2 * (size_t)ntile * ntile;
+}
+
+size_t DagPlan::trace_words() const { return (size_t)ntasks * 8 + 4096 * 8 + 1024 * 8; }
+
 static mnk::DagInst dag_instance(mnk_ls* ls) {
     const int ntile = (int)(ls->Np / 128), nblk = (int)(ls->Np / NBI);
-    int* front = ls->dag_flags.p + 2;
+    int* front = ls->plan.flags.p + 2;   // (the layout DagPlan::progress_words sizes)
     int* af = front + nblk;
     int* tprog = af + (size_t)ntile * ntile;
     // the spare factor buffer is zeroed by the queue's DAG_FILL tasks when the NEXT transfer will want it (a sparse source was
-    // transferred for this factorization: mnk_ls::spare_pending) and no background fill of it is in flight
-    double* zfill = (ls->dag_fill && ls->dag_has_fill && ls->spare_pending && ls->fact_spare.p && !ls->spare_zeroed) ? ls->fact_spare.p : nullptr;
+    // transferred for this factorization) and no background fill of it is in flight
+    double* zfill = ls->dag_fill && ls->plan.key.has_fill ? ls->spare.dag_target() : nullptr;
     // the envelope of a sparse source (ls.hip: set_envelope); the bulk kernel reads the verdict on its finiteness (env_word[1])
-    const bool env = ls->envelope && ls->env_dev != nullptr && ls->env_word.p != nullptr;
+    const bool env = ls->envelope && ls->src.env_dev != nullptr && ls->env_word.p != nullptr;
     return mnk::DagInst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
-                        front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N, env ? ls->env_dev : nullptr,
-                        env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->envh_dev : nullptr};
+                        front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N, env ? ls->src.env_dev : nullptr,
+                        env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->src.envh_dev : nullptr};
 }
 
 // Buffers of the task-DAG schedule: the task list (built once per matrix order and option set), the progress words and,
@@ -1133,18 +1141,17 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
     hipStream_t s = ctx->stream;
     const int64_t Np = ls->Np, ld = ls->ld;
     const bool ldl = ls->algo == MNK_LDL;
-    const int ntile = (int)(Np / 128), nblk = (int)(Np / NBI), nsc = (int)((Np + 255) / 256);
-    const size_t nflags = (size_t)2 + nblk + 2 * (size_t)ntile * ntile;  // two queue counters | front | af | tprog
+    const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256);
     auto give_up = [&]() {
         (void)hipGetLastError();
-        ls->dag_tasks.release();
-        ls->dag_flags.release();
-        ls->dag_qoff.release();
-        ls->dag_qheads.release();
+        ls->plan.invalidate();
+        ls->plan.flags.release();
+        ls->plan.qoff.release();
+        ls->plan.qheads.release();
         ls->vfull.release();
         return 1;
     };
-    if (!ls->dag_tasks.p) {
+    if (!ls->plan.valid()) {
         // Two band shapes.  Large systems (more than dag_cus2 strips of 64 rows): a shallow band on a handful of CUs, the
         // rows below it closed by the bulk kernel's own tasks -- the factorization is bound by the bulk work for most of its
         // columns.  Small systems: EVERY row is a strip of the chain's band (one CU each, on a larger partition) and the
@@ -1158,63 +1165,55 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         // above that every strip's left-looking prologue on its one CU costs more than the bulk kernel's closing tasks; the limit
         // was the partition's 96 strips = 6144 rows: dag_deep_rows)
         const int64_t deep_rows = std::min<int64_t>((int64_t)ctx->dag_cus2 * NBI, ls->dag_deep_rows);
-        ls->dag_js2 = (ctx->dag_cus2 > 0 && Np <= deep_rows) ? 0 : nsc;
-        if (ls->dag_js2_override >= 0) ls->dag_js2 = std::min(nsc, ls->dag_js2_override);
-        std::vector<int>& h = ls->dag_host_tasks;   // (kept on the host: a batch merges the lists of its instances)
-        ls->dag_ntasks1 = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->dag_js2, h, ls->dag_taper0, &ls->dag_host_ready);
+        ls->plan.key.js2 = (ctx->dag_cus2 > 0 && Np <= deep_rows) ? 0 : nsc;
+        if (ls->dag_js2_override >= 0) ls->plan.key.js2 = std::min(nsc, ls->dag_js2_override);
+        std::vector<int>& h = ls->plan.host_tasks;   // (kept on the host: a batch merges the lists of its instances)
+        ls->plan.key.chunk = ls->dag_chunk; ls->plan.key.taper0 = ls->dag_taper0; ls->plan.key.band = ls->dag_band;
+        ls->plan.ntasks1 = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->plan.key.js2, h, ls->dag_taper0, &ls->plan.host_ready);
         // zero-fill of the next factorization's buffer as tasks of the queue (sparse sources; see dag_fill_tile)
-        ls->dag_has_fill = ls->dag_fill && ls->prefill && Np <= mnk_ls::PREFILL_MAX_ROWS;
-        if (ls->dag_has_fill && h.empty()) ls->dag_has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
-        if (ls->dag_has_fill) ls->dag_ntasks1 = mnk::dag_add_fill_tasks(ntile, h, ls->dag_host_ready, ls->dag_ntasks1);
-        ls->dag_ntasks = (int)(h.size() / 4);
+        ls->plan.key.has_fill = ls->dag_fill && ls->spare.wanted(Np);
+        if (ls->plan.key.has_fill && h.empty()) ls->plan.key.has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
+        if (ls->plan.key.has_fill) ls->plan.ntasks1 = mnk::dag_add_fill_tasks(ntile, h, ls->plan.host_ready, ls->plan.ntasks1);
+        ls->plan.ntasks = (int)(h.size() / 4);
         // Per-XCD queues: the device list is the host list dealt per phase (dag_deal_tasks; the host list stays as built -- the
         // statistics and the merged queue of a batch read it).  A phase keeps ONE queue when its bulk grid might leave an XCD
         // without a workgroup -- a queue nobody owns is only served by thieves, which come when their own queues are empty, and
         // the progress argument needs an owner -- or when a list position does not fit beside the tile column (20 | 12 bits).
         std::vector<int> dev_list = h, qoff(32, 0);
-        ls->dag_nq[0] = ls->dag_nq[1] = 0;
-        if (ls->dag_xcd_queues && ls->dag_ntasks < (1 << 20) && ntile < 4096) {
-            const int part[3] = {0, ls->dag_ntasks1, ls->dag_ntasks};
+        ls->plan.nq[0] = ls->plan.nq[1] = 0;
+        if (ls->dag_xcd_queues && ls->plan.ntasks < (1 << 20) && ntile < 4096) {
+            const int part[3] = {0, ls->plan.ntasks1, ls->plan.ntasks};
             const int chain_cus[2] = {ctx->dag_cus, ctx->dag_cus2};
             for (int ph = 0; ph < 2; ++ph) {
                 const int t0 = part[ph], t1 = part[ph + 1];
                 if (t1 - t0 < mnk_ctx_bulk_wgs(ctx, chain_cus[ph], 3) || bulk_xcds(ctx, chain_cus[ph]) != mnk::DAG_NQ) continue;
                 std::vector<int> order, off;
-                mnk::dag_deal_tasks(h, ls->dag_host_ready, t0, t1, mnk::DAG_NQ, ls->dag_gang, order, off);
+                mnk::dag_deal_tasks(h, ls->plan.host_ready, t0, t1, mnk::DAG_NQ, ls->dag_gang, order, off);
                 for (int p = 0; p < t1 - t0; ++p) {
                     for (int k = 0; k < 4; ++k) dev_list[4 * (size_t)(t0 + p) + k] = h[4 * (size_t)order[p] + k];
                     dev_list[4 * (size_t)(t0 + p) + 2] |= (order[p] - t0) << 12;
                 }
                 for (int x = 0; x <= mnk::DAG_NQ; ++x) qoff[16 * ph + x] = off[x];
-                ls->dag_nq[ph] = mnk::DAG_NQ;
+                ls->plan.nq[ph] = mnk::DAG_NQ;
             }
         }
-        if (ls->dag_tasks.alloc(h.size() + 4)) return give_up();
-        if (!ls->dag_qoff.p && ls->dag_qoff.alloc(qoff.size())) return give_up();
-        if (!ls->dag_qheads.p && ls->dag_qheads.alloc(2 * (size_t)mnk::DAG_QHEAD_WORDS)) return give_up();
+        if (ls->plan.tasks.alloc(h.size() + 4)) return give_up();
+        if (!ls->plan.qoff.p && ls->plan.qoff.alloc(qoff.size())) return give_up();
+        if (!ls->plan.qheads.p && ls->plan.qheads.alloc(2 * (size_t)mnk::DAG_QHEAD_WORDS)) return give_up();
         {
             mnk::H2DGuard h2d;   // (a pageable upload beside another context's persistent group would stop that group: common.h)
-            if (!h.empty() && hipMemcpyAsync(ls->dag_tasks.p, dev_list.data(), dev_list.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
-            if (hipMemcpyAsync(ls->dag_qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
+            if (!h.empty() && hipMemcpyAsync(ls->plan.tasks.p, dev_list.data(), dev_list.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
+            if (hipMemcpyAsync(ls->plan.qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
             if (mnk::stream_wait(s) != hipSuccess) return give_up();
         }
-        if (ls->dag_flags.alloc(nflags)) return give_up();
+        if (ls->plan.flags.alloc(DagPlan::progress_words(Np))) return give_up();
     }
     if (ldl && !ls->vfull.p && ls->vfull.alloc((size_t)ld * Np + SLACK)) {   // V = L D of every column (LDL^T)
         (void)hipGetLastError();
-        bool ok = false;
-        if (ls->fact_spare.p && !ls->spare_zeroed) {
-            // (spare_zeroed: a background fill of the spare buffer has been queued and the next transfer will swap it in)
-            ls->fact_spare.release();
-            ls->prefill = 0;
-            ls->spare_pending = false;
-            ok = ls->vfull.alloc((size_t)ld * Np + SLACK) == 0;
-        }
-        if (!ok) return give_up();
+        if (!ls->spare.give_up() || ls->vfull.alloc((size_t)ld * Np + SLACK) != 0) return give_up();
     }
     if (ls->dag_trace_on) {
-        const size_t ntr = (size_t)ls->dag_ntasks * 8 + 4096 * 8 + 1024 * 8;  // tasks | chain strips | per-workgroup statistics (2 x 512)
-        if (ls->dag_trace.n < ntr && ls->dag_trace.alloc(ntr)) return give_up();   // (the task list may have been rebuilt with more tasks)
+        if (ls->dag_trace.n < ls->plan.trace_words() && ls->dag_trace.alloc(ls->plan.trace_words())) return give_up();   // (the task list may have been rebuilt with more tasks)
     }
     return 0;
 }
@@ -1228,28 +1227,27 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
     hipStream_t s = ctx->stream;
     const int64_t Np = ls->Np;
     const bool ldl = ls->algo == MNK_LDL;
-    const int ntile = (int)(Np / 128), nblk = (int)(Np / NBI), nsc = (int)((Np + 255) / 256);
-    const size_t nflags = (size_t)2 + nblk + 2 * (size_t)ntile * ntile;  // two queue counters | front | af | tprog
-    MNK_REQUIRE(ls->dag_tasks.p && ls->dag_flags.p && (!ldl || ls->vfull.p), "task-DAG schedule: mnk_ls_dag_prepare was not called");
+    const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256);
+    const size_t nflags = DagPlan::progress_words(Np);
+    MNK_REQUIRE(ls->plan.tasks.p && ls->plan.flags.p && (!ldl || ls->vfull.p), "task-DAG schedule: mnk_ls_dag_prepare was not called");
     // progress words and `info` in ONE launch (two memsets are two fill kernels, ~8 us each in front of the pivot chain)
     const mnk::DagInst inst = dag_instance(ls);
-    ls->dag_filled = inst.zfill != nullptr;
+    ls->spare.dag_fills(inst.zfill != nullptr);
     ls->env_used = inst.env != nullptr;
     ls->envh_used = inst.envh != nullptr;
     hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, s,
-                       ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
-                       ls->env_word.p, ls->dag_qheads.p, ls->dag_qheads.p ? 2 * mnk::DAG_QHEAD_WORDS : 0);
-    ls->env_armed = false;
-    int* qctr = ls->dag_flags.p;
+                       ls->plan.flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
+                       ls->env_word.p, ls->plan.qheads.p, ls->plan.qheads.p ? 2 * mnk::DAG_QHEAD_WORDS : 0);
+    ls->src.env_armed = false;
+    int* qctr = ls->plan.flags.p;
     int* front = inst.front;
     const long spin_limit = mnk_ls_dag_spin_limit(ls);
     unsigned long long* trace = nullptr;
     if (ls->dag_trace_on && ls->dag_trace.p) {
-        const size_t ntr = (size_t)ls->dag_ntasks * 8 + 4096 * 8 + 1024 * 8;
-        MNK_HIP(hipMemsetAsync(ls->dag_trace.p, 0, ntr * sizeof(unsigned long long), s));
+        MNK_HIP(hipMemsetAsync(ls->dag_trace.p, 0, ls->plan.trace_words() * sizeof(unsigned long long), s));
         trace = ls->dag_trace.p;
     }
-    const int js2 = ls->dag_js2;
+    const int js2 = ls->plan.key.js2;
     // one phase = one persistent bulk launch (update stream) beside one persistent chain launch (panel stream)
     auto phase = [&](hipStream_t sp, hipStream_t su, int chain_cus, int task0, int ntask, int* counter, int js_begin, int js_end,
                      unsigned strips) -> int {
@@ -1262,21 +1260,21 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         MNK_HIP(hipEventRecord(ctx->ev_a, s));
         if (!small) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
         MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
-        mnk::PpDag dag{front, inst.af, ntile, 0, 0, -1, spin_limit, trace ? trace + (size_t)ls->dag_ntasks * 8 + (size_t)js_begin * 8 * 16 : nullptr,
+        mnk::PpDag dag{front, inst.af, ntile, 0, 0, -1, spin_limit, trace ? trace + (size_t)ls->plan.ntasks * 8 + (size_t)js_begin * 8 * 16 : nullptr,
                   mnk_ls_growth_word(ls), ls->dag_debug ? ls->dag_dbg.p : nullptr};
         // (the chain first: its first diagonal block is the start of the critical path, the bulk kernel has nothing to do before it)
         int rc = mnk_launch_pchain(ls, sp, dag, js_begin, js_end, strips);
         if (rc) return rc;
         // (more than three workgroups per CU -- to fill slots a shader-engine-imbalanced mask might leave empty -- measured
         // no difference: 4 / 5 / 6 per CU 9.63-9.67 vs 9.64-9.68 ms)
-        const int ph = (int)(counter - qctr), nq = ls->dag_nq[ph];
+        const int ph = (int)(counter - qctr), nq = ls->plan.nq[ph];
         // (per-XCD queues: every queue needs workgroups of its own XCD -- the grid the list was dealt for, see mnk_ls_dag_prepare)
         MNK_REQUIRE(nq == 0 || (ntask >= mnk_ctx_bulk_wgs(ctx, chain_cus, 3) && bulk_xcds(ctx, chain_cus) == nq),
                     "task-DAG schedule: the bulk grid does not cover the XCDs the task list was dealt for");
-        rc = mnk::launch_dag_bulk(su, ldl, inst, nullptr, ls->dag_tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
+        rc = mnk::launch_dag_bulk(su, ldl, inst, nullptr, ls->plan.tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
                                   std::min(ntask, mnk_ctx_bulk_wgs(ctx, chain_cus, 3)), trace ? trace + 8 * (size_t)task0 : nullptr,
-                                  trace ? trace + (size_t)ls->dag_ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
-                                  ls->dag_qoff.p + 16 * ph, ls->dag_qheads.p + ph * mnk::DAG_QHEAD_WORDS, nq);
+                                  trace ? trace + (size_t)ls->plan.ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
+                                  ls->plan.qoff.p + 16 * ph, ls->plan.qheads.p + ph * mnk::DAG_QHEAD_WORDS, nq);
         if (rc) return rc;
         // Once the bulk kernel has run out of tasks every tile-closing task is done, hence every strip-column that still
         // had rows below the band is final: its diagonal blocks are inverted for the solves here, behind the bulk kernel
@@ -1304,14 +1302,14 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         return 0;
     };
     if (js2 > 0) {
-        int rc = phase(ctx->sp_dag, ctx->su_dag, ctx->dag_cus, 0, ls->dag_ntasks1, qctr, 0, std::min(js2, nsc),
+        int rc = phase(ctx->sp_dag, ctx->su_dag, ctx->dag_cus, 0, ls->plan.ntasks1, qctr, 0, std::min(js2, nsc),
                        (unsigned)std::min<int64_t>(ls->dag_band, Np / NBI));
         if (rc) return rc;
     }
     if (js2 < nsc) {
         const int64_t rows2 = Np - 256 * (int64_t)js2;
         MNK_REQUIRE(ctx->sp_dag2 != nullptr, "task-DAG schedule: the deep-band streams are missing");   // (mnk_ls_run_factorization made them)
-        int rc = phase(ctx->sp_dag2, ctx->su_dag2, ctx->dag_cus2, ls->dag_ntasks1, ls->dag_ntasks - ls->dag_ntasks1,
+        int rc = phase(ctx->sp_dag2, ctx->su_dag2, ctx->dag_cus2, ls->plan.ntasks1, ls->plan.ntasks - ls->plan.ntasks1,
                        qctr + 1, js2, nsc, (unsigned)(rows2 / NBI));
         if (rc) return rc;
     }
@@ -1343,8 +1341,11 @@ struct BatchBuffers {   // per device, reused from batch to batch (guarded by th
     char* stage = nullptr;        // pinned host memory: the records of one batch (instances | chain table | small-system records)
     size_t stage_bytes = 0;
     hipEvent_t stage_ev = nullptr;   // recorded behind the last upload from `stage`
-    int ntile = 0, ninst = 0, period = 0, chunk = 0, taper0 = 0, band = 0, ntasks = 0;
-    bool fill = false;
+    int ntile = 0, ninst = 0, period = 0, ntasks = 0;   // what `tasks` was merged for: ntile, the instances, their shift ...
+    DagPlan::Key key;                                   // ... and the plan of the group's first solver
+    bool holds(int ntile_, int ninst_, int period_, const DagPlan::Key& k) const {
+        return tasks.p && ntile == ntile_ && ninst == ninst_ && period == period_ && key == k;
+    }
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 BatchBuffers g_batch[64];
@@ -1357,7 +1358,7 @@ bool mnk_batch_defer(mnk_ls* ls) {
     const int nsc = (int)((ls->Np + 255) / 256);
     // (two merged launches: the large-system mode of the schedule -- band + bulk + two alternating chains -- and the small
     // one, every row in the chain's band, many chains side by side; a second phase in mid-factorization is simply run now)
-    if (ls->algo_now != 5 || (ls->dag_js2 != nsc && ls->dag_js2 != 0) || ls->dag_trace_on || ls->ctx->partitioned) return false;
+    if (ls->algo_now != 5 || (ls->plan.key.js2 != nsc && ls->plan.key.js2 != 0) || ls->dag_trace_on || ls->ctx->partitioned) return false;
     if (mnk_ctx_ensure_batch_streams(ls->ctx) != 0) (void)hipGetLastError();   // (made with the first batch of a process)
     if (!ls->ctx->sp_dagB) return false;
     if (!ls->ev_defer && hipEventCreateWithFlags(&ls->ev_defer, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -1367,11 +1368,19 @@ bool mnk_batch_defer(mnk_ls* ls) {
     return true;
 }
 
-static void batch_mark_done(mnk_ls* ls) {
-    ls->factorized = true;
-    ls->info_valid = false;
-    ls->bk_active = false;
-    ls->deferred = false;
+// the group's launches are queued on `h`: everybody's stream continues behind them, and every member is a queued factorization
+static int batch_finish(std::vector<mnk_ls*>& g, hipStream_t h) {
+    MNK_HIP(hipEventRecord(g[0]->ev_defer, h));
+    for (mnk_ls* ls : g) {
+        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(ls->ctx->stream, g[0]->ev_defer, 0));
+        ls->factorized = true;
+        ls->info_valid = false;
+        ls->bk_active = false;
+        ls->deferred = false;
+        int r = ls->spare.queued(ls);
+        if (r) return r;
+    }
+    return 0;
 }
 
 // the merged launch of g.size() >= 2 deferred factorizations of one order / algorithm / option set on one device
@@ -1383,7 +1392,7 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
     const int64_t Np = l0->Np;
     const bool ldl = l0->algo == MNK_LDL;
     const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256), ninst = (int)g.size();
-    const size_t nflags = (size_t)2 + (size_t)(Np / NBI) + 2 * (size_t)ntile * ntile;
+    const size_t nflags = DagPlan::progress_words(Np);
     for (mnk_ls* ls : g)
         if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(h, ls->ev_defer, 0));
     int rc = mnk_persist_begin(c0, h);
@@ -1391,31 +1400,29 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
     auto body = [&]() -> int {
         BatchBuffers& B = g_batch[c0->device & 63];
         const int period = (ntile + 1) / 2;   // shift between consecutive instances in the merged queue, in tile columns of chain position: half the matrix, the minimum
-        if (B.ntile != ntile || B.ninst != ninst || B.period != period || B.chunk != l0->dag_chunk || B.taper0 != l0->dag_taper0 ||
-            B.band != l0->dag_band || B.fill != l0->dag_has_fill || !B.tasks.p) {
+        if (!B.holds(ntile, ninst, period, l0->plan.key)) {
             std::vector<int> merged;
-            mnk::dag_merge_tasks(l0->dag_host_tasks, l0->dag_host_ready, ninst, period, merged);
+            mnk::dag_merge_tasks(l0->plan.host_tasks, l0->plan.host_ready, ninst, period, merged);
             if (B.tasks.alloc(merged.size() + 4)) return -2;
             { mnk::H2DGuard h2d; MNK_HIP(hipMemcpy(B.tasks.p, merged.data(), merged.size() * sizeof(int), hipMemcpyHostToDevice)); }
             if (!B.qctr.p && B.qctr.alloc(4)) return -2;
             if (B.insts.alloc(sizeof(mnk::DagInst) * (size_t)ninst)) return -2;
             for (hipEvent_t& e : B.ev)
                 if (!e) MNK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            B.ntile = ntile; B.ninst = ninst; B.period = period; B.chunk = l0->dag_chunk; B.taper0 = l0->dag_taper0;
-            B.band = l0->dag_band; B.fill = l0->dag_has_fill; B.ntasks = (int)(merged.size() / 4);
+            B.ntile = ntile; B.ninst = ninst; B.period = period; B.key = l0->plan.key; B.ntasks = (int)(merged.size() / 4);
         }
         std::vector<mnk::DagInst> hin;
         mnk::DagInst* insts_dev = reinterpret_cast<mnk::DagInst*>(B.insts.p);
         for (mnk_ls* ls : g) {
             hin.push_back(dag_instance(ls));
-            ls->dag_filled = hin.back().zfill != nullptr;
+            ls->spare.dag_fills(hin.back().zfill != nullptr);
             ls->env_used = hin.back().env != nullptr;
             ls->envh_used = false;   // (the merged kernel of a batch skips by tiles only)
             // (the instance's record for the bulk kernel rides along with the reset of its progress words)
             hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, h,
-                               ls->dag_flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1),
+                               ls->plan.flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1),
                                (const mnk::SmallSysRec*)nullptr, ls->env_word.p);
-            ls->env_armed = false;
+            ls->src.env_armed = false;
         }
         MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
         hipStream_t sp[2] = {c0->sp_dag, c0->sp_dagB}, su = c0->su_dagB;
@@ -1465,15 +1472,7 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
     rc = body();
     rc = mnk_persist_end(c0, h, rc);
     if (rc) return rc;
-    // everybody's stream continues behind the batch
-    MNK_HIP(hipEventRecord(l0->ev_defer, h));
-    for (mnk_ls* ls : g) {
-        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(ls->ctx->stream, l0->ev_defer, 0));
-        batch_mark_done(ls);
-        int r = mnk_ls_prefill_spare(ls);
-        if (r) return r;
-    }
-    return 0;
+    return batch_finish(g, h);
 }
 
 // Small systems (every row a strip of the chain, dag_js2 == 0): rounds of K systems whose chains run SIDE BY SIDE in one
@@ -1488,8 +1487,8 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
     const int64_t Np = l0->Np;
     const bool ldl = l0->algo == MNK_LDL;
     const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256), strips = (int)(Np / NBI);
-    const size_t nflags = (size_t)2 + (size_t)(Np / NBI) + 2 * (size_t)ntile * ntile;
-    const int ntasks1 = l0->dag_ntasks;   // (single phase: all tasks)
+    const size_t nflags = DagPlan::progress_words(Np);
+    const int ntasks1 = l0->plan.ntasks;   // (single phase: all tasks)
     const int bulk_min = ntasks1 > 0 ? std::max(32, c0->num_cu / 4) : 0;
     // The chains' CU partition is a multiple of 32 CUs: every workgroup of the chain launch must be RESIDENT (one per CU), and
     // the dispatcher places them all only when the mask gives every shader engine of every XCD the same number of CUs --
@@ -1521,14 +1520,12 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
         rc = mnk_persist_begin(c0, h);
         if (rc) return rc;
         auto body = [&]() -> int {
-            if (ntasks1 > 0 && (B.ntile != ntile || B.ninst != k || B.period != 0 || B.chunk != l0->dag_chunk || B.taper0 != l0->dag_taper0 ||
-                                B.band != l0->dag_band || B.fill != l0->dag_has_fill || !B.tasks.p)) {
+            if (ntasks1 > 0 && !B.holds(ntile, k, 0, l0->plan.key)) {
                 std::vector<int> merged;
-                mnk::dag_merge_tasks(l0->dag_host_tasks, l0->dag_host_ready, k, 0, merged);
+                mnk::dag_merge_tasks(l0->plan.host_tasks, l0->plan.host_ready, k, 0, merged);
                 if (B.tasks.alloc(merged.size() + 4)) return -2;
                 { mnk::H2DGuard h2d; MNK_HIP(hipMemcpy(B.tasks.p, merged.data(), merged.size() * sizeof(int), hipMemcpyHostToDevice)); }
-                B.ntile = ntile; B.ninst = k; B.period = 0; B.chunk = l0->dag_chunk; B.taper0 = l0->dag_taper0;
-                B.band = l0->dag_band; B.fill = l0->dag_has_fill; B.ntasks = (int)(merged.size() / 4);
+                B.ntile = ntile; B.ninst = k; B.period = 0; B.key = l0->plan.key; B.ntasks = (int)(merged.size() / 4);
             }
             if (!B.qctr.p && B.qctr.alloc(4)) return -2;
             if (B.insts.n < sizeof(mnk::DagInst) * (size_t)k && B.insts.alloc(sizeof(mnk::DagInst) * (size_t)std::max(k, 32))) return -2;
@@ -1561,7 +1558,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             for (int i = 0; i < k; ++i) {
                 mnk_ls* ls = g[r0 + i];
                 hin.push_back(dag_instance(ls));
-                ls->dag_filled = hin.back().zfill != nullptr;
+                ls->spare.dag_fills(hin.back().zfill != nullptr);
                 hin.back().env = nullptr;   // (batches of small systems run dense: their bulk tasks only accumulate band tiles)
                 hin.back().envgate = nullptr;
                 hin.back().envh = nullptr;
@@ -1637,14 +1634,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
         rc = mnk_persist_end(c0, h, rc);
         if (rc) return rc;
     }
-    MNK_HIP(hipEventRecord(l0->ev_defer, h));
-    for (mnk_ls* ls : g) {
-        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(ls->ctx->stream, l0->ev_defer, 0));
-        batch_mark_done(ls);
-        int r = mnk_ls_prefill_spare(ls);
-        if (r) return r;
-    }
-    return 0;
+    return batch_finish(g, h);
 }
 
 static int batch_flush() {
@@ -1656,14 +1646,13 @@ static int batch_flush() {
         mnk_ls* l0 = pend.front();
         std::vector<mnk_ls*> g, rest;
         for (mnk_ls* ls : pend) {
-            const bool same = ls->ctx->device == l0->ctx->device && ls->Np == l0->Np && ls->algo == l0->algo && ls->dag_js2 == l0->dag_js2 && ls->dag_chunk == l0->dag_chunk &&
-                              ls->dag_taper0 == l0->dag_taper0 && ls->dag_band == l0->dag_band && ls->dag_has_fill == l0->dag_has_fill;
+            const bool same = ls->ctx->device == l0->ctx->device && ls->Np == l0->Np && ls->algo == l0->algo && ls->plan.key == l0->plan.key;
             (same && std::find(g.begin(), g.end(), ls) == g.end() ? g : rest).push_back(ls);
         }
         pend.swap(rest);
         int rc;
         if (g.size() >= 2) {
-            rc = l0->dag_js2 == 0 ? batch_run_group_small(g) : batch_run_group(g);
+            rc = l0->plan.key.js2 == 0 ? batch_run_group_small(g) : batch_run_group(g);
             if (rc)   // (nothing of the group counts as factorized: the factor buffers already hold the NEW, unfactored matrices, so
                       // a solve or an inertia call that ignores this error must not find the previous factorization's flag)
                 for (mnk_ls* ls : g) { ls->deferred = false; ls->factorized = false; ls->info_valid = false; }

@@ -1205,7 +1205,7 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     {   // info[2]: the leaf stops the factorization at the first pivot that is not positive (leaf64.h: early rejection)
         // (also inside a factorization batch: a member that stops early leaves the others alone -- dag.hip, the workgroup-uniform
         // `dead` of the batch kernel; tests/test_hip_round5.py::test_a_batch_in_which_some_instances_are_indefinite)
-        const int want = (ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->src_persistent) ? 1 : 0;
+        const int want = (ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->src.persistent) ? 1 : 0;
         if (want != ls->reject_on_device) {
             MNK_HIP(hipMemsetAsync(ls->info_dev.p + 2, want, sizeof(int), s));
             ls->reject_on_device = want;
@@ -1223,12 +1223,10 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     if (ls->algo_now == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) ls->algo_now = 4;
     if (ls->algo_now == 5 && ctx->sp_dag == nullptr && mnk_ctx_ensure_dag(ctx) != 0) { (void)hipGetLastError(); ls->algo_now = 4; }   // (released while idle)
     if (ls->algo_now == 5 && ctx->sp_dag == nullptr) ls->algo_now = 4;
-    ++ls->fact_count;
-    if (ls->pp_blocked && ls->fact_count >= ls->pp_retry_at) ls->pp_blocked = false;   // (a time-out may have been transient)
-    if (ls->algo_now >= 4 && ls->pp_blocked) ls->algo_now = 1;
+    if (ls->pp.blocked_now() && ls->algo_now >= 4) ls->algo_now = 1;
     // the task-DAG schedule's buffers (task list, progress words, V = L D): a device that cannot hold them keeps schedule 4
     if (ls->algo_now == 5 && mnk_ls_dag_prepare(ls) != 0) ls->algo_now = 4;
-    if (ls->algo_now == 5 && ls->dag_js2 < (Np + 255) / 256) {   // (the deep-band stream pair: made with the first such factorization)
+    if (ls->algo_now == 5 && ls->plan.key.js2 < (Np + 255) / 256) {   // (the deep-band stream pair: made with the first such factorization)
         if (mnk_ctx_ensure_dag2(ctx) != 0) (void)hipGetLastError();
         if (ctx->sp_dag2 == nullptr) ls->algo_now = 4;
     }
@@ -1438,14 +1436,13 @@ static int run_factorization_body(mnk_ls* ls) {
         int rc = mnk_ls_launch_finish_info(ls, s);
         if (rc) return rc;
     }
-    return mnk_ls_prefill_spare(ls);
+    return ls->spare.queued(ls);
 }
 
 void mnk_ls_fill_small_rec(mnk_ls* ls, mnk::SmallSysRec* rec) {
     const bool lmode = ls->algo == MNK_LDL;
-    const int64_t ntile = ls->Np / 128;
-    rec->flags = ls->dag_flags.p;
-    rec->nflags = 2 + ls->Np / NBI + 2 * ntile * ntile;
+    rec->flags = ls->plan.flags.p;
+    rec->nflags = (int64_t)DagPlan::progress_words(ls->Np);
     rec->info = ls->info_dev.p;
     rec->F = ls->fact.p; rec->ld = ls->ld; rec->dblk = ls->dblk.p; rec->linv = ls->linv.p;
     rec->linv256 = ls->linv256.p; rec->linv256t = ls->linv256t.p; rec->Np = ls->Np;
@@ -1517,14 +1514,14 @@ int mnk_launch_trsm64_batch(hipStream_t s, bool ldl, const mnk::TrsmBatchRec* re
 // Tier 2 of BUNCHKAUFMAN: fetch the matrix again, factor it with pivoting (bk.hip), rebuild the inverses the solves use.
 static int bk_fallback(mnk_ls* ls) {
     hipStream_t s = ls->ctx->stream;
-    int rc = ls->retransfer();
+    int rc = ls->src.retransfer();
     if (rc) return rc;
     rc = mnk_ls_run_bunchkaufman(ls);
     if (rc) return rc;
     rc = mnk_ls_invert_blocks(ls, s, 0, (ls->Np + 255) / 256);
     if (rc) return rc;
     ++ls->bk_count;
-    return mnk_ls_prefill_spare(ls);   // (the second transfer swapped the factor buffers again: the spare one holds the discarded static factor)
+    return ls->spare.queued(ls);   // (the second transfer swapped the factor buffers again: the spare one holds the discarded static factor)
 }
 
 int mnk_ls_fetch_info(mnk_ls* ls) {
@@ -1552,7 +1549,7 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         return 0;
     }
     // growth guard of the static-pivot tier (BUNCHKAUFMAN): max|a_ij| was recorded when the matrix was transferred
-    const bool guard = ls->algo == MNK_LDL && ls->bk_requested && ls->bk_fallback && ls->retransfer && ls->amax_dev.p != nullptr;
+    const bool guard = ls->algo == MNK_LDL && ls->bk_requested && ls->bk_fallback && ls->src.retransfer && ls->amax_dev.p != nullptr;
     // (finish_info_kernel, queued behind the factorization, has stored everything in the pinned words)
     if (ls->ev_info_recorded) MNK_HIP(hipEventSynchronize(ls->ev_info));
     else MNK_HIP(mnk::stream_wait(s));
@@ -1567,37 +1564,29 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         ls->last_growth = am > 0.0 ? dm / am : (dm > 0.0 ? HUGE_VAL : 0.0);
         ls->last_sign_changes = (int64_t)pw[6];
     }
-    if (hinfo == -7) ls->last_timeout_site = (int)(long long)pw[7];
-    if (hinfo == -7 && ls->dag_debug && ls->dag_flags.p && ls->dag_dbg.p) {
+    if (hinfo == -7) ls->pp.last_site = (int)(long long)pw[7];
+    if (hinfo == -7 && ls->dag_debug && ls->plan.flags.p && ls->dag_dbg.p) {
         // diagnostics: the schedule's progress words and what the chain's strips were waiting for, as the time-out left them
         MNK_HIP(mnk::stream_wait(s));
-        const int64_t ntile = ls->Np / 128;
-        ls->dbg_flags.resize((size_t)(2 + ls->Np / NBI + 2 * ntile * ntile));
+        ls->dbg_flags.resize(DagPlan::progress_words(ls->Np));
         ls->dbg_chain.resize(ls->dag_dbg.n);
-        MNK_HIP(mnk::d2h_copy(ls->dbg_flags.data(), ls->dag_flags.p, ls->dbg_flags.size() * sizeof(int), s));
+        MNK_HIP(mnk::d2h_copy(ls->dbg_flags.data(), ls->plan.flags.p, ls->dbg_flags.size() * sizeof(int), s));
         MNK_HIP(mnk::d2h_copy(ls->dbg_chain.data(), ls->dag_dbg.p, ls->dbg_chain.size() * sizeof(int), s));
     }
-    if (hinfo != 0 && ls->spare_by_dag) {
-        // The spare factor buffer was to be zeroed by the DAG_FILL tasks of this factorization's queue -- which its
-        // workgroups dropped when `info` became non-zero.  Found as an intermittent wrong matrix behind a time-out: the redo
-        // below swapped the half-zeroed buffer (the previous factor) in and scattered the sparse entries over it (1 in ~40
-        // runs of tests/test_hip_c5.py once the waits' bound had come down from 3 s to 0.3 s; tools/c5_loop.py).
-        ls->spare_zeroed = false;
-        ls->spare_by_dag = false;
-    }
-    if (hinfo == -7 && ls->algo_now >= 4 && ls->retransfer) {
+    // DAG_FILL tasks of this factorization's queue were dropped by its workgroups when `info` became non-zero.  Found as an intermittent
+    // wrong matrix behind a time-out: the redo below swapped the half-zeroed spare buffer (the previous factor) in and scattered the sparse
+    // entries over it (1 in ~40 runs of tests/test_hip_c5.py once the waits' bound had come down from 3 s to 0.3 s; tools/c5_loop.py).
+    if (hinfo != 0) ls->spare.failed();
+    if (hinfo == -7 && ls->algo_now >= 4 && ls->src.retransfer) {
         // the persistent panel kernel gave up on a dependency (CUs shared with another process' persistent kernels):
         // factor again with one launch per panel piece, and stay there for a while (16, 64, 256, ... factorizations)
-        ls->pp_blocked = true;
-        ls->pp_retry_at = ls->fact_count + ls->pp_backoff + 1;   // (+1: the redo below counts)
-        ls->pp_backoff *= 4;
-        ++ls->pp_fallbacks;
+        ls->pp.wait_expired();
         {   // what the expired wait cost: from the launch of that factorization to this moment (the redo below comes on top)
             const double lost = std::max(0.0, mnk_host_ms() - ls->t_fact_launch_ms);
             ls->stall_ms_total += lost;
             mnk_add_process_stall_ms(lost);
         }
-        int rc = ls->retransfer();
+        int rc = ls->src.retransfer();
         if (rc) return rc;
         rc = mnk_ls_run_factorization(ls);
         if (rc) return rc;
@@ -1644,7 +1633,7 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         // LDL^T PROVES that the matrix is not positive definite -- the pivoted tier could only confirm a rejection, at
         // 0.47 s for N = 11 192 -- so the static tier's counts are reported as they are.
         const bool verdict_final = ls->accept_only_pd && (ls->nzero > 0 || ls->nneg > 0);
-        if (!verdict_final && (ls->nzero > 0 || (guard && !(ls->last_growth <= gtol))) && ls->bk_requested && ls->bk_fallback && ls->retransfer) {
+        if (!verdict_final && (ls->nzero > 0 || (guard && !(ls->last_growth <= gtol))) && ls->bk_requested && ls->bk_fallback && ls->src.retransfer) {
             // the static-pivot factorization broke down (a zero pivot) or grew (tiny pivots: the Schur complements left the
             // scale of the matrix) on a matrix that is not quasi-definite in the given order: BUNCHKAUFMAN means dsytrf
             // semantics, so factor it again with 1x1 / 2x2 pivoting

@@ -19,7 +19,7 @@ struct mnk_sc {
     // first nonzero, so the tiles L(I, J), J < tile_env[I], are exact zeros (the task-DAG bulk kernel skips them, dag.hip)
     std::vector<int32_t> tile_env;
     mnk::DevBuf<int32_t> d_tile_env;
-    // the same per 64-row HALF of a tile row, in 64-column units (mnk_tile_envelope_half): tile_envh[2I], tile_envh[2I + 1];
+    // the same per 64-row HALF of a tile row, in 64-column units (mnk_tile_envelope with 64-row blocks): tile_envh[2I], tile_envh[2I + 1];
     // tile_env[I] = min of the two / 2.  The bulk kernel's waves skip the k-tiles left of their own half (option "envelope_half")
     std::vector<int32_t> tile_envh;
     mnk::DevBuf<int32_t> d_tile_envh;
@@ -36,43 +36,28 @@ struct mnk_sc {
     // device values
     mnk::DevBuf<double> jac_coo, hess_coo, jt_nz, h_nz, aug_nz, diag_buffer, pr_diag, du_diag;
     void* extra = nullptr;  // unit-private device structures (sparse_kkt.hip), owned by the handle
-    // dies with the handle: a linear solver that keeps a way back to this handle's matrix (mnk_ls::retransfer) holds a
+    // dies with the handle: a linear solver that keeps a way back to this handle's matrix (mnk_ls::src) holds a
     // weak reference and refuses to touch a destroyed handle
     std::shared_ptr<int> alive = std::make_shared<int>(0);
 };
 
-// tile_env (see mnk_sc) of a lower-triangular pattern of order n: entries (row[k], col[k]), col <= row; entries outside the
-// order are ignored.  One entry per 128-row tile of the padded order.
-inline std::vector<int32_t> mnk_tile_envelope(int64_t n, const int32_t* row, const int32_t* col, int64_t nnz) {
+// Envelope of a lower-triangular pattern of order n per block of `block` rows (128: tile_env, 64: tile_envh; see mnk_sc):
+// entries (row[k], col[k]), col <= row; entries outside the order are ignored.  One entry per row block of the order padded to
+// 128: (first nonzero column over the block's rows) / block.  A padding row is its own first nonzero, so a block of padding
+// rows points at its own diagonal.
+inline std::vector<int32_t> mnk_tile_envelope(int64_t n, const int32_t* row, const int32_t* col, int64_t nnz, int64_t block) {
     std::vector<int32_t> fnz(n);
     for (int64_t i = 0; i < n; ++i) fnz[i] = (int32_t)i;
     for (int64_t k = 0; k < nnz; ++k)
         if (row[k] >= 0 && row[k] < n && col[k] < fnz[row[k]]) fnz[row[k]] = col[k];
-    const int64_t ntile = (n + 127) / 128;
-    std::vector<int32_t> env(ntile);
-    for (int64_t I = 0; I < ntile; ++I) {
-        int32_t f = (int32_t)(128 * I);   // (a padding row is its own first nonzero)
-        for (int64_t i = 128 * I; i < std::min<int64_t>(n, 128 * I + 128); ++i) f = std::min(f, fnz[i]);
-        env[I] = f / 128;
+    const int64_t nblock = (n + 127) / 128 * (128 / block);
+    std::vector<int32_t> env(nblock);
+    for (int64_t I = 0; I < nblock; ++I) {
+        int32_t f = (int32_t)(block * I);
+        for (int64_t i = block * I; i < std::min<int64_t>(n, block * I + block); ++i) f = std::min(f, fnz[i]);
+        env[I] = (int32_t)(f / block);
     }
     return env;
-}
-
-// tile_envh (see mnk_sc) of the same pattern: two entries per 128-row tile of the padded order, the first nonzero column over the
-// rows of each 64-row half / 64 (a padding row is its own first nonzero: a half of padding rows points at its own diagonal).
-inline std::vector<int32_t> mnk_tile_envelope_half(int64_t n, const int32_t* row, const int32_t* col, int64_t nnz) {
-    std::vector<int32_t> fnz(n);
-    for (int64_t i = 0; i < n; ++i) fnz[i] = (int32_t)i;
-    for (int64_t k = 0; k < nnz; ++k)
-        if (row[k] >= 0 && row[k] < n && col[k] < fnz[row[k]]) fnz[row[k]] = col[k];
-    const int64_t nhalf = 2 * ((n + 127) / 128);
-    std::vector<int32_t> envh(nhalf);
-    for (int64_t h = 0; h < nhalf; ++h) {
-        int32_t f = (int32_t)(64 * h);
-        for (int64_t i = 64 * h; i < std::min<int64_t>(n, 64 * h + 64); ++i) f = std::min(f, fnz[i]);
-        envh[h] = f / 64;
-    }
-    return envh;
 }
 
 struct mnk_dc {
@@ -109,6 +94,87 @@ struct mnk_ls_alt {
     virtual double stat(const char* key) { (void)key; return 0.0; }      // mnk_ls_get_stat keys that belong to one algorithm
 };
 
+// The spare factor buffer and its zero-fill (operations: ls.hip).  Sparse sources are scattered into a ZEROED dense buffer (8 Np^2 / 2
+// bytes of zeros per factorization: 116 us at C3, HBM-bound).  With `prefill` the zeros are written in the background into a second
+// buffer -- on the context's side stream, or (option dag_fill) by DAG_FILL tasks of the factorization's own bulk queue -- and the
+// next transfer swaps the two (costs a second factor buffer, so only up to MAX_ROWS).  States:
+//   Dirty            no spare buffer, or an old factor in it: the next transfer fills the factor buffer in line
+//   Pending          a sparse matrix was transferred; the spare buffer is to be zeroed once its factorization is queued
+//   PendingDagFills  ... and the launch that was just queued zeroes it itself
+//   ZeroedBySide     a fill on the side stream is queued (ev_zeroed): the next transfer swaps
+//   ZeroedByDag      the queue of the factorization queued last zeroes it -- IF that one runs to its end (a time-out or a breakdown
+//                    drops the rest of its queue): trusted only once somebody has looked at `info`; failed() takes it back to Dirty
+// acquire() leaves Pending (with prefill off: what it found), so a second transfer for the same factorize! (the pivoted tier, a redo
+// after a time-out) never swaps the old factor back in; only a COMPLETED queued() makes the other buffer count as zeroed again.
+struct SpareFill {
+    static constexpr int64_t MAX_ROWS = 24576;
+    int prefill = 1;    // option
+    bool wanted(int64_t Np) const { return prefill && Np <= MAX_ROWS; }
+    int acquire(mnk_ls* ls);      // a sparse transfer begins: a zeroed lower triangle in ls->fact (by swap or in line) on the home stream
+    double* dag_target() const { return pending() ? buf.p : nullptr; }   // what the DAG_FILL tasks of the launch being built should zero
+    void dag_fills(bool yes) { if (pending()) state = yes ? State::PendingDagFills : State::Pending; }   // ... and whether it took it
+    int queued(mnk_ls* ls);       // the factorization has been queued: the side-stream fill, if one is due
+    void failed() { if (state == State::ZeroedByDag) state = State::Dirty; }   // the factorization queued last ended with info != 0
+    bool give_up();               // memory is short: frees the buffer (and turns prefill off) unless a fill of it is queued
+    void destroy(mnk_ctx* ctx);   // waits for the side stream, destroys the events (the buffer frees itself)
+   private:
+    enum class State { Dirty, Pending, PendingDagFills, ZeroedBySide, ZeroedByDag };
+    State state = State::Dirty;
+    bool pending() const { return state == State::Pending || state == State::PendingDagFills; }
+    bool zeroed() const { return state == State::ZeroedBySide || state == State::ZeroedByDag; }
+    mnk::DevBuf<double> buf;
+    hipEvent_t ev_zeroed = nullptr, ev_free = nullptr;   // "the fill is done" / "everything queued before the fill has run"
+};
+
+// The task-DAG plan (dag.hip): the task list of the schedule for this solver's order and what is derived from it.  Built by
+// mnk_ls_dag_prepare when there is none; every option the list depends on calls invalidate().
+struct DagPlan {
+    // What batch_flush groups solvers of one device, order and algorithm by, and what (with ntile, the instances and their shift)
+    // makes a merged list reusable.  dag_deep_rows and the dag_js2 override enter through js2, dag_fill and prefill through
+    // has_fill; dag_xcd_queues and dag_gang only deal the DEVICE list of a single factorization and are not compared.
+    struct Key {
+        int chunk = 0, taper0 = 0, band = 0;   // the options dag_chunk, dag_taper0, dag_band the list was built with
+        int js2 = 0;                           // first strip-column of the second phase
+        bool has_fill = false;                 // the list contains DAG_FILL tasks
+        bool operator==(const Key& o) const { return chunk == o.chunk && taper0 == o.taper0 && band == o.band && js2 == o.js2 && has_fill == o.has_fill; }
+    };
+    Key key;
+    mnk::DevBuf<int> tasks;                  // 4 ints per task, dealt into the per-XCD queues of the single-factorization bulk kernel (dag_deal_tasks)
+    std::vector<int> host_tasks, host_ready; // the list as built and the chain position that makes each task ready: merged per batch
+    int ntasks = 0, ntasks1 = 0;             // all tasks / tasks of the first phase
+    int nq[2] = {0, 0};                      // queues per phase (0: one queue, the list as built)
+    mnk::DevBuf<int> qoff;                   // per phase 16 ints: the nq + 1 offsets of the queues in the phase's part of the list
+    mnk::DevBuf<int> qheads;                 // per phase DAG_QHEAD_WORDS ints: the queue heads, 128 bytes apart, then the count of stolen tasks
+    mnk::DevBuf<int> flags;                  // progress words [2 queue counters | front: Np/64 | af, tprog: ntile^2 each], zeroed per factorization
+    bool valid() const { return tasks.p != nullptr; }
+    void invalidate() { tasks.release(); }   // the next task-DAG factorization builds the plan again
+    static size_t progress_words(int64_t Np);
+    size_t trace_words() const;              // option dag_trace: tasks | chain strips | per-workgroup statistics (2 x 512), 8 words each
+};
+
+// What the last factorize! call factored (ls.hip).
+struct MatrixSource {
+    std::function<int()> retransfer;   // puts the matrix back into `fact` (the pivoted tier, a redo after a time-out, the completion of an early-rejected factorization); empty once the source is gone
+    bool persistent = false;           // the source outlives the call (KKT handles): a rejected factorization can be completed later
+    // Envelope (options "envelope", "envelope_half"; set_envelope): the device arrays tile_env / tile_envh of the source (a KKT handle's, or
+    // env_own / envh_own for a lower CSC), nullptr for dense sources, and their host copies (statistics).  Only the task-DAG schedule reads them.
+    const int32_t *env_dev = nullptr, *envh_dev = nullptr;
+    std::vector<int32_t> env_host, envh_host;
+    bool env_armed = false;            // a transfer may have marked env_word[0] since a task-DAG factorization last consumed it
+};
+
+// Back-off of the persistent schedules (4 and 5) after a bounded device-side wait expired: schedule 1 for 16, then 64, 256, ...
+// factorizations, then another try (a time-out may have been transient).
+struct PersistBackoff {
+    int64_t count = 0;                 // factorizations of this solver
+    int fallbacks = 0, last_site = 0;  // statistics "pp_fallbacks" / "timeout_site": which wait expired last
+    bool blocked_now() { ++count; if (count >= retry_at) blocked = false; return blocked; }   // counts a factorization; true: it keeps to schedule 1
+    void wait_expired() { blocked = true; retry_at = count + backoff + 1; backoff *= 4; ++fallbacks; }   // (+1: the redo that follows counts)
+   private:
+    bool blocked = false;
+    int64_t retry_at = 0, backoff = 16;
+};
+
 struct mnk_ls {
     mnk_ctx* ctx = nullptr;
     int64_t N = 0, Np = 0, ld = 0, ldw = 0, nbo = 512;
@@ -121,44 +187,23 @@ struct mnk_ls {
     int64_t single_rows = 2560;  // systems up to this (padded) order are factored as ONE outer panel on the whole chip (with the fused tail panels the look-ahead schedule wins from N = 3072 on: 2.12 vs 2.34 ms at 4096)
     mnk::DevBuf<int> tile_ctr;  // one work-queue counter per outer step
     mnk::DevBuf<double> fact, wbuf[2], linv, dblk, inv16, linv256, linv256t, dvec, dinv, xwork;
-    // Sparse sources are scattered into a ZEROED dense buffer (8 Np^2 / 2 bytes of zeros per factorization: 116 us at C3,
-    // HBM-bound).  With `prefill` the zeros are written in the background into a second buffer while the current
-    // factorization / its solves run; the next factorize! swaps the two (costs a second factor buffer, so only up to
-    // PREFILL_MAX_ROWS).
-    mnk::DevBuf<double> fact_spare;
-    hipEvent_t ev_spare = nullptr, ev_free = nullptr;
-    bool spare_zeroed = false, spare_pending = false;
-    int prefill = 1;
-    static constexpr int64_t PREFILL_MAX_ROWS = 24576;
+    SpareFill spare;   // the second factor buffer of sparse sources and its background zero-fill
     int epoch = 0;    // value the hand-off flags of the current factorization carry
     mnk::DevBuf<int> flag_p;
     int algo_now = 1;    // the panel algorithm of the current factorization (panel_algo, or 1 where 4 is not safe)
-    bool pp_blocked = false;
-    int64_t fact_count = 0, pp_retry_at = 0, pp_backoff = 16;   // a schedule that timed out is tried again after 16, 64, 256, ... factorizations
-    int pp_fallbacks = 0;
-    int last_timeout_site = 0;   // diagnostics: which bounded device-side wait expired (get_stat "timeout_site")
+    PersistBackoff pp;
     double stall_ms_total = 0.0; // host time between the launch of a factorization whose bounded wait expired and the moment the expiry was seen: what the fall-backs of this solver have cost (get_stat "stall_ms_total"; "stall_ms_process": all solvers)
     double t_fact_launch_ms = 0.0;   // host clock (ms) when the current factorization was enqueued
     int64_t pp_fuse_rows = 4096; // > 0: once this many rows (or fewer) remain, persistent panel launches apply the columns in front of them themselves
     // task-DAG schedule (panel_algo = 5, dag.hip)
-    mnk::DevBuf<int> dag_tasks;   // 4 ints per task, built once per order
-    int dag_ntasks = 0, dag_ntasks1 = 0, dag_js2 = 0;  // all tasks / tasks of the first phase / first strip-column of the second
-    std::vector<int> dag_host_tasks, dag_host_ready;   // the list on the host (4 ints per task) and the chain position that makes each task ready: merged per batch (dag.hip)
+    DagPlan plan;
     int dag_fill = 1;             // option: the zero-fill of the spare factor buffer (sparse sources) runs as DAG_FILL tasks of the bulk queue instead of on a side stream beside the solves
-    bool dag_has_fill = false;    // the current task list contains them
-    bool dag_filled = false;      // the factorization that was just queued zeroes the spare buffer itself (mnk_ls_prefill_spare has nothing to launch)
     hipEvent_t ev_info = nullptr;    // recorded behind finish_info_kernel: what mnk_ls_fetch_info waits for
     bool ev_info_recorded = false;
     hipEvent_t ev_defer = nullptr;   // batch: "matrix transferred" on this solver's stream / "batch done"
     bool deferred = false;        // a factorize! call of this solver is pending in an open batch
-    // Per-XCD queues of the single-factorization bulk kernel (dag.hip: dag_deal_tasks): the device task list is dealt into DAG_NQ
-    // subsequences, a workgroup pops the head of its own XCD's queue and steals from the head of another once that one is empty.
-    int dag_xcd_queues = 1;       // option: 0 = one queue popped by every workgroup
+    int dag_xcd_queues = 1;      // option: 0 = one queue popped by every workgroup
     int dag_gang = 4;             // option: tasks of one group (same B rows, same k-range) dealt to one queue together; < 0: all tasks to queue 0 (tests)
-    int dag_nq[2] = {0, 0};       // queues of the current device list per phase (0: one queue, the list as built)
-    mnk::DevBuf<int> dag_qoff;    // per phase 16 ints: the nq + 1 offsets of the queues in the phase's part of the device list
-    mnk::DevBuf<int> dag_qheads;  // per phase DAG_QHEAD_WORDS ints: the queue heads, 128 bytes apart, then the count of stolen tasks; zeroed per factorization
-    mnk::DevBuf<int> dag_flags;   // [queue counter | front: Np/64 | af: 4 * Np/128], zeroed per factorization
     mnk::DevBuf<double> vfull;    // LDL^T: V = L D of every column, same layout as `fact` (B operand of the left-looking updates)
     mnk::DevBuf<unsigned long long> dag_trace;  // diagnostics (option dag_trace): time stamps per bulk task / chain strip
     bool dag_trace_on = false;
@@ -170,23 +215,13 @@ struct mnk_ls {
     int dag_chunk = 64;           // tile columns (of 128) per bulk task behind the doubling taper 1, 2, 4, ... (every task ends with a read-modify-write of its tile; C3 at the end of round 3: 12 -> 9.58 ms, 48 / 64 / 88 / 128 / 1024 -> 9.30; N = 16 384: 26.3 -> 25.9 ms, N = 24 576: 82.0 / 82.5 ms; in the middle of the round, with slower closing tasks, 10-16 was the optimum)
     int64_t dag_min_rows = 1280;  // smaller systems keep the launch-per-panel schedules (round 6, LDL: N = 1024 0.441 (schedule 4) / 0.452 ms (this one), N = 1280 0.573 / 0.551; rounds 3-5: 1536)
     int64_t dag_deep_rows = 5376; // systems up to this order put every row into the chain's band (and at most 64 x MNK_DAG_CUS2 rows); larger ones: band + bulk kernel
-    // Envelope of the matrix being factored (option "envelope"; dag.hip): the device array tile_env of the source of the
-    // last transfer (a KKT handle's, or env_own for a lower CSC), nullptr for dense sources.  Only the task-DAG schedule uses it.
-    int envelope = 1;
-    const int32_t* env_dev = nullptr;
-    std::vector<int32_t> env_host;   // its host copy (statistics)
-    mnk::DevBuf<int32_t> env_own;
-    // ... and per 64-row half in 64-column units (option "envelope_half", ignored with envelope = 0; mnk_sc::tile_envh)
-    int envelope_half = 1;
-    const int32_t* envh_dev = nullptr;
-    std::vector<int32_t> envh_host;
-    mnk::DevBuf<int32_t> envh_own;
-    bool envh_used = false;          // the last task-DAG factorization was launched with the half-tile envelope (statistics)
+    MatrixSource src;
+    int envelope = 1, envelope_half = 1;   // options: the bulk kernel skips by the tile envelope of a sparse source / by its 64-row halves too (ignored with envelope = 0)
+    mnk::DevBuf<int32_t> env_own, envh_own;   // the envelopes of a lower-CSC source (a KKT handle keeps its own)
     // [0] set by a transfer that met a NaN / Inf entry, [1] that verdict for the factorization being run: dag_reset_kernel moves
     // [0] into [1] and clears [0]; the bulk kernel skips nothing when [1] != 0 (a NaN spreads through 0 * NaN in the dense order)
     mnk::DevBuf<int> env_word;
-    bool env_used = false;           // the last task-DAG factorization was launched with an envelope (statistics)
-    bool env_armed = false;          // a transfer may have marked env_word[0] since a task-DAG factorization last consumed it
+    bool env_used = false, envh_used = false;   // the last task-DAG factorization was launched with the envelope / the half-tile envelope (statistics)
     int64_t dag_max_rows = 30720; // larger ones too: their trailing updates already run at the update kernel's rate (round 6, LDL, schedule 4 / this one: N = 24 576 87.4 / 81.7 ms, 28 672 133.6 / 128.6, 32 768 188.2 / 190.2; rounds 3-5: 24 576)
     int panel_algo = 5;  // 5: task-DAG schedule (dag.hip: persistent pivot chain + persistent left-looking bulk kernel); 4: persistent panel kernel per 256 columns + one trailing update per outer panel (also what 5 uses outside [dag_min_rows, dag_max_rows]); 1: one launch per piece, the fallback of 4 and 5
     int persistent_solve = 1;  // both sweeps of a solve in one launch (solve.hip); 0: one launch per step
@@ -212,7 +247,6 @@ struct mnk_ls {
     int early_reject = 0;        // option (with accept_only_pd): stop the static-pivot LDL^T at the first pivot that is not positive (leaf64.h); the factor
                                  // of a rejected matrix is then not usable and its inertia is a lower bound on num_neg
     int reject_on_device = -1;   // what info[2] on the device currently says
-    bool src_persistent = false; // the source of the last factorize! call outlives the call (KKT handles): a rejected factorization can be completed later
     bool factor_invalid = false; // the last factorization was rejected early: solve / get_factor refuse
     int64_t early_rejects = 0, early_reject_col = -1, early_reject_redone = 0;   // statistics ("early_rejects", "early_reject_col")
     // LEADING-BLOCK PROBE (round 6; option "probe", effective while early rejection is armed): after a rejection that stopped in
@@ -240,7 +274,6 @@ struct mnk_ls {
     mnk::DevBuf<unsigned long long> amax_dev;  // [0] max|a_ij| as transferred (folded from the slots below when the info is published), [1] max(|d_k|, |v_ik|) (bit patterns), [2] sign changes of the pivots; [AMAX_SLOT0 + AMAX_STRIDE i]: partial max|a_ij| of the transfer kernels
     bool bk_active = false;      // the current factor is P A P^T = L D L^T with 2x2 blocks (solves use perm / dcoup)
     int bk_count = 0;            // how many factorizations took the pivoted tier (diagnostics, tests)
-    std::function<int()> retransfer;  // puts the matrix of the last factorize! call back into `fact`
     mnk::DevBuf<int> bk_perm, bk_ptype;
     mnk::DevBuf<double> bk_doff, bk_dcoup, bk_work;  // (bk_work: the panel's W = L D and its zero-padded copy of L, 2 x Np x 72)
     mnk::DevBuf<char> bk_state;
@@ -259,8 +292,6 @@ struct mnk_ls {
     int dag_debug = 0;           // option: keep the progress words of a factorization that timed out (mnk_ls_debug_dag_state)
     mnk::DevBuf<int> dag_dbg;    // 8 words per chain strip (PpDag::dbg)
     std::vector<int> dbg_flags, dbg_chain;
-    bool spare_by_dag = false;   // the spare buffer's zero-fill was left to the DAG_FILL tasks of the factorization queued last: it
-                                 // only happened if that factorization ran to its end (info == 0)
     int info = 0;
     int64_t npos = 0, nzero = 0, nneg = 0;
     std::unique_ptr<mnk_ls_alt> alt;   // QR / LU / EVD: the algorithm that factors and solves instead of the tiled path (null for CHOLESKY / LDL)
@@ -293,7 +324,6 @@ int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t
 bool mnk_batch_defer(mnk_ls* ls);                  // dag.hip: true if the calling thread has a batch open and took the factorization into it
 int mnk_ls_sync_deferred(mnk_ls* ls);              // dag.hip: runs what the open batches of this thread hold for this solver (queued solves, a pending factorization)
 int mnk_ls_sync_deferred_fact(mnk_ls* ls);         // dag.hip: ... the pending factorization only
-int mnk_ls_prefill_spare(mnk_ls* ls);   // ls.hip: queue the background zero-fill of the spare factor buffer (if one is due)
 int mnk_ls_fetch_info(mnk_ls* ls);
 int mnk_ls_run_factorization_dag(mnk_ls* ls);   // dag.hip: the task-DAG schedule (panel_algo = 5)
 int mnk_ls_dag_prepare(mnk_ls* ls);             // dag.hip: its buffers (0: ready; otherwise the device cannot hold them -> schedule 4)

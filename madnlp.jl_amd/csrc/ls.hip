@@ -660,7 +660,7 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     ls->alt = mnk_ls_alt_new(algo);
     if (ls->alt) {
         rc |= ls->alt->alloc(ls);
-        ls->prefill = 0;   // (they write the whole factor buffer, the upper triangle included: no background zero-fill)
+        ls->spare.prefill = 0;   // (they write the whole factor buffer, the upper triangle included: no background zero-fill)
     }
     if (rc) { delete ls; return -2; }
     MNK_HIP(hipMemsetAsync(ls->fact.p, 0, ((size_t)ls->ld * ls->Np + SLACK) * sizeof(double), ctx->stream));
@@ -685,9 +685,7 @@ int mnk_ls_destroy(mnk_ls* ls) {
     mnk::quiesce_persistent();
     if (ls->solve_abort) (void)hipHostFree(ls->solve_abort);
     if (ls->pin) (void)hipHostFree(ls->pin);
-    if (ls->ctx->s_fill) (void)mnk::stream_wait(ls->ctx->s_fill);   // a background fill of this solver's spare buffer
-    if (ls->ev_spare) (void)hipEventDestroy(ls->ev_spare);
-    if (ls->ev_free) (void)hipEventDestroy(ls->ev_free);
+    ls->spare.destroy(ls->ctx);
     if (ls->ev_defer) (void)hipEventDestroy(ls->ev_defer);
     if (ls->ev_info) (void)hipEventDestroy(ls->ev_info);
     mnk_ctx* ctx = ls->ctx;
@@ -726,7 +724,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     }
     if (!strcmp(key, "solve512")) { ls->solve512 = value != 0; return 0; }   // 512-column steps of the one-launch solve
     if (!strcmp(key, "linv_mfma")) { ls->linv_mfma = value != 0.0; return 0; }
-    if (!strcmp(key, "prefill")) { ls->prefill = value != 0; return 0; }   // background zero-fill into a second factor buffer
+    if (!strcmp(key, "prefill")) { ls->spare.prefill = value != 0; return 0; }   // background zero-fill into a second factor buffer
     if (!strcmp(key, "single_rows")) {  // systems up to this order: one outer panel, no look-ahead (0: never)
         ls->single_rows = (int64_t)value;
         ls->wbuf[0].release();
@@ -750,19 +748,19 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     if (!strcmp(key, "dag_taper0")) {
         MNK_REQUIRE(value >= 1.0 && value <= 16.0, "dag_taper0 must be in 1..16");
         ls->dag_taper0 = (int)value;
-        ls->dag_tasks.release();
+        ls->plan.invalidate();
         return 0;
     }
     if (!strcmp(key, "dag_chunk")) {   // tile columns per bulk task of the task-DAG schedule (the task list is rebuilt)
         MNK_REQUIRE(value >= 1.0 && value <= 64.0, "dag_chunk must be in 1..64");
         ls->dag_chunk = (int)value;
-        ls->dag_tasks.release();
+        ls->plan.invalidate();
         return 0;
     }
     if (!strcmp(key, "dag_band")) {    // 64-row strips of the pivot chain's band
         MNK_REQUIRE(value >= 8.0 && value <= 64.0 && (int)value % 4 == 0 && (double)(int)value == value, "dag_band must be a multiple of 4 in 8..64");
         ls->dag_band = (int)value;
-        ls->dag_tasks.release();
+        ls->plan.invalidate();
         return 0;
     }
     if (!strcmp(key, "dag_spin_limit")) {  // polls a wait of the task-DAG schedule's kernels may take before it gives up
@@ -770,18 +768,18 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         ls->dag_spin_limit = (long)value;
         return 0;
     }
-    if (!strcmp(key, "dag_fill")) { ls->dag_fill = value != 0.0; ls->dag_tasks.release(); return 0; }   // zero-fill of the spare buffer as tasks of the bulk queue
+    if (!strcmp(key, "dag_fill")) { ls->dag_fill = value != 0.0; ls->plan.invalidate(); return 0; }   // zero-fill of the spare buffer as tasks of the bulk queue
     // per-XCD queues of the bulk kernel (dag.hip: dag_deal_tasks); the task list is dealt again
-    if (!strcmp(key, "dag_xcd_queues")) { ls->dag_xcd_queues = value != 0.0; ls->dag_tasks.release(); return 0; }   // 0: one queue, popped by every workgroup
+    if (!strcmp(key, "dag_xcd_queues")) { ls->dag_xcd_queues = value != 0.0; ls->plan.invalidate(); return 0; }   // 0: one queue, popped by every workgroup
     if (!strcmp(key, "dag_gang")) {   // tasks of one group that go to one queue together; negative: every task to queue 0 (tests of the steal path)
         MNK_REQUIRE(value <= 64.0 && value != 0.0 && (double)(int)value == value, "dag_gang must be an integer in 1..64 (or negative)");
         ls->dag_gang = (int)value;
-        ls->dag_tasks.release();
+        ls->plan.invalidate();
         return 0;
     }
     if (!strcmp(key, "dag_trace")) { ls->dag_trace_on = value != 0.0; return 0; }  // diagnostics: tools/dag_timeline.py
     if (!strcmp(key, "dag_max_rows")) { ls->dag_max_rows = (int64_t)value; return 0; }
-    if (!strcmp(key, "dag_deep_rows")) { ls->dag_deep_rows = (int64_t)value; ls->dag_tasks.release(); return 0; }   // largest order with every row in the chain's band
+    if (!strcmp(key, "dag_deep_rows")) { ls->dag_deep_rows = (int64_t)value; ls->plan.invalidate(); return 0; }   // largest order with every row in the chain's band
     // BUNCHKAUFMAN only: 1 (default) = refactor with the pivoted Bunch-Kaufman tier when the static-pivot
     // factorization breaks down; 0 = report the breakdown as num_zero and let the IPM regularize
     if (!strcmp(key, "bk_fallback")) { ls->bk_fallback = (int)value; return 0; }
@@ -865,36 +863,30 @@ static unsigned long long* amax_word(mnk_ls* ls) {
     return ls->amax_dev.p;
 }
 
-static int prepare_fill(mnk_ls* ls) {
+}  // extern "C"
+// ---- SpareFill (ls.h): the only code that touches the spare factor buffer, its events and its state ----
+int SpareFill::acquire(mnk_ls* ls) {
     mnk_ctx* ctx = ls->ctx;
     hipStream_t s = ctx->stream;
-    dim3 grid((unsigned)ls->Np, (unsigned)((ls->Np / 2 + 255) / 256));
-    bool pre = ls->prefill && ls->Np <= mnk_ls::PREFILL_MAX_ROWS;
-    if (pre && !ls->fact_spare.p) {
+    bool pre = wanted(ls->Np);
+    if (pre && !buf.p) {
         // second factor buffer, events, side stream; if any of it cannot be had the fill stays in line
-        if (ls->fact_spare.alloc(ls->fact.n) != 0) { (void)hipGetLastError(); ls->prefill = 0; pre = false; }
-        if (pre && !ctx->s_fill && hipStreamCreateWithFlags(&ctx->s_fill, hipStreamNonBlocking) != hipSuccess) { ls->prefill = 0; pre = false; }
-        if (pre && (hipEventCreateWithFlags(&ls->ev_spare, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&ls->ev_free, hipEventDisableTiming) != hipSuccess)) { ls->prefill = 0; pre = false; }
-        if (pre) MNK_HIP(hipMemsetAsync(ls->fact_spare.p, 0, ls->fact_spare.n * sizeof(double), s));  // (slack behind the matrix)
+        if (buf.alloc(ls->fact.n) != 0) { (void)hipGetLastError(); prefill = 0; pre = false; }
+        if (pre && !ctx->s_fill && hipStreamCreateWithFlags(&ctx->s_fill, hipStreamNonBlocking) != hipSuccess) { prefill = 0; pre = false; }
+        if (pre && (hipEventCreateWithFlags(&ev_zeroed, hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&ev_free, hipEventDisableTiming) != hipSuccess)) { prefill = 0; pre = false; }
+        if (pre) MNK_HIP(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), s));  // (slack behind the matrix)
     }
-    if (pre && ls->spare_zeroed && ls->spare_by_dag && !ls->info_valid) {
-        // The zero-fill was left to the task queue of the previous factorization, and nobody has looked at its `info` yet: a
-        // factorization that fails (a time-out, a Cholesky breakdown) drops the rest of its queue, fill tasks included.
-        ls->spare_zeroed = false;
-        ls->spare_by_dag = false;
-    }
-    if (pre && ls->spare_zeroed) {
-        std::swap(ls->fact.p, ls->fact_spare.p);          // the buffer zeroed in the background becomes the factor buffer
-        MNK_HIP(hipStreamWaitEvent(s, ls->ev_spare, 0));
-        // the other buffer now holds the previous factor: it counts as zeroed again only after a COMPLETED
-        // mnk_ls_prefill_spare() (a second transfer for the same factorize! -- the pivoted tier, a redo after a time-out --
-        // would otherwise swap the old factor back in and scatter the sparse entries over it)
-        ls->spare_zeroed = false;
+    // (the fill was left to the task queue of the previous factorization, and nobody has looked at its `info` yet)
+    if (pre && state == State::ZeroedByDag && !ls->info_valid) state = State::Dirty;
+    if (pre && zeroed()) {
+        std::swap(ls->fact.p, buf.p);          // the buffer zeroed in the background becomes the factor buffer
+        MNK_HIP(hipStreamWaitEvent(s, ev_zeroed, 0));
     } else {
-        hipLaunchKernelGGL(fill_lower_kernel, grid, dim3(256), 0, s, ls->fact.p, ls->ld, ls->N, ls->Np);
+        hipLaunchKernelGGL(fill_lower_kernel, dim3((unsigned)ls->Np, (unsigned)((ls->Np / 2 + 255) / 256)), dim3(256), 0, s, ls->fact.p, ls->ld, ls->N, ls->Np);
     }
-    ls->spare_pending = pre;   // mnk_ls_prefill_spare() zeroes the other buffer once this factorization is queued
+    if (pre) state = State::Pending;           // (after a swap the other buffer holds the previous factor)
+    else if (!zeroed()) state = State::Dirty;
     MNK_HIP(hipGetLastError());
     return 0;
 }
@@ -902,37 +894,47 @@ static int prepare_fill(mnk_ls* ls) {
 // The other factor buffer (the previous factor, or fresh memory) is free once everything queued so far has run: from then
 // on it is zeroed on the side stream, behind the factorization that was just queued (whose persistent kernels want the
 // whole chip from their first microsecond) and concurrently with the inertia fetch and the solves that follow.
-}  // extern "C"
-int mnk_ls_prefill_spare(mnk_ls* ls) {
-    if (!ls->spare_pending) return 0;
-    ls->spare_pending = false;
-    if (ls->dag_filled) {   // the bulk queue of the factorization that was just queued zeroes the spare buffer (DAG_FILL tasks): stream order does the rest
-        ls->dag_filled = false;
-        MNK_HIP(hipEventRecord(ls->ev_spare, ls->ctx->stream));
-        ls->spare_zeroed = true;
-        ls->spare_by_dag = true;
+int SpareFill::queued(mnk_ls* ls) {
+    if (!pending()) return 0;
+    const bool by_dag = state == State::PendingDagFills;
+    state = State::Dirty;   // (until the fill is queued)
+    mnk_ctx* ctx = ls->ctx;
+    if (by_dag) {   // the bulk queue of the factorization that was just queued zeroes the buffer (DAG_FILL tasks): stream order does the rest
+        MNK_HIP(hipEventRecord(ev_zeroed, ctx->stream));
+        state = State::ZeroedByDag;
         return 0;
     }
-    ls->spare_by_dag = false;
-    mnk_ctx* ctx = ls->ctx;
-    dim3 grid((unsigned)ls->Np, (unsigned)((ls->Np / 2 + 255) / 256));
-    MNK_HIP(hipEventRecord(ls->ev_free, ctx->stream));
-    MNK_HIP(hipStreamWaitEvent(ctx->s_fill, ls->ev_free, 0));
-    hipLaunchKernelGGL(fill_lower_kernel, grid, dim3(256), 0, ctx->s_fill, ls->fact_spare.p, ls->ld, ls->N, ls->Np);
+    MNK_HIP(hipEventRecord(ev_free, ctx->stream));
+    MNK_HIP(hipStreamWaitEvent(ctx->s_fill, ev_free, 0));
+    hipLaunchKernelGGL(fill_lower_kernel, dim3((unsigned)ls->Np, (unsigned)((ls->Np / 2 + 255) / 256)), dim3(256), 0, ctx->s_fill, buf.p, ls->ld, ls->N, ls->Np);
     MNK_HIP(hipGetLastError());
-    MNK_HIP(hipEventRecord(ls->ev_spare, ctx->s_fill));
-    ls->spare_zeroed = true;
+    MNK_HIP(hipEventRecord(ev_zeroed, ctx->s_fill));
+    state = State::ZeroedBySide;
     return 0;
+}
+
+bool SpareFill::give_up() {
+    if (!buf.p || zeroed()) return false;   // (zeroed: a fill of the buffer has been queued and the next transfer will swap it in)
+    buf.release();
+    prefill = 0;
+    state = State::Dirty;
+    return true;
+}
+
+void SpareFill::destroy(mnk_ctx* ctx) {
+    if (ctx->s_fill) (void)mnk::stream_wait(ctx->s_fill);   // a background fill of this solver's buffer
+    if (ev_zeroed) (void)hipEventDestroy(ev_zeroed);
+    if (ev_free) (void)hipEventDestroy(ev_free);
 }
 extern "C" {
 
-// The envelope of a sparse source for the factorization that follows (mnk_ls::env_dev; nullptr: none), and the word its
+// The envelope of a sparse source for the factorization that follows (MatrixSource::env_dev; nullptr: none), and the word its
 // transfer marks when it meets a NaN / Inf entry.  `env_host`: the envelope of the source's order, truncated to this solver's
 // tiles (a leading principal block of the source has the leading part of its envelope).
 static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<int32_t>& env_host, const int32_t* envh_dev,
                          const std::vector<int32_t>& envh_host) {
-    ls->env_dev = nullptr;
-    ls->envh_dev = nullptr;
+    ls->src.env_dev = nullptr;
+    ls->src.envh_dev = nullptr;
     if (!ls->envelope || env_dev == nullptr || ls->alt) return nullptr;
     if (!ls->env_word.p) {
         if (ls->env_word.alloc(2) || hipMemsetAsync(ls->env_word.p, 0, 2 * sizeof(int), ls->ctx->stream) != hipSuccess) {
@@ -943,20 +945,36 @@ static int* set_envelope(mnk_ls* ls, const int32_t* env_dev, const std::vector<i
     }
     // (a transfer whose mark no task-DAG factorization consumed -- another schedule ran, or the pivoted tier transferred the
     // matrix again -- must not close the envelope of this one)
-    if (ls->env_armed && hipMemsetAsync(ls->env_word.p, 0, sizeof(int), ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    ls->env_armed = true;
-    ls->env_dev = env_dev;
-    ls->env_host.assign(env_host.begin(), env_host.begin() + std::min<size_t>(env_host.size(), (size_t)(ls->Np / 128)));
+    if (ls->src.env_armed && hipMemsetAsync(ls->env_word.p, 0, sizeof(int), ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    ls->src.env_armed = true;
+    ls->src.env_dev = env_dev;
+    ls->src.env_host.assign(env_host.begin(), env_host.begin() + std::min<size_t>(env_host.size(), (size_t)(ls->Np / 128)));
     // the half-tile envelope rides on the tile envelope: the same source, the same gate
     if (ls->envelope_half && envh_dev != nullptr && envh_host.size() == 2 * env_host.size()) {
-        ls->envh_dev = envh_dev;
-        ls->envh_host.assign(envh_host.begin(), envh_host.begin() + 2 * ls->env_host.size());
+        ls->src.envh_dev = envh_dev;
+        ls->src.envh_host.assign(envh_host.begin(), envh_host.begin() + 2 * ls->src.env_host.size());
     }
     return ls->env_word.p;
 }
 
+// The way back to a matrix that lives in a KKT handle: the handle's buffers may be reallocated and the handle may be destroyed
+// before the inertia of an asynchronous call is fetched, so the transfer goes through the handle and refuses once it is gone.
+static std::function<int()> handle_retransfer(std::weak_ptr<int> alive, std::function<int()> transfer) {
+    return [alive, transfer]() {
+        if (alive.expired()) {
+            set_error("factorize!: the KKT handle of the last factorize! call was destroyed before its inertia was fetched; the "
+                      "matrix cannot be transferred again for the fall-back tier");
+            return -5;
+        }
+        return transfer();
+    };
+}
+
+// A source that is only guaranteed for the duration of the call (the caller's arrays, staging buffers): no way back behind it.
+struct SourceEndsWithCall { mnk_ls* ls; ~SourceEndsWithCall() { ls->src.retransfer = nullptr; } };
+
 static int transfer_sc(mnk_ls* ls, mnk_sc* sc) {
-    int rc = prepare_fill(ls);
+    int rc = ls->spare.acquire(ls);
     if (rc) return rc;
     const int64_t nnz = sc->nnz_aug;
     int* nonfinite = set_envelope(ls, sc->d_tile_env.p, sc->tile_env, sc->d_tile_envh.p, sc->tile_envh);
@@ -1001,7 +1019,7 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
     if (c->dag_xcd_queues != ls->dag_xcd_queues || c->dag_gang != ls->dag_gang) {
         c->dag_xcd_queues = ls->dag_xcd_queues;
         c->dag_gang = ls->dag_gang;
-        c->dag_tasks.release();
+        c->plan.invalidate();
     }
     int rc = mnk_ls_factorize_sc_async(c, sc);
     if (!rc) rc = mnk_ls_fetch_info(c);
@@ -1044,21 +1062,14 @@ int mnk_ls_factorize_sc_async(mnk_ls* ls, mnk_sc* sc) {
     }
     // (the KKT handle keeps aug_com until the next build_kkt!, so the pivoted tier can fetch the matrix again when
     // the inertia is asked for)
-    ls->src_persistent = true;   // (the handle keeps aug_com until the next build_kkt!)
-    ls->retransfer = [ls, sc, w = std::weak_ptr<int>(sc->alive)]() {
-        if (w.expired()) {
-            set_error("factorize!: the KKT handle of the last factorize! call was destroyed before its inertia was fetched; the "
-                      "matrix cannot be transferred again for the fall-back tier");
-            return -5;
-        }
-        return transfer_sc(ls, sc);
-    };
+    ls->src.persistent = true;
+    ls->src.retransfer = handle_retransfer(sc->alive, [ls, sc]() { return transfer_sc(ls, sc); });
     if (probe_rejected) return 0;   // (the verdict is in; ensure_complete_factor knows the way back to the matrix)
     return mnk_ls_run_factorization(ls);
 }
 
 static int transfer_dense(mnk_ls* ls, const double* Adev, int64_t lda) {
-    ls->env_dev = nullptr;   // (no envelope: the dense order)
+    ls->src.env_dev = nullptr;   // (no envelope: the dense order)
     dim3 grid((unsigned)ls->Np, (unsigned)((ls->Np + 1023) / 1024));
     hipLaunchKernelGGL(copy_lower_kernel, grid, dim3(256), 0, ls->ctx->stream, ls->fact.p, ls->ld, Adev, lda,
                        ls->N, ls->Np, amax_word(ls));
@@ -1071,8 +1082,8 @@ static int factorize_dense_dev(mnk_ls* ls, const double* Adev, int64_t lda, bool
     if (rc) return rc;
     rc = transfer_dense(ls, Adev, lda);
     if (rc) return rc;
-    ls->src_persistent = src_persistent;   // (early rejection needs a source that outlives the call: ensure_complete_factor)
-    ls->retransfer = [ls, Adev, lda]() { return transfer_dense(ls, Adev, lda); };  // (callers clear it when Adev's life ends)
+    ls->src.persistent = src_persistent;   // (early rejection needs a source that outlives the call: ensure_complete_factor)
+    ls->src.retransfer = [ls, Adev, lda]() { return transfer_dense(ls, Adev, lda); };  // (SourceEndsWithCall where Adev's life ends with the call)
     return mnk_ls_run_factorization(ls);
 }
 
@@ -1093,16 +1104,8 @@ int mnk_ls_factorize_dc_async(mnk_ls* ls, mnk_dc* dc) {
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }   // (a factorize! of this solver pending in an open batch runs first)
     int rc = factorize_dense_dev(ls, dc->aug.p, round_up(dc->order, PAD), true);
-    // the way back goes through the handle (its buffer may be reallocated, the handle may be destroyed before the inertia
-    // of this asynchronous call is fetched)
-    ls->retransfer = [ls, dc, w = std::weak_ptr<int>(dc->alive)]() {
-        if (w.expired()) {
-            set_error("factorize!: the KKT handle of the last factorize! call was destroyed before its inertia was fetched; the "
-                      "matrix cannot be transferred again for the fall-back tier");
-            return -5;
-        }
-        return transfer_dense(ls, dc->aug.p, round_up(dc->order, PAD));
-    };
+    // (behind the run, as ever: until here the way back was factorize_dense_dev's, through the buffer's address)
+    ls->src.retransfer = handle_retransfer(dc->alive, [ls, dc]() { return transfer_dense(ls, dc->aug.p, round_up(dc->order, PAD)); });
     return rc;
 }
 
@@ -1128,24 +1131,19 @@ int mnk_ls_factorize_dense(mnk_ls* ls, const double* A, int64_t lda, int loc, in
     MNK_REQUIRE(lda >= ls->N, "mnk_ls_factorize_dense: lda < N");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }   // (a factorize! of this solver pending in an open batch runs first)
-    int rc;
-    if (loc == MNK_DEVICE) {
-        rc = factorize_dense_dev(ls, A, lda);
-    } else {
-        DevBuf<double> tmp;
-        rc = tmp.alloc((size_t)ls->N * ls->N);
-        if (rc) return rc;
+    DevBuf<double> tmp;   // staging of a host matrix
+    if (loc != MNK_DEVICE) {
+        int rc_t = tmp.alloc((size_t)ls->N * ls->N);
+        if (rc_t) return rc_t;
         MNK_HIP(mnk::h2d_copy_2d(tmp.p, ls->N * sizeof(double), A, lda * sizeof(double), ls->N * sizeof(double), ls->N,
                                  ls->ctx->stream));
-        rc = factorize_dense_dev(ls, tmp.p, ls->N);
-        MNK_HIP(mnk::stream_wait(ls->ctx->stream));
-        if (!rc) rc = finish_info(ls, info);  // (a breakdown is handled while the staging buffer is alive)
-        ls->retransfer = nullptr;
-        return rc;
+        A = tmp.p;
+        lda = ls->N;
     }
-    rc = rc ? rc : finish_info(ls, info);
-    ls->retransfer = nullptr;  // the caller's device buffer is only guaranteed for the duration of the call
-    return rc;
+    SourceEndsWithCall ends{ls};   // (a breakdown is handled below, while the caller's buffer / the staging buffer is alive)
+    const int rc = factorize_dense_dev(ls, A, lda);
+    if (loc != MNK_DEVICE) MNK_HIP(mnk::stream_wait(ls->ctx->stream));
+    return rc ? rc : finish_info(ls, info);
 }
 
 int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowval, const double* nzval,
@@ -1169,15 +1167,15 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
     rc |= dcol.upload(col, ls->ctx->stream);
     rc |= dnz.upload(nzv, ls->ctx->stream);
     // the envelope of this pattern (only the task-DAG schedule reads it)
-    const std::vector<int32_t> env = ls->envelope ? mnk_tile_envelope(N, row.data(), col.data(), nnz) : std::vector<int32_t>();
-    const std::vector<int32_t> envh = ls->envelope && ls->envelope_half ? mnk_tile_envelope_half(N, row.data(), col.data(), nnz) : std::vector<int32_t>();
+    const std::vector<int32_t> env = ls->envelope ? mnk_tile_envelope(N, row.data(), col.data(), nnz, 128) : std::vector<int32_t>();
+    const std::vector<int32_t> envh = ls->envelope && ls->envelope_half ? mnk_tile_envelope(N, row.data(), col.data(), nnz, 64) : std::vector<int32_t>();
     if (ls->envelope) rc |= ls->env_own.upload(env, ls->ctx->stream);
     if (!envh.empty()) rc |= ls->envh_own.upload(envh, ls->ctx->stream);
     if (rc) return -2;
     rc = ensure_wbuf(ls);
     if (rc) return rc;
     auto transfer = [ls, nnz, &drow, &dcol, &dnz, &env, &envh]() -> int {
-        int r = prepare_fill(ls);
+        int r = ls->spare.acquire(ls);
         if (r) return r;
         int* nonfinite = set_envelope(ls, env.empty() ? nullptr : ls->env_own.p, env, envh.empty() ? nullptr : ls->envh_own.p, envh);
         if (nnz > 0)
@@ -1188,39 +1186,33 @@ int mnk_ls_factorize_csc(mnk_ls* ls, const int32_t* colptr, const int32_t* rowva
     };
     rc = transfer();
     if (rc) return rc;
-    ls->src_persistent = false;
-    ls->retransfer = transfer;
+    SourceEndsWithCall ends{ls};   // (the staging buffers die with this call)
+    ls->src.persistent = false;
+    ls->src.retransfer = transfer;
     rc = mnk_ls_run_factorization(ls);
-    if (!rc) {
-        MNK_HIP(mnk::stream_wait(ls->ctx->stream));
-        rc = finish_info(ls, info);
-    }
-    ls->retransfer = nullptr;  // the staging buffers die with this call
-    return rc;
+    if (rc) return rc;
+    MNK_HIP(mnk::stream_wait(ls->ctx->stream));
+    return finish_info(ls, info);
 }
 
-int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap) {
+static int debug_envelope_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap, int64_t block) {
     if (n <= 0 || colptr == nullptr || rowval == nullptr || cap < 0) return -1;
     const int64_t nnz = colptr[n] - index_base;
     std::vector<int32_t> row(nnz), col(nnz);
     for (int64_t c = 0; c < n; ++c)
         for (int64_t k = colptr[c] - index_base; k < colptr[c + 1] - index_base; ++k) { row[k] = rowval[k] - index_base; col[k] = (int32_t)c; }
-    const std::vector<int32_t> env = mnk_tile_envelope(n, row.data(), col.data(), nnz);
+    const std::vector<int32_t> env = mnk_tile_envelope(n, row.data(), col.data(), nnz, block);
     if (out != nullptr)
         for (int I = 0; I < std::min((int)env.size(), cap); ++I) out[I] = env[I];
     return (int)env.size();
 }
 
+int mnk_debug_tile_env_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap) {
+    return debug_envelope_csc(n, colptr, rowval, index_base, out, cap, 128);
+}
+
 int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* rowval, int index_base, int32_t* out, int cap) {
-    if (n <= 0 || colptr == nullptr || rowval == nullptr || cap < 0) return -1;
-    const int64_t nnz = colptr[n] - index_base;
-    std::vector<int32_t> row(nnz), col(nnz);
-    for (int64_t c = 0; c < n; ++c)
-        for (int64_t k = colptr[c] - index_base; k < colptr[c + 1] - index_base; ++k) { row[k] = rowval[k] - index_base; col[k] = (int32_t)c; }
-    const std::vector<int32_t> envh = mnk_tile_envelope_half(n, row.data(), col.data(), nnz);
-    if (out != nullptr)
-        for (int h = 0; h < std::min((int)envh.size(), cap); ++h) out[h] = envh[h];
-    return (int)envh.size();
+    return debug_envelope_csc(n, colptr, rowval, index_base, out, cap, 64);
 }
 
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
@@ -1260,14 +1252,14 @@ static int ensure_complete_factor(mnk_ls* ls, const char* who) {
     if (ls->reject_on_device == 1) { int rc_i = mnk_ls_fetch_info(ls); if (rc_i) return rc_i; }   // (known when the pivots are)
     if (!ls->factor_invalid) return 0;
     { static const bool peek = getenv("MNK_DBG_NO_REDO") != nullptr; if (peek) return 0; }   // (diagnostics: look at what a rejected factorization left)
-    if (!ls->retransfer) {
+    if (!ls->src.retransfer) {
         set_error("%s: the last factorization was stopped at its first non-positive pivot (early_reject) and its source is gone: "
                   "there is no factor", who);
         return -1;
     }
     const int keep = ls->early_reject;
     ls->early_reject = 0;
-    int rc = ls->retransfer();
+    int rc = ls->src.retransfer();
     if (!rc) rc = mnk_ls_run_factorization(ls);
     if (!rc) rc = mnk_ls_fetch_info(ls);
     ls->early_reject = keep;
@@ -1422,9 +1414,9 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
         return 0;
     }
     if (!strcmp(key, "panel_algo")) { *value = ls->algo_now; return 0; }
-    if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp_fallbacks; return 0; }
+    if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp.fallbacks; return 0; }
     // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
-    if (!strcmp(key, "timeout_site")) { *value = ls->last_timeout_site; return 0; }
+    if (!strcmp(key, "timeout_site")) { *value = ls->pp.last_site; return 0; }
     if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe_hits; return 0; }       // matrices rejected by the leading-block probe alone
     if (!strcmp(key, "probe_misses")) { *value = (double)ls->probe_misses; return 0; }   // probes that passed (the full factorization followed)
     if (!strcmp(key, "early_rejects")) { *value = (double)ls->early_rejects; return 0; }       // factorizations stopped at their first non-positive pivot
@@ -1439,15 +1431,15 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk_multi_last ? 1.0 : 0.0; return 0; }
     if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk_mw_fallbacks; return 0; }
     if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain
-    if (!strcmp(key, "dag_ntasks")) { *value = ls->dag_ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
-    if (!strcmp(key, "dag_ntasks1")) { *value = ls->dag_ntasks1; return 0; }  // ... of them in the first phase, ...
-    if (!strcmp(key, "dag_js2")) { *value = ls->dag_js2; return 0; }          // ... first strip-column of the second phase
-    if (!strcmp(key, "dag_nq")) { *value = std::max(ls->dag_nq[0], ls->dag_nq[1]); return 0; }   // ... queues the device list is dealt into (0: one)
+    if (!strcmp(key, "dag_ntasks")) { *value = ls->plan.ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
+    if (!strcmp(key, "dag_ntasks1")) { *value = ls->plan.ntasks1; return 0; }  // ... of them in the first phase, ...
+    if (!strcmp(key, "dag_js2")) { *value = ls->plan.key.js2; return 0; }          // ... first strip-column of the second phase
+    if (!strcmp(key, "dag_nq")) { *value = std::max(ls->plan.nq[0], ls->plan.nq[1]); return 0; }   // ... queues the device list is dealt into (0: one)
     if (!strcmp(key, "dag_steals")) {   // ... tasks the last factorization's workgroups took from another XCD's queue
         int st[2] = {0, 0};
-        if (ls->dag_qheads.p != nullptr)
+        if (ls->plan.qheads.p != nullptr)
             for (int ph = 0; ph < 2; ++ph)
-                MNK_HIP(mnk::d2h_copy(&st[ph], ls->dag_qheads.p + ph * mnk::DAG_QHEAD_WORDS + mnk::DAG_NQ * mnk::DAG_QHEAD_STRIDE, sizeof(int), ls->ctx->stream));
+                MNK_HIP(mnk::d2h_copy(&st[ph], ls->plan.qheads.p + ph * mnk::DAG_QHEAD_WORDS + mnk::DAG_NQ * mnk::DAG_QHEAD_STRIDE, sizeof(int), ls->ctx->stream));
         *value = (double)st[0] + (double)st[1];
         return 0;
     }
@@ -1458,14 +1450,14 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
         int64_t total = 0, skipped = 0;
         int gate = 1;
         if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
-        const std::vector<int>& h = ls->dag_host_tasks;
-        const int ne = (int)ls->env_host.size();
+        const std::vector<int>& h = ls->plan.host_tasks;
+        const int ne = (int)ls->src.env_host.size();
         for (size_t t = 0; t + 3 < h.size(); t += 4) {
             const int flags = h[t] & 255, I = h[t + 1] & 0xffff, J = h[t + 2], kb = h[t + 3] & 0xffff, ke = h[t + 3] >> 16;
             if (flags & 8) continue;   // (DAG_FILL)
             total += ke - kb;
             if (!ls->env_used || gate != 0 || I >= ne || J >= ne) continue;
-            const int e = std::max(ls->env_host[I], ls->env_host[J]);
+            const int e = std::max(ls->src.env_host[I], ls->src.env_host[J]);
             skipped += std::min(ke, std::max(kb, e)) - kb;
         }
         *value = (double)(!strcmp(key, "env_ksteps") ? total : skipped);
@@ -1479,8 +1471,8 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
         if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
         const bool on = ls->env_used && gate == 0;
         int64_t cnt[2] = {0, 0};
-        mnk::dag_envh_count(ls->dag_host_tasks, on ? ls->env_host.data() : nullptr, on && ls->envh_used ? ls->envh_host.data() : nullptr,
-                            (int)ls->env_host.size(), cnt);
+        mnk::dag_envh_count(ls->plan.host_tasks, on ? ls->src.env_host.data() : nullptr, on && ls->envh_used ? ls->src.envh_host.data() : nullptr,
+                            (int)ls->src.env_host.size(), cnt);
         *value = (double)(!strcmp(key, "envh_ksteps") ? cnt[0] : cnt[1]);
         return 0;
     }

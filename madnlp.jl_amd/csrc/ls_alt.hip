@@ -14,7 +14,7 @@ std::unique_ptr<mnk_ls_alt> mnk_ls_alt_new(int algo) {
 
 // factorize! (not merged into a factorization batch: runs when called; EVD also runs to its end before it returns)
 int mnk_ls_alt_factorize(mnk_ls* ls) {
-    ++ls->fact_count;
+    ++ls->pp.count;
     ls->factor_invalid = false;
     ls->bk_active = false;
     ls->t_fact_launch_ms = mnk_host_ms();

@@ -271,8 +271,8 @@ int mnk_sc_create(mnk_ctx* ctx, int64_t n, int64_t m, int64_t nnzj, const int32_
     for (int64_t c = 0; c < n; ++c) sc->aug_colptr[c + 1] += sc->aug_colptr[c];
     sc->nnz_aug = slot + 1;
     sc->len_jptr = L;
-    sc->tile_env = mnk_tile_envelope(n, a_row.data(), a_col.data(), sc->nnz_aug);
-    sc->tile_envh = mnk_tile_envelope_half(n, a_row.data(), a_col.data(), sc->nnz_aug);
+    sc->tile_env = mnk_tile_envelope(n, a_row.data(), a_col.data(), sc->nnz_aug, 128);
+    sc->tile_envh = mnk_tile_envelope(n, a_row.data(), a_col.data(), sc->nnz_aug, 64);
 
     if (!ctx) { *out = sc; return 0; }
     // ---- upload ----
