@@ -704,6 +704,10 @@ int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* row
  * tiles: half-tile k-steps (a 64 x 64 quadrant of a tile over 64 columns) that the tile envelope `env` leaves of the bulk tasks /
  * of them skipped with the half-tile envelope `envh` (NULL: none).  Returns the number of tasks. */
 int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int taper0, const int* env, const int* envh, int64_t* count);
+/* The schedule of the leading-block probe (option "probe") for a solver of order N over `n` verdicts (host only, no device is
+ * opened): cols[i] is the column at which verdict i was rejected early, or -1 for an acceptance; orders[i] receives the order of the
+ * leading block through which the matrix of verdict i would be probed first (0: no probe), i.e. before verdict i is noted. */
+int mnk_debug_probe_schedule(int64_t N, int n, const int64_t* cols, int64_t* orders);
 
 #ifdef __cplusplus
 }

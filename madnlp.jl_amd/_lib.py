@@ -252,6 +252,7 @@ SIGNATURES = {
     "mnk_sc_debug_tile_envh": (C.c_int, [_vp, C.c_int64, _vp, C.c_int]),
     "mnk_debug_tile_envh_csc": (C.c_int, [C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int]),
     "mnk_debug_envh_ksteps": (C.c_int, [C.c_int] * 5 + [_vp, _vp, _vp]),
+    "mnk_debug_probe_schedule": (C.c_int, [C.c_int64, C.c_int, _vp, _vp]),
     "mnk_factorize_batch_begin": (C.c_int, []),
     "mnk_factorize_batch_end": (C.c_int, []),
     "mnk_solve_batch_begin": (C.c_int, []),

@@ -838,37 +838,37 @@ using namespace mnk;
 
 // Factor the matrix currently in ls->fact (lower triangle, padded with a unit diagonal) by Bunch-Kaufman.
 // `multi`: panels by bkp_panel_mw_kernel (all its workgroups resident: the whole factorization holds the device
-// arbiter's turn) wherever a workgroup per 256 rows fits the device; mnk_ls_bk_failed tells afterwards whether one of
-// its bounded waits expired (the caller then transfers the matrix again and comes back with multi = false).
-static int run_bunchkaufman(mnk_ls* ls, bool multi) {
+// arbiter's turn) wherever a workgroup per 256 rows fits the device; run() looks afterwards whether one of its bounded waits
+// expired (it then transfers the matrix again and comes back with multi = false).
+int BkTier::factor(mnk_ls* ls, bool multi) {
     hipStream_t s = ls->ctx->stream;
     const int Np = (int)ls->Np;
     const int64_t ld = ls->ld;
     double* F = ls->fact.p;
     int rc = 0;
-    if (!ls->bk_perm.p) {
-        rc |= ls->bk_perm.alloc(Np);
-        rc |= ls->bk_ptype.alloc(Np);
-        rc |= ls->bk_doff.alloc(Np);
-        rc |= ls->bk_dcoup.alloc(Np);
-        rc |= ls->bk_state.alloc(sizeof(BkState));
-        rc |= ls->bk_work.alloc((size_t)2 * Np * BK_NBW + SLACK);
+    if (!perm.p) {
+        rc |= perm.alloc(Np);
+        rc |= ptype.alloc(Np);
+        rc |= doff.alloc(Np);
+        rc |= dcoup.alloc(Np);
+        rc |= state.alloc(sizeof(BkState));
+        rc |= work.alloc((size_t)2 * Np * BK_NBW + SLACK);
         if (rc) return -2;
     }
-    if (multi && !ls->bk_wv.p) {
-        rc |= ls->bk_wv.alloc((size_t)Np * BK_NB + SLACK);
-        rc |= ls->bk_tmp.alloc((size_t)192 * Np + SLACK);
-        rc |= ls->bk_msg.alloc((size_t)BKM_RING * BKM_GMAX * BKM_F * 2);
-        rc |= ls->bk_aux.alloc((size_t)Np + 192 + 128 + 64);
+    if (multi && !wv.p) {
+        rc |= wv.alloc((size_t)Np * BK_NB + SLACK);
+        rc |= tmp.alloc((size_t)192 * Np + SLACK);
+        rc |= msg.alloc((size_t)BKM_RING * BKM_GMAX * BKM_F * 2);
+        rc |= aux.alloc((size_t)Np + 192 + 128 + 64);
         if (rc) {   // (not enough memory for the staging buffers: the one-workgroup panel needs none)
             (void)hipGetLastError();
-            ls->bk_wv.release(); ls->bk_tmp.release(); ls->bk_msg.release(); ls->bk_aux.release();
+            wv.release(); tmp.release(); msg.release(); aux.release();
             multi = false;
             rc = 0;
         }
     }
-    BkState* st = reinterpret_cast<BkState*>(ls->bk_state.p);
-    double* W = ls->bk_work.p;
+    BkState* st = reinterpret_cast<BkState*>(state.p);
+    double* W = work.p;
     double* LW = W + (size_t)Np * BK_NBW;
     const size_t smem = 2 * 8 * ((128 + 16) + (128 + 16)) * sizeof(double);
     const size_t smem_mw = (size_t)(64 * BKM_ROWS + 4 * 64 + 64 + BKM_GMAX * BKM_F + 8 + 4) * sizeof(double) + (8 + 68 + 4) * sizeof(int) + sizeof(BkmCtl) + 64;
@@ -883,19 +883,19 @@ static int run_bunchkaufman(mnk_ls* ls, bool multi) {
         }
     }
     int gcap = std::min(BKM_GMAX, ls->ctx->num_cu);
-    if (ls->bk_max_wgs > 0) gcap = std::min(gcap, ls->bk_max_wgs);
+    if (bk_max_wgs > 0) gcap = std::min(gcap, bk_max_wgs);
     if (multi) {
         rc = mnk_persist_begin(ls->ctx, s);
         if (rc) return rc;
-        (void)hipMemsetAsync(ls->bk_msg.p, 0, ls->bk_msg.n * sizeof(unsigned long long), s);
+        (void)hipMemsetAsync(msg.p, 0, msg.n * sizeof(unsigned long long), s);
     }
     auto body = [&]() -> int {
         MNK_HIP(hipMemsetAsync(ls->info_dev.p, 0, sizeof(int), s));
-        hipLaunchKernelGGL(bkp_init_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, st, ls->bk_perm.p, Np);
+        hipLaunchKernelGGL(bkp_init_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, st, perm.p, Np);
         // a panel takes 63 or 64 columns: the p-th panel starts at column >= 63 p, so its update touches no tile row above
         // floor(63 (p + 1) / 128); one more (empty) round covers the case that every panel was 63 wide
         const int npanel = (Np + BK_NB - 2) / (BK_NB - 1) + 1;
-        int* rowof = ls->bk_aux.p;
+        int* rowof = aux.p;
         int* dlist = rowof ? rowof + Np : nullptr;
         int* perm_tmp = rowof ? dlist + 192 : nullptr;
         int* cnt = rowof ? perm_tmp + 128 : nullptr;   // two {nT, nS} pairs, used alternately
@@ -905,18 +905,18 @@ static int run_bunchkaufman(mnk_ls* ls, bool multi) {
             const int rows_max = Np - (BK_NB - 1) * p;   // (the panel starts at column >= 63 p)
             const int G = (rows_max + BKM_ROWS - 1) / BKM_ROWS;
             if (multi && G <= gcap) {
-                BkMw a{F, ld, Np, st, W, LW, (int64_t)Np, ls->bk_wv.p, ls->bk_msg.p, rowof, dlist, nullptr, nullptr, ls->dvec.p, ls->bk_doff.p,
-                       ls->bk_ptype.p, (unsigned)(1 + 130 * p), ls->bk_spin_limit, ls->debug_bk_missing};
+                BkMw a{F, ld, Np, st, W, LW, (int64_t)Np, wv.p, msg.p, rowof, dlist, nullptr, nullptr, ls->dvec.p, doff.p,
+                       ptype.p, (unsigned)(1 + 130 * p), bk_spin_limit, debug_bk_missing};
                 a.cnt = cnt + 2 * (p & 1);
                 a.cnt_next = cnt + 2 * ((p + 1) & 1);
                 hipLaunchKernelGGL(bkp_panel_mw_kernel, dim3(G), dim3(BKM_T), smem_mw, s, a);
-                hipLaunchKernelGGL(bkp_perm_gather_kernel, dim3(8, 192), dim3(256), 0, s, F, ld, Np, st, rowof, dlist, ls->bk_tmp.p,
-                                   ls->bk_perm.p, perm_tmp, a.cnt);
-                hipLaunchKernelGGL(bkp_perm_scatter_kernel, dim3(8, 256), dim3(256), 0, s, F, ld, Np, st, dlist, ls->bk_tmp.p,
-                                   ls->bk_perm.p, perm_tmp, LW, (int64_t)Np, ls->dvec.p, ls->bk_ptype.p, a.cnt);
+                hipLaunchKernelGGL(bkp_perm_gather_kernel, dim3(8, 192), dim3(256), 0, s, F, ld, Np, st, rowof, dlist, tmp.p,
+                                   perm.p, perm_tmp, a.cnt);
+                hipLaunchKernelGGL(bkp_perm_scatter_kernel, dim3(8, 256), dim3(256), 0, s, F, ld, Np, st, dlist, tmp.p,
+                                   perm.p, perm_tmp, LW, (int64_t)Np, ls->dvec.p, ptype.p, a.cnt);
             } else {
-                hipLaunchKernelGGL(bkp_panel_kernel, dim3(1), dim3(BK_T), 0, s, F, ld, Np, st, W, LW, (int64_t)Np, ls->dvec.p, ls->bk_doff.p,
-                                   ls->bk_ptype.p, ls->bk_perm.p);
+                hipLaunchKernelGGL(bkp_panel_kernel, dim3(1), dim3(BK_T), 0, s, F, ld, Np, st, W, LW, (int64_t)Np, ls->dvec.p, doff.p,
+                                   ptype.p, perm.p);
             }
             const int tile0 = (int)(((int64_t)(BK_NB - 1) * (p + 1)) / 128);
             const int nt = Np / 128 - tile0;
@@ -924,8 +924,8 @@ static int run_bunchkaufman(mnk_ls* ls, bool multi) {
                 hipLaunchKernelGGL(bkp_update_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), smem, s, F, ld, Np, st, W, LW,
                                    (int64_t)Np, tile0);
         }
-        hipLaunchKernelGGL(bk_finish_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, F, ld, Np, ls->dvec.p, ls->bk_doff.p,
-                           ls->bk_ptype.p, ls->dinv.p, ls->bk_dcoup.p, ls->dblk.p);
+        hipLaunchKernelGGL(bk_finish_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, F, ld, Np, ls->dvec.p, doff.p,
+                           ptype.p, ls->dinv.p, dcoup.p, ls->dblk.p);
         MNK_HIP(hipGetLastError());
         // LAPACK-style info -> the solver's info word
         MNK_HIP(hipMemcpyAsync(ls->info_dev.p, &st->info, sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -934,52 +934,65 @@ static int run_bunchkaufman(mnk_ls* ls, bool multi) {
     rc = body();
     if (multi) rc = mnk_persist_end(ls->ctx, s, rc);
     if (rc) return rc;
-    ls->bk_active = true;
-    ls->bk_multi_last = multi;
+    ls->verdict.pivoted();
+    ran_multi = multi;
     return 0;
 }
 
-int mnk_ls_run_bunchkaufman(mnk_ls* ls) {
-    const bool multi = ls->bk_panel_wgs != 1 && !ls->bk_mw_blocked;
-    int rc = run_bunchkaufman(ls, multi);
-    if (rc || !ls->bk_multi_last) return rc;
+int BkTier::run(mnk_ls* ls) {
+    const bool multi = bk_panel_wgs != 1 && !mw_blocked;
+    int rc = factor(ls, multi);
+    if (rc || !ran_multi) return rc;
     // the multi-workgroup panels wait for each other's messages with a bound: did one expire?  (This tier is entered from
     // mnk_ls_fetch_info, which waits for the stream anyway.)
     MNK_HIP(mnk::stream_wait(ls->ctx->stream));
     int fail = 0;
-    MNK_HIP(mnk::d2h_copy(&fail, &reinterpret_cast<BkState*>(ls->bk_state.p)->fail, sizeof(int), ls->ctx->stream));
+    MNK_HIP(mnk::d2h_copy(&fail, &reinterpret_cast<BkState*>(state.p)->fail, sizeof(int), ls->ctx->stream));
     if (fail == 0) return 0;
     // (another process' kernels on the CUs, as for the persistent schedules of factor.hip: redo with one workgroup per panel
     // and stay there)
-    ++ls->bk_mw_fallbacks;
-    ls->bk_mw_blocked = true;
+    ++n_mw_fallbacks;
+    mw_blocked = true;
     MNK_REQUIRE((bool)ls->src.retransfer, "Bunch-Kaufman tier: a panel hand-off timed out and the matrix cannot be transferred again");
     rc = ls->src.retransfer();
     if (rc) return rc;
-    return run_bunchkaufman(ls, false);
+    return factor(ls, false);
 }
 
-int mnk_ls_bk_permute(mnk_ls* ls, double* x, double* tmp, bool forward) {
+int BkTier::permute(mnk_ls* ls, double* x, double* xtmp, bool forward) {
     hipStream_t s = ls->ctx->stream;
     const int Np = (int)ls->Np;
-    if (forward) hipLaunchKernelGGL(bk_gather_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, tmp, x, ls->bk_perm.p, Np);
-    else hipLaunchKernelGGL(bk_scatter_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, tmp, x, ls->bk_perm.p, Np);
-    MNK_HIP(hipMemcpyAsync(x, tmp, (size_t)Np * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (forward) hipLaunchKernelGGL(bk_gather_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, xtmp, x, perm.p, Np);
+    else hipLaunchKernelGGL(bk_scatter_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, xtmp, x, perm.p, Np);
+    MNK_HIP(hipMemcpyAsync(x, xtmp, (size_t)Np * sizeof(double), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
-int mnk_ls_bk_dsolve(mnk_ls* ls, double* y) {
+int BkTier::dsolve(mnk_ls* ls, double* y) {
     const int Np = (int)ls->Np;
     hipLaunchKernelGGL(bk_dsolve_kernel, dim3((Np + 255) / 256), dim3(256), 0, ls->ctx->stream, y, ls->dinv.p,
-                       ls->bk_dcoup.p, ls->bk_ptype.p, Np);
+                       dcoup.p, ptype.p, Np);
     MNK_HIP(hipGetLastError());
     return 0;
 }
 
-int mnk_ls_bk_inertia(mnk_ls* ls, unsigned long long* out_dev) {
+int BkTier::inertia(mnk_ls* ls, unsigned long long* out_dev) {
     const int blocks = (int)std::min<int64_t>(256, (ls->N + 255) / 256);
-    hipLaunchKernelGGL(bk_inertia_kernel, dim3(blocks), dim3(256), 0, ls->ctx->stream, ls->dvec.p, ls->bk_doff.p,
-                       ls->bk_ptype.p, ls->N, out_dev);
+    hipLaunchKernelGGL(bk_inertia_kernel, dim3(blocks), dim3(256), 0, ls->ctx->stream, ls->dvec.p, doff.p,
+                       ptype.p, ls->N, out_dev);
     MNK_HIP(hipGetLastError());
     return 0;
 }
+
+int BkTier::read_pivots(mnk_ls* ls, int32_t* perm_host, double* doff_host) {
+    hipStream_t s = ls->ctx->stream;
+    if (perm_host) MNK_HIP(mnk::d2h_copy(perm_host, perm.p, ls->N * sizeof(int32_t), s));
+    if (doff_host) MNK_HIP(mnk::d2h_copy(doff_host, doff.p, ls->N * sizeof(double), s));
+    return 0;
+}
+
+// ---- the growth guard: who may ask for what (ls.h) ----
+bool BkTier::wanted(const mnk_ls* ls) const { return requested && bk_fallback && ls->algo == MNK_LDL; }
+unsigned long long* BkTier::growth_word(const mnk_ls* ls) const { return wanted(ls) && amax_dev.p ? amax_dev.p + 1 : nullptr; }
+bool BkTier::guard_fetched(const mnk_ls* ls) const { return growth_word(ls) != nullptr && ls->src.retransfer; }
+bool BkTier::may_take_over(const mnk_ls* ls) const { return requested && bk_fallback && ls->src.retransfer; }

@@ -1128,7 +1128,7 @@ static mnk::DagInst dag_instance(mnk_ls* ls) {
     // the envelope of a sparse source (ls.hip: set_envelope); the bulk kernel reads the verdict on its finiteness (env_word[1])
     const bool env = ls->envelope && ls->src.env_dev != nullptr && ls->env_word.p != nullptr;
     return mnk::DagInst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
-                        front, af, tprog, ls->info_dev.p, mnk_ls_growth_word(ls), zfill, ls->N, env ? ls->src.env_dev : nullptr,
+                        front, af, tprog, ls->info_dev.p, ls->bk.growth_word(ls), zfill, ls->N, env ? ls->src.env_dev : nullptr,
                         env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->src.envh_dev : nullptr};
 }
 
@@ -1261,7 +1261,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         if (!small) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
         MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
         mnk::PpDag dag{front, inst.af, ntile, 0, 0, -1, spin_limit, trace ? trace + (size_t)ls->plan.ntasks * 8 + (size_t)js_begin * 8 * 16 : nullptr,
-                  mnk_ls_growth_word(ls), ls->dag_debug ? ls->dag_dbg.p : nullptr};
+                  ls->bk.growth_word(ls), ls->dag_debug ? ls->dag_dbg.p : nullptr};
         // (the chain first: its first diagonal block is the start of the critical path, the bulk kernel has nothing to do before it)
         int rc = mnk_launch_pchain(ls, sp, dag, js_begin, js_end, strips);
         if (rc) return rc;
@@ -1373,9 +1373,7 @@ static int batch_finish(std::vector<mnk_ls*>& g, hipStream_t h) {
     MNK_HIP(hipEventRecord(g[0]->ev_defer, h));
     for (mnk_ls* ls : g) {
         if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(ls->ctx->stream, g[0]->ev_defer, 0));
-        ls->factorized = true;
-        ls->info_valid = false;
-        ls->bk_active = false;
+        ls->verdict.queued();
         ls->deferred = false;
         int r = ls->spare.queued(ls);
         if (r) return r;
@@ -1438,7 +1436,7 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
         // (the next chain of the stream starts behind them; the bulk kernel has work of the other instance meanwhile).
         auto launch_chain = [&](int i) -> int {
             mnk_ls* ls = g[i];
-            mnk::PpDag dag{hin[i].front, hin[i].af, ntile, 0, 0, -1, mnk_ls_dag_spin_limit(ls), nullptr, mnk_ls_growth_word(ls)};
+            mnk::PpDag dag{hin[i].front, hin[i].af, ntile, 0, 0, -1, mnk_ls_dag_spin_limit(ls), nullptr, ls->bk.growth_word(ls)};
             return mnk_launch_pchain(ls, sp[i & 1], dag, 0, nsc, strips);
         };
         auto launch_tail = [&](int i) -> int {
@@ -1536,8 +1534,6 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             // need) go through pinned host memory in ONE piece each: a kernel launch per record and per small kernel made the
             // host the bound of a batch of many small systems (~8 launches per system).
             std::vector<mnk::DagInst> hin;
-            std::vector<int*> fronts;
-            std::vector<const int*> afs;
             mnk::DagInst* insts_dev = reinterpret_cast<mnk::DagInst*>(B.insts.p);
             const size_t pc_bytes = mnk_pchain_sys_bytes();
             const size_t need = (size_t)k * (sizeof(mnk::DagInst) + pc_bytes + sizeof(mnk::SmallSysRec));
@@ -1554,7 +1550,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             mnk::DagInst* st_inst = reinterpret_cast<mnk::DagInst*>(B.stage);
             char* st_pc = B.stage + (size_t)k * sizeof(mnk::DagInst);
             mnk::SmallSysRec* st_aux = reinterpret_cast<mnk::SmallSysRec*>(st_pc + (size_t)k * pc_bytes);
-            const bool batch_aux = l0->linv_mfma && !l0->solve512;   // (the other inverse kernels have no batched form)
+            const bool batch_aux = l0->solves.linv_mfma && !l0->solves.solve512;   // (the other inverse kernels have no batched form)
             for (int i = 0; i < k; ++i) {
                 mnk_ls* ls = g[r0 + i];
                 hin.push_back(dag_instance(ls));
@@ -1564,8 +1560,6 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
                 hin.back().envh = nullptr;
                 ls->env_used = false;
                 ls->envh_used = false;
-                fronts.push_back(hin.back().front);
-                afs.push_back(hin.back().af);
                 st_inst[i] = hin.back();
                 mnk_pchain_fill_sys(ls, st_pc + (size_t)i * pc_bytes, hin.back().front, hin.back().af);
                 mnk_ls_fill_small_rec(ls, st_aux + i);
@@ -1582,7 +1576,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             MNK_HIP(hipStreamWaitEvent(sp, B.ev[0], 0));
             if (su != nullptr) MNK_HIP(hipStreamWaitEvent(su, B.ev[0], 0));
             // (the records of the chains' table are written on the home stream before the fork)
-            int r = mnk_launch_pchain_multi(g.data() + r0, k, sp, nullptr, B.pcsys.p, fronts.data(), afs.data());
+            int r = mnk_launch_pchain_multi(g.data() + r0, k, sp, B.pcsys.p);
             if (r) return r;
             if (ntasks1 > 0) {
                 const int bulk_wgs = mnk_ctx_bulk_wgs(c0, chain_cus_for(k), 3);
@@ -1606,9 +1600,8 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
                 for (int i = 0; i < k; ++i) {
                     mnk_ls* ls = g[r0 + i];
                     ls->inv_done = nsc;
-                    if (!ls->ev_info) MNK_HIP(hipEventCreateWithFlags(&ls->ev_info, hipEventDisableTiming));
-                    MNK_HIP(hipEventRecord(ls->ev_info, h));
-                    ls->ev_info_recorded = true;
+                    r = ls->verdict.record_info_event(h);
+                    if (r) return r;
                 }
                 return 0;
             }
@@ -1655,12 +1648,12 @@ static int batch_flush() {
             rc = l0->plan.key.js2 == 0 ? batch_run_group_small(g) : batch_run_group(g);
             if (rc)   // (nothing of the group counts as factorized: the factor buffers already hold the NEW, unfactored matrices, so
                       // a solve or an inertia call that ignores this error must not find the previous factorization's flag)
-                for (mnk_ls* ls : g) { ls->deferred = false; ls->factorized = false; ls->info_valid = false; }
+                for (mnk_ls* ls : g) { ls->deferred = false; ls->verdict.launch_failed(); }
         } else {
             g[0]->deferred = false;
             if (g[0]->Np < g[0]->dag_min_rows) g[0]->algo_now = 4;   // (alone, a system below the schedule's window keeps its usual one)
             rc = mnk_ls_run_factorization_now(g[0]);
-            if (rc) { g[0]->factorized = false; g[0]->info_valid = false; }
+            if (rc) g[0]->verdict.launch_failed();
         }
         if (rc && !rc_all) rc_all = rc;
     }

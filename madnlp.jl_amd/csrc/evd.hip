@@ -580,7 +580,6 @@ struct EvdSolver final : mnk_ls_alt {
                            ls->ld, ls->dvec.p);
         hipLaunchKernelGGL(evd_inertia_kernel, dim3(1), dim3(256), 0, s, evd_lam.p, N, info, ls->pin_dev);
         MNK_HIP(hipGetLastError());
-        ls->info = info;
         return 0;
     }
 
@@ -589,11 +588,7 @@ struct EvdSolver final : mnk_ls_alt {
     int fetch_info(mnk_ls* ls) override {
         MNK_HIP(stream_wait(ls->ctx->stream));
         volatile unsigned long long* pw = ls->pin;
-        ls->npos = (int64_t)pw[0];
-        ls->nzero = (int64_t)pw[1];
-        ls->nneg = (int64_t)pw[2];
-        ls->info = (int)(long long)pw[3];
-        ls->info_valid = true;
+        ls->verdict.accept((int)(long long)pw[3], (int64_t)pw[0], (int64_t)pw[1], (int64_t)pw[2]);
         return 0;
     }
 

@@ -793,8 +793,6 @@ __global__ __launch_bounds__(256) void pchain_multi_kernel(const PcSys* __restri
     }
 }
 
-__global__ void pc_set_sys_kernel(PcSys rec, PcSys* __restrict__ dst) { *dst = rec; }
-
 // inv(L_jj) of every 64x64 diagonal block (unit diagonal for LDL), for the triangular solves.
 // One workgroup of 4 waves per block: thread (c, p) solves L x = e_c for the rows r = 4i + p by column-oriented
 // substitution; the owner of row k publishes x_k through LDS (one barrier per pivot, double-buffered), so every
@@ -937,11 +935,6 @@ __global__ __launch_bounds__(1024) void finish_info_kernel(const double* __restr
 
 using namespace mnk;
 
-// the word the kernels fold max|V| into (zeroed with max|a_ij| when the matrix was transferred), or NULL: guard off
-unsigned long long* mnk_ls_growth_word(mnk_ls* ls) {
-    return (ls->algo == MNK_LDL && ls->bk_requested && ls->bk_fallback && ls->amax_dev.p) ? ls->amax_dev.p + 1 : nullptr;
-}
-
 // middle-level updates (inside an outer panel) with fewer 128x128 tiles than this use 64x64 workgroup tiles
 constexpr int SMALL_TILES_MID = 1000;
 
@@ -978,7 +971,7 @@ static int factor_outer_panel_pp(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t 
             waited = true;
         }
         const unsigned grid = (unsigned)((Np - p) / NBI);
-    unsigned long long* vmaxw = mnk_ls_growth_word(ls);
+    unsigned long long* vmaxw = ls->bk.growth_word(ls);
 #define MNK_PP(LD, NBT)                                                                                              \
     hipLaunchKernelGGL((ppanel_kernel<LD, NBT>), dim3(grid), dim3(256), PP_LDS_BYTES, s, F, ld, p, nbk, Np, ls->dblk.p, \
                        ls->inv16.p, ls->dvec.p, ls->dinv.p, LD ? wbase : (double*)nullptr, LD ? ls->ldw : (int64_t)0,  \
@@ -1035,7 +1028,7 @@ static int factor_outer_panel(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t ken
         double* inv16 = ls->inv16.p + (j / NBI) * 1024;
         if (ldl)
             hipLaunchKernelGGL(potrf64w_kernel<true>, dim3(1), dim3(64), 0, s, F, ld, j, dblk, inv16, ls->dvec.p, ls->dinv.p,
-                               ls->info_dev.p, ls->pivot_tol, mnk_ls_growth_word(ls));
+                               ls->info_dev.p, ls->pivot_tol, ls->bk.growth_word(ls));
         else
             hipLaunchKernelGGL(potrf64w_kernel<false>, dim3(1), dim3(64), 0, s, F, ld, j, dblk, inv16, ls->dvec.p, ls->dinv.p,
                                ls->info_dev.p, ls->pivot_tol, (unsigned long long*)nullptr);
@@ -1047,7 +1040,7 @@ static int factor_outer_panel(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t ken
 #define MNK_TRSM(LD, NS)                                                                                          \
     hipLaunchKernelGGL((trsm64_mfma_kernel<LD, NS>), dim3(grid), dim3(256), 0, s, F, ld, j, Np, dblk, inv16,    \
                        ls->dinv.p, LD ? wbase : (double*)nullptr, LD ? ls->ldw : (int64_t)0, j - ko, ls->info_dev.p,  \
-                       mnk_ls_growth_word(ls))
+                       ls->bk.growth_word(ls))
         if (ldl) { if (two) MNK_TRSM(true, 2); else MNK_TRSM(true, 1); }
         else { if (two) MNK_TRSM(false, 2); else MNK_TRSM(false, 1); }
 #undef MNK_TRSM
@@ -1104,7 +1097,7 @@ double mnk_process_stall_ms() { return (double)g_stall_us.load(std::memory_order
 int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
     if (sc1 <= sc0) return 0;
     const int64_t b0 = 4 * sc0, b1 = std::min<int64_t>(4 * sc1, ls->Np / NBI);
-    const bool ldl = ls->algo == MNK_LDL || ls->bk_active;
+    const bool ldl = ls->algo == MNK_LDL || ls->verdict.is_pivoted();
     if (ldl)
         hipLaunchKernelGGL(linv64_kernel<true>, dim3((unsigned)(b1 - b0)), dim3(256), 0, s, ls->fact.p, ls->ld, ls->dblk.p,
                            ls->linv.p, ls->info_dev.p, (int)b0);
@@ -1145,19 +1138,18 @@ int mnk_launch_pchain(mnk_ls* ls, hipStream_t sp, const mnk::PpDag& dag, int js_
 static int run_factorization_body(mnk_ls* ls);
 
 // The chains of the `n` systems v[0..n) (same order and algorithm, every row in the band: `strips` = Np / 64 workgroups each)
-// in ONE launch on `sp` (its CU mask must hold n * strips CUs); `table`: device memory for n records (>= n * mnk_pchain_sys_bytes()).
+// in ONE launch on `sp` (its CU mask must hold n * strips CUs); `table`: their n records on the device (mnk_pchain_fill_sys fills one
+// on the host, mnk_pchain_sys_bytes() each; the caller uploads them in front of the launch).
 size_t mnk_pchain_sys_bytes() { return sizeof(mnk::PcSys); }
 void mnk_pchain_fill_sys(mnk_ls* ls, void* rec_host, int* front, const int* af) {
     const bool ldl = ls->algo == MNK_LDL;
     *static_cast<mnk::PcSys*>(rec_host) = mnk::PcSys{ls->fact.p, ls->ld, ls->Np, ls->dblk.p, ls->inv16.p, ls->dvec.p, ls->dinv.p,
                                                        ldl ? ls->vfull.p : nullptr, ls->info_dev.p, ls->pivot_tol, ls->flag_p.p,
                                                        ls->epoch * 16, front, af, (int)(ls->Np / 128), mnk_ls_dag_spin_limit(ls),
-                                                       mnk_ls_growth_word(ls)};
+                                                       ls->bk.growth_word(ls)};
 }
 
-// (fill_stream == nullptr: the table has been uploaded by the caller -- mnk_pchain_fill_sys)
-int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t fill_stream, void* table, int* const* front,
-                            const int* const* af) {
+int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, void* table) {
     {   // 96 KB of dynamic LDS: the attribute belongs to the (kernel, device) pair
         static std::atomic<uint64_t> attr_devs{0};
         int dev = 0;
@@ -1168,17 +1160,9 @@ int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t
             attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
         }
     }
-    mnk::PcSys* dst = static_cast<mnk::PcSys*>(table);
+    const mnk::PcSys* dst = static_cast<const mnk::PcSys*>(table);
     const bool ldl = v[0]->algo == MNK_LDL;
     const int strips = (int)(v[0]->Np / NBI);
-    for (int i = 0; i < n && fill_stream != nullptr; ++i) {
-        mnk_ls* ls = v[i];
-        mnk::PcSys rec{ls->fact.p, ls->ld, ls->Np, ls->dblk.p, ls->inv16.p, ls->dvec.p, ls->dinv.p, ldl ? ls->vfull.p : nullptr,
-                       ls->info_dev.p, ls->pivot_tol, ls->flag_p.p, ls->epoch * 16, front[i], af[i], (int)(ls->Np / 128),
-                       mnk_ls_dag_spin_limit(ls), mnk_ls_growth_word(ls)};
-        hipLaunchKernelGGL(pc_set_sys_kernel, dim3(1), dim3(1), 0, fill_stream, rec, dst + i);
-    }
-    MNK_HIP(hipGetLastError());
     if (ldl)
         hipLaunchKernelGGL(pchain_multi_kernel<true>, dim3((unsigned)(n * strips)), dim3(256), PC_LDS_BYTES, sp, dst, strips);
     else
@@ -1198,19 +1182,8 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     }
     ++ls->epoch;  // the hand-off flags of this factorization carry this value (never reset)
     ls->inv_done = 0;
-    // (a verdict belongs to ONE factorization -- a new one with rejection disarmed, followed by a solve that never
-    // fetches the info word, must not meet the previous factorization's "rejected early" and refactor a valid factor)
-    ls->factor_invalid = false;
     ls->t_fact_launch_ms = mnk_host_ms();
-    {   // info[2]: the leaf stops the factorization at the first pivot that is not positive (leaf64.h: early rejection)
-        // (also inside a factorization batch: a member that stops early leaves the others alone -- dag.hip, the workgroup-uniform
-        // `dead` of the batch kernel; tests/test_hip_round5.py::test_a_batch_in_which_some_instances_are_indefinite)
-        const int want = (ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->src.persistent) ? 1 : 0;
-        if (want != ls->reject_on_device) {
-            MNK_HIP(hipMemsetAsync(ls->info_dev.p + 2, want, sizeof(int), s));
-            ls->reject_on_device = want;
-        }
-    }
+    { int rc_a = ls->verdict.arm_reject(ls, s); if (rc_a) return rc_a; }
     // The persistent kernels keep waiting workgroups resident.  Two of them from different contexts on the same CUs can
     // starve each other's diagonal strips (per-XCD dispatch order), so the persistent operations of one process take turns
     // on the device (the arbiter below); a wait that expires anyway (another PROCESS) falls back (mnk_ls_fetch_info) and the
@@ -1429,9 +1402,7 @@ static int run_factorization_body(mnk_ls* ls) {
         int rc = mnk_ls_invert_blocks(ls, s, ls->inv_done, (Np + 255) / 256);
         if (rc) return rc;
     }
-    ls->factorized = true;
-    ls->info_valid = false;
-    ls->bk_active = false;
+    ls->verdict.queued();
     {   // inertia / growth words / info go to the pinned host words right behind the factorization (mnk_ls_fetch_info only waits)
         int rc = mnk_ls_launch_finish_info(ls, s);
         if (rc) return rc;
@@ -1447,7 +1418,7 @@ void mnk_ls_fill_small_rec(mnk_ls* ls, mnk::SmallSysRec* rec) {
     rec->F = ls->fact.p; rec->ld = ls->ld; rec->dblk = ls->dblk.p; rec->linv = ls->linv.p;
     rec->linv256 = ls->linv256.p; rec->linv256t = ls->linv256t.p; rec->Np = ls->Np;
     rec->dvec = ls->dvec.p; rec->ninertia = lmode ? ls->N : 0; rec->pin_dev = ls->pin_dev;
-    rec->amax = mnk_ls_growth_word(ls) != nullptr ? ls->amax_dev.p : nullptr;
+    rec->amax = ls->bk.growth_word(ls) != nullptr ? ls->bk.amax_dev.p : nullptr;
 }
 
 int mnk_ls_invert_blocks_batch(hipStream_t s, bool ldl, const mnk::SmallSysRec* recs_dev, int n, int64_t Np) {
@@ -1471,18 +1442,40 @@ int mnk_ls_launch_finish_info(mnk_ls* ls, hipStream_t s) {
     const bool lmode = ls->algo == MNK_LDL;
     const int threads = lmode ? (ls->N >= 4096 ? 1024 : 256) : 64;
     hipLaunchKernelGGL(finish_info_kernel, dim3(1), dim3(threads), 0, s, ls->dvec.p, lmode ? ls->N : (int64_t)0, ls->info_dev.p, ls->pin_dev,
-                       mnk_ls_growth_word(ls) != nullptr ? ls->amax_dev.p : (const unsigned long long*)nullptr);
+                       ls->bk.growth_word(ls) != nullptr ? ls->bk.amax_dev.p : (const unsigned long long*)nullptr);
     MNK_HIP(hipGetLastError());
-    // mnk_ls_fetch_info waits for THIS point, not for the stream: whatever the caller has queued behind the factorization
-    // (the solves of other instances of a batch, the next assembly) does not delay the inertia
-    if (!ls->ev_info) MNK_HIP(hipEventCreateWithFlags(&ls->ev_info, hipEventDisableTiming));
-    MNK_HIP(hipEventRecord(ls->ev_info, s));
-    ls->ev_info_recorded = true;
+    return ls->verdict.record_info_event(s);
+}
+
+// ---- FactorVerdict (ls.h): the event and the device's early-rejection switch ----
+// info[2]: the leaf stops the factorization at the first pivot that is not positive (leaf64.h: early rejection)
+// (also inside a factorization batch: a member that stops early leaves the others alone -- dag.hip, the workgroup-uniform
+// `dead` of the batch kernel; tests/test_hip_round5.py::test_a_batch_in_which_some_instances_are_indefinite)
+int FactorVerdict::arm_reject(mnk_ls* ls, hipStream_t s) {
+    const int want = (ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->src.persistent) ? 1 : 0;
+    if (want != reject_on_device) {
+        MNK_HIP(hipMemsetAsync(ls->info_dev.p + 2, want, sizeof(int), s));
+        reject_on_device = want;
+    }
+    return 0;
+}
+
+// (whatever the caller has queued behind the factorization -- the solves of other instances of a batch, the next assembly -- does not delay the inertia)
+int FactorVerdict::record_info_event(hipStream_t s) {
+    if (!ev_info) MNK_HIP(hipEventCreateWithFlags(&ev_info, hipEventDisableTiming));
+    MNK_HIP(hipEventRecord(ev_info, s));
+    ev_info_recorded = true;
+    return 0;
+}
+
+int FactorVerdict::wait_info(hipStream_t s) {
+    if (ev_info_recorded) MNK_HIP(hipEventSynchronize(ev_info));
+    else MNK_HIP(mnk::stream_wait(s));
     return 0;
 }
 
 int mnk_ls_right_trsm_rows(mnk_ls* ls, hipStream_t s, int64_t j0, double* Xrows, double* Vrows, int64_t ldr, int64_t nrows) {
-    MNK_REQUIRE(ls->factorized && !ls->bk_active && nrows % 16 == 0 && j0 % NBI == 0 && j0 < ls->Np,
+    MNK_REQUIRE(ls->verdict.has_factorization() && !ls->verdict.is_pivoted() && nrows % 16 == 0 && j0 % NBI == 0 && j0 < ls->Np,
                 "mnk_ls_right_trsm_rows: needs a static-pivot factor, 16-row multiples and a block-aligned column");
     // the kernel addresses rows j0 + 64 ... of ONE matrix: shift the row blocks so that its row r0 is their row 0
     double* Fp = Xrows - (j0 + NBI);
@@ -1516,43 +1509,41 @@ static int bk_fallback(mnk_ls* ls) {
     hipStream_t s = ls->ctx->stream;
     int rc = ls->src.retransfer();
     if (rc) return rc;
-    rc = mnk_ls_run_bunchkaufman(ls);
+    rc = ls->bk.run(ls);
     if (rc) return rc;
     rc = mnk_ls_invert_blocks(ls, s, 0, (ls->Np + 255) / 256);
     if (rc) return rc;
-    ++ls->bk_count;
+    ++ls->bk.count;
     return ls->spare.queued(ls);   // (the second transfer swapped the factor buffers again: the spare one holds the discarded static factor)
 }
 
 int mnk_ls_fetch_info(mnk_ls* ls) {
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    if (ls->info_valid) return 0;
+    FactorVerdict& v = ls->verdict;
+    if (v.known()) return 0;
     if (ls->alt) return ls->alt->fetch_info(ls);
     hipStream_t s = ls->ctx->stream;
-    if (ls->bk_active) {
+    const int64_t N = ls->N;
+    if (v.is_pivoted()) {
         MNK_HIP(hipMemsetAsync(ls->inertia_dev.p, 0, 3 * sizeof(unsigned long long), s));
         // reference rule for a Bunch-Kaufman factor (src/LinearSolvers/lapack.jl:240-268): numzero = info > 0,
         // numneg from the 1x1 / 2x2 blocks of D (-1 if a block is exactly singular), numpos the rest
-        int rc = mnk_ls_bk_inertia(ls, ls->inertia_dev.p);
+        int rc = ls->bk.inertia(ls, ls->inertia_dev.p);
         if (rc) return rc;
         hipLaunchKernelGGL(publish_info_kernel, dim3(1), dim3(64), 0, s, ls->inertia_dev.p, ls->info_dev.p, ls->pin_dev);
         MNK_HIP(hipGetLastError());
         MNK_HIP(mnk::stream_wait(s));
         volatile unsigned long long* pw = ls->pin;
         unsigned long long h[3] = {pw[0], pw[1], pw[2]};
-        int hinfo = (int)(long long)pw[3];
-        ls->info = hinfo;
-        ls->nneg = h[1] > 0 ? -1 : (int64_t)h[0];
-        ls->nzero = hinfo > 0 ? 1 : 0;
-        ls->npos = ls->N - ls->nneg - ls->nzero;
-        ls->info_valid = true;
+        const int hinfo = (int)(long long)pw[3];
+        const int64_t nneg = h[1] > 0 ? -1 : (int64_t)h[0], nzero = hinfo > 0 ? 1 : 0;
+        v.accept(hinfo, N - nneg - nzero, nzero, nneg);
         return 0;
     }
     // growth guard of the static-pivot tier (BUNCHKAUFMAN): max|a_ij| was recorded when the matrix was transferred
-    const bool guard = ls->algo == MNK_LDL && ls->bk_requested && ls->bk_fallback && ls->src.retransfer && ls->amax_dev.p != nullptr;
+    const bool guard = ls->bk.guard_fetched(ls);
     // (finish_info_kernel, queued behind the factorization, has stored everything in the pinned words)
-    if (ls->ev_info_recorded) MNK_HIP(hipEventSynchronize(ls->ev_info));
-    else MNK_HIP(mnk::stream_wait(s));
+    { int rc_w = v.wait_info(s); if (rc_w) return rc_w; }
     volatile unsigned long long* pw = ls->pin;
     unsigned long long h[3] = {pw[0], pw[1], pw[2]};
     int hinfo = (int)(long long)pw[3];
@@ -1561,8 +1552,7 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         const unsigned long long wa = pw[4], wd = pw[5];
         memcpy(&am, &wa, sizeof am);
         memcpy(&dm, &wd, sizeof dm);
-        ls->last_growth = am > 0.0 ? dm / am : (dm > 0.0 ? HUGE_VAL : 0.0);
-        ls->last_sign_changes = (int64_t)pw[6];
+        ls->bk.note_growth(am, dm, (int64_t)pw[6]);
     }
     if (hinfo == -7) ls->pp.last_site = (int)(long long)pw[7];
     if (hinfo == -7 && ls->dag_debug && ls->plan.flags.p && ls->dag_dbg.p) {
@@ -1592,25 +1582,14 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         if (rc) return rc;
         return mnk_ls_fetch_info(ls);
     }
-    ls->factor_invalid = false;
     if (hinfo == -9) {
         // EARLY REJECTION (option early_reject with accept_only_pd; leaf64.h): the static-pivot LDL^T met a pivot that is not
         // positive and every kernel behind that diagonal block dropped its work.  The matrix is not positive definite -- all the
         // caller asked.  Reported: the signs of the pivots that were computed, everything behind them counted as negative
         // (num_neg >= 1 is the statement; the reference's Cholesky path reports a failed factorization as (0, n, 0) in the
         // same spirit, lapack_common.jl:96-98).  The factor is not usable: solve / get_factor refuse it.
-        ls->info = 1;
-        ls->npos = (int64_t)h[0];
-        ls->nzero = (int64_t)h[1];
-        ls->nneg = ls->N - ls->npos - ls->nzero;
-        ls->factor_invalid = true;
-        ++ls->early_rejects;
-        ls->early_reject_col = (int64_t)(long long)pw[7];
-        ls->info_valid = true;
-        // (history of the leading-block probe, ls.h)
-        ls->probe_last_rejected = true;
-        if (2 * ls->early_reject_col < ls->N) { ls->probe_hint_col = ls->early_reject_col; ls->probe_since_hint = 0; }
-        else if (ls->probe_since_hint < (1 << 20)) ++ls->probe_since_hint;
+        v.reject_early((int64_t)h[0], (int64_t)h[1], N, (int64_t)(long long)pw[7]);
+        ls->probe.note_verdict(true, v.early_reject_col, N);
         return 0;
     }
     if (hinfo < 0) {
@@ -1619,21 +1598,18 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
                   "factor is invalid -- set panel_algo = 1", hinfo);
         return -4;
     }
-    ls->info = hinfo;
+    int64_t npos, nzero, nneg = 0;
     if (ls->algo == MNK_LDL) {
-        ls->npos = (int64_t)h[0];
-        ls->nzero = (int64_t)h[1];
-        ls->nneg = (int64_t)h[2];
-        if (ls->nzero > 0 && ls->info == 0) ls->info = 1;  // LAPACK-style "singular D" signal
-        // (pivots that are all positive and then all negative: a positive definite leading block and a negative definite Schur
-        // complement, the quasi-definite structure of the KKT systems, whose growth |J|^2 / lambda_min(H) is in the data)
-        const double gtol = ls->last_sign_changes <= 1 ? ls->bk_growth_tol_qd : ls->bk_growth_tol;
+        npos = (int64_t)h[0];
+        nzero = (int64_t)h[1];
+        nneg = (int64_t)h[2];
+        if (nzero > 0 && hinfo == 0) hinfo = 1;  // LAPACK-style "singular D" signal
         // accept_only_pd: the caller's inertia test accepts positive definite matrices only (the condensed KKT systems
         // without equality rows, reference src/KKT/Sparse/condensed.jl:138-140).  A zero or negative pivot of the unpivoted
         // LDL^T PROVES that the matrix is not positive definite -- the pivoted tier could only confirm a rejection, at
         // 0.47 s for N = 11 192 -- so the static tier's counts are reported as they are.
-        const bool verdict_final = ls->accept_only_pd && (ls->nzero > 0 || ls->nneg > 0);
-        if (!verdict_final && (ls->nzero > 0 || (guard && !(ls->last_growth <= gtol))) && ls->bk_requested && ls->bk_fallback && ls->src.retransfer) {
+        const bool verdict_final = ls->accept_only_pd && (nzero > 0 || nneg > 0);
+        if (!verdict_final && (nzero > 0 || (guard && ls->bk.grew())) && ls->bk.may_take_over(ls)) {
             // the static-pivot factorization broke down (a zero pivot) or grew (tiny pivots: the Schur complements left the
             // scale of the matrix) on a matrix that is not quasi-definite in the given order: BUNCHKAUFMAN means dsytrf
             // semantics, so factor it again with 1x1 / 2x2 pivoting
@@ -1643,12 +1619,11 @@ int mnk_ls_fetch_info(mnk_ls* ls) {
         }
     } else {
         // inertia_cholesky, reference src/LinearSolvers/lapack_common.jl:96-98
-        if (hinfo == 0) { ls->npos = ls->N; ls->nzero = 0; ls->nneg = 0; }
-        else { ls->npos = 0; ls->nzero = ls->N; ls->nneg = 0; }
+        npos = hinfo == 0 ? N : 0;
+        nzero = hinfo == 0 ? 0 : N;
     }
-    ls->probe_last_rejected = false;   // (history of the leading-block probe: a verdict that is not an early rejection)
-    if (ls->probe_since_hint < (1 << 20)) ++ls->probe_since_hint;
-    ls->info_valid = true;
+    v.accept(hinfo, npos, nzero, nneg);
+    ls->probe.note_verdict(false, -1, N);
     return 0;
 }
 

@@ -85,8 +85,8 @@ struct mnk_ls;
 struct mnk_ls_alt {
     virtual ~mnk_ls_alt() = default;
     virtual int alloc(mnk_ls* ls) = 0;
-    virtual int factor(mnk_ls* ls) = 0;       // enqueues the factorization of the transferred lower triangle and sets ls->info (0, or what is known by then)
-    virtual int fetch_info(mnk_ls* ls) = 0;   // waits for it; fills info, info_valid and (where the algorithm reveals it) the inertia
+    virtual int factor(mnk_ls* ls) = 0;       // enqueues the factorization of the transferred lower triangle and (ls_alt.hip: verdict.queued() follows)
+    virtual int fetch_info(mnk_ls* ls) = 0;   // waits for it; verdict.accept() with info and (where the algorithm reveals it) the inertia
     // One right-hand side of N entries on the device, b -> x (x may be b).  Workspace: the solver's xwork BEHIND its first Np
     // entries, which are the staging slot of host-resident right-hand sides (mnk_ls_alt_solve).
     virtual int solve_vec(mnk_ls* ls, const double* b, double* x) = 0;
@@ -175,6 +175,152 @@ struct PersistBackoff {
     int64_t retry_at = 0, backoff = 16;
 };
 
+// The verdict of the factorization queued last (operations: factor.hip).  A verdict belongs to ONE factorization: queued() forgets
+// the previous one's, "rejected early" included, so a solve that never fetches the info word cannot meet it and refactor a valid
+// factor.  Stages and who moves them:
+//   None      nothing counts as factorized (a new solver; launch_failed(): a batch launch failed with the NEW matrices in the buffers)
+//   Queued    queued(): the launches are in the stream, nothing is known (run_factorization_body, batch_finish, mnk_ls_alt_factorize)
+//   Accepted  accept(): info and inertia fetched, the factor is usable (mnk_ls_fetch_info, the fetch_info of QR / LU / EVD)
+//   Rejected  reject_early(): stopped at its first non-positive pivot, or never started because the leading-block probe failed:
+//             info = 1, the inertia is a lower bound on num_neg and there is NO usable factor (solve / get_factor complete it first)
+// pivoted(): the factor in the buffer is the pivoted tier's, P A P^T = L D L^T with 2x2 blocks (bk.hip sets it between Queued and
+// Accepted; every queued() and reject_early() clears it, launch_failed() leaves it).
+struct FactorVerdict {
+    // what a known verdict says (everybody reads, only accept() and reject_early() write) and the statistics "early_rejects",
+    // "early_reject_col" (the last valid pivot of the latest one), "early_reject_redone"
+    int info = 0;
+    int64_t npos = 0, nzero = 0, nneg = 0;
+    int64_t early_rejects = 0, early_reject_col = -1, early_reject_redone = 0;
+    void queued() { stage = Stage::Queued; bk = false; }
+    void launch_failed() { stage = Stage::None; }
+    void accept(int info_, int64_t npos_, int64_t nzero_, int64_t nneg_) { stage = Stage::Accepted; info = info_; npos = npos_; nzero = nzero_; nneg = nneg_; }
+    void reject_early(int64_t npos_, int64_t nzero_, int64_t N, int64_t col) {   // the one place that writes an early-rejected verdict
+        stage = Stage::Rejected; bk = false; info = 1; npos = npos_; nzero = nzero_; nneg = N - npos_ - nzero_;
+        ++early_rejects; early_reject_col = col;
+    }
+    void pivoted() { bk = true; }
+    void completed_after_all() { ++early_reject_redone; }   // ensure_complete_factor factored a rejected matrix to the end
+    bool has_factorization() const { return stage != Stage::None; }
+    bool known() const { return stage == Stage::Accepted || stage == Stage::Rejected; }
+    bool usable() const { return stage != Stage::Rejected; }
+    bool is_pivoted() const { return bk; }
+    int arm_reject(mnk_ls* ls, hipStream_t s);   // sets info[2] on the device (the leaf stops at the first pivot that is not positive) to what this factorization wants
+    bool reject_armed() const { return reject_on_device == 1; }
+    int record_info_event(hipStream_t s);   // behind finish_info_kernel: mnk_ls_fetch_info waits for THAT point, not for what the caller queued behind it
+    int wait_info(hipStream_t s);           // ... or for the stream, while no event has been recorded (QR / LU / EVD never do)
+    void destroy() { if (ev_info) (void)hipEventDestroy(ev_info); ev_info = nullptr; }
+   private:
+    enum class Stage { None, Queued, Accepted, Rejected } stage = Stage::None;
+    bool bk = false, ev_info_recorded = false;
+    int reject_on_device = -1;           // what info[2] on the device currently says
+    hipEvent_t ev_info = nullptr;
+};
+
+// LEADING-BLOCK PROBE (operations: ls.hip; option "probe", effective while early rejection is armed): after a rejection that stopped
+// in the first half of the columns, a matrix that follows an ACCEPTED one is first probed through its leading principal block (a
+// child solver of that order on the same KKT handle) -- probe_leading_block.  History, moved by note_verdict() alone:
+//   hint_col       where the last early rejection of the first half stopped (-1: none yet)
+//   since_hint     verdicts noted since then (saturating): a rejection in the first half re-arms the hint, every other verdict ages it
+//   last_rejected  the verdict noted last was an early rejection (the matrix that follows is the regularized one: no probe)
+struct LeadingBlockProbe {
+    int on = 1;                          // option "probe"
+    int64_t hits = 0, misses = 0;        // statistics: matrices rejected by the probe alone / probes that passed
+    void note_verdict(bool rejected, int64_t col, int64_t N) {
+        last_rejected = rejected;
+        if (rejected && 2 * col < N) { hint_col = col; since_hint = 0; }
+        else if (since_hint < (1 << 20)) ++since_hint;
+    }
+    int64_t order_due(int64_t N) const {   // 0, or the order of the block the next matrix is probed through
+        if (last_rejected || hint_col < 0 || since_hint > 3) return 0;
+        const int64_t m = (hint_col + 256) / 256 * 256;
+        return m >= 512 && 2 * m <= N ? m : 0;
+    }
+    mnk_ls* child(mnk_ls* ls, int64_t m);   // the child of order m (created, recreated or reused) with the parent's verdict-deciding options; nullptr: no memory, no probe
+    void destroy() { if (ls_child) (void)mnk_ls_destroy(ls_child); ls_child = nullptr; }
+   private:
+    mnk_ls* ls_child = nullptr;          // owned, of order `order`
+    int64_t order = 0, hint_col = -1;
+    int since_hint = 1 << 20;
+    bool last_rejected = false;
+};
+
+// The pivoted (Bunch-Kaufman) tier and the growth guard of the static-pivot tier in front of it (operations: bk.hip; BUNCHKAUFMAN
+// only; options under the names of their keys).  mnk_ls_fetch_info takes the tier when the static-pivot factorization broke down or grew.
+// The guard: the pivots are entries of the successive Schur complements, so max|d_k| / max|a_ij| is a lower bound of the element
+// growth of the elimination; dsytrf's pivoting bounds the growth, static pivoting does not on a matrix that is not quasi-definite
+// (a pivot of 1e-14 is "not zero" and the next Schur complement is 1e14 times the matrix).  Above bk_growth_tol the factor is
+// discarded and the pivoted tier takes over.  SPD matrices never trip it (growth <= 1).  Matrices whose pivots come out "all
+// positive, then all negative" have a positive definite leading block and a negative definite Schur complement -- the
+// quasi-definite structure of the KKT systems, for which the unpivoted factorization is the intended one and whose growth
+// |J|^2 / lambda_min(H) is a property of the data, not of the pivot order: they get the lenient bound bk_growth_tol_qd.
+// ran_multi / mw_blocked: the multi-workgroup panel ran last / one of its bounded waits expired once, so run() keeps to one
+// workgroup per panel from then on (n_mw_fallbacks counts); only run() moves them.
+struct BkTier {
+    bool requested = false;      // mnk_ls_create was called with MNK_BUNCHKAUFMAN (MNK_LDL: static pivoting only)
+    int bk_fallback = 1;         // option: 0 = never take the pivoted tier (a breakdown is reported as num_zero)
+    int bk_panel_wgs = 0;        // option: 0 = a workgroup per 256 rows of the panel, 1 = one workgroup per panel (round 3)
+    int bk_max_wgs = 0;          // option: cap on the workgroups of a multi-workgroup panel (0: one per CU); panels with more
+                                 // than 256 x this many rows are factored by the one-workgroup kernel
+    long bk_spin_limit = 1L << 21;   // option: polls one of its message rounds may take (~1 s) before the tier falls back
+    int debug_bk_missing = -1;   // option (tests): a workgroup of the multi-workgroup panel that never takes part
+    double bk_growth_tol = 64.0, bk_growth_tol_qd = 1e8;   // options
+    double last_growth = 0.0;    // max(|d_k|, |v_ik|) / max|a_ij| of the last static-pivot factorization (diagnostics, tests)
+    int64_t last_sign_changes = 0;
+    int count = 0;               // how many factorizations took the pivoted tier (diagnostics, tests)
+    mnk::DevBuf<unsigned long long> amax_dev;  // [0] max|a_ij| as transferred (folded from the slots below when the info is published), [1] max(|d_k|, |v_ik|) (bit patterns), [2] sign changes of the pivots; [AMAX_SLOT0 + AMAX_STRIDE i]: partial max|a_ij| of the transfer kernels
+    bool wanted(const mnk_ls* ls) const;                        // the tier may be needed: the transfers record max|a_ij| (amax_word)
+    unsigned long long* growth_word(const mnk_ls* ls) const;    // ... and the word exists: where the kernels being launched fold max(|d|, |v|) (NULL: guard off)
+    bool guard_fetched(const mnk_ls* ls) const;                 // ... and there is a way back to the matrix: mnk_ls_fetch_info reads the growth and may act on it
+    bool may_take_over(const mnk_ls* ls) const;                 // the pivoted tier may factor again (a zero pivot takes it without the guard: no amax word asked for)
+    void note_growth(double am, double dm, int64_t sign_changes) { last_growth = am > 0.0 ? dm / am : (dm > 0.0 ? HUGE_VAL : 0.0); last_sign_changes = sign_changes; }
+    bool grew() const { return !(last_growth <= (last_sign_changes <= 1 ? bk_growth_tol_qd : bk_growth_tol)); }
+    int run(mnk_ls* ls);                  // factors the matrix in ls->fact with 1x1 / 2x2 pivoting (falls back to one workgroup per panel by itself)
+    int permute(mnk_ls* ls, double* x, double* tmp, bool forward);   // x <- P x (forward) / P^T x
+    int dsolve(mnk_ls* ls, double* y);                               // y <- D^-1 y, 1x1 / 2x2 blocks
+    int inertia(mnk_ls* ls, unsigned long long* out_dev);
+    int read_pivots(mnk_ls* ls, int32_t* perm_host, double* doff_host);   // mnk_ls_bk_info (either may be NULL)
+    bool multi_last() const { return ran_multi; }
+    int mw_fallbacks() const { return n_mw_fallbacks; }
+   private:
+    int factor(mnk_ls* ls, bool multi);
+    mnk::DevBuf<int> perm, ptype;
+    mnk::DevBuf<double> doff, dcoup, work;  // (work: the panel's W = L D and its zero-padded copy of L, 2 x Np x 72)
+    mnk::DevBuf<char> state;
+    // multi-workgroup panel: W by stored row, staging of the per-panel permutation, message ring, rowof | lists
+    mnk::DevBuf<double> wv, tmp; mnk::DevBuf<unsigned long long> msg; mnk::DevBuf<int> aux;
+    bool ran_multi = false, mw_blocked = false;
+    int n_mw_fallbacks = 0;
+};
+
+// The state of the solves (operations: solve.hip; options under the names of their keys).  The one-launch (persistent) solve
+// publishes its blocks through two buffers used alternately: the next solve polls pub_next, which must be all sentinel (pub_clean),
+// and every solve clears the other one in passing; mnk_ls_run_solve and the solve batch move them through the operations below.
+// A solve that gives up raises the pinned abort word; take_abort() is the one answer to it: the word is cleared, `persistent_solve`
+// goes off for this solver and both publication buffers count as dirty.
+struct SolveState {
+    int persistent_solve = 1;  // option: both sweeps of a solve in one launch; 0: one launch per step
+    int solve512 = 0;          // option: the one-launch solve steps over 512 columns (32-row blocks, 512x512 explicit inverses) from 4096 rows on.  C3: solve! 0.46 -> 0.33 ms, but the extra inverses cost factorize! +0.37 ms (they finish 0.3 ms after the chain): worth it from ~4 solves per factorization
+    int linv_mfma = 1;         // option: 256x256 explicit inverses on the matrix cores (0: the scalar LDS kernel, ~70 us per workgroup)
+    long ps_spin_limit = 6000000;   // option: polls (~0.5 us each) a persistent-solve wait may take before it gives up
+    int debug_ps_missing = -1; // option (tests): this workgroup of the persistent solve leaves at once (a peer that never became resident)
+    mnk::DevBuf<double> linv512, linv512t, linv512tmp;
+    mnk::DevBuf<unsigned long long> trace;  // diagnostics: 8 time stamps per 64-row block (option solve_trace)
+    int create();                            // the pinned abort word
+    void destroy();
+    int* abort_word() const { return abort; }   // what the solve kernels raise (the host reads it without a sync)
+    bool abort_raised() const { return abort && *abort != 0; }
+    bool take_abort();                       // after a stream synchronization: true (and the give-up sequence above) if a persistent solve gave up since the last check
+    int poll_buffer() const { return pub_next; }
+    bool reset_due(int b) { const bool due = !pub_clean[b]; pub_clean[b] = true; return due; }   // b is about to be polled: true if the caller must queue the sentinel fill first
+    void dirtied(int b) { pub_clean[b] = false; }   // b was used as scratch (the pivoted tier's permutation, the 512-column solve)
+    // a one-launch solve polls poll_buffer() and leaves the other one all sentinel (not with a test's missing workgroup): they swap roles
+    void solve_queued(bool other_cleared) { pub_clean[pub_next] = false; pub_clean[pub_next ^ 1] = other_cleared; pub_next ^= 1; }
+   private:
+    int* abort = nullptr;                // pinned host word
+    int pub_next = 0;
+    bool pub_clean[2] = {false, false};
+};
+
 struct mnk_ls {
     mnk_ctx* ctx = nullptr;
     int64_t N = 0, Np = 0, ld = 0, ldw = 0, nbo = 512;
@@ -198,8 +344,6 @@ struct mnk_ls {
     // task-DAG schedule (panel_algo = 5, dag.hip)
     DagPlan plan;
     int dag_fill = 1;             // option: the zero-fill of the spare factor buffer (sparse sources) runs as DAG_FILL tasks of the bulk queue instead of on a side stream beside the solves
-    hipEvent_t ev_info = nullptr;    // recorded behind finish_info_kernel: what mnk_ls_fetch_info waits for
-    bool ev_info_recorded = false;
     hipEvent_t ev_defer = nullptr;   // batch: "matrix transferred" on this solver's stream / "batch done"
     bool deferred = false;        // a factorize! call of this solver is pending in an open batch
     int dag_xcd_queues = 1;      // option: 0 = one queue popped by every workgroup
@@ -224,76 +368,23 @@ struct mnk_ls {
     bool env_used = false, envh_used = false;   // the last task-DAG factorization was launched with the envelope / the half-tile envelope (statistics)
     int64_t dag_max_rows = 30720; // larger ones too: their trailing updates already run at the update kernel's rate (round 6, LDL, schedule 4 / this one: N = 24 576 87.4 / 81.7 ms, 28 672 133.6 / 128.6, 32 768 188.2 / 190.2; rounds 3-5: 24 576)
     int panel_algo = 5;  // 5: task-DAG schedule (dag.hip: persistent pivot chain + persistent left-looking bulk kernel); 4: persistent panel kernel per 256 columns + one trailing update per outer panel (also what 5 uses outside [dag_min_rows, dag_max_rows]); 1: one launch per piece, the fallback of 4 and 5
-    int persistent_solve = 1;  // both sweeps of a solve in one launch (solve.hip); 0: one launch per step
-    int solve512 = 0;          // 1: the one-launch solve steps over 512 columns (32-row blocks, 512x512 explicit inverses) from 4096 rows on.  C3: solve! 0.46 -> 0.33 ms, but the extra inverses cost factorize! +0.37 ms (they finish 0.3 ms after the chain): worth it from ~4 solves per factorization
+    SolveState solves;
     std::vector<std::string> env_keys;   // options fixed by MNK_OPTIONS for this process
     int dag_js2_override = -1;
-    int linv_mfma = 1;         // 256x256 explicit inverses on the matrix cores (0: the scalar LDS kernel, ~70 us per workgroup)
-    mnk::DevBuf<double> linv512, linv512t, linv512tmp;
-    int pub_next = 0;            // the one-launch solve's publication buffers (two, used alternately): the next solve polls this one ...
-    bool pub_clean[2] = {false, false};   // ... which must be all sentinel; every solve clears the other one in passing (solve.hip)
-    int* solve_abort = nullptr;  // pinned host word the solve kernel raises when it gives up (host can read it without a sync)
-    long ps_spin_limit = 6000000;  // polls (~0.5 us each) a persistent-solve wait may take before it gives up
     int debug_pp_missing = -1;     // tests only: this diagonal strip of every persistent panel launch never publishes
-    int debug_ps_missing = -1;     // tests only: this workgroup of the persistent solve leaves at once (a peer that never became resident)
-    mnk::DevBuf<unsigned long long> solve_trace;  // diagnostics: 8 time stamps per 64-row block (option solve_trace)
     mnk::DevBuf<int> info_dev;
     mnk::DevBuf<unsigned long long> inertia_dev;
     unsigned long long* pin = nullptr;  // 7 pinned, device-mapped host words: inertia counters, info, max|A|, growth numerator (bit patterns), sign changes are stored here by a kernel
     unsigned long long* pin_dev = nullptr;  // the same words as the device sees them
-    // Bunch-Kaufman tier (bk.hip): taken when BUNCHKAUFMAN was requested and the static-pivot factorization broke down
-    bool bk_requested = false;   // mnk_ls_create was called with MNK_BUNCHKAUFMAN (MNK_LDL: static pivoting only)
-    int bk_fallback = 1;         // option: 0 = never take the pivoted tier (a breakdown is reported as num_zero)
+    FactorVerdict verdict;       // of the factorization queued last
+    BkTier bk;                   // the pivoted tier (BUNCHKAUFMAN) and the growth guard in front of it
     int early_reject = 0;        // option (with accept_only_pd): stop the static-pivot LDL^T at the first pivot that is not positive (leaf64.h); the factor
                                  // of a rejected matrix is then not usable and its inertia is a lower bound on num_neg
-    int reject_on_device = -1;   // what info[2] on the device currently says
-    bool factor_invalid = false; // the last factorization was rejected early: solve / get_factor refuse
-    int64_t early_rejects = 0, early_reject_col = -1, early_reject_redone = 0;   // statistics ("early_rejects", "early_reject_col")
-    // LEADING-BLOCK PROBE (round 6; option "probe", effective while early rejection is armed): after a rejection that stopped in
-    // the first half of the columns, a matrix that follows an ACCEPTED one is first probed through its leading principal block (a
-    // child solver of that order on the same KKT handle) -- mnk_ls_factorize_sc_async
-    int probe = 1;
-    mnk_ls* probe_ls = nullptr;      // the child (order probe_order), owned
-    int64_t probe_order = 0;
-    int64_t probe_hint_col = -1;     // where the last early rejection of the first half stopped
-    int probe_since_hint = 1 << 20;  // verdicts fetched since then
-    bool probe_last_rejected = false;
-    int64_t probe_hits = 0, probe_misses = 0;   // statistics: matrices rejected by the probe alone / probes that passed
+    LeadingBlockProbe probe;
     int accept_only_pd = 0;      // option: the caller accepts positive definite matrices only: "not PD" from the static tier is final
-    // Growth guard of the static-pivot tier (BUNCHKAUFMAN only).  The pivots are entries of the successive Schur complements,
-    // so max|d_k| / max|a_ij| is a lower bound of the element growth of the elimination; dsytrf's pivoting bounds the growth,
-    // static pivoting does not on a matrix that is not quasi-definite (a pivot of 1e-14 is "not zero" and the next Schur
-    // complement is 1e14 times the matrix).  Above bk_growth_tol the factor is discarded and the pivoted tier takes over.
-    // SPD matrices never trip it (growth <= 1).  Matrices whose pivots come out "all positive, then all negative" have a
-    // positive definite leading block and a negative definite Schur complement -- the quasi-definite structure of the KKT
-    // systems, for which the unpivoted factorization is the intended one and whose growth |J|^2 / lambda_min(H) is a property
-    // of the data, not of the pivot order: they get the lenient bound bk_growth_tol_qd.
-    double bk_growth_tol = 64.0, bk_growth_tol_qd = 1e8;
-    double last_growth = 0.0;    // max(|d_k|, |v_ik|) / max|a_ij| of the last static-pivot factorization (diagnostics, tests)
-    int64_t last_sign_changes = 0;
-    mnk::DevBuf<unsigned long long> amax_dev;  // [0] max|a_ij| as transferred (folded from the slots below when the info is published), [1] max(|d_k|, |v_ik|) (bit patterns), [2] sign changes of the pivots; [AMAX_SLOT0 + AMAX_STRIDE i]: partial max|a_ij| of the transfer kernels
-    bool bk_active = false;      // the current factor is P A P^T = L D L^T with 2x2 blocks (solves use perm / dcoup)
-    int bk_count = 0;            // how many factorizations took the pivoted tier (diagnostics, tests)
-    mnk::DevBuf<int> bk_perm, bk_ptype;
-    mnk::DevBuf<double> bk_doff, bk_dcoup, bk_work;  // (bk_work: the panel's W = L D and its zero-padded copy of L, 2 x Np x 72)
-    mnk::DevBuf<char> bk_state;
-    // multi-workgroup panel (bk.hip): W by stored row, staging of the per-panel permutation, message ring, rowof | lists
-    mnk::DevBuf<double> bk_wv, bk_tmp;
-    mnk::DevBuf<unsigned long long> bk_msg;
-    mnk::DevBuf<int> bk_aux;
-    int bk_panel_wgs = 0;        // option: 0 = a workgroup per 256 rows of the panel, 1 = one workgroup per panel (round 3)
-    int bk_max_wgs = 0;              // option: cap on the workgroups of a multi-workgroup panel (0: one per CU); panels with more
-                                     // than 256 x this many rows are factored by the one-workgroup kernel
-    long bk_spin_limit = 1L << 21;   // option: polls one of its message rounds may take (~1 s) before the tier falls back
-    int debug_bk_missing = -1;       // tests: a workgroup of the multi-workgroup panel that never takes part
-    bool bk_multi_last = false, bk_mw_blocked = false;
-    int bk_mw_fallbacks = 0;
-    bool factorized = false, info_valid = false;
     int dag_debug = 0;           // option: keep the progress words of a factorization that timed out (mnk_ls_debug_dag_state)
     mnk::DevBuf<int> dag_dbg;    // 8 words per chain strip (PpDag::dbg)
     std::vector<int> dbg_flags, dbg_chain;
-    int info = 0;
-    int64_t npos = 0, nzero = 0, nneg = 0;
     std::unique_ptr<mnk_ls_alt> alt;   // QR / LU / EVD: the algorithm that factors and solves instead of the tiled path (null for CHOLESKY / LDL)
 };
 
@@ -319,8 +410,7 @@ double mnk_process_stall_ms();
 bool mnk_ls_pending_elsewhere(const mnk_ls* ls);   // dag.hip: queued in a factorization batch of ANOTHER thread
 bool mnk_batch_active();                           // dag.hip: the calling thread has a factorization batch open
 size_t mnk_pchain_sys_bytes();                     // factor.hip: size of one record of mnk_launch_pchain_multi's table
-int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, hipStream_t fill_stream, void* table, int* const* front,
-                            const int* const* af);   // factor.hip: the chains of n small systems in one launch
+int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, void* table);   // factor.hip: the chains of n small systems in one launch (table: n records of mnk_pchain_fill_sys, uploaded)
 bool mnk_batch_defer(mnk_ls* ls);                  // dag.hip: true if the calling thread has a batch open and took the factorization into it
 int mnk_ls_sync_deferred(mnk_ls* ls);              // dag.hip: runs what the open batches of this thread hold for this solver (queued solves, a pending factorization)
 int mnk_ls_sync_deferred_fact(mnk_ls* ls);         // dag.hip: ... the pending factorization only
@@ -328,7 +418,6 @@ int mnk_ls_fetch_info(mnk_ls* ls);
 int mnk_ls_run_factorization_dag(mnk_ls* ls);   // dag.hip: the task-DAG schedule (panel_algo = 5)
 int mnk_ls_dag_prepare(mnk_ls* ls);             // dag.hip: its buffers (0: ready; otherwise the device cannot hold them -> schedule 4)
 int mnk_launch_pchain(mnk_ls* ls, hipStream_t sp, const mnk::PpDag& dag, int js_begin, int js_end, unsigned strips);  // factor.hip
-unsigned long long* mnk_ls_growth_word(mnk_ls* ls);  // factor.hip: where the kernels fold max(|d|, |v|) (NULL: guard off)
 int mnk_ls_run_solve(mnk_ls* ls, double* xdev /* the solver's work vector */, double* xuser = nullptr /* N entries on the device, or NULL: xdev holds the padded rhs */);
 int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);  // 256x256 triangles of the strip-columns [sc0, sc1)
 int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);   // 64x64 blocks + 256x256 triangles
@@ -336,7 +425,6 @@ int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);  
 // starts at column j0: V = B L_jj^-T, X = V D^-1 (LDL) / X = B L_jj^-T (Cholesky).  B is read from / X written to
 // Xrows(:, j0:j0+64), V written to Vrows(:, j0:j0+64) (LDL only); both row blocks have leading dimension ldr.
 int mnk_ls_right_trsm_rows(mnk_ls* ls, hipStream_t s, int64_t j0, double* Xrows, double* Vrows, int64_t ldr, int64_t nrows);
-int mnk_ls_run_bunchkaufman(mnk_ls* ls);                                  // bk.hip
 long mnk_ls_dag_spin_limit(const mnk_ls* ls);   // dag.hip
 namespace mnk {
 // One system of a batch of SMALL factorizations (dag.hip: batch_run_group_small): what the kernels around the shared chain
@@ -355,9 +443,4 @@ void mnk_ls_fill_small_rec(mnk_ls* ls, mnk::SmallSysRec* rec);                  
 void mnk_pchain_fill_sys(mnk_ls* ls, void* rec_host, int* front, const int* af);                               // factor.hip (one PcSys record)
 int mnk_launch_trsm64_batch(hipStream_t s, bool ldl, const mnk::TrsmBatchRec* recs_dev, int nbatch, int64_t j0, int64_t nrows,
                             int64_t ldr);   // factor.hip
-int mnk_ls_bk_permute(mnk_ls* ls, double* x, double* tmp, bool forward);  // x <- P x (forward) / P^T x
-int mnk_ls_bk_dsolve(mnk_ls* ls, double* y);                              // y <- D^-1 y, 1x1 / 2x2 blocks
-int mnk_ls_bk_inertia(mnk_ls* ls, unsigned long long* out_dev);
-// after a stream synchronization: true (and the solver switched to the stepwise solve, abort word cleared) if a
-// persistent solve gave up since the last check
-bool mnk_ls_take_solve_abort(mnk_ls* ls);
+inline bool mnk_ls_take_solve_abort(mnk_ls* ls) { return ls->solves.take_abort(); }   // (SolveState::take_abort, for the KKT units)

@@ -269,14 +269,6 @@ void mnk_ctx_child_gone(mnk_ctx* ctx) {
     if (free_now) ctx_free(ctx);
 }
 
-bool mnk_ls_take_solve_abort(mnk_ls* ls) {
-    if (!ls->solve_abort || *ls->solve_abort == 0) return false;
-    *ls->solve_abort = 0;
-    ls->persistent_solve = 0;
-    ls->pub_clean[0] = ls->pub_clean[1] = false;
-    return true;
-}
-
 extern "C" {
 
 int mnk_version(void) { return MNK_VERSION; }
@@ -606,7 +598,7 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     ls->ctx = ctx;
     ls->N = N;
     ls->algo = algo;
-    ls->bk_requested = bk_requested;
+    ls->bk.requested = bk_requested;
     // Tuning overrides from the environment, for runs of unmodified callers: MNK_OPTIONS="key=value,key=value" with the keys
     // of mnk_ls_set_option (plus MNK_PANEL_ALGO / MNK_PERSISTENT_SOLVE, the two a deployment may need: INTEGRATION.md).  An
     // option set this way is not changed by later mnk_ls_set_option calls.
@@ -643,13 +635,7 @@ int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     rc |= ls->dvec.alloc(ls->Np);
     rc |= ls->dinv.alloc(ls->Np);
     rc |= ls->xwork.alloc(10 * ls->Np);
-    if (hipHostMalloc((void**)&ls->solve_abort, sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        ls->solve_abort = nullptr;
-        rc |= -2;
-    } else {
-        *ls->solve_abort = 0;
-    }
+    rc |= ls->solves.create();
     if (hipHostMalloc((void**)&ls->pin, 8 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&ls->pin_dev, ls->pin, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -680,14 +666,14 @@ int mnk_ls_destroy(mnk_ls* ls) {
     }
     (void)mnk_ls_sync_deferred(ls);
     (void)mnk::stream_wait(ls->ctx->stream);
-    if (ls->probe_ls) { (void)mnk_ls_destroy(ls->probe_ls); ls->probe_ls = nullptr; }
+    ls->probe.destroy();
     mnk::LaunchLock lock;   // (host-memory frees and event destruction below; the device buffers lock for themselves)
     mnk::quiesce_persistent();
-    if (ls->solve_abort) (void)hipHostFree(ls->solve_abort);
+    ls->solves.destroy();
     if (ls->pin) (void)hipHostFree(ls->pin);
     ls->spare.destroy(ls->ctx);
     if (ls->ev_defer) (void)hipEventDestroy(ls->ev_defer);
-    if (ls->ev_info) (void)hipEventDestroy(ls->ev_info);
+    ls->verdict.destroy();
     mnk_ctx* ctx = ls->ctx;
     delete ls;
     mnk_ctx_child_gone(ctx);
@@ -722,8 +708,8 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         ls->wbuf[1].release();
         return 0;
     }
-    if (!strcmp(key, "solve512")) { ls->solve512 = value != 0; return 0; }   // 512-column steps of the one-launch solve
-    if (!strcmp(key, "linv_mfma")) { ls->linv_mfma = value != 0.0; return 0; }
+    if (!strcmp(key, "solve512")) { ls->solves.solve512 = value != 0; return 0; }   // 512-column steps of the one-launch solve
+    if (!strcmp(key, "linv_mfma")) { ls->solves.linv_mfma = value != 0.0; return 0; }
     if (!strcmp(key, "prefill")) { ls->spare.prefill = value != 0; return 0; }   // background zero-fill into a second factor buffer
     if (!strcmp(key, "single_rows")) {  // systems up to this order: one outer panel, no look-ahead (0: never)
         ls->single_rows = (int64_t)value;
@@ -782,14 +768,14 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     if (!strcmp(key, "dag_deep_rows")) { ls->dag_deep_rows = (int64_t)value; ls->plan.invalidate(); return 0; }   // largest order with every row in the chain's band
     // BUNCHKAUFMAN only: 1 (default) = refactor with the pivoted Bunch-Kaufman tier when the static-pivot
     // factorization breaks down; 0 = report the breakdown as num_zero and let the IPM regularize
-    if (!strcmp(key, "bk_fallback")) { ls->bk_fallback = (int)value; return 0; }
+    if (!strcmp(key, "bk_fallback")) { ls->bk.bk_fallback = (int)value; return 0; }
     if (!strcmp(key, "bk_panel_wgs")) {   // pivoted tier: 0 = a workgroup per 256 rows of a panel, 1 = one workgroup per panel
         MNK_REQUIRE(value == 0.0 || value == 1.0, "bk_panel_wgs must be 0 or 1");
-        ls->bk_panel_wgs = (int)value;
+        ls->bk.bk_panel_wgs = (int)value;
         return 0;
     }
     if (!strcmp(key, "accept_only_pd")) { ls->accept_only_pd = value != 0; return 0; }  // see mnk_ls_fetch_info
-    if (!strcmp(key, "probe")) { ls->probe = value != 0; return 0; }   // leading-block probe in front of a factorization that is likely to be rejected early (ls.h)
+    if (!strcmp(key, "probe")) { ls->probe.on = value != 0; return 0; }   // leading-block probe in front of a factorization that is likely to be rejected early (ls.h)
     if (!strcmp(key, "early_reject")) { ls->early_reject = value != 0; return 0; }      // with accept_only_pd: stop at the first non-positive pivot (leaf64.h)
     // BUNCHKAUFMAN only: element growth max|d_k| / max|a_ij| of the static-pivot tier above which the pivoted tier takes over
     if (!strcmp(key, "dag_debug")) {
@@ -803,42 +789,42 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     }
     if (!strcmp(key, "bk_max_wgs")) {
         MNK_REQUIRE(value >= 0.0 && value <= 256.0, "bk_max_wgs must be in 0..256");
-        ls->bk_max_wgs = (int)value;
+        ls->bk.bk_max_wgs = (int)value;
         return 0;
     }
     if (!strcmp(key, "bk_spin_limit")) {
         MNK_REQUIRE(value >= 1024.0, "bk_spin_limit must be at least 1024");
-        ls->bk_spin_limit = (long)value;
+        ls->bk.bk_spin_limit = (long)value;
         return 0;
     }
-    if (!strcmp(key, "debug_bk_missing")) { ls->debug_bk_missing = (int)value; return 0; }
+    if (!strcmp(key, "debug_bk_missing")) { ls->bk.debug_bk_missing = (int)value; return 0; }
     if (!strcmp(key, "bk_growth_tol")) {
         MNK_REQUIRE(value > 1.0, "bk_growth_tol must be > 1");
-        ls->bk_growth_tol = value;
+        ls->bk.bk_growth_tol = value;
         return 0;
     }
     if (!strcmp(key, "bk_growth_tol_qd")) {  // the same for pivot sequences "all positive, then all negative"
         MNK_REQUIRE(value > 1.0, "bk_growth_tol_qd must be > 1");
-        ls->bk_growth_tol_qd = value;
+        ls->bk.bk_growth_tol_qd = value;
         return 0;
     }
-    if (!strcmp(key, "persistent_solve")) { ls->persistent_solve = value != 0.0; return 0; }
+    if (!strcmp(key, "persistent_solve")) { ls->solves.persistent_solve = value != 0.0; return 0; }
     if (!strcmp(key, "ps_spin_limit")) {  // polls a persistent-solve wait may take before it gives up
         MNK_REQUIRE(value >= 1024.0, "ps_spin_limit must be at least 1024");
-        ls->ps_spin_limit = (long)value;
+        ls->solves.ps_spin_limit = (long)value;
         return 0;
     }
     // tests only: workgroup `value` of every persistent solve leaves at once, as a peer that never became
     // resident would (< 0: off); the others must give up after ps_spin_limit polls instead of hanging
     if (!strcmp(key, "debug_pp_missing")) { ls->debug_pp_missing = (int)value; return 0; }
-    if (!strcmp(key, "debug_ps_missing")) { ls->debug_ps_missing = (int)value; return 0; }
+    if (!strcmp(key, "debug_ps_missing")) { ls->solves.debug_ps_missing = (int)value; return 0; }
     if (!strcmp(key, "solve_trace")) {  // diagnostics: time stamps of the forward sweep's critical path
         if (value != 0.0) {
-            int rc = ls->solve_trace.alloc((size_t)(ls->Np / 64) * 8);
+            int rc = ls->solves.trace.alloc((size_t)(ls->Np / 64) * 8);
             if (rc) return rc;
-            MNK_HIP(hipMemset(ls->solve_trace.p, 0, (size_t)(ls->Np / 64) * 8 * sizeof(unsigned long long)));
+            MNK_HIP(hipMemset(ls->solves.trace.p, 0, (size_t)(ls->Np / 64) * 8 * sizeof(unsigned long long)));
         } else {
-            ls->solve_trace.release();
+            ls->solves.trace.release();
         }
         return 0;
     }
@@ -857,10 +843,10 @@ static int ensure_wbuf(mnk_ls* ls) {
 
 // The word that receives max|a_ij| of the matrix being transferred (zeroed here), or NULL when nobody will ask for it.
 static unsigned long long* amax_word(mnk_ls* ls) {
-    if (!(ls->bk_requested && ls->bk_fallback && ls->algo == MNK_LDL)) return nullptr;
-    if (!ls->amax_dev.p && ls->amax_dev.alloc(AMAX_WORDS)) return nullptr;
-    (void)hipMemsetAsync(ls->amax_dev.p, 0, AMAX_WORDS * sizeof(unsigned long long), ls->ctx->stream);
-    return ls->amax_dev.p;
+    if (!ls->bk.wanted(ls)) return nullptr;
+    if (!ls->bk.amax_dev.p && ls->bk.amax_dev.alloc(AMAX_WORDS)) return nullptr;
+    (void)hipMemsetAsync(ls->bk.amax_dev.p, 0, AMAX_WORDS * sizeof(unsigned long long), ls->ctx->stream);
+    return ls->bk.amax_dev.p;
 }
 
 }  // extern "C"
@@ -878,7 +864,7 @@ int SpareFill::acquire(mnk_ls* ls) {
         if (pre) MNK_HIP(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), s));  // (slack behind the matrix)
     }
     // (the fill was left to the task queue of the previous factorization, and nobody has looked at its `info` yet)
-    if (pre && state == State::ZeroedByDag && !ls->info_valid) state = State::Dirty;
+    if (pre && state == State::ZeroedByDag && !ls->verdict.known()) state = State::Dirty;
     if (pre && zeroed()) {
         std::swap(ls->fact.p, buf.p);          // the buffer zeroed in the background becomes the factor buffer
         MNK_HIP(hipStreamWaitEvent(s, ev_zeroed, 0));
@@ -996,21 +982,35 @@ static int transfer_sc(mnk_ls* ls, mnk_sc* sc) {
 // positive pivots, everything else negative; a solve that comes all the same completes the factorization from the handle).
 static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
     *rejected = false;
-    if (!(ls->probe && ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->N == sc->n && !mnk_batch_active())) return 0;
-    if (ls->probe_last_rejected || ls->probe_hint_col < 0 || ls->probe_since_hint > 3) return 0;
-    const int64_t m = (ls->probe_hint_col + 256) / 256 * 256;
-    if (m < 512 || 2 * m > ls->N) return 0;
-    if (ls->probe_ls == nullptr || ls->probe_order != m) {
-        if (ls->probe_ls) { (void)mnk_ls_destroy(ls->probe_ls); ls->probe_ls = nullptr; }
-        mnk_ls* child = nullptr;
-        if (mnk_ls_create(ls->ctx, m, ls->algo, &child) != 0) { (void)hipGetLastError(); return 0; }   // (no memory for it: no probe)
-        child->probe = 0;
-        child->accept_only_pd = 1;
-        child->early_reject = 1;
-        ls->probe_ls = child;
-        ls->probe_order = m;
+    if (!(ls->probe.on && ls->early_reject && ls->accept_only_pd && ls->algo == MNK_LDL && ls->N == sc->n && !mnk_batch_active())) return 0;
+    const int64_t m = ls->probe.order_due(ls->N);
+    mnk_ls* c = m > 0 ? ls->probe.child(ls, m) : nullptr;
+    if (c == nullptr) return 0;
+    int rc = mnk_ls_factorize_sc_async(c, sc);
+    if (!rc) rc = mnk_ls_fetch_info(c);
+    if (rc) return rc;
+    const FactorVerdict& cv = c->verdict;
+    if (cv.npos == m && cv.nzero == 0 && cv.nneg == 0) { ++ls->probe.misses; return 0; }
+    // not positive definite: the verdict, without the full factorization (the factor buffer still holds the PREVIOUS matrix's
+    // factor: a solve that comes all the same goes through ensure_complete_factor)
+    ++ls->probe.hits;
+    ls->verdict.reject_early(cv.npos, cv.nzero, ls->N, cv.usable() ? m - 1 : cv.early_reject_col);
+    ls->probe.note_verdict(true, ls->verdict.early_reject_col, ls->N);
+    *rejected = true;
+    return 0;
+}
+
+// ---- LeadingBlockProbe (ls.h): the child solver ----
+mnk_ls* LeadingBlockProbe::child(mnk_ls* ls, int64_t m) {
+    if (ls_child == nullptr || order != m) {
+        destroy();
+        if (mnk_ls_create(ls->ctx, m, ls->algo, &ls_child) != 0) { (void)hipGetLastError(); ls_child = nullptr; return nullptr; }   // (no memory for it: no probe)
+        ls_child->probe.on = 0;
+        ls_child->accept_only_pd = 1;
+        ls_child->early_reject = 1;
+        order = m;
     }
-    mnk_ls* c = ls->probe_ls;
+    mnk_ls* c = ls_child;
     // (the options that decide a verdict follow the parent's at every probe, not at the child's creation: a pivot_tol lowered
     // since then would otherwise count a small positive pivot of the block as zero and reject what the parent accepts)
     c->pivot_tol = ls->pivot_tol;
@@ -1021,26 +1021,7 @@ static int probe_leading_block(mnk_ls* ls, mnk_sc* sc, bool* rejected) {
         c->dag_gang = ls->dag_gang;
         c->plan.invalidate();
     }
-    int rc = mnk_ls_factorize_sc_async(c, sc);
-    if (!rc) rc = mnk_ls_fetch_info(c);
-    if (rc) return rc;
-    if (c->npos == m && c->nzero == 0 && c->nneg == 0) { ++ls->probe_misses; return 0; }
-    // not positive definite: the verdict, without the full factorization
-    ++ls->probe_hits;
-    ++ls->early_rejects;
-    ls->early_reject_col = c->factor_invalid ? c->early_reject_col : m - 1;
-    ls->info = 1;
-    ls->npos = c->npos;
-    ls->nzero = c->nzero;
-    ls->nneg = ls->N - ls->npos - ls->nzero;
-    ls->factor_invalid = true;
-    ls->info_valid = true;
-    ls->factorized = true;
-    ls->bk_active = false;
-    ls->probe_last_rejected = true;
-    if (2 * ls->early_reject_col < ls->N) { ls->probe_hint_col = ls->early_reject_col; ls->probe_since_hint = 0; }
-    *rejected = true;
-    return 0;
+    return c;
 }
 
 int mnk_ls_factorize_sc_async(mnk_ls* ls, mnk_sc* sc) {
@@ -1112,7 +1093,7 @@ int mnk_ls_factorize_dc_async(mnk_ls* ls, mnk_dc* dc) {
 static int finish_info(mnk_ls* ls, int* info) {
     int rc = mnk_ls_fetch_info(ls);
     if (rc) return rc;
-    if (info) *info = ls->info;
+    if (info) *info = ls->verdict.info;
     return 0;
 }
 
@@ -1215,17 +1196,27 @@ int mnk_debug_tile_envh_csc(int64_t n, const int32_t* colptr, const int32_t* row
     return debug_envelope_csc(n, colptr, rowval, index_base, out, cap, 64);
 }
 
+int mnk_debug_probe_schedule(int64_t N, int n, const int64_t* cols, int64_t* orders) {
+    if (N <= 0 || n < 0 || (n > 0 && (cols == nullptr || orders == nullptr))) return -1;
+    LeadingBlockProbe probe;
+    for (int i = 0; i < n; ++i) {
+        orders[i] = probe.order_due(N);
+        probe.note_verdict(cols[i] >= 0, cols[i], N);
+    }
+    return 0;
+}
+
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg) {
     MNK_REQUIRE(ls, "mnk_ls_inertia: NULL argument");
     if (ls->alt) { const char* refusal = ls->alt->no_inertia_message(); MNK_REQUIRE(refusal == nullptr, refusal); }
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    MNK_REQUIRE(ls->factorized, "mnk_ls_inertia: factorize first");
+    MNK_REQUIRE(ls->verdict.has_factorization(), "mnk_ls_inertia: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     int rc = mnk_ls_fetch_info(ls);
     if (rc) return rc;
-    if (num_pos) *num_pos = ls->npos;
-    if (num_zero) *num_zero = ls->nzero;
-    if (num_neg) *num_neg = ls->nneg;
+    if (num_pos) *num_pos = ls->verdict.npos;
+    if (num_zero) *num_zero = ls->verdict.nzero;
+    if (num_neg) *num_neg = ls->verdict.nneg;
     return 0;
 }
 
@@ -1249,8 +1240,8 @@ int mnk_ls_check_solve(mnk_ls* ls) {
 // followed by solve_refine_wrapper! without inertia_correction!).  The matrix is then factored again, to the end: early
 // rejection is an optimization of the rejected trials, never a change of what the solver can do.
 static int ensure_complete_factor(mnk_ls* ls, const char* who) {
-    if (ls->reject_on_device == 1) { int rc_i = mnk_ls_fetch_info(ls); if (rc_i) return rc_i; }   // (known when the pivots are)
-    if (!ls->factor_invalid) return 0;
+    if (ls->verdict.reject_armed()) { int rc_i = mnk_ls_fetch_info(ls); if (rc_i) return rc_i; }   // (known when the pivots are)
+    if (ls->verdict.usable()) return 0;
     { static const bool peek = getenv("MNK_DBG_NO_REDO") != nullptr; if (peek) return 0; }   // (diagnostics: look at what a rejected factorization left)
     if (!ls->src.retransfer) {
         set_error("%s: the last factorization was stopped at its first non-positive pivot (early_reject) and its source is gone: "
@@ -1263,25 +1254,22 @@ static int ensure_complete_factor(mnk_ls* ls, const char* who) {
     if (!rc) rc = mnk_ls_run_factorization(ls);
     if (!rc) rc = mnk_ls_fetch_info(ls);
     ls->early_reject = keep;
-    ++ls->early_reject_redone;
+    ls->verdict.completed_after_all();
     return rc;
 }
 
 int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
     MNK_REQUIRE(ls && x, "mnk_ls_solve: NULL argument");
     { int rc_d = mnk_ls_sync_deferred_fact(ls); if (rc_d) return rc_d; }
-    MNK_REQUIRE(ls->factorized, "mnk_ls_solve: factorize first");
+    MNK_REQUIRE(ls->verdict.has_factorization(), "mnk_ls_solve: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_f = ensure_complete_factor(ls, "mnk_ls_solve"); if (rc_f) return rc_f; }
     MNK_REQUIRE(nrhs >= 1 && ldx >= ls->N, "mnk_ls_solve: bad nrhs/ldx");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     if (ls->alt) return mnk_ls_alt_solve(ls, x, nrhs, ldx, loc);   // (never queued in a solve batch: runs at once)
-    if (ls->solve_abort && *ls->solve_abort != 0) {
+    if (ls->solves.take_abort()) {
         // a previous solve on device-resident vectors gave up (its result is invalid): fail loudly now and use
         // the stepwise solve from here on
-        *ls->solve_abort = 0;
-        ls->persistent_solve = 0;
-        ls->pub_clean[0] = ls->pub_clean[1] = false;
         set_error("mnk_ls_solve: an earlier persistent solve on device-resident data gave up waiting for a peer "
                   "workgroup (device oversubscribed by another process?); its result is invalid -- refactorize/solve "
                   "again (persistent_solve is now off for this solver)");
@@ -1305,7 +1293,7 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
         MNK_HIP(mnk::h2d_copy(w, xk, N * sizeof(double), s));
         int rc = mnk_ls_run_solve(ls, w);
         if (rc) return rc;
-        if (loc != MNK_DEVICE && ls->persistent_solve) {
+        if (loc != MNK_DEVICE && ls->solves.persistent_solve) {
             // The one-launch solve gives up (instead of hanging the device) if its workgroups cannot all become
             // resident, e.g. another process saturates the GPU with its own persistent kernels.  The host still
             // owns the right-hand side here: redo this and all later solves with one launch per step.
@@ -1374,18 +1362,18 @@ int mnk_ls_debug_solve_trace(mnk_ls* ls, unsigned long long* out, int64_t n) {
         MNK_HIP(mnk::d2h_copy(out, ls->dag_trace.p, cnt * sizeof(unsigned long long), ls->ctx->stream));
         return 0;
     }
-    MNK_REQUIRE(ls && out && ls->solve_trace.p, "mnk_ls_debug_solve_trace: tracing is off (option solve_trace)");
+    MNK_REQUIRE(ls && out && ls->solves.trace.p, "mnk_ls_debug_solve_trace: tracing is off (option solve_trace)");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     MNK_HIP(mnk::stream_wait(ls->ctx->stream));
     const int64_t cnt = std::min<int64_t>(n, (ls->Np / 64) * 8);
-    MNK_HIP(mnk::d2h_copy(out, ls->solve_trace.p, cnt * sizeof(unsigned long long), ls->ctx->stream));
+    MNK_HIP(mnk::d2h_copy(out, ls->solves.trace.p, cnt * sizeof(unsigned long long), ls->ctx->stream));
     return 0;
 }
 
 int mnk_ls_get_factor(mnk_ls* ls, double* L, double* D, int loc) {
     MNK_REQUIRE(ls && L, "mnk_ls_get_factor: NULL argument");
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    MNK_REQUIRE(ls->factorized, "mnk_ls_get_factor: factorize first");
+    MNK_REQUIRE(ls->verdict.has_factorization(), "mnk_ls_get_factor: factorize first");
     { int rc_f = ensure_complete_factor(ls, "mnk_ls_get_factor"); if (rc_f) return rc_f; }
     MNK_HIP(hipSetDevice(ls->ctx->device));
     hipStream_t s = ls->ctx->stream;
@@ -1405,7 +1393,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     MNK_REQUIRE(ls && key && value, "mnk_ls_get_stat: NULL argument");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    if (ls->factorized) {
+    if (ls->verdict.has_factorization()) {
         int rc = mnk_ls_fetch_info(ls);
         if (rc) return rc;
     }
@@ -1417,19 +1405,19 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp.fallbacks; return 0; }
     // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
     if (!strcmp(key, "timeout_site")) { *value = ls->pp.last_site; return 0; }
-    if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe_hits; return 0; }       // matrices rejected by the leading-block probe alone
-    if (!strcmp(key, "probe_misses")) { *value = (double)ls->probe_misses; return 0; }   // probes that passed (the full factorization followed)
-    if (!strcmp(key, "early_rejects")) { *value = (double)ls->early_rejects; return 0; }       // factorizations stopped at their first non-positive pivot
-    if (!strcmp(key, "early_reject_redone")) { *value = (double)ls->early_reject_redone; return 0; }   // ... rejected factorizations completed after all because the caller solved
-    if (!strcmp(key, "early_reject_col")) { *value = (double)ls->early_reject_col; return 0; } // ... the last valid pivot of the latest one
+    if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe.hits; return 0; }       // matrices rejected by the leading-block probe alone
+    if (!strcmp(key, "probe_misses")) { *value = (double)ls->probe.misses; return 0; }   // probes that passed (the full factorization followed)
+    if (!strcmp(key, "early_rejects")) { *value = (double)ls->verdict.early_rejects; return 0; }       // factorizations stopped at their first non-positive pivot
+    if (!strcmp(key, "early_reject_redone")) { *value = (double)ls->verdict.early_reject_redone; return 0; }   // ... rejected factorizations completed after all because the caller solved
+    if (!strcmp(key, "early_reject_col")) { *value = (double)ls->verdict.early_reject_col; return 0; } // ... the last valid pivot of the latest one
     if (!strcmp(key, "stall_ms_total")) { *value = ls->stall_ms_total; return 0; }      // what this solver's expired waits (fall-backs) have cost, host ms
     if (!strcmp(key, "stall_ms_process")) { *value = mnk_process_stall_ms(); return 0; }  // ... all solvers of the process
-    if (!strcmp(key, "growth")) { *value = ls->last_growth; return 0; }  // BUNCHKAUFMAN: max|d_k| / max|a_ij| of the static-pivot tier
-    if (!strcmp(key, "sign_changes")) { *value = (double)ls->last_sign_changes; return 0; }  // ... and sign changes along its pivots
-    if (!strcmp(key, "bk_count")) { *value = ls->bk_count; return 0; }
+    if (!strcmp(key, "growth")) { *value = ls->bk.last_growth; return 0; }  // BUNCHKAUFMAN: max|d_k| / max|a_ij| of the static-pivot tier
+    if (!strcmp(key, "sign_changes")) { *value = (double)ls->bk.last_sign_changes; return 0; }  // ... and sign changes along its pivots
+    if (!strcmp(key, "bk_count")) { *value = ls->bk.count; return 0; }
     if (!strcmp(key, "evd_sweeps")) { *value = ls->alt ? ls->alt->stat(key) : 0.0; return 0; }   // EVD: block Jacobi sweeps of the last factorization
-    if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk_multi_last ? 1.0 : 0.0; return 0; }
-    if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk_mw_fallbacks; return 0; }
+    if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk.multi_last() ? 1.0 : 0.0; return 0; }
+    if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk.mw_fallbacks(); return 0; }
     if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain
     if (!strcmp(key, "dag_ntasks")) { *value = ls->plan.ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
     if (!strcmp(key, "dag_ntasks1")) { *value = ls->plan.ntasks1; return 0; }  // ... of them in the first phase, ...
@@ -1484,18 +1472,13 @@ int mnk_ls_bk_info(mnk_ls* ls, int* active, int* count, int32_t* perm, double* d
     MNK_REQUIRE(ls, "mnk_ls_bk_info: NULL argument");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    if (ls->factorized) {
+    if (ls->verdict.has_factorization()) {
         int rc = mnk_ls_fetch_info(ls);  // the tier is decided when the static factorization's pivots are known
         if (rc) return rc;
     }
-    if (active) *active = ls->bk_active ? 1 : 0;
-    if (count) *count = ls->bk_count;
-    if (ls->bk_active && (perm || doff)) {
-        hipStream_t s = ls->ctx->stream;
-        if (perm) MNK_HIP(mnk::d2h_copy(perm, ls->bk_perm.p, ls->N * sizeof(int32_t), s));
-        if (doff) MNK_HIP(mnk::d2h_copy(doff, ls->bk_doff.p, ls->N * sizeof(double), s));
-    }
-    return 0;
+    if (active) *active = ls->verdict.is_pivoted() ? 1 : 0;
+    if (count) *count = ls->bk.count;
+    return ls->verdict.is_pivoted() ? ls->bk.read_pivots(ls, perm, doff) : 0;
 }
 
 int mnk_gemm_nt(mnk_ctx* ctx, int mode, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,

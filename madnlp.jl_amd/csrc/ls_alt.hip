@@ -15,14 +15,10 @@ std::unique_ptr<mnk_ls_alt> mnk_ls_alt_new(int algo) {
 // factorize! (not merged into a factorization batch: runs when called; EVD also runs to its end before it returns)
 int mnk_ls_alt_factorize(mnk_ls* ls) {
     ++ls->pp.count;
-    ls->factor_invalid = false;
-    ls->bk_active = false;
     ls->t_fact_launch_ms = mnk_host_ms();
-    int rc = ls->alt->factor(ls);   // (sets ls->info: 0 for QR and LU, the sweep verdict for EVD)
+    int rc = ls->alt->factor(ls);
     if (rc) return rc;
-    ls->npos = ls->nzero = ls->nneg = 0;
-    ls->factorized = true;
-    ls->info_valid = false;
+    ls->verdict.queued();
     return 0;
 }
 

@@ -373,7 +373,6 @@ struct LuSolver final : mnk_ls_alt {
             }
         }
         MNK_HIP(hipGetLastError());
-        ls->info = 0;
         return 0;
     }
 
@@ -381,8 +380,7 @@ struct LuSolver final : mnk_ls_alt {
     int fetch_info(mnk_ls* ls) override {
         int info = 0;
         MNK_HIP(d2h_copy(&info, lu_info.p, sizeof(int), ls->ctx->stream));
-        ls->info = info;
-        ls->info_valid = true;
+        ls->verdict.accept(info, 0, 0, 0);
         return 0;
     }
 
@@ -424,7 +422,7 @@ int mnk_ls_get_pivots(mnk_ls* ls, int64_t* ipiv, int loc) {
     MNK_REQUIRE(ls && ipiv, "mnk_ls_get_pivots: NULL argument");
     MNK_REQUIRE(ls->algo == MNK_LU, "mnk_ls_get_pivots: only an LU factorization has row interchanges");
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }
-    MNK_REQUIRE(ls->factorized, "mnk_ls_get_pivots: factorize first");
+    MNK_REQUIRE(ls->verdict.has_factorization(), "mnk_ls_get_pivots: factorize first");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     hipStream_t s = ls->ctx->stream;
     const int64_t N = ls->N;

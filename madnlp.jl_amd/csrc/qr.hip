@@ -454,14 +454,13 @@ struct QrSolver final : mnk_ls_alt {
             }
         }
         MNK_HIP(hipGetLastError());
-        ls->info = 0;
         return 0;
     }
 
-    // geqrf's info is always 0 (factor set it); a singular matrix shows up in the solve
+    // geqrf's info is always 0; a singular matrix shows up in the solve
     int fetch_info(mnk_ls* ls) override {
         MNK_HIP(stream_wait(ls->ctx->stream));
-        ls->info_valid = true;
+        ls->verdict.accept(0, 0, 0, 0);
         return 0;
     }
 

@@ -315,8 +315,8 @@ int mnk_schur_build_local(mnk_schur* h, const double* S0, int64_t lds0, int loc_
     for (int64_t k = 0; k < h->ns; ++k) {
         int rc = mnk_ls_fetch_info(h->ls_k[k]);
         if (rc) return rc;
-        h->info_k[k] = h->ls_k[k]->info;
-        const bool grouped = !h->ls_k[k]->bk_active && h->info_k[k] == 0 && h->ls_k[k]->algo == h->ls_k[0]->algo &&
+        h->info_k[k] = h->ls_k[k]->verdict.info;
+        const bool grouped = !h->ls_k[k]->verdict.is_pivoted() && h->info_k[k] == 0 && h->ls_k[k]->algo == h->ls_k[0]->algo &&
                              h->ls_k[k]->ld == h->ls_k[0]->ld;
         (grouped ? fast : slow).push_back((int)k);
     }

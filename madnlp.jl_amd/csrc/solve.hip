@@ -966,7 +966,7 @@ using namespace mnk;
 int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
     const int64_t nblk = std::min<int64_t>(sc1, (ls->Np + SB - 1) / SB) - sc0;
     if (nblk <= 0) return 0;
-    if (!ls->linv_mfma)
+    if (!ls->solves.linv_mfma)
         hipLaunchKernelGGL(linv_tri_kernel<256>, dim3((unsigned)nblk, 4, 4), dim3(256), 0, s, ls->fact.p, ls->ld, ls->linv.p,
                            ls->linv256.p, ls->linv256t.p, ls->Np, ls->info_dev.p, (int)sc0);
     else
@@ -978,15 +978,15 @@ int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
     // (a 512 x 512 triangle inverted block by block with the scalar kernel above costs 35 dependent 64x64x16 products:
     // +0.63 ms on factorize! at C3, measured).
     constexpr int64_t SOLVE512_MIN_ROWS = 4096;
-    if (ls->solve512 && ls->Np >= SOLVE512_MIN_ROWS && ls->Np % 512 != 384 && !ls->linv512.p) {
+    if (ls->solves.solve512 && ls->Np >= SOLVE512_MIN_ROWS && ls->Np % 512 != 384 && !ls->solves.linv512.p) {
         const size_t ntri = (size_t)((ls->Np + 511) / 512);
-        if (ls->linv512.alloc(ntri * 512 * 512) || ls->linv512t.alloc(ntri * 512 * 512) || ls->linv512tmp.alloc(ntri * 256 * 256)) {
+        if (ls->solves.linv512.alloc(ntri * 512 * 512) || ls->solves.linv512t.alloc(ntri * 512 * 512) || ls->solves.linv512tmp.alloc(ntri * 256 * 256)) {
             (void)hipGetLastError();
-            ls->linv512.release(); ls->linv512t.release(); ls->linv512tmp.release();
-            ls->solve512 = 0;
+            ls->solves.linv512.release(); ls->solves.linv512t.release(); ls->solves.linv512tmp.release();
+            ls->solves.solve512 = 0;
         }
     }
-    if (ls->solve512 && ls->linv512.p) {
+    if (ls->solves.solve512 && ls->solves.linv512.p) {
         const int64_t nsc = (ls->Np + SB - 1) / SB;
         const int64_t t0 = (sc0 + 1) / 2, t1 = std::min<int64_t>(sc1, nsc) == nsc ? (ls->Np + 511) / 512 : sc1 / 2;
         if (t1 > t0) {
@@ -1000,12 +1000,12 @@ int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
                 MNK_HIP(hipFuncSetAttribute((const void*)inv512_gemm_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
                 attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
             }
-            hipLaunchKernelGGL(inv512_assemble_kernel, dim3(nt, 512), dim3(512), 0, s, ls->linv256.p, ls->linv256t.p, ls->linv512.p,
-                               ls->linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
+            hipLaunchKernelGGL(inv512_assemble_kernel, dim3(nt, 512), dim3(512), 0, s, ls->linv256.p, ls->linv256t.p, ls->solves.linv512.p,
+                               ls->solves.linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
             hipLaunchKernelGGL(inv512_gemm_kernel<1>, dim3(nt, 4, 1), dim3(256), smem, s, ls->fact.p, ls->ld, ls->linv256.p, ls->linv256t.p,
-                               ls->linv512tmp.p, ls->linv512.p, ls->linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
+                               ls->solves.linv512tmp.p, ls->solves.linv512.p, ls->solves.linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
             hipLaunchKernelGGL(inv512_gemm_kernel<2>, dim3(nt, 4, 2), dim3(256), smem, s, ls->fact.p, ls->ld, ls->linv256.p, ls->linv256t.p,
-                               ls->linv512tmp.p, ls->linv512.p, ls->linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
+                               ls->solves.linv512tmp.p, ls->solves.linv512.p, ls->solves.linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
         }
     }
     MNK_HIP(hipGetLastError());
@@ -1036,6 +1036,23 @@ int mnk_solve_warmup(hipStream_t s) {
     return 0;
 }
 
+// ---- SolveState (ls.h): the pinned abort word and the one answer to a solve that gave up ----
+int SolveState::create() {
+    if (hipHostMalloc((void**)&abort, sizeof(int), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); abort = nullptr; return -2; }
+    *abort = 0;
+    return 0;
+}
+
+void SolveState::destroy() { if (abort) (void)hipHostFree(abort); abort = nullptr; }
+
+bool SolveState::take_abort() {
+    if (!abort_raised()) return false;
+    *abort = 0;
+    persistent_solve = 0;
+    pub_clean[0] = pub_clean[1] = false;
+    return true;
+}
+
 // xdev: the solver's work vector (10*Np doubles: x | y | two publication buffers of 4*Np).
 // xuser == NULL: on entry xdev[0:Np] = rhs (zero padded); on exit xdev[0:Np] = solution.
 // xuser != NULL: a device vector of N entries, rhs on entry, solution on exit; the one-launch solve reads and writes it
@@ -1049,11 +1066,11 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     // Bunch-Kaufman factor (bk.hip): P A P^T = L D L^T with 2x2 blocks in D -- gather, stepwise unit-lower sweeps,
     // block-diagonal D^-1, scatter (a 2x2 block may straddle two 64-row blocks, which the one-launch solve's
     // block ownership does not allow)
-    const bool bk = ls->bk_active;
-    const bool persistent = !bk && ls->persistent_solve && G >= 1 && (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G);
+    const bool bk = ls->verdict.is_pivoted();
+    const bool persistent = !bk && ls->solves.persistent_solve && G >= 1 && (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G);
     const int64_t nb32 = Np / P5_RB;
     const int G5 = (int)std::min<int64_t>(nb32, ls->ctx->num_cu);
-    const bool use512 = persistent && ls->solve512 && ls->linv512.p && (nb32 + G5 - 1) / G5 <= PS_MAXOWN && (G5 >= P5_NBS || nb32 <= G5);
+    const bool use512 = persistent && ls->solves.solve512 && ls->solves.linv512.p && (nb32 + G5 - 1) / G5 <= PS_MAXOWN && (G5 >= P5_NBS || nb32 <= G5);
     const bool direct = persistent && !use512;
     auto stage_in = [&]() -> int {
         if (xuser != nullptr) hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, xdev, xuser, N, Np);
@@ -1071,8 +1088,8 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     if (bk) {
         // (the permutation's scratch is the first publication buffer of the one-launch solve: it no longer holds the sentinel --
         // a later solve on the static-pivot tier must reset it before it polls it)
-        ls->pub_clean[0] = false;
-        int rc = mnk_ls_bk_permute(ls, xdev, xdev + 2 * Np, true);
+        ls->solves.dirtied(0);
+        int rc = ls->bk.permute(ls, xdev, xdev + 2 * Np, true);
         if (rc) return rc;
     }
     if (persistent) {
@@ -1084,48 +1101,45 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
         const int ps_near = PS_NEAR, ps_nap = 6;
         double* pubs[2] = {xdev + 2 * Np, xdev + 6 * Np};
         auto ensure_clean = [&](int b) {
-            if (!ls->pub_clean[b])
+            if (ls->solves.reset_due(b))
                 hipLaunchKernelGGL(ps_reset_kernel, dim3((unsigned)((4 * Np + 255) / 256)), dim3(256), 0, s,
                                    reinterpret_cast<unsigned long long*>(pubs[b]), 4 * Np);
-            ls->pub_clean[b] = true;
         };
         if (use512) {
             // steps of 512 columns, blocks of 32 rows (half the steps, the same two hops per step)
-            ls->pub_clean[0] = false;
+            ls->solves.dirtied(0);
             ensure_clean(0);
             double* pub = pubs[0];
             if (ldl)
-                hipLaunchKernelGGL(persistent_solve512_kernel<true>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->linv512.p,
-                                   ls->linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solve_abort, ls->info_dev.p, ps_near, ps_nap,
-                                   ls->ps_spin_limit, ls->debug_ps_missing);
+                hipLaunchKernelGGL(persistent_solve512_kernel<true>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->solves.linv512.p,
+                                   ls->solves.linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solves.abort_word(), ls->info_dev.p, ps_near, ps_nap,
+                                   ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
             else
-                hipLaunchKernelGGL(persistent_solve512_kernel<false>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->linv512.p,
-                                   ls->linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solve_abort, ls->info_dev.p, ps_near, ps_nap,
-                                   ls->ps_spin_limit, ls->debug_ps_missing);
-            ls->pub_clean[0] = false;
+                hipLaunchKernelGGL(persistent_solve512_kernel<false>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->solves.linv512.p,
+                                   ls->solves.linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solves.abort_word(), ls->info_dev.p, ps_near, ps_nap,
+                                   ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
+            ls->solves.dirtied(0);
             rc = hipGetLastError() == hipSuccess ? 0 : -2;
             rc = mnk_persist_end(ls->ctx, s, rc);
             return rc ? rc : stage_out();
         }
         // two publication buffers: this solve polls `cur` (all sentinel) and fills `oth` with the sentinel for the next one
-        const int cur = ls->pub_next, oth = cur ^ 1;
+        const int cur = ls->solves.poll_buffer(), oth = cur ^ 1;
         ensure_clean(cur);
         const double* xin = xuser != nullptr ? xuser : xdev;
         double* xout = xuser != nullptr ? xuser : xdev;
         const int64_t nio = xuser != nullptr ? N : Np;
         if (ldl)
             hipLaunchKernelGGL(persistent_solve_kernel<true>, dim3(G), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->linv256.p,
-                               ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solve_abort, ls->info_dev.p,
-                               ls->solve_trace.p, ps_near, ps_nap, ls->ps_spin_limit, ls->debug_ps_missing);
+                               ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solves.abort_word(), ls->info_dev.p,
+                               ls->solves.trace.p, ps_near, ps_nap, ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
         else
             hipLaunchKernelGGL(persistent_solve_kernel<false>, dim3(G), dim3(PS_NT), 0, s, ls->fact.p, ld,
-                               ls->linv256.p, ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solve_abort,
-                               ls->info_dev.p, ls->solve_trace.p, ps_near, ps_nap, ls->ps_spin_limit,
-                               ls->debug_ps_missing);
-        ls->pub_clean[cur] = false;
-        // (a test's "missing" workgroup does not clear its blocks either; a solve that gives up marks both buffers dirty: mnk_ls_take_solve_abort)
-        ls->pub_clean[oth] = ls->debug_ps_missing < 0;
-        ls->pub_next = oth;
+                               ls->linv256.p, ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solves.abort_word(),
+                               ls->info_dev.p, ls->solves.trace.p, ps_near, ps_nap, ls->solves.ps_spin_limit,
+                               ls->solves.debug_ps_missing);
+        // (a test's "missing" workgroup does not clear its blocks either; a solve that gives up marks both buffers dirty: take_abort)
+        ls->solves.solve_queued(ls->solves.debug_ps_missing < 0);
         rc = hipGetLastError() == hipSuccess ? 0 : -2;
         return mnk_persist_end(ls->ctx, s, rc);
     }
@@ -1144,7 +1158,7 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     }
     // L D L^T: z = D^-1 y before the backward sweep
     if (bk) {
-        int rc = mnk_ls_bk_dsolve(ls, y);
+        int rc = ls->bk.dsolve(ls, y);
         if (rc) return rc;
     } else if (ldl)
         hipLaunchKernelGGL(scale_vec_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, y, ls->dinv.p, Np);
@@ -1159,8 +1173,8 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     }
     MNK_HIP(hipGetLastError());
     if (bk) {
-        ls->pub_clean[0] = false;
-        int rc = mnk_ls_bk_permute(ls, xdev, xdev + 2 * Np, false);
+        ls->solves.dirtied(0);
+        int rc = ls->bk.permute(ls, xdev, xdev + 2 * Np, false);
         if (rc) return rc;
     }
     return stage_out();
@@ -1185,9 +1199,9 @@ constexpr int PS_BATCH_MAXQ = 32;
 static bool solve_eligible(const mnk_ls* ls) {
     const int64_t nb64 = ls->Np / 64;
     const int G = (int)std::min<int64_t>(nb64, ls->ctx->num_cu);
-    return !ls->bk_active && ls->persistent_solve && !(ls->solve512 && ls->linv512.p) && !ls->ctx->partitioned &&
-           (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G) && !(ls->solve_abort && *ls->solve_abort != 0) &&
-           ls->debug_ps_missing < 0 && !ls->solve_trace.p;
+    return !ls->verdict.is_pivoted() && ls->solves.persistent_solve && !(ls->solves.solve512 && ls->solves.linv512.p) && !ls->ctx->partitioned &&
+           (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G) && !ls->solves.abort_raised() &&
+           ls->solves.debug_ps_missing < 0 && !ls->solves.trace.p;
 }
 
 bool mnk_solve_defer(mnk_ls* ls, double* xuser) {
@@ -1219,22 +1233,20 @@ static int solve_batch_launch(const std::vector<SolveReq>& v) {
         for (int i = 0; i < q; ++i) {
             mnk_ls* ls = v[i].ls;
             double* pubs[2] = {ls->xwork.p + 2 * Np, ls->xwork.p + 6 * Np};
-            const int cur = ls->pub_next, oth = cur ^ 1;
-            if (!ls->pub_clean[cur])
+            const int cur = ls->solves.poll_buffer(), oth = cur ^ 1;
+            if (ls->solves.reset_due(cur))
                 hipLaunchKernelGGL(ps_reset_kernel, dim3((unsigned)((4 * Np + 255) / 256)), dim3(256), 0, h,
                                    reinterpret_cast<unsigned long long*>(pubs[cur]), 4 * Np);
             PsSys rec{ls->fact.p, ls->ld, ls->linv256.p, ls->linv256t.p, ls->dinv.p, v[i].x, v[i].x, ls->N, pubs[cur], pubs[oth],
-                      ls->solve_abort, ls->info_dev.p};
+                      ls->solves.abort_word(), ls->info_dev.p};
             hipLaunchKernelGGL(ps_set_sys_kernel, dim3(1), dim3(1), 0, h, rec, dsys + i);
-            ls->pub_clean[cur] = false;
-            ls->pub_clean[oth] = true;
-            ls->pub_next = oth;
+            ls->solves.solve_queued(true);
         }
         const bool ldl = l0->algo == MNK_LDL;
         if (ldl)
-            hipLaunchKernelGGL(persistent_solve_multi_kernel<true>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->ps_spin_limit);
+            hipLaunchKernelGGL(persistent_solve_multi_kernel<true>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->solves.ps_spin_limit);
         else
-            hipLaunchKernelGGL(persistent_solve_multi_kernel<false>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->ps_spin_limit);
+            hipLaunchKernelGGL(persistent_solve_multi_kernel<false>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->solves.ps_spin_limit);
         MNK_HIP(hipGetLastError());
         return 0;
     };

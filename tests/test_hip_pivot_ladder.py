@@ -411,6 +411,39 @@ def test_probe_follows_the_parents_pivot_tol(ctx):
     assert res[1][2] == 1, tag + f": the last matrix was not probed ({res[1][2]} probes)"   # (the fix was exercised)
 
 
+def test_solve_after_a_probe_hit_completes_the_factorization(ctx):
+    """N = 1300 (the parent on the task-DAG schedule, the child of order 512 on schedule 4): a rejection at pivot 300, an acceptance,
+    the same rejection again -- the last one is the probe's alone, so the factor buffer still holds the factor of the ACCEPTED
+    matrix.  A solve on it must transfer the rejected matrix and factor it to the end: the inertia after that, the count of such
+    redos and the solution are the bits of a solver with the probe off, and so are the verdict and its column before the solve."""
+    n = 1300
+    pos = make_exact(n, 9200 + n)
+    pat = pos.lower_pattern()
+    bad = with_pivot(pos, 300, -pos.d[300])
+    b = np.random.default_rng(n).standard_normal(n)
+    res = {}
+    for probe in (0, 1):
+        K = _KKT(ctx, n, mj.BUNCHKAUFMAN, pat)
+        K.M.set_option("probe", probe)
+        try:
+            before = _verdicts(K, [bad, pos])
+            hits = K.M.get_stat("probe_hits")
+            before += _verdicts(K, [bad])
+            hit = K.M.get_stat("probe_hits") - hits
+            x = K.M.solve_linear_system(b.copy())
+            res[probe] = (before, hit, x, np.array(K.M.inertia()), K.M.get_stat("early_reject_redone"))
+        finally:
+            K.close()
+    tag = f"N={n} path=kkt alg=BUNCHKAUFMAN kind=probe hit + solve col=300"
+    assert (res[0][1], res[1][1]) == (0, 1), tag + f": probe hits at the last step, off {res[0][1]}, on {res[1][1]}"
+    assert res[0][0] == res[1][0], tag + f": verdicts before the solve, probe off {res[0][0]}, on {res[1][0]}"
+    assert res[1][0][2][2] == 300 // 64 * 64 + 63 and not res[1][0][2][1], tag + f": {res[1][0][2]}"
+    assert np.array_equal(res[0][3], res[1][3]), tag + f": inertia after the redo, probe off {res[0][3]}, on {res[1][3]}"
+    assert np.array_equal(res[0][3], np.array(bad.inertia())), tag + f": {res[0][3]} != {bad.inertia()}"
+    assert res[0][4] == res[1][4] == 1, tag + f": early_reject_redone off {res[0][4]}, on {res[1][4]}"
+    assert np.array_equal(res[0][2], res[1][2]), tag + ": the solution is not the bits of the solver with the probe off"
+
+
 # --------------------------------------------------------------------------------------------------------- NaN / Inf
 def _nonfinite_cases(n):
     """(where, (i, j)): a diagonal, an off-diagonal in one 4-pivot group, one in a 16-row block but another group, far below."""
