@@ -674,7 +674,7 @@ int mnk_debug_grid_at_launch(int cu_first, int num_cu, int first, int per_cu);
  * 100 MHz s_memrealtime over the second of two ~2.5 ms launches of MFMAs on every CU, on the context's stream). */
 int mnk_debug_shader_clock(mnk_ctx* ctx, double* mhz);
 
-/* Diagnostics / tests (host only): the task list of the task-DAG factorization schedule (csrc/dag.hip) for a matrix of `ntile`
+/* Diagnostics / tests (host only): the task list of the task-DAG factorization schedule (csrc/dag_plan.hip) for a matrix of `ntile`
  * 128-row tiles: 4 ints per task (flags | chunk index << 8, tile row I, tile column J, kbeg | kend << 16) in queue order, at most
  * `cap` tasks written; returns the number of tasks (negative: bad arguments). */
 int mnk_debug_dag_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int* out, int cap, int* first_phase);

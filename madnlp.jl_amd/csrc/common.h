@@ -172,7 +172,7 @@ struct mnk_ctx {
     int panel_cus = 0;  // > 0: sp is restricted to this many CUs and su to the others (CU masks)
     // task-DAG schedule (dag.hip): the pivot chain needs only a few CUs, the persistent bulk kernel gets all the others
     hipStream_t sp_dag = nullptr, su_dag = nullptr;
-    hipStream_t sp_dagB = nullptr, su_dagB = nullptr;   // batches (dag.hip): a second chain partition (the next dag_cus mask bits) and a bulk stream on the CUs outside both
+    hipStream_t sp_dagB = nullptr, su_dagB = nullptr;   // batches (dag_batch.hip): a second chain partition (the next dag_cus mask bits) and a bulk stream on the CUs outside both
     bool shared_dag_streams = false;   // the four task-DAG streams belong to the device's shared set (ls.hip), not to this context
     int dag_cus = 0;    // > 0: sp_dag is restricted to this many CUs and su_dag to the others
     // ... and a third pair for its second phase, where every remaining row is in the chain's band (one CU per 64 rows)
@@ -255,22 +255,5 @@ int gemm_nt_lower_tiles(int64_t M, int64_t N);
 int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                          const double* B, int64_t ldb, double* C, int64_t ldc, int* counter, int cus,
                          const int* info_flag);
-
-// ---- task-DAG schedule (dag.hip): persistent left-looking tile kernel beside the pivot chain -------------------------
-// Task list (4 ints per task, see dag.hip).  Strip-columns Js < js2 have a band of `band_tiles` tile rows, the others a band
-// that covers every remaining row; returns the number of tasks of the first phase (ready before the chain enters js2).
-int dag_build_tasks(int ntile, int chunk, int band_tiles, int js2, std::vector<int>& out, int taper0, std::vector<int>* ready);
-int dag_add_fill_tasks(int ntile, std::vector<int>& tasks, std::vector<int>& ready, int n1);
-void dag_merge_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int ninst, int period, std::vector<int>& out);
-// The tasks [t0, t1) of a finished list dealt into `nq` queues, each a subsequence of the list in list order: `order` receives the list
-// positions queue after queue, `off` the nq + 1 offsets of the queues in it.  `gang`: tasks of one group (same B rows, same k-range) that
-// go to one queue together; 1: every task on its own; < 0: everything to queue 0 (tests of the steal path).
-constexpr int DAG_NQ = 8;             // queues of the bulk kernel: one per XCD
-constexpr int DAG_QHEAD_STRIDE = 32;  // ints between two queue heads (128 bytes)
-constexpr int DAG_QHEAD_WORDS = (DAG_NQ + 1) * DAG_QHEAD_STRIDE;   // the heads of one launch and, behind them, its count of stolen tasks
-void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
-                    std::vector<int>& off);
-// half-tile k-steps of a task list under the tile envelope `env` (NULL: none) / of them skipped with the half-tile envelope `envh` (NULL: none)
-void dag_envh_count(const std::vector<int>& tasks, const int* env, const int* envh, int nenv, int64_t* count);
 
 }  // namespace mnk

@@ -19,7 +19,8 @@
 //     column they read), band tiles and rows next to the band first: a drawn task can start at once or nearly so, and a
 //     workgroup that holds a task only ever waits for tasks drawn before it, so any number of resident workgroups makes
 //     progress.  (A single factorization deals that list into one queue per XCD, each a subsequence of it popped from its head:
-//     dag_deal_tasks / dag_pop below.)
+//     dag_plan.h: dag_deal_list, and dag_pop below.  The planner that builds and deals the lists is dag_plan.hip; the batches that
+//     merge them are dag_batch.hip.)
 //   * progress: front[t] = number of leading 128-column tile columns for which the 64-row strip t of L is final
 //     (monotone; zeroed per factorization); af[] = "band tile accumulated"; tprog[I, J] = chunks applied to tile (I, J).
 //     Producer: stores -> barrier -> one lane's
@@ -48,36 +49,14 @@ namespace mnk {
 // with the subtract order it follows it to three digits through all 20 iterations (47 -> 30 back-solves).  Cost: a tile's
 // chunks run one after the other (+0.5 % at N = 11 192 against the old order: profiles/r05_diag_subtract_order_ab.txt).
 
-// What a bulk task needs to know about the factorization it belongs to.  One launch may serve SEVERAL independent
-// factorizations of the same order (mnk_factorize_batch_*: the task lists of the instances are merged into one queue, each
-// task carries its instance index), so these live in a per-instance record instead of the kernel's argument block.
-struct DagInst {
-    double* F;
-    int64_t ld;
-    double* V;            // LDL^T: V = L D, same layout as F (the B operand of the updates); Cholesky: nullptr (V = L)
-    const double* dinv;   // 1 / d_k
-    const double* dblk;   // factored 64x64 diagonal blocks
-    const double* inv16;  // inverses of their 16x16 diagonal sub-blocks
-    int* front;
-    int* af;
-    int* tprog;           // [I * ntile + J]: chunks of tile (I, J) that are in memory
-    int* info;
-    unsigned long long* vmax;   // growth monitor of the static-pivot LDL^T (factor.hip growth_fold): receives max|V|, or NULL
-    double* zfill;        // DAG_FILL tasks: the buffer that becomes the NEXT factorization's zeroed factor buffer (or NULL)
-    int64_t N;            // order of the matrix (rows / columns N .. Np - 1 are padding: unit diagonal)
-    const int* env;       // envelope per tile row (mnk_sc::tile_env): L(I, k) = 0 for tile columns k < env[I]; NULL: dense
-    const int* envgate;   // != 0: a NaN / Inf entry was transferred, the envelope is off for this factorization (mnk_ls::env_word)
-    const int* envh;      // envelope per 64-row half of a tile row in 64-column units (mnk_sc::tile_envh; only dag_bulk_kernel1 reads it); NULL: none
-};
-
-// (read through the constant address space: the fields are uniform and never written while a bulk kernel runs, so every use
-// is a scalar load that can be repeated instead of a value that must stay live -- a by-value copy of the record in the task
-// loop cost 88 spilled registers and a scratch access inside the K-loop)
+// (the instance record of a task, DagInst: ls.h.  It is read through the constant address space: the fields are uniform and
+// never written while a bulk kernel runs, so every use is a scalar load that can be repeated instead of a value that must stay
+// live -- a by-value copy of the record in the task loop cost 88 spilled registers and a scratch access inside the K-loop)
 typedef const DagInst __attribute__((address_space(4))) * DagInstP;
 
 struct DagArgs {       // (the batch kernel's; a single factorization: DagArgs1 / dag_bulk_kernel1 below)
     const DagInst* insts; // the instance records in device memory (written by dag_reset_kernel), indexed by the task's instance field
-    const int4* tasks;    // (flags | chunk index << 8, I | instance << 16, J, kbeg | kend << 16)
+    const int4* tasks;    // a merged list of DagTask (dag_plan.h)
     int ntasks;
     int ntile;
     int* qctr;
@@ -87,7 +66,13 @@ struct DagArgs {       // (the batch kernel's; a single factorization: DagArgs1 
     int fake_share;             // DIAGNOSTIC (env MNK_DAG_FAKE_SHARE, wrong results): every chunk reads the operand rows of tile rows 0..n-1
 };
 
-constexpr int DAG_BANDACC = 1, DAG_FINAL = 2, DAG_FIRST = 4, DAG_FILL = 8;  // task flags
+// The bulk kernels decode a task's words with literal masks and shifts (readfirstlane per word: the text the tuned register
+// allocation was measured with); these tie the literals to the field widths of DagTask.
+static_assert(sizeof(int4) == sizeof(DagTask), "a task is one int4");
+static_assert(DagTask::FLAG_BITS == 8, "tk.x & 255: flags, tk.x >> 8: chunk index");
+static_assert(DagTask::ROW_BITS == 16, "tk.y & 0xffff: I, tk.y >> 16: instance (dag_bulk_kernel1: no instance, tk.y is I)");
+static_assert(DagTask::COL_BITS == 12, "tk.z & 0xfff: J, tk.z >> 12: list position (dag_bulk_kernel: no position, tk.z is J)");
+static_assert(DagTask::KBEG_BITS == 16, "tk.w & 0xffff: kbeg, tk.w >> 16: kend");
 
 // Wave 0 waits until min(front[s0..s3]) > c and returns that minimum (clamped to kend): tile columns [c, ret) are final
 // for all four strips.  -1: the factorization failed elsewhere or the wait expired.  Ends with an acquire + barrier.
@@ -545,7 +530,7 @@ struct DagArgs1 {
     const double* dinv;   // 1 / d_k
     const double* dblk;   // factored 64x64 diagonal blocks
     const double* inv16;  // inverses of their 16x16 diagonal sub-blocks
-    const int4* tasks;    // (flags | chunk index << 8, I, J, kbeg | kend << 16)
+    const int4* tasks;    // the list of DagTask (dag_plan.h), as built or dealt (below)
     int ntasks;
     int* front;
     int* af;
@@ -563,7 +548,7 @@ struct DagArgs1 {
     const int* env;             // (as in DagInst)
     const int* envgate;
     const int* envh;
-    // per-XCD queues (dag_deal_tasks): nq > 0: `tasks` is the dealt copy of the list, queue x = tasks [qoff[x], qoff[x + 1]), its head
+    // per-XCD queues (dag_plan.h: dag_deal_list): nq > 0: `tasks` is the dealt copy of the list, queue x = tasks [qoff[x], qoff[x + 1]), its head
     // qheads[x * DAG_QHEAD_STRIDE]; a task's position in the LIST (the index of its trace record) rides in the third word above
     // the tile column.  nq == 0: one queue, the list as built, popped through `qctr`.
     const int* qoff;
@@ -797,249 +782,74 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------------------------------
-// Task list for a matrix of `ntile` 128-row tiles, chunks of at most `chunk` tile columns and a band of `band_tiles` tile
-// rows for the strip-columns Js < js2, every remaining row from js2 on (depends on these four only; cached by the caller).
-// 4 ints per task: flags | chunk index << 8, I, J, kbeg | kend << 16.  Returns the number of first-phase tasks: the ones
-// that are ready before the chain enters strip-column js2 (they come first in the list).
-int dag_build_tasks(int ntile, int chunk, int band_tiles, int js2, std::vector<int>& out, int taper0, std::vector<int>* ready) {
-    struct T { int ready, cls, J, I, flags, q, kbeg, kend; };
-    std::vector<T> ts;
-    // Tile (I, J), tile columns [0, K) to accumulate.  A bulk tile's last tile column is a task of its own (paced by the pivot
-    // chain: K = 128 step, then the finalization); the columns in front of it -- all columns of a band tile -- go in chunks:
-    //   * STAGGERED from tile to tile (first chunk 1 .. chunk tile columns long, by a hash of the tile's coordinates): at
-    //     every chain position about 1 / chunk of the tiles have a chunk that just became ready, so ready work arrives
-    //     evenly.  (With boundaries at multiples of `chunk` the queue alternated between a big batch of ready chunks and a
-    //     stretch of tile-closing tasks that are serialized along every row of tiles: 23 % of the slot-time waiting.)
-    //   * TAPERED towards K (..., chunk, 4, 2, 1): a chunk [b, e) cannot start before the chain has passed tile column
-    //     e - 1 and the tile is due when the chain reaches K, so a full-length chunk that becomes ready one chain step
-    //     before the tile is due was 100-300 us late for the band, every time (measured).
-    auto add_tile = [&](int I, int J, int K, bool band) {
-        const int body = band ? K : std::max(0, K - 1);
-        std::vector<int> cuts{body};  // chunk boundaries, back to front
-        int e = body;
-        for (int len = taper0; len < chunk && e > 0; len *= 2) { e = std::max(0, e - len); cuts.push_back(e); }   // (factors 3 / 4 instead of 2: +2 / +5 %)
-        const int first = 1 + (I * 5 + J * 3) % chunk;
-        while (e > first) { e = std::max(first, e - chunk); cuts.push_back(e); }
-        if (e > 0) cuts.push_back(0);
-        int q = 0;
-        for (int c = (int)cuts.size() - 1; c > 0; --c, ++q) {
-            const int kb = cuts[c], ke = cuts[c - 1];
-            const bool last = band && ke == K;
-            ts.push_back({ke, band ? 0 : 2, J, I, (band ? DAG_BANDACC : 0) | (last ? DAG_FINAL : 0) | (q == 0 ? DAG_FIRST : 0), q, kb, ke});
-        }
-        if (!band) ts.push_back({K, 1, J, I, DAG_FINAL | (q == 0 ? DAG_FIRST : 0), q, body, K});
-    };
-    for (int Jt = 0; Jt < ntile; ++Jt) {
-        const int Js = Jt / 2;
-        const int bt = Js >= js2 ? ntile : band_tiles;
-        for (int I = 2 * Js + bt; I < ntile; ++I) add_tile(I, Jt, Jt, false);
-        // band tiles of strip-column Js (tile rows 2Js .. 2Js + bt - 1, lower part): accumulated over the tile columns
-        // k < 2Js - 2 (the chain's prologue applies strip-column Js - 1 itself)
-        if (2 * Js - 2 > 0)
-            for (int I = std::max(2 * Js, Jt); I < 2 * Js + bt && I < ntile; ++I) add_tile(I, Jt, 2 * Js - 2, true);
-    }
-    // by the chain position that makes a task ready (the last tile column it reads), then band tiles, then the tile-closing
-    // tasks, then by column and row (rows next to the band first)
-    std::stable_sort(ts.begin(), ts.end(), [](const T& x, const T& y) {
-        if (x.ready != y.ready) return x.ready < y.ready;
-        if (x.cls != y.cls) return x.cls < y.cls;
-        if (x.J != y.J) return x.J < y.J;
-        return x.I < y.I;
-    });
-    out.clear();
-    out.reserve(ts.size() * 4);
-    if (ready != nullptr) { ready->clear(); ready->reserve(ts.size()); }
-    int n1 = 0;
-    for (const T& t : ts) {
-        if (t.ready <= 2 * js2) ++n1;  // needs only tile columns the first phase's chain has passed (sorted by `ready`)
-        if (ready != nullptr) ready->push_back(t.ready);
-        out.push_back(t.flags | (t.q << 8));
-        out.push_back(t.I);
-        out.push_back(t.J);
-        out.push_back(t.kbeg | (t.kend << 16));
-    }
-    return n1;
-}
-
-// Zero-fill tasks (DAG_FILL) for the lower tiles of the NEXT factorization's buffer, one after every few tasks of the first
-// phase: 128 KB of stores each, absorbed by the queue while the matrix cores are the bound.  `ready` gets the value of the
-// task in front (the merge of several instances keeps them where they are).  Returns the new number of first-phase tasks.
-int dag_add_fill_tasks(int ntile, std::vector<int>& tasks, std::vector<int>& ready, int n1) {
-    const int nt = (int)(tasks.size() / 4), nfill = ntile * (ntile + 1) / 2;
-    const int span = n1 > 0 ? n1 : nt;   // (spread over the first phase; a list without one: over everything)
-    if (span <= 0) return n1;
-    std::vector<int> out, rdy;
-    out.reserve(tasks.size() + 4 * (size_t)nfill);
-    rdy.reserve(ready.size() + nfill);
-    int fi = 0, fj = 0, done = 0;
-    auto emit_fill = [&](int r) {
-        out.push_back(DAG_FILL); out.push_back(fi); out.push_back(fj); out.push_back(0);
-        rdy.push_back(r);
-        if (++fi >= ntile) { ++fj; fi = fj; }
-        ++done;
-    };
-    for (int t = 0; t < nt; ++t) {
-        for (int k = 0; k < 4; ++k) out.push_back(tasks[4 * t + k]);
-        rdy.push_back(ready[t]);
-        // after task t of the span, (t + 1) * nfill / span fill tasks are out
-        if (t < span)
-            while (done < (int)((int64_t)(t + 1) * nfill / span)) emit_fill(ready[t]);
-    }
-    tasks.swap(out);
-    ready.swap(rdy);
-    return n1 > 0 ? n1 + nfill : 0;
-}
-
-// One queue for `ninst` independent factorizations of the same order (mnk_factorize_batch_*): instance i's tasks keep their
-// order and are shifted by i * period chain positions (tile columns) against instance 0's, so that an instance's
-// saturated middle runs under the chain-bound ends of its neighbours.  Two pivot chains run at a time (instances i and
-// i + 1; chain i + 2 follows chain i on its stream), hence period >= ntile / 2: every task of instance i then precedes
-// every task of instance i + 2, and a workgroup that holds a task waits only for tasks in front of it or for a chain that
-// is running or will run once tasks in front of it are done.
-void dag_merge_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int ninst, int period, std::vector<int>& out) {
-    const int nt = (int)ready.size();
-    out.clear();
-    out.reserve((size_t)ninst * nt * 4);
-    std::vector<int> pos(ninst, 0);
-    for (;;) {   // k-way merge by (i * period + ready, i); every list is sorted by `ready`
-        int best = -1;
-        long bkey = 0;
-        for (int i = 0; i < ninst; ++i) {
-            if (pos[i] >= nt) continue;
-            const long key = (long)i * period + ready[pos[i]];
-            if (best < 0 || key < bkey) { best = i; bkey = key; }
-        }
-        if (best < 0) break;
-        const int t = pos[best]++;
-        out.push_back(tasks[4 * t]);
-        out.push_back(tasks[4 * t + 1] | (best << 16));
-        out.push_back(tasks[4 * t + 2]);
-        out.push_back(tasks[4 * t + 3]);
-    }
-}
-
-// Per-XCD queues.  Neighbours in the list are chunks of one tile column with the same [kbeg, kend): they walk the same B rows
-// V(J, kbeg..kend).  Popped from one counter by workgroups that the dispatcher deals round-robin over the eight XCDs, they land in
-// eight different L2s; dealt to the queue of ONE XCD they can share that stream.  The list is only PARTITIONED: every queue is a
-// subsequence of the list in list order and no task changes, so every tile still sees its chunks in the same order (same bits),
-// and a queue popped from its head keeps the list's progress argument.
-//   * group: a maximal run of consecutive chunk tasks (body chunks, band accumulation) with the same (ready, class, J, kbeg, kend);
-//     it is cut into gangs of `gang` consecutive tasks.  Tile-closing tasks, zero-fill tasks and runs of one are gangs of one.
-//   * a gang goes whole to the queue with the fewest k-steps dealt so far (ties: round-robin), so the queues carry equal work at
-//     every position of the list: the heaviest and the lightest differ by at most one gang.
-// The envelope is ignored (gang-mates whose K-loops start later join the shared stream later): one deal serves every matrix of an order.
-// (Balancing the queues by the K-loop lengths under the envelope, kend - max(kbeg, env[I], env[J]), was measured on C3 and is not
-// built: 9.101 against 9.080 ms per step)
-void dag_deal_tasks(const std::vector<int>& tasks, const std::vector<int>& ready, int t0, int t1, int nq, int gang, std::vector<int>& order,
-                    std::vector<int>& off) {
-    nq = std::max(nq, 1);
-    std::vector<std::vector<int>> qs(nq);
-    std::vector<int64_t> load(nq, 0);
-    int rr = 0;
-    auto cls = [&](int t) { const int f = tasks[4 * (size_t)t] & 255; return (f & DAG_FILL) ? 3 : ((f & DAG_BANDACC) ? 0 : ((f & DAG_FINAL) ? 1 : 2)); };
-    auto ksteps = [&](int t) { return (tasks[4 * (size_t)t] & DAG_FILL) ? 0 : (tasks[4 * (size_t)t + 3] >> 16) - (tasks[4 * (size_t)t + 3] & 0xffff); };
-    auto same = [&](int x, int y) {   // (the instance too: the second word carries it in a merged list)
-        return ready[x] == ready[y] && cls(x) == cls(y) && tasks[4 * (size_t)x + 2] == tasks[4 * (size_t)y + 2] &&
-               tasks[4 * (size_t)x + 3] == tasks[4 * (size_t)y + 3] && (tasks[4 * (size_t)x + 1] >> 16) == (tasks[4 * (size_t)y + 1] >> 16);
-    };
-    auto deal = [&](int b, int e) {   // the gang [b, e)
-        int q = 0;
-        if (gang >= 0) {
-            q = rr % nq;
-            for (int i = 1; i < nq; ++i)
-                if (load[(rr + i) % nq] < load[q]) q = (rr + i) % nq;
-            rr = q + 1;
-        }
-        for (int t = b; t < e; ++t) { qs[q].push_back(t); load[q] += ksteps(t); }
-    };
-    for (int i = t0; i < t1;) {
-        int j = i + 1;
-        const int c = cls(i);
-        if (gang > 1 && (c == 0 || c == 2))
-            while (j < t1 && same(i, j)) ++j;
-        for (int b = i; b < j; b += std::max(gang, 1)) deal(b, std::min(j, b + std::max(gang, 1)));
-        i = j;
-    }
-    order.clear();
-    off.assign(1, 0);
-    for (int q = 0; q < nq; ++q) {
-        order.insert(order.end(), qs[q].begin(), qs[q].end());
-        off.push_back((int)order.size());
-    }
-}
-
-// Statistics (envh_ksteps / envh_ksteps_skipped): the bulk tasks of a list in half-tile k-steps -- one 64 x 64 quadrant of a tile
-// over 64 columns, 8 per 128-column k-step of a tile.  count[0]: what the tile envelope `env` leaves (NULL: everything);
-// count[1]: of that, what the waves of dag_bulk_kernel1 skip with the half-tile envelope `envh` (NULL: nothing) -- in a chunk's
-// K-loop the quadrant (r, c) of tile (I, J) starts at max(envh[2I + r], envh[2J + c]), and the upper quadrant of a diagonal
-// tile is never multiplied.  Tile-closing tasks skip nothing by halves.
-void dag_envh_count(const std::vector<int>& tasks, const int* env, const int* envh, int nenv, int64_t* count) {
-    count[0] = count[1] = 0;
-    for (size_t t = 0; t + 3 < tasks.size(); t += 4) {
-        const int flags = tasks[t] & 255, I = tasks[t + 1] & 0xffff, J = tasks[t + 2] & 0xfff, kb = tasks[t + 3] & 0xffff, ke = tasks[t + 3] >> 16;
-        if (flags & DAG_FILL) continue;
-        const bool in = env != nullptr && I < nenv && J < nenv;
-        const int k0 = in ? std::min(ke, std::max(kb, std::max(env[I], env[J]))) : kb;
-        if (in && (flags & DAG_FINAL) && !(flags & DAG_BANDACC) && J < env[I]) continue;   // (a structurally zero tile is closed without its K-step)
-        count[0] += 8 * (int64_t)(ke - k0);
-        if (!in || envh == nullptr || ((flags & DAG_FINAL) && !(flags & DAG_BANDACC))) continue;
-        for (int r = 0; r < 2; ++r)
-            for (int c = 0; c < 2; ++c) {
-                const int h0 = (I == J && r == 0 && c == 1) ? 2 * ke : std::max(envh[2 * I + r], envh[2 * J + c]);
-                count[1] += std::min(2 * ke, std::max(2 * k0, h0)) - 2 * k0;
-            }
-    }
-}
-
-template <bool LDL>
-static int launch_bulk_t(hipStream_t s, const DagArgs& a, int nwg) {
+// One launcher for the four bulk kernels (template on the kernel, hence one `attr_devs` per kernel): the dynamic LDS attribute is
+// set once per device, the grid is `nwg` persistent workgroups.
+template <class Args, void (*Kern)(Args)>
+static int launch_bulk(hipStream_t s, const Args& a, int nwg) {
     const size_t smem = TILE3_LDS_BYTES;  // three k-tile buffers of the tile-closing tasks (gemm_nt_mainloop3); chunks use two, the finalization 32 KB
-    auto kern = dag_bulk_kernel<LDL>;
     static std::atomic<uint64_t> attr_devs{0};
     int dev = 0;
     MNK_HIP(hipGetDevice(&dev));
     if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        MNK_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), smem, s, a);
+    hipLaunchKernelGGL(Kern, dim3(nwg), dim3(256), smem, s, a);
     MNK_HIP(hipGetLastError());
     return 0;
 }
-
-template <bool LDL>
-static int launch_bulk1_t(hipStream_t s, const DagArgs1& a, int nwg) {
-    const size_t smem = TILE3_LDS_BYTES;
-    auto kern = dag_bulk_kernel1<LDL>;
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    MNK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), smem, s, a);
-    MNK_HIP(hipGetLastError());
-    return 0;
+static int launch_bulk1(hipStream_t s, bool ldl, const DagArgs1& a, int nwg) {
+    return ldl ? launch_bulk<DagArgs1, dag_bulk_kernel1<true>>(s, a, nwg) : launch_bulk<DagArgs1, dag_bulk_kernel1<false>>(s, a, nwg);
+}
+static int launch_bulk_batch(hipStream_t s, bool ldl, const DagArgs& a, int nwg) {
+    return ldl ? launch_bulk<DagArgs, dag_bulk_kernel<true>>(s, a, nwg) : launch_bulk<DagArgs, dag_bulk_kernel<false>>(s, a, nwg);
 }
 
-// `insts` == nullptr: one factorization (dag_bulk_kernel1, the record `one` flattened into its argument block); otherwise a batch
-static int launch_dag_bulk(hipStream_t s, bool ldl, const DagInst& one, const DagInst* insts, const int* tasks, int ntasks, int ntile,
-                           int* qctr, long spin_limit, int nwg, unsigned long long* trace, unsigned long long* wgstat,
-                           const int* qoff = nullptr, int* qheads = nullptr, int nq = 0) {
-    if (ntasks <= 0) return 0;
+static int dag_fake_share() {
     static const int fake = getenv("MNK_DAG_FAKE_SHARE") ? atoi(getenv("MNK_DAG_FAKE_SHARE")) : 0;
-    if (insts == nullptr) {
-        DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
-                   one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, fake, one.zfill, one.N, one.env, one.envgate, one.envh,
-                   qoff, qheads, nq};
-        return ldl ? launch_bulk1_t<true>(s, a, nwg) : launch_bulk1_t<false>(s, a, nwg);
-    }
-    DagArgs a{insts, reinterpret_cast<const int4*>(tasks), ntasks, ntile, qctr, spin_limit, trace, wgstat, fake};
-    return ldl ? launch_bulk_t<true>(s, a, nwg) : launch_bulk_t<false>(s, a, nwg);
+    return fake;
+}
+
+// one factorization: dag_bulk_kernel1, the record `one` flattened into its argument block
+static int launch_dag_bulk_single(hipStream_t s, bool ldl, const DagInst& one, const int* tasks, int ntasks, int ntile, int* qctr,
+                                  long spin_limit, int nwg, unsigned long long* trace, unsigned long long* wgstat, const int* qoff,
+                                  int* qheads, int nq) {
+    if (ntasks <= 0) return 0;
+    DagArgs1 a{one.F, one.ld, one.V, one.dinv, one.dblk, one.inv16, reinterpret_cast<const int4*>(tasks), ntasks, one.front, one.af,
+               one.tprog, ntile, qctr, one.info, spin_limit, trace, wgstat, one.vmax, dag_fake_share(), one.zfill, one.N, one.env, one.envgate,
+               one.envh, qoff, qheads, nq};
+    return launch_bulk1(s, ldl, a, nwg);
+}
+
+int launch_dag_bulk_merged(hipStream_t s, bool ldl, const DagInst* insts, const int* tasks, int ntasks, int ntile, int* qctr,
+                           long spin_limit, int nwg) {
+    if (ntasks <= 0) return 0;
+    DagArgs a{insts, reinterpret_cast<const int4*>(tasks), ntasks, ntile, qctr, spin_limit, nullptr, nullptr, dag_fake_share()};
+    return launch_bulk_batch(s, ldl, a, nwg);
+}
+
+// dag_reset_kernel in its three uses.  (progress words and `info` in ONE launch: two memsets are two fill kernels, ~8 us each in
+// front of the pivot chain)
+static dim3 dag_reset_grid(int64_t Np, int systems) {
+    return dim3((unsigned)std::min<size_t>((DagPlan::progress_words(Np) + 1023) / 1024, 64), (unsigned)systems);
+}
+// one factorization: also the heads of its per-XCD queues; consumes the envelope word
+static void dag_reset_single(hipStream_t s, mnk_ls* ls, const DagInst& rec) {
+    hipLaunchKernelGGL(dag_reset_kernel, dag_reset_grid(ls->Np, 1), dim3(256), 0, s, ls->plan.flags.p, (int64_t)DagPlan::progress_words(ls->Np),
+                       ls->info_dev.p, rec, (DagInst*)nullptr, (const SmallSysRec*)nullptr, ls->env_word.p, ls->plan.qheads.p,
+                       ls->plan.qheads.p ? 2 * DAG_QHEAD_WORDS : 0);
+    ls->src.env_armed = false;
+}
+// (the instance's record for the bulk kernel rides along with the reset of its progress words)
+void dag_reset_member(hipStream_t s, mnk_ls* ls, const DagInst& rec, DagInst* rec_dst) {
+    hipLaunchKernelGGL(dag_reset_kernel, dag_reset_grid(ls->Np, 1), dim3(256), 0, s, ls->plan.flags.p, (int64_t)DagPlan::progress_words(ls->Np),
+                       ls->info_dev.p, rec, rec_dst, (const SmallSysRec*)nullptr, ls->env_word.p);
+    ls->src.env_armed = false;
+}
+// (blockIdx.y = system; the instance records are uploaded by the host, no envelope word is consumed: the round runs dense)
+void dag_reset_round(hipStream_t s, int64_t Np, const SmallSysRec* recs_dev, int k) {
+    hipLaunchKernelGGL(dag_reset_kernel, dag_reset_grid(Np, k), dim3(256), 0, s, (int*)nullptr, (int64_t)0, (int*)nullptr, DagInst{},
+                       (DagInst*)nullptr, recs_dev);
 }
 
 }  // namespace mnk
@@ -1066,10 +876,10 @@ int mnk_dag_warmup(hipStream_t* streams, int n, int nwg) {
         mnk::DagArgs a{};
         a.qctr = ctr.p;
         // (a FULL-size grid: the runtime sizes a queue's scratch by the dispatch that asks for it)
-        int rc = mnk::launch_bulk1_t<true>(streams[i], a1, nwg);
-        if (!rc) rc = mnk::launch_bulk1_t<false>(streams[i], a1, nwg);
-        if (!rc) rc = mnk::launch_bulk_t<true>(streams[i], a, nwg);
-        if (!rc) rc = mnk::launch_bulk_t<false>(streams[i], a, nwg);
+        int rc = mnk::launch_bulk1(streams[i], true, a1, nwg);
+        if (!rc) rc = mnk::launch_bulk1(streams[i], false, a1, nwg);
+        if (!rc) rc = mnk::launch_bulk_batch(streams[i], true, a, nwg);
+        if (!rc) rc = mnk::launch_bulk_batch(streams[i], false, a, nwg);
         if (rc) return rc;
     }
     for (int i = 0; i < n; ++i)
@@ -1115,9 +925,9 @@ size_t DagPlan::progress_words(int64_t Np) {   // two queue counters | front | a
     return (size_t)2 + (size_t)(Np / NBI) + 2 * (size_t)ntile * ntile;
 }
 
-size_t DagPlan::trace_words() const { return (size_t)ntasks * 8 + 4096 * 8 + 1024 * 8; }
+size_t DagPlan::trace_words() const { return (size_t)list.size() * 8 + 4096 * 8 + 1024 * 8; }
 
-static mnk::DagInst dag_instance(mnk_ls* ls) {
+mnk::DagInst mnk::dag_prepare_instance(mnk_ls* ls, bool dense) {
     const int ntile = (int)(ls->Np / 128), nblk = (int)(ls->Np / NBI);
     int* front = ls->plan.flags.p + 2;   // (the layout DagPlan::progress_words sizes)
     int* af = front + nblk;
@@ -1126,10 +936,15 @@ static mnk::DagInst dag_instance(mnk_ls* ls) {
     // transferred for this factorization) and no background fill of it is in flight
     double* zfill = ls->dag_fill && ls->plan.key.has_fill ? ls->spare.dag_target() : nullptr;
     // the envelope of a sparse source (ls.hip: set_envelope); the bulk kernel reads the verdict on its finiteness (env_word[1])
-    const bool env = ls->envelope && ls->src.env_dev != nullptr && ls->env_word.p != nullptr;
-    return mnk::DagInst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
-                        front, af, tprog, ls->info_dev.p, ls->bk.growth_word(ls), zfill, ls->N, env ? ls->src.env_dev : nullptr,
-                        env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->src.envh_dev : nullptr};
+    const bool env = !dense && ls->envelope && ls->src.env_dev != nullptr && ls->env_word.p != nullptr;
+    const mnk::DagInst inst{ls->fact.p, ls->ld, ls->algo == MNK_LDL ? ls->vfull.p : nullptr, ls->dinv.p, ls->dblk.p, ls->inv16.p,
+                            front, af, tprog, ls->info_dev.p, ls->bk.growth_word(ls), zfill, ls->N, env ? ls->src.env_dev : nullptr,
+                            env ? ls->env_word.p + 1 : nullptr, env && ls->envelope_half ? ls->src.envh_dev : nullptr};
+    // what the solver remembers about this launch: the spare buffer is being zeroed by it, the statistics count its envelope
+    ls->spare.dag_fills(inst.zfill != nullptr);
+    ls->env_used = inst.env != nullptr;
+    ls->envh_used = inst.envh != nullptr;
+    return inst;
 }
 
 // Buffers of the task-DAG schedule: the task list (built once per matrix order and option set), the progress words and,
@@ -1167,42 +982,34 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         const int64_t deep_rows = std::min<int64_t>((int64_t)ctx->dag_cus2 * NBI, ls->dag_deep_rows);
         ls->plan.key.js2 = (ctx->dag_cus2 > 0 && Np <= deep_rows) ? 0 : nsc;
         if (ls->dag_js2_override >= 0) ls->plan.key.js2 = std::min(nsc, ls->dag_js2_override);
-        std::vector<int>& h = ls->plan.host_tasks;   // (kept on the host: a batch merges the lists of its instances)
+        mnk::DagTaskList& h = ls->plan.list;
         ls->plan.key.chunk = ls->dag_chunk; ls->plan.key.taper0 = ls->dag_taper0; ls->plan.key.band = ls->dag_band;
-        ls->plan.ntasks1 = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->plan.key.js2, h, ls->dag_taper0, &ls->plan.host_ready);
+        h = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->plan.key.js2, ls->dag_taper0);
         // zero-fill of the next factorization's buffer as tasks of the queue (sparse sources; see dag_fill_tile)
         ls->plan.key.has_fill = ls->dag_fill && ls->spare.wanted(Np);
-        if (ls->plan.key.has_fill && h.empty()) ls->plan.key.has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
-        if (ls->plan.key.has_fill) ls->plan.ntasks1 = mnk::dag_add_fill_tasks(ntile, h, ls->plan.host_ready, ls->plan.ntasks1);
-        ls->plan.ntasks = (int)(h.size() / 4);
-        // Per-XCD queues: the device list is the host list dealt per phase (dag_deal_tasks; the host list stays as built -- the
-        // statistics and the merged queue of a batch read it).  A phase keeps ONE queue when its bulk grid might leave an XCD
-        // without a workgroup -- a queue nobody owns is only served by thieves, which come when their own queues are empty, and
-        // the progress argument needs an owner -- or when a list position does not fit beside the tile column (20 | 12 bits).
-        std::vector<int> dev_list = h, qoff(32, 0);
-        ls->plan.nq[0] = ls->plan.nq[1] = 0;
-        if (ls->dag_xcd_queues && ls->plan.ntasks < (1 << 20) && ntile < 4096) {
-            const int part[3] = {0, ls->plan.ntasks1, ls->plan.ntasks};
-            const int chain_cus[2] = {ctx->dag_cus, ctx->dag_cus2};
-            for (int ph = 0; ph < 2; ++ph) {
-                const int t0 = part[ph], t1 = part[ph + 1];
-                if (t1 - t0 < mnk_ctx_bulk_wgs(ctx, chain_cus[ph], 3) || bulk_xcds(ctx, chain_cus[ph]) != mnk::DAG_NQ) continue;
-                std::vector<int> order, off;
-                mnk::dag_deal_tasks(h, ls->plan.host_ready, t0, t1, mnk::DAG_NQ, ls->dag_gang, order, off);
-                for (int p = 0; p < t1 - t0; ++p) {
-                    for (int k = 0; k < 4; ++k) dev_list[4 * (size_t)(t0 + p) + k] = h[4 * (size_t)order[p] + k];
-                    dev_list[4 * (size_t)(t0 + p) + 2] |= (order[p] - t0) << 12;
-                }
-                for (int x = 0; x <= mnk::DAG_NQ; ++x) qoff[16 * ph + x] = off[x];
-                ls->plan.nq[ph] = mnk::DAG_NQ;
-            }
+        if (ls->plan.key.has_fill && h.tasks.empty()) ls->plan.key.has_fill = false;   // (a system of a few hundred rows has no bulk task: nothing to ride on)
+        if (ls->plan.key.has_fill) mnk::dag_add_fill_tasks(ntile, h);
+        // Per-XCD queues: the device list is the host list dealt per phase (dag_plan.h: dag_deal_list).  A phase keeps ONE queue
+        // when its bulk grid might leave an XCD without a workgroup -- a queue nobody owns is only served by thieves, which come
+        // when their own queues are empty, and the progress argument needs an owner -- or when the list does not fit the task's
+        // fields (a list position beside the tile column: 20 | 12 bits).
+        const bool queues = ls->dag_xcd_queues && mnk::DagTask::fits(ntile, 1, h.size());
+        const int part[3] = {0, h.n1, h.size()}, chain_cus[2] = {ctx->dag_cus, ctx->dag_cus2};
+        bool may_queue[2];
+        for (int ph = 0; ph < 2; ++ph)
+            may_queue[ph] = queues && part[ph + 1] - part[ph] >= mnk_ctx_bulk_wgs(ctx, chain_cus[ph], 3) && bulk_xcds(ctx, chain_cus[ph]) == mnk::DAG_NQ;
+        const mnk::DagDealtList dev_list = mnk::dag_deal_list(h, mnk::DAG_NQ, ls->dag_gang, may_queue);
+        std::vector<int> qoff(32, 0);   // (16 per phase)
+        for (int ph = 0; ph < 2; ++ph) {
+            std::copy_n(dev_list.qoff.begin() + ph * (mnk::DAG_NQ + 1), mnk::DAG_NQ + 1, qoff.begin() + 16 * ph);
+            ls->plan.nq[ph] = dev_list.nq[ph];
         }
-        if (ls->plan.tasks.alloc(h.size() + 4)) return give_up();
+        if (ls->plan.tasks.alloc(4 * h.tasks.size() + 4)) return give_up();
         if (!ls->plan.qoff.p && ls->plan.qoff.alloc(qoff.size())) return give_up();
         if (!ls->plan.qheads.p && ls->plan.qheads.alloc(2 * (size_t)mnk::DAG_QHEAD_WORDS)) return give_up();
         {
             mnk::H2DGuard h2d;   // (a pageable upload beside another context's persistent group would stop that group: common.h)
-            if (!h.empty() && hipMemcpyAsync(ls->plan.tasks.p, dev_list.data(), dev_list.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
+            if (!h.tasks.empty() && hipMemcpyAsync(ls->plan.tasks.p, dev_list.tasks.data(), dev_list.tasks.size() * sizeof(mnk::DagTask), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
             if (hipMemcpyAsync(ls->plan.qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) return give_up();
             if (mnk::stream_wait(s) != hipSuccess) return give_up();
         }
@@ -1228,17 +1035,9 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
     const int64_t Np = ls->Np;
     const bool ldl = ls->algo == MNK_LDL;
     const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256);
-    const size_t nflags = DagPlan::progress_words(Np);
     MNK_REQUIRE(ls->plan.tasks.p && ls->plan.flags.p && (!ldl || ls->vfull.p), "task-DAG schedule: mnk_ls_dag_prepare was not called");
-    // progress words and `info` in ONE launch (two memsets are two fill kernels, ~8 us each in front of the pivot chain)
-    const mnk::DagInst inst = dag_instance(ls);
-    ls->spare.dag_fills(inst.zfill != nullptr);
-    ls->env_used = inst.env != nullptr;
-    ls->envh_used = inst.envh != nullptr;
-    hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, s,
-                       ls->plan.flags.p, (int64_t)nflags, ls->info_dev.p, inst, (mnk::DagInst*)nullptr, (const mnk::SmallSysRec*)nullptr,
-                       ls->env_word.p, ls->plan.qheads.p, ls->plan.qheads.p ? 2 * mnk::DAG_QHEAD_WORDS : 0);
-    ls->src.env_armed = false;
+    const mnk::DagInst inst = mnk::dag_prepare_instance(ls, false);
+    mnk::dag_reset_single(s, ls, inst);
     int* qctr = ls->plan.flags.p;
     int* front = inst.front;
     const long spin_limit = mnk_ls_dag_spin_limit(ls);
@@ -1247,7 +1046,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         MNK_HIP(hipMemsetAsync(ls->dag_trace.p, 0, ls->plan.trace_words() * sizeof(unsigned long long), s));
         trace = ls->dag_trace.p;
     }
-    const int js2 = ls->plan.key.js2;
+    const int js2 = ls->plan.key.js2, ntasks = ls->plan.list.size(), ntasks1 = ls->plan.list.n1;
     // one phase = one persistent bulk launch (update stream) beside one persistent chain launch (panel stream)
     auto phase = [&](hipStream_t sp, hipStream_t su, int chain_cus, int task0, int ntask, int* counter, int js_begin, int js_end,
                      unsigned strips) -> int {
@@ -1260,7 +1059,7 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         MNK_HIP(hipEventRecord(ctx->ev_a, s));
         if (!small) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
         MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
-        mnk::PpDag dag{front, inst.af, ntile, 0, 0, -1, spin_limit, trace ? trace + (size_t)ls->plan.ntasks * 8 + (size_t)js_begin * 8 * 16 : nullptr,
+        mnk::PpDag dag{front, inst.af, ntile, 0, 0, -1, spin_limit, trace ? trace + (size_t)ntasks * 8 + (size_t)js_begin * 8 * 16 : nullptr,
                   ls->bk.growth_word(ls), ls->dag_debug ? ls->dag_dbg.p : nullptr};
         // (the chain first: its first diagonal block is the start of the critical path, the bulk kernel has nothing to do before it)
         int rc = mnk_launch_pchain(ls, sp, dag, js_begin, js_end, strips);
@@ -1271,9 +1070,9 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         // (per-XCD queues: every queue needs workgroups of its own XCD -- the grid the list was dealt for, see mnk_ls_dag_prepare)
         MNK_REQUIRE(nq == 0 || (ntask >= mnk_ctx_bulk_wgs(ctx, chain_cus, 3) && bulk_xcds(ctx, chain_cus) == nq),
                     "task-DAG schedule: the bulk grid does not cover the XCDs the task list was dealt for");
-        rc = mnk::launch_dag_bulk(su, ldl, inst, nullptr, ls->plan.tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
+        rc = mnk::launch_dag_bulk_single(su, ldl, inst, ls->plan.tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
                                   std::min(ntask, mnk_ctx_bulk_wgs(ctx, chain_cus, 3)), trace ? trace + 8 * (size_t)task0 : nullptr,
-                                  trace ? trace + (size_t)ls->plan.ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
+                                  trace ? trace + (size_t)ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
                                   ls->plan.qoff.p + 16 * ph, ls->plan.qheads.p + ph * mnk::DAG_QHEAD_WORDS, nq);
         if (rc) return rc;
         // Once the bulk kernel has run out of tasks every tile-closing task is done, hence every strip-column that still
@@ -1302,471 +1101,17 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         return 0;
     };
     if (js2 > 0) {
-        int rc = phase(ctx->sp_dag, ctx->su_dag, ctx->dag_cus, 0, ls->plan.ntasks1, qctr, 0, std::min(js2, nsc),
+        int rc = phase(ctx->sp_dag, ctx->su_dag, ctx->dag_cus, 0, ntasks1, qctr, 0, std::min(js2, nsc),
                        (unsigned)std::min<int64_t>(ls->dag_band, Np / NBI));
         if (rc) return rc;
     }
     if (js2 < nsc) {
         const int64_t rows2 = Np - 256 * (int64_t)js2;
         MNK_REQUIRE(ctx->sp_dag2 != nullptr, "task-DAG schedule: the deep-band streams are missing");   // (mnk_ls_run_factorization made them)
-        int rc = phase(ctx->sp_dag2, ctx->su_dag2, ctx->dag_cus2, ls->plan.ntasks1, ls->plan.ntasks - ls->plan.ntasks1,
+        int rc = phase(ctx->sp_dag2, ctx->su_dag2, ctx->dag_cus2, ntasks1, ntasks - ntasks1,
                        qctr + 1, js2, nsc, (unsigned)(rows2 / NBI));
         if (rc) return rc;
     }
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Batches of independent factorizations (mnk_factorize_batch_begin / _end; BASELINE config C5: scenario batches per GPU).
-// A single factorization of N ~ 1e4 leaves the bulk CUs nearly idle at both ends -- 0.5 ms of start-up and ~2.6 ms of a
-// tail that is bound by the pivot chain -- which no schedule of ONE matrix can fill.  Between begin and end the
-// factorize! calls of the calling thread only transfer their matrices; `end` launches them together: ONE bulk kernel
-// drains the merged task queue of all instances (dag_merge_tasks) beside TWO pivot chains on two CU partitions (even
-// instances on one, odd ones on the other), so that instance i + 1's saturated middle runs under instance i's tail.  The
-// arithmetic per instance is exactly that of a single factorization (same task list, same order per tile): bit-identical
-// factors.  Reference behaviour: distinct solver instances are driven concurrently (src/KKT/Schur/schur.jl:953).
-// ---------------------------------------------------------------------------------------------------------------------
-namespace {
-struct BatchState {
-    int depth = 0;             // (begin / end pairs nest: the outermost end launches)
-    bool active = false;
-    std::vector<mnk_ls*> pend;
-};
-thread_local BatchState t_batch;
-
-struct BatchBuffers {   // per device, reused from batch to batch (guarded by the arbiter's mutex while in use)
-    mnk::DevBuf<int> tasks;
-    mnk::DevBuf<int> qctr;
-    mnk::DevBuf<char> insts, pcsys, aux;
-    char* stage = nullptr;        // pinned host memory: the records of one batch (instances | chain table | small-system records)
-    size_t stage_bytes = 0;
-    hipEvent_t stage_ev = nullptr;   // recorded behind the last upload from `stage`
-    int ntile = 0, ninst = 0, period = 0, ntasks = 0;   // what `tasks` was merged for: ntile, the instances, their shift ...
-    DagPlan::Key key;                                   // ... and the plan of the group's first solver
-    bool holds(int ntile_, int ninst_, int period_, const DagPlan::Key& k) const {
-        return tasks.p && ntile == ntile_ && ninst == ninst_ && period == period_ && key == k;
-    }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-};
-BatchBuffers g_batch[64];
-}  // namespace
-
-bool mnk_batch_active() { return t_batch.active; }
-
-bool mnk_batch_defer(mnk_ls* ls) {
-    if (!t_batch.active) return false;
-    const int nsc = (int)((ls->Np + 255) / 256);
-    // (two merged launches: the large-system mode of the schedule -- band + bulk + two alternating chains -- and the small
-    // one, every row in the chain's band, many chains side by side; a second phase in mid-factorization is simply run now)
-    if (ls->algo_now != 5 || (ls->plan.key.js2 != nsc && ls->plan.key.js2 != 0) || ls->dag_trace_on || ls->ctx->partitioned) return false;
-    if (mnk_ctx_ensure_batch_streams(ls->ctx) != 0) (void)hipGetLastError();   // (made with the first batch of a process)
-    if (!ls->ctx->sp_dagB) return false;
-    if (!ls->ev_defer && hipEventCreateWithFlags(&ls->ev_defer, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipEventRecord(ls->ev_defer, ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
-    ls->deferred = true;
-    t_batch.pend.push_back(ls);
-    return true;
-}
-
-// the group's launches are queued on `h`: everybody's stream continues behind them, and every member is a queued factorization
-static int batch_finish(std::vector<mnk_ls*>& g, hipStream_t h) {
-    MNK_HIP(hipEventRecord(g[0]->ev_defer, h));
-    for (mnk_ls* ls : g) {
-        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(ls->ctx->stream, g[0]->ev_defer, 0));
-        ls->verdict.queued();
-        ls->deferred = false;
-        int r = ls->spare.queued(ls);
-        if (r) return r;
-    }
-    return 0;
-}
-
-// the merged launch of g.size() >= 2 deferred factorizations of one order / algorithm / option set on one device
-static int batch_run_group(std::vector<mnk_ls*>& g) {
-    mnk_ls* l0 = g[0];
-    mnk_ctx* c0 = l0->ctx;
-    hipStream_t h = c0->stream;
-    MNK_HIP(hipSetDevice(c0->device));
-    const int64_t Np = l0->Np;
-    const bool ldl = l0->algo == MNK_LDL;
-    const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256), ninst = (int)g.size();
-    const size_t nflags = DagPlan::progress_words(Np);
-    for (mnk_ls* ls : g)
-        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(h, ls->ev_defer, 0));
-    int rc = mnk_persist_begin(c0, h);
-    if (rc) return rc;
-    auto body = [&]() -> int {
-        BatchBuffers& B = g_batch[c0->device & 63];
-        const int period = (ntile + 1) / 2;   // shift between consecutive instances in the merged queue, in tile columns of chain position: half the matrix, the minimum
-        if (!B.holds(ntile, ninst, period, l0->plan.key)) {
-            std::vector<int> merged;
-            mnk::dag_merge_tasks(l0->plan.host_tasks, l0->plan.host_ready, ninst, period, merged);
-            if (B.tasks.alloc(merged.size() + 4)) return -2;
-            { mnk::H2DGuard h2d; MNK_HIP(hipMemcpy(B.tasks.p, merged.data(), merged.size() * sizeof(int), hipMemcpyHostToDevice)); }
-            if (!B.qctr.p && B.qctr.alloc(4)) return -2;
-            if (B.insts.alloc(sizeof(mnk::DagInst) * (size_t)ninst)) return -2;
-            for (hipEvent_t& e : B.ev)
-                if (!e) MNK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            B.ntile = ntile; B.ninst = ninst; B.period = period; B.key = l0->plan.key; B.ntasks = (int)(merged.size() / 4);
-        }
-        std::vector<mnk::DagInst> hin;
-        mnk::DagInst* insts_dev = reinterpret_cast<mnk::DagInst*>(B.insts.p);
-        for (mnk_ls* ls : g) {
-            hin.push_back(dag_instance(ls));
-            ls->spare.dag_fills(hin.back().zfill != nullptr);
-            ls->env_used = hin.back().env != nullptr;
-            ls->envh_used = false;   // (the merged kernel of a batch skips by tiles only)
-            // (the instance's record for the bulk kernel rides along with the reset of its progress words)
-            hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64)), dim3(256), 0, h,
-                               ls->plan.flags.p, (int64_t)nflags, ls->info_dev.p, hin.back(), insts_dev + (hin.size() - 1),
-                               (const mnk::SmallSysRec*)nullptr, ls->env_word.p);
-            ls->src.env_armed = false;
-        }
-        MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
-        hipStream_t sp[2] = {c0->sp_dag, c0->sp_dagB}, su = c0->su_dagB;
-        MNK_HIP(hipEventRecord(B.ev[0], h));
-        MNK_HIP(hipStreamWaitEvent(sp[0], B.ev[0], 0));
-        MNK_HIP(hipStreamWaitEvent(sp[1], B.ev[0], 0));
-        MNK_HIP(hipStreamWaitEvent(su, B.ev[0], 0));
-        const unsigned strips = (unsigned)std::min<int64_t>(l0->dag_band, Np / NBI);
-        const int bulk_wgs = mnk_ctx_bulk_wgs(c0, 2 * c0->dag_cus, 3);   // (the grid that is resident at launch: see ls.hip)
-        // Launch order: the first two chains, THEN the bulk kernel, then everything else -- the host needs ~3 ms for the
-        // 4 x ninst launches of the chains' streams (measured: the bulk kernel used to start 3 ms after the first chain,
-        // 2 % of a 16-instance step).  Per chain stream: chain i, its inverses for the solves and its inertia / info words
-        // (the next chain of the stream starts behind them; the bulk kernel has work of the other instance meanwhile).
-        auto launch_chain = [&](int i) -> int {
-            mnk_ls* ls = g[i];
-            mnk::PpDag dag{hin[i].front, hin[i].af, ntile, 0, 0, -1, mnk_ls_dag_spin_limit(ls), nullptr, ls->bk.growth_word(ls)};
-            return mnk_launch_pchain(ls, sp[i & 1], dag, 0, nsc, strips);
-        };
-        auto launch_tail = [&](int i) -> int {
-            mnk_ls* ls = g[i];
-            int r = mnk_ls_invert_blocks(ls, sp[i & 1], 0, nsc);
-            if (r) return r;
-            ls->inv_done = nsc;
-            return mnk_ls_launch_finish_info(ls, sp[i & 1]);
-        };
-        for (int i = 0; i < std::min(2, ninst); ++i) {
-            int r = launch_chain(i);
-            if (r) return r;
-        }
-        int r = mnk::launch_dag_bulk(su, ldl, hin[0], insts_dev, B.tasks.p, B.ntasks, ntile, B.qctr.p,
-                                     mnk_ls_dag_spin_limit(l0), std::min(B.ntasks, bulk_wgs), nullptr, nullptr);
-        if (r) return r;
-        for (int i = 0; i < ninst; ++i) {
-            r = launch_tail(i);
-            if (r) return r;
-            if (i + 2 < ninst) {
-                r = launch_chain(i + 2);
-                if (r) return r;
-            }
-        }
-        MNK_HIP(hipEventRecord(B.ev[1], sp[0]));
-        MNK_HIP(hipEventRecord(B.ev[2], sp[1]));
-        MNK_HIP(hipEventRecord(B.ev[3], su));
-        for (int e = 1; e < 4; ++e) MNK_HIP(hipStreamWaitEvent(h, B.ev[e], 0));
-        return 0;
-    };
-    rc = body();
-    rc = mnk_persist_end(c0, h, rc);
-    if (rc) return rc;
-    return batch_finish(g, h);
-}
-
-// Small systems (every row a strip of the chain, dag_js2 == 0): rounds of K systems whose chains run SIDE BY SIDE in one
-// launch (factor.hip: pchain_multi_kernel) on K * strips CUs, the band tiles of all of them accumulated by one bulk
-// launch on the other CUs (systems of up to 768 rows have no bulk task at all).  A system this small is bound by its own
-// pivot chain from the first column on -- 0.9 ms for N = 2048 on the whole chip, of which it uses 32 CUs.
-static int batch_run_group_small(std::vector<mnk_ls*>& g) {
-    mnk_ls* l0 = g[0];
-    mnk_ctx* c0 = l0->ctx;
-    hipStream_t h = c0->stream;
-    MNK_HIP(hipSetDevice(c0->device));
-    const int64_t Np = l0->Np;
-    const bool ldl = l0->algo == MNK_LDL;
-    const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256), strips = (int)(Np / NBI);
-    const size_t nflags = DagPlan::progress_words(Np);
-    const int ntasks1 = l0->plan.ntasks;   // (single phase: all tasks)
-    const int bulk_min = ntasks1 > 0 ? std::max(32, c0->num_cu / 4) : 0;
-    // The chains' CU partition is a multiple of 32 CUs: every workgroup of the chain launch must be RESIDENT (one per CU), and
-    // the dispatcher places them all only when the mask gives every shader engine of every XCD the same number of CUs --
-    // 8 XCDs x 4 SEs = 32 (tools/hip/mask_resident.hip: masks of 32 / 64 / 96 / 192 / 256 bits hold as many 96-KB workgroups
-    // as they have bits; 40, 48, 56, 72, 104, 176 do not, e.g. 34 workgroups on a 40-bit mask: 32 resident -- five 34-strip
-    // systems on 176 CUs stalled into the schedule's time-out).
-    // (... and of 64, so that a process ends up with three such stream pairs at most: every masked stream is a hardware queue,
-    // and the device runs only so many of them side by side -- ls.hip, ctx_create_common)
-    auto chain_cus_for = [&](int k) { return std::min(c0->num_cu, (k * strips + 63) / 64 * 64); };
-    int kmax = std::min(32, (c0->num_cu - bulk_min) / strips);
-    while (kmax > 1 && chain_cus_for(kmax) > c0->num_cu - bulk_min) --kmax;
-    if (kmax < 2) {   // (no room for two chains: one after the other, as without a batch)
-        for (mnk_ls* ls : g) {
-            ls->deferred = false;
-            int rc = mnk_ls_run_factorization_now(ls);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    for (mnk_ls* ls : g)
-        if (ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(h, ls->ev_defer, 0));
-    BatchBuffers& B = g_batch[c0->device & 63];
-    for (size_t r0 = 0; r0 < g.size(); r0 += (size_t)kmax) {
-        const int k = (int)std::min<size_t>(kmax, g.size() - r0);
-        hipStream_t sp = nullptr, su = nullptr;
-        int rc = mnk_masked_stream_pair(c0, chain_cus_for(k), &sp, &su);
-        if (rc) return rc;
-        if (ntasks1 > 0 && su == nullptr) { set_error("factorize batch: no CUs left for the bulk kernel"); return -1; }
-        rc = mnk_persist_begin(c0, h);
-        if (rc) return rc;
-        auto body = [&]() -> int {
-            if (ntasks1 > 0 && !B.holds(ntile, k, 0, l0->plan.key)) {
-                std::vector<int> merged;
-                mnk::dag_merge_tasks(l0->plan.host_tasks, l0->plan.host_ready, k, 0, merged);
-                if (B.tasks.alloc(merged.size() + 4)) return -2;
-                { mnk::H2DGuard h2d; MNK_HIP(hipMemcpy(B.tasks.p, merged.data(), merged.size() * sizeof(int), hipMemcpyHostToDevice)); }
-                B.ntile = ntile; B.ninst = k; B.period = 0; B.key = l0->plan.key; B.ntasks = (int)(merged.size() / 4);
-            }
-            if (!B.qctr.p && B.qctr.alloc(4)) return -2;
-            if (B.insts.n < sizeof(mnk::DagInst) * (size_t)k && B.insts.alloc(sizeof(mnk::DagInst) * (size_t)std::max(k, 32))) return -2;
-            if (B.pcsys.n < mnk_pchain_sys_bytes() * (size_t)k && B.pcsys.alloc(mnk_pchain_sys_bytes() * (size_t)std::max(k, 32))) return -2;
-            for (hipEvent_t& e : B.ev)
-                if (!e) MNK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            // The records of this round (instances for the bulk kernel, the chains' table, what the kernels around them
-            // need) go through pinned host memory in ONE piece each: a kernel launch per record and per small kernel made the
-            // host the bound of a batch of many small systems (~8 launches per system).
-            std::vector<mnk::DagInst> hin;
-            mnk::DagInst* insts_dev = reinterpret_cast<mnk::DagInst*>(B.insts.p);
-            const size_t pc_bytes = mnk_pchain_sys_bytes();
-            const size_t need = (size_t)k * (sizeof(mnk::DagInst) + pc_bytes + sizeof(mnk::SmallSysRec));
-            if (B.aux.n < sizeof(mnk::SmallSysRec) * (size_t)k && B.aux.alloc(sizeof(mnk::SmallSysRec) * (size_t)std::max(k, 32))) return -2;
-            if (B.stage_ev == nullptr) MNK_HIP(hipEventCreateWithFlags(&B.stage_ev, hipEventDisableTiming));
-            else MNK_HIP(hipEventSynchronize(B.stage_ev));   // (the previous round's uploads have left the staging memory)
-            if (B.stage_bytes < need) {
-                mnk::LaunchLock lock;
-                if (B.stage) { mnk::quiesce_persistent(); (void)hipHostFree(B.stage); B.stage = nullptr; }
-                const size_t cap = (size_t)std::max(k, 32) * (sizeof(mnk::DagInst) + pc_bytes + sizeof(mnk::SmallSysRec));
-                MNK_HIP(hipHostMalloc((void**)&B.stage, cap, hipHostMallocDefault));
-                B.stage_bytes = cap;
-            }
-            mnk::DagInst* st_inst = reinterpret_cast<mnk::DagInst*>(B.stage);
-            char* st_pc = B.stage + (size_t)k * sizeof(mnk::DagInst);
-            mnk::SmallSysRec* st_aux = reinterpret_cast<mnk::SmallSysRec*>(st_pc + (size_t)k * pc_bytes);
-            const bool batch_aux = l0->solves.linv_mfma && !l0->solves.solve512;   // (the other inverse kernels have no batched form)
-            for (int i = 0; i < k; ++i) {
-                mnk_ls* ls = g[r0 + i];
-                hin.push_back(dag_instance(ls));
-                ls->spare.dag_fills(hin.back().zfill != nullptr);
-                hin.back().env = nullptr;   // (batches of small systems run dense: their bulk tasks only accumulate band tiles)
-                hin.back().envgate = nullptr;
-                hin.back().envh = nullptr;
-                ls->env_used = false;
-                ls->envh_used = false;
-                st_inst[i] = hin.back();
-                mnk_pchain_fill_sys(ls, st_pc + (size_t)i * pc_bytes, hin.back().front, hin.back().af);
-                mnk_ls_fill_small_rec(ls, st_aux + i);
-            }
-            MNK_HIP(hipMemcpyAsync(B.insts.p, st_inst, (size_t)k * sizeof(mnk::DagInst), hipMemcpyHostToDevice, h));
-            MNK_HIP(hipMemcpyAsync(B.pcsys.p, st_pc, (size_t)k * pc_bytes, hipMemcpyHostToDevice, h));
-            MNK_HIP(hipMemcpyAsync(B.aux.p, st_aux, (size_t)k * sizeof(mnk::SmallSysRec), hipMemcpyHostToDevice, h));
-            MNK_HIP(hipEventRecord(B.stage_ev, h));
-            const mnk::SmallSysRec* aux_dev = reinterpret_cast<const mnk::SmallSysRec*>(B.aux.p);
-            hipLaunchKernelGGL(mnk::dag_reset_kernel, dim3((unsigned)std::min<size_t>((nflags + 1023) / 1024, 64), (unsigned)k), dim3(256), 0, h,
-                               (int*)nullptr, (int64_t)0, (int*)nullptr, hin[0], (mnk::DagInst*)nullptr, aux_dev);
-            MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
-            MNK_HIP(hipEventRecord(B.ev[0], h));
-            MNK_HIP(hipStreamWaitEvent(sp, B.ev[0], 0));
-            if (su != nullptr) MNK_HIP(hipStreamWaitEvent(su, B.ev[0], 0));
-            // (the records of the chains' table are written on the home stream before the fork)
-            int r = mnk_launch_pchain_multi(g.data() + r0, k, sp, B.pcsys.p);
-            if (r) return r;
-            if (ntasks1 > 0) {
-                const int bulk_wgs = mnk_ctx_bulk_wgs(c0, chain_cus_for(k), 3);
-                r = mnk::launch_dag_bulk(su, ldl, hin[0], insts_dev, B.tasks.p, B.ntasks, ntile, B.qctr.p, mnk_ls_dag_spin_limit(l0),
-                                         std::min(B.ntasks, bulk_wgs), nullptr, nullptr);
-                if (r) return r;
-                MNK_HIP(hipEventRecord(B.ev[2], su));
-                MNK_HIP(hipStreamWaitEvent(h, B.ev[2], 0));
-            }
-            MNK_HIP(hipEventRecord(B.ev[1], sp));
-            MNK_HIP(hipStreamWaitEvent(h, B.ev[1], 0));
-            if (su != nullptr) MNK_HIP(hipStreamWaitEvent(su, B.ev[1], 0));   // (all chains done: every system's factor is final)
-            if (su != nullptr) MNK_HIP(hipStreamWaitEvent(sp, B.ev[2], 0));
-            // inverses for the solves, inertia / info words: small latency-bound kernels, spread over the three streams
-            if (batch_aux) {
-                // ONE launch each for all systems of the round: 64 x 64 inverses, 256 x 256 inverses, inertia / info words
-                r = mnk_ls_invert_blocks_batch(h, ldl, aux_dev, k, Np);
-                if (r) return r;
-                r = mnk_ls_finish_info_batch(h, aux_dev, k, ldl ? (l0->N >= 4096 ? 1024 : 256) : 64);
-                if (r) return r;
-                for (int i = 0; i < k; ++i) {
-                    mnk_ls* ls = g[r0 + i];
-                    ls->inv_done = nsc;
-                    r = ls->verdict.record_info_event(h);
-                    if (r) return r;
-                }
-                return 0;
-            }
-            hipStream_t inv_s[3] = {h, sp, su != nullptr ? su : sp};
-            for (int i = 0; i < k; ++i) {
-                mnk_ls* ls = g[r0 + i];
-                hipStream_t si = inv_s[i % 3];
-                r = mnk_ls_invert_blocks(ls, si, 0, nsc);
-                if (r) return r;
-                ls->inv_done = nsc;
-                r = mnk_ls_launch_finish_info(ls, si);
-                if (r) return r;
-            }
-            MNK_HIP(hipEventRecord(B.ev[1], sp));
-            MNK_HIP(hipStreamWaitEvent(h, B.ev[1], 0));
-            if (su != nullptr) {
-                MNK_HIP(hipEventRecord(B.ev[2], su));
-                MNK_HIP(hipStreamWaitEvent(h, B.ev[2], 0));
-            }
-            return 0;
-        };
-        rc = body();
-        rc = mnk_persist_end(c0, h, rc);
-        if (rc) return rc;
-    }
-    return batch_finish(g, h);
-}
-
-static int batch_flush() {
-    std::vector<mnk_ls*> pend;
-    pend.swap(t_batch.pend);
-    int rc_all = 0;
-    while (!pend.empty()) {
-        // group: same device, order, algorithm and schedule options as the first one pending
-        mnk_ls* l0 = pend.front();
-        std::vector<mnk_ls*> g, rest;
-        for (mnk_ls* ls : pend) {
-            const bool same = ls->ctx->device == l0->ctx->device && ls->Np == l0->Np && ls->algo == l0->algo && ls->plan.key == l0->plan.key;
-            (same && std::find(g.begin(), g.end(), ls) == g.end() ? g : rest).push_back(ls);
-        }
-        pend.swap(rest);
-        int rc;
-        if (g.size() >= 2) {
-            rc = l0->plan.key.js2 == 0 ? batch_run_group_small(g) : batch_run_group(g);
-            if (rc)   // (nothing of the group counts as factorized: the factor buffers already hold the NEW, unfactored matrices, so
-                      // a solve or an inertia call that ignores this error must not find the previous factorization's flag)
-                for (mnk_ls* ls : g) { ls->deferred = false; ls->verdict.launch_failed(); }
-        } else {
-            g[0]->deferred = false;
-            if (g[0]->Np < g[0]->dag_min_rows) g[0]->algo_now = 4;   // (alone, a system below the schedule's window keeps its usual one)
-            rc = mnk_ls_run_factorization_now(g[0]);
-            if (rc) g[0]->verdict.launch_failed();
-        }
-        if (rc && !rc_all) rc_all = rc;
-    }
-    return rc_all;
-}
-
-int mnk_ls_sync_deferred(mnk_ls* ls) {
-    {   // (queued solves of this solver run before anything else touches it)
-        int rc_s = mnk_solve_sync_deferred(ls);
-        if (rc_s) return rc_s;
-    }
-    return mnk_ls_sync_deferred_fact(ls);
-}
-
-// true: a factorize! call of this solver is queued in a batch that ANOTHER thread opened (its thread-local list holds the pointer)
-bool mnk_ls_pending_elsewhere(const mnk_ls* ls) {
-    return ls->deferred && std::find(t_batch.pend.begin(), t_batch.pend.end(), ls) == t_batch.pend.end();
-}
-
-int mnk_ls_sync_deferred_fact(mnk_ls* ls) {
-    if (!ls->deferred) return 0;
-    if (std::find(t_batch.pend.begin(), t_batch.pend.end(), ls) == t_batch.pend.end()) {
-        set_error("a factorize! call of this solver is pending in a batch that another thread opened (mnk_factorize_batch_end must come first)");
-        return -1;
-    }
-    return batch_flush();   // (the batch stays open: later factorize! calls form the next group)
-}
-
-extern "C" int mnk_factorize_batch_begin(void) {
-    ++t_batch.depth;
-    t_batch.active = true;
-    return 0;
-}
-
-extern "C" int mnk_factorize_batch_end(void) {
-    if (t_batch.depth <= 0) { set_error("mnk_factorize_batch_end: no batch is open on this thread"); return -1; }
-    if (--t_batch.depth > 0) return 0;
-    t_batch.active = false;
-    return batch_flush();
-}
-
-// Diagnostics / tests: the task list of the schedule for a matrix of `ntile` 128-row tiles (host only, no device needed).
-// out: 4 ints per task as the bulk kernel reads them (flags | chunk index << 8, I, J, kbeg | kend << 16), at most `cap`
-// tasks are written; returns the number of tasks, *first_phase receives the number of first-phase tasks.
-extern "C" int mnk_debug_dag_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int* out, int cap, int* first_phase) {
-    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0) return -1;
-    std::vector<int> h;
-    const int n1 = mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, nullptr);
-    const int n = (int)(h.size() / 4);
-    if (first_phase != nullptr) *first_phase = n1;
-    if (out != nullptr)
-        for (int i = 0; i < std::min(n, cap) * 4; ++i) out[i] = h[i];
-    return n;
-}
-
-// Diagnostics / tests: the merged queue of `ninst` instances (with the zero-fill tasks if `fill`), 4 ints per task with the
-// instance index in the upper half of the second one; returns the number of tasks.
-extern "C" int mnk_debug_dag_merged_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period,
-                                          int* out, int cap) {
-    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0 || ninst <= 0 || period < 0) return -1;
-    std::vector<int> h, ready, merged;
-    int n1 = mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, &ready);
-    if (fill) n1 = mnk::dag_add_fill_tasks(ntile, h, ready, n1);
-    mnk::dag_merge_tasks(h, ready, ninst, period, merged);
-    const int n = (int)(merged.size() / 4);
-    if (out != nullptr)
-        for (int i = 0; i < std::min(n, cap) * 4; ++i) out[i] = merged[i];
-    return n;
-}
-
-// Diagnostics / tests: the list above (with the zero-fill tasks if `fill`; merged over `ninst` > 1 instances with shift `period`)
-// dealt into `nq` queues per phase as the single-factorization bulk kernel pops them (dag_deal_tasks; nq <= 1: the list itself).
-// order: the list positions, queue after queue -- the first phase's queues, then the second phase's; off: 2 x (nq + 1) offsets into
-// `order`.  Returns the number of tasks; at most `cap` positions are written.  Host only.
-extern "C" int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period, int nq,
-                                  int gang, int* tasks_out, int* order, int cap, int* off, int* first_phase) {
-    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0 || ninst <= 0 || period < 0 || nq <= 0 || nq > 64 || gang == 0) return -1;
-    std::vector<int> h, ready;
-    int n1 = mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, &ready);
-    if (fill) n1 = mnk::dag_add_fill_tasks(ntile, h, ready, n1);
-    if (ninst > 1) {   // (the merged list of a batch: one part; `ready` of a merged task is its key of the merge)
-        std::vector<int> merged, mready, pos(ninst, 0);
-        mnk::dag_merge_tasks(h, ready, ninst, period, merged);
-        for (size_t t = 0; t < merged.size() / 4; ++t) { const int i = merged[4 * t + 1] >> 16; mready.push_back(i * period + ready[pos[i]++]); }
-        h.swap(merged);
-        ready.swap(mready);
-        n1 = (int)ready.size();
-    }
-    const int n = (int)ready.size();
-    if (first_phase != nullptr) *first_phase = n1;
-    const int part[3] = {0, n1, n};
-    int written = 0;
-    for (int ph = 0; ph < 2; ++ph) {
-        std::vector<int> ord, o;
-        mnk::dag_deal_tasks(h, ready, part[ph], part[ph + 1], nq, gang, ord, o);
-        for (int x = 0; x <= nq; ++x)
-            if (off != nullptr) off[ph * (nq + 1) + x] = part[ph] + o[x];
-        for (int v : ord) {
-            if (order != nullptr && written < cap) order[written] = v;
-            ++written;
-        }
-    }
-    if (tasks_out != nullptr)
-        for (int i = 0; i < std::min(n, cap) * 4; ++i) tasks_out[i] = h[i];
-    return n;
-}
-
-// Diagnostics / tests: the statistics envh_ksteps (count[0]) and envh_ksteps_skipped (count[1]) of the task list of `ntile` tiles
-// under the tile envelope `env` (ntile entries) and the half-tile envelope `envh` (2 ntile entries; NULL: nothing skipped).  Host only.
-extern "C" int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int taper0, const int* env, const int* envh, int64_t* count) {
-    if (ntile <= 0 || chunk <= 0 || band_tiles <= 0 || taper0 <= 0 || count == nullptr) return -1;
-    std::vector<int> h;
-    (void)mnk::dag_build_tasks(ntile, chunk, band_tiles, js2, h, taper0, nullptr);
-    mnk::dag_envh_count(h, env, envh, ntile, count);
-    return (int)(h.size() / 4);
-}

@@ -1191,7 +1191,7 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     ls->algo_now = ls->panel_algo;
     ls->env_used = false;   // (the task-DAG schedule sets it when it launches with an envelope)
     ls->envh_used = false;
-    // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag.hip)
+    // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag_batch.hip)
     const int64_t min_rows = mnk_batch_active() ? std::min<int64_t>(ls->dag_min_rows, 256) : ls->dag_min_rows;
     if (ls->algo_now == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) ls->algo_now = 4;
     if (ls->algo_now == 5 && ctx->sp_dag == nullptr && mnk_ctx_ensure_dag(ctx) != 0) { (void)hipGetLastError(); ls->algo_now = 4; }   // (released while idle)
@@ -1205,7 +1205,7 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     }
     // Persistent schedules of different contexts take turns on the device (common.h: mnk_persist_begin); round 3 sent every
     // solver to schedule 1 as soon as a second context was alive (12.4 instead of 9.3 ms at C3).
-    // a batch of independent factorizations (dag.hip: mnk_factorize_batch_begin / _end) launches them together later
+    // a batch of independent factorizations (dag_batch.hip: mnk_factorize_batch_begin / _end) launches them together later
     if (ls->algo_now == 5 && mnk_batch_defer(ls)) return 0;
     return mnk_ls_run_factorization_now(ls);
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dag_plan.h"
 
 struct mnk_sc {
     mnk_ctx* ctx = nullptr;
@@ -126,8 +127,8 @@ struct SpareFill {
     hipEvent_t ev_zeroed = nullptr, ev_free = nullptr;   // "the fill is done" / "everything queued before the fill has run"
 };
 
-// The task-DAG plan (dag.hip): the task list of the schedule for this solver's order and what is derived from it.  Built by
-// mnk_ls_dag_prepare when there is none; every option the list depends on calls invalidate().
+// The task-DAG plan: the task list of the schedule for this solver's order (dag_plan.h) and what is derived from it.  Built by
+// mnk_ls_dag_prepare (dag.hip) when there is none; every option the list depends on calls invalidate().
 struct DagPlan {
     // What batch_flush groups solvers of one device, order and algorithm by, and what (with ntile, the instances and their shift)
     // makes a merged list reusable.  dag_deep_rows and the dag_js2 override enter through js2, dag_fill and prefill through
@@ -139,9 +140,8 @@ struct DagPlan {
         bool operator==(const Key& o) const { return chunk == o.chunk && taper0 == o.taper0 && band == o.band && js2 == o.js2 && has_fill == o.has_fill; }
     };
     Key key;
-    mnk::DevBuf<int> tasks;                  // 4 ints per task, dealt into the per-XCD queues of the single-factorization bulk kernel (dag_deal_tasks)
-    std::vector<int> host_tasks, host_ready; // the list as built and the chain position that makes each task ready: merged per batch
-    int ntasks = 0, ntasks1 = 0;             // all tasks / tasks of the first phase
+    mnk::DevBuf<int> tasks;                  // 4 ints per task, dealt into the per-XCD queues of the single-factorization bulk kernel (dag_plan.h: dag_deal_list)
+    mnk::DagTaskList list;                   // the list as built (kept on the host: a batch merges the lists of its instances, the statistics count from it)
     int nq[2] = {0, 0};                      // queues per phase (0: one queue, the list as built)
     mnk::DevBuf<int> qoff;                   // per phase 16 ints: the nq + 1 offsets of the queues in the phase's part of the list
     mnk::DevBuf<int> qheads;                 // per phase DAG_QHEAD_WORDS ints: the queue heads, 128 bytes apart, then the count of stolen tasks
@@ -407,13 +407,13 @@ int mnk_ls_factorize_dense_dev_async(mnk_ls* ls, const double* Adev, int64_t lda
 double mnk_host_ms();                               // factor.hip: steady host clock in ms
 void mnk_add_process_stall_ms(double ms);           // factor.hip: time lost to expired device-side waits, all solvers of the process
 double mnk_process_stall_ms();
-bool mnk_ls_pending_elsewhere(const mnk_ls* ls);   // dag.hip: queued in a factorization batch of ANOTHER thread
-bool mnk_batch_active();                           // dag.hip: the calling thread has a factorization batch open
+bool mnk_ls_pending_elsewhere(const mnk_ls* ls);   // dag_batch.hip: queued in a factorization batch of ANOTHER thread
+bool mnk_batch_active();                           // dag_batch.hip: the calling thread has a factorization batch open
 size_t mnk_pchain_sys_bytes();                     // factor.hip: size of one record of mnk_launch_pchain_multi's table
 int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, void* table);   // factor.hip: the chains of n small systems in one launch (table: n records of mnk_pchain_fill_sys, uploaded)
-bool mnk_batch_defer(mnk_ls* ls);                  // dag.hip: true if the calling thread has a batch open and took the factorization into it
-int mnk_ls_sync_deferred(mnk_ls* ls);              // dag.hip: runs what the open batches of this thread hold for this solver (queued solves, a pending factorization)
-int mnk_ls_sync_deferred_fact(mnk_ls* ls);         // dag.hip: ... the pending factorization only
+bool mnk_batch_defer(mnk_ls* ls);                  // dag_batch.hip: true if the calling thread has a batch open and took the factorization into it
+int mnk_ls_sync_deferred(mnk_ls* ls);              // dag_batch.hip: runs what the open batches of this thread hold for this solver (queued solves, a pending factorization)
+int mnk_ls_sync_deferred_fact(mnk_ls* ls);         // dag_batch.hip: ... the pending factorization only
 int mnk_ls_fetch_info(mnk_ls* ls);
 int mnk_ls_run_factorization_dag(mnk_ls* ls);   // dag.hip: the task-DAG schedule (panel_algo = 5)
 int mnk_ls_dag_prepare(mnk_ls* ls);             // dag.hip: its buffers (0: ready; otherwise the device cannot hold them -> schedule 4)
@@ -427,7 +427,40 @@ int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);  
 int mnk_ls_right_trsm_rows(mnk_ls* ls, hipStream_t s, int64_t j0, double* Xrows, double* Vrows, int64_t ldr, int64_t nrows);
 long mnk_ls_dag_spin_limit(const mnk_ls* ls);   // dag.hip
 namespace mnk {
-// One system of a batch of SMALL factorizations (dag.hip: batch_run_group_small): what the kernels around the shared chain
+// What a bulk task needs to know about the factorization it belongs to.  One launch may serve SEVERAL independent
+// factorizations of the same order (mnk_factorize_batch_*: the task lists of the instances are merged into one queue, each
+// task carries its instance index), so these live in a per-instance record instead of the kernel's argument block.
+struct DagInst {
+    double* F;
+    int64_t ld;
+    double* V;            // LDL^T: V = L D, same layout as F (the B operand of the updates); Cholesky: nullptr (V = L)
+    const double* dinv;   // 1 / d_k
+    const double* dblk;   // factored 64x64 diagonal blocks
+    const double* inv16;  // inverses of their 16x16 diagonal sub-blocks
+    int* front;
+    int* af;
+    int* tprog;           // [I * ntile + J]: chunks of tile (I, J) that are in memory
+    int* info;
+    unsigned long long* vmax;   // growth monitor of the static-pivot LDL^T (factor.hip growth_fold): receives max|V|, or NULL
+    double* zfill;        // DAG_FILL tasks: the buffer that becomes the NEXT factorization's zeroed factor buffer (or NULL)
+    int64_t N;            // order of the matrix (rows / columns N .. Np - 1 are padding: unit diagonal)
+    const int* env;       // envelope per tile row (mnk_sc::tile_env): L(I, k) = 0 for tile columns k < env[I]; NULL: dense
+    const int* envgate;   // != 0: a NaN / Inf entry was transferred, the envelope is off for this factorization (mnk_ls::env_word)
+    const int* envh;      // envelope per 64-row half of a tile row in 64-column units (mnk_sc::tile_envh; only dag_bulk_kernel1 reads it); NULL: none
+};
+struct SmallSysRec;
+// dag.hip, for the batches of dag_batch.hip.  The record of `ls` for its next task-DAG launch, with what the solver remembers
+// about that launch (spare fill, env_used / envh_used); `dense`: the launch ignores the envelope.
+DagInst dag_prepare_instance(mnk_ls* ls, bool dense);
+// dag_reset_kernel for a member of a merged launch: its progress words, info and envelope word; its record goes to `rec_dst`
+void dag_reset_member(hipStream_t s, mnk_ls* ls, const DagInst& rec, DagInst* rec_dst);
+// ... for a round of `k` small systems of padded order Np (their records and progress words: recs_dev)
+void dag_reset_round(hipStream_t s, int64_t Np, const SmallSysRec* recs_dev, int k);
+// the bulk kernel of a merged queue (dag_plan.h: dag_merge_tasks) over the instance records `insts`
+int launch_dag_bulk_merged(hipStream_t s, bool ldl, const DagInst* insts, const int* tasks, int ntasks, int ntile, int* qctr,
+                           long spin_limit, int nwg);
+
+// One system of a batch of SMALL factorizations (dag_batch.hip: batch_run_group_small): what the kernels around the shared chain
 // launch need, so that they are ONE launch per batch round instead of one per system (blockIdx.z / .y / .x = system; the
 // host's launch rate was the bound: ~8 launches per system, 9 of the 10.9 ms of a 128-scenario Schur build).
 struct SmallSysRec {

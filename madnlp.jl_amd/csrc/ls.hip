@@ -755,7 +755,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
         return 0;
     }
     if (!strcmp(key, "dag_fill")) { ls->dag_fill = value != 0.0; ls->plan.invalidate(); return 0; }   // zero-fill of the spare buffer as tasks of the bulk queue
-    // per-XCD queues of the bulk kernel (dag.hip: dag_deal_tasks); the task list is dealt again
+    // per-XCD queues of the bulk kernel (dag_plan.hip: dag_deal_list); the task list is dealt again
     if (!strcmp(key, "dag_xcd_queues")) { ls->dag_xcd_queues = value != 0.0; ls->plan.invalidate(); return 0; }   // 0: one queue, popped by every workgroup
     if (!strcmp(key, "dag_gang")) {   // tasks of one group that go to one queue together; negative: every task to queue 0 (tests of the steal path)
         MNK_REQUIRE(value <= 64.0 && value != 0.0 && (double)(int)value == value, "dag_gang must be an integer in 1..64 (or negative)");
@@ -1419,8 +1419,8 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk.multi_last() ? 1.0 : 0.0; return 0; }
     if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk.mw_fallbacks(); return 0; }
     if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain
-    if (!strcmp(key, "dag_ntasks")) { *value = ls->plan.ntasks; return 0; }    // task-DAG schedule: bulk tasks, ...
-    if (!strcmp(key, "dag_ntasks1")) { *value = ls->plan.ntasks1; return 0; }  // ... of them in the first phase, ...
+    if (!strcmp(key, "dag_ntasks")) { *value = ls->plan.list.size(); return 0; }    // task-DAG schedule: bulk tasks, ...
+    if (!strcmp(key, "dag_ntasks1")) { *value = ls->plan.list.n1; return 0; }  // ... of them in the first phase, ...
     if (!strcmp(key, "dag_js2")) { *value = ls->plan.key.js2; return 0; }          // ... first strip-column of the second phase
     if (!strcmp(key, "dag_nq")) { *value = std::max(ls->plan.nq[0], ls->plan.nq[1]); return 0; }   // ... queues the device list is dealt into (0: one)
     if (!strcmp(key, "dag_steals")) {   // ... tasks the last factorization's workgroups took from another XCD's queue
@@ -1435,20 +1435,11 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
         // task-DAG schedule: 128-column k-steps of the bulk tasks (tile columns of the chunks' K-loops, one per closing task) in
         // the task list / of them skipped by the last factorization as structurally zero (0 without an envelope, with the
         // envelope off, or when a NaN / Inf entry closed it)
-        int64_t total = 0, skipped = 0;
         int gate = 1;
         if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
-        const std::vector<int>& h = ls->plan.host_tasks;
-        const int ne = (int)ls->src.env_host.size();
-        for (size_t t = 0; t + 3 < h.size(); t += 4) {
-            const int flags = h[t] & 255, I = h[t + 1] & 0xffff, J = h[t + 2], kb = h[t + 3] & 0xffff, ke = h[t + 3] >> 16;
-            if (flags & 8) continue;   // (DAG_FILL)
-            total += ke - kb;
-            if (!ls->env_used || gate != 0 || I >= ne || J >= ne) continue;
-            const int e = std::max(ls->src.env_host[I], ls->src.env_host[J]);
-            skipped += std::min(ke, std::max(kb, e)) - kb;
-        }
-        *value = (double)(!strcmp(key, "env_ksteps") ? total : skipped);
+        int64_t cnt[2] = {0, 0};
+        mnk::dag_env_count(ls->plan.list, ls->env_used && gate == 0 ? ls->src.env_host.data() : nullptr, (int)ls->src.env_host.size(), cnt);
+        *value = (double)(!strcmp(key, "env_ksteps") ? cnt[0] : cnt[1]);
         return 0;
     }
     if (!strcmp(key, "envh_ksteps") || !strcmp(key, "envh_ksteps_skipped")) {
@@ -1459,7 +1450,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
         if (ls->env_used && ls->env_word.p) MNK_HIP(mnk::d2h_copy(&gate, ls->env_word.p + 1, sizeof(int), ls->ctx->stream));
         const bool on = ls->env_used && gate == 0;
         int64_t cnt[2] = {0, 0};
-        mnk::dag_envh_count(ls->plan.host_tasks, on ? ls->src.env_host.data() : nullptr, on && ls->envh_used ? ls->src.envh_host.data() : nullptr,
+        mnk::dag_envh_count(ls->plan.list, on ? ls->src.env_host.data() : nullptr, on && ls->envh_used ? ls->src.envh_host.data() : nullptr,
                             (int)ls->src.env_host.size(), cnt);
         *value = (double)(!strcmp(key, "envh_ksteps") ? cnt[0] : cnt[1]);
         return 0;

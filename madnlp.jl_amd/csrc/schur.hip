@@ -301,7 +301,7 @@ int mnk_schur_build_local(mnk_schur* h, const double* S0, int64_t lds0, int loc_
             MNK_HIP(mnk::h2d_copy_2d(h->Sp.p, ndp * sizeof(double), S0, lds0 * sizeof(double), nd * sizeof(double), nd, s));
     }
     // Phase 1a (reference :955-990, `@blas_safe_threads for k in 1:ns`): the scenario blocks are factored TOGETHER -- one
-    // batch (dag.hip): the pivot chains of up to 32 blocks side by side in one launch instead of one whole-chip factorization
+    // batch (dag_batch.hip): the pivot chains of up to 32 blocks side by side in one launch instead of one whole-chip factorization
     // and one host synchronization per scenario (a 512-row block is chain-bound at 0.03 of the peak on its own)
     {
         int rc = mnk_factorize_batch_begin();
