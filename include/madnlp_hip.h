@@ -708,6 +708,13 @@ int mnk_debug_envh_ksteps(int ntile, int chunk, int band_tiles, int js2, int tap
  * opened): cols[i] is the column at which verdict i was rejected early, or -1 for an acceptance; orders[i] receives the order of the
  * leading block through which the matrix of verdict i would be probed first (0: no probe), i.e. before verdict i is noted. */
 int mnk_debug_probe_schedule(int64_t N, int n, const int64_t* cols, int64_t* orders);
+/* The steps of one factorization under the launch-per-panel schedules (option "panel_algo" 1 or 4; csrc/factor_plan.hip; host only,
+ * no device is opened) for a padded order Np (a multiple of 64): 16 ints per step in the order of FactorStep's members (kind, stream,
+ * col, n, rows, src, K, variant, slot, cus, whalf, wko, rhalf, rko, event, index), in the order the host enqueues them; at most `cap`
+ * steps written.  shape[0] receives the number of outer panels, shape[1] whether the look-ahead streams are used (NULL: neither).
+ * Returns the number of steps, -1 on bad arguments. */
+int mnk_debug_factor_plan(int64_t Np, int ldl, int algo_now, int lookahead, int64_t outer_width, int64_t pp_fuse_rows, int share,
+                          int small_tiles, int num_cu, int panel_cus, int32_t* out, int cap, int* shape);
 
 #ifdef __cplusplus
 }

@@ -873,14 +873,9 @@ int BkTier::factor(mnk_ls* ls, bool multi) {
     const size_t smem = 2 * 8 * ((128 + 16) + (128 + 16)) * sizeof(double);
     const size_t smem_mw = (size_t)(64 * BKM_ROWS + 4 * 64 + 64 + BKM_GMAX * BKM_F + 8 + 4) * sizeof(double) + (8 + 68 + 4) * sizeof(int) + sizeof(BkmCtl) + 64;
     {
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        MNK_HIP(hipGetDevice(&dev));
-        if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-            MNK_HIP(hipFuncSetAttribute((const void*)bkp_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            MNK_HIP(hipFuncSetAttribute((const void*)bkp_panel_mw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_mw));
-            attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
+        static DynLdsAttr attr_update, attr_panel;
+        if (int rc_a = attr_update.set((int)smem, bkp_update_kernel)) return rc_a;
+        if (int rc_a = attr_panel.set((int)smem_mw, bkp_panel_mw_kernel)) return rc_a;
     }
     int gcap = std::min(BKM_GMAX, ls->ctx->num_cu);
     if (bk_max_wgs > 0) gcap = std::min(gcap, bk_max_wgs);

@@ -1,6 +1,7 @@
 // Shared declarations for libmadnlp_hip.so (gfx950 / MI355X only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -50,6 +51,22 @@ constexpr int AMAX_SLOT0 = 16, AMAX_STRIDE = 16, AMAX_SLOTS = 64, AMAX_WORDS = A
 inline hipError_t stream_wait(hipStream_t s) { return hipStreamSynchronize(s); }
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (kernel, device) pair: a launch site keeps one function-local static
+// instance for its kernels and calls set() in front of the launch; the attribute is set once per device of this process.
+struct DynLdsAttr {
+    std::atomic<uint64_t> devs{0};
+    template <class... Kern>
+    int set(int bytes, Kern... kernels) {
+        int dev = 0;
+        MNK_HIP(hipGetDevice(&dev));
+        if (!(devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
+            for (const void* k : {(const void*)kernels...}) MNK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+            devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+        }
+        return 0;
+    }
+};
 
 // One process-wide lock around (a) the launch sequence of every group of PERSISTENT kernels (pivot chain + bulk kernel,
 // persistent panel launches, the one-launch solve: mnk_persist_begin / _end) and (b) every runtime call of this library
@@ -251,7 +268,7 @@ int launch_gemm_nt_batch(hipStream_t s, int64_t M, int64_t N, int64_t K, const G
                          int64_t ldb, int64_t ldc);
 int launch_gemm_nt_lower_small(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                                const double* B, int64_t ldb, double* C, int64_t ldc, const int* info_flag);
-int gemm_nt_lower_tiles(int64_t M, int64_t N);
+int gemm_nt_lower_tiles(int64_t M, int64_t N);   // (factor_plan.hip)
 int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
                          const double* B, int64_t ldb, double* C, int64_t ldc, int* counter, int cus,
                          const int* info_flag);

@@ -782,18 +782,13 @@ __global__ __launch_bounds__(256, 3) void dag_bulk_kernel1(DagArgs1 a) {
     }
 }
 
-// One launcher for the four bulk kernels (template on the kernel, hence one `attr_devs` per kernel): the dynamic LDS attribute is
+// One launcher for the four bulk kernels (template on the kernel, hence one DynLdsAttr per kernel): the dynamic LDS attribute is
 // set once per device, the grid is `nwg` persistent workgroups.
 template <class Args, void (*Kern)(Args)>
 static int launch_bulk(hipStream_t s, const Args& a, int nwg) {
     const size_t smem = TILE3_LDS_BYTES;  // three k-tile buffers of the tile-closing tasks (gemm_nt_mainloop3); chunks use two, the finalization 32 KB
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    MNK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-    }
+    static DynLdsAttr attr;
+    if (int rc = attr.set((int)smem, Kern)) return rc;
     hipLaunchKernelGGL(Kern, dim3(nwg), dim3(256), smem, s, a);
     MNK_HIP(hipGetLastError());
     return 0;

@@ -532,13 +532,8 @@ struct EvdSolver final : mnk_ls_alt {
         const int nb = (int)(Np / EB), npairs = nb / 2;
         double *A = evd_a.p, *V = evd_v.p;
         {   // the pair kernel's LDS is above the static limit: once per (kernel, device) pair of this process
-            static std::atomic<uint64_t> attr_devs{0};
-            int dev = 0;
-            MNK_HIP(hipGetDevice(&dev));
-            if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-                MNK_HIP(hipFuncSetAttribute((const void*)evd_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EVD_PAIR_LDS));
-                attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-            }
+            static DynLdsAttr attr;
+            if (int rc_a = attr.set((int)EVD_PAIR_LDS, evd_pair_kernel)) return rc_a;
         }
         hipLaunchKernelGGL(evd_init_kernel, dim3((unsigned)Np), dim3(256), 0, s, ls->fact.p, ls->ld, N, Np, A, V);
         MNK_HIP(hipGetLastError());

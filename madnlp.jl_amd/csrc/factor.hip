@@ -935,134 +935,118 @@ __global__ __launch_bounds__(1024) void finish_info_kernel(const double* __restr
 
 using namespace mnk;
 
-// middle-level updates (inside an outer panel) with fewer 128x128 tiles than this use 64x64 workgroup tiles
-constexpr int SMALL_TILES_MID = 1000;
-
-// panel_algo = 4: persistent panel launches (ppanel_kernel) of 4 blocks, recursive updates between them
-static int factor_outer_panel_pp(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t kend, double* wbase,
-                                 hipEvent_t rest_ready, int64_t rest_from, const double* Vfirst, int64_t ldvfirst,
-                                 int64_t Kfirst) {
-    const int64_t Np = ls->Np, ld = ls->ld;
+// Schedules 1 and 4: the factorization as the planner lists it (factor_plan.h: what is launched where, in which order, and the
+// invariants every list keeps), executed step by step -- indices become pointers, steps become launches, records and waits.
+// (It stands in front of the pivot-chain launchers because the device side emits kernel templates in the order the host code
+// first names them: here the code object keeps the order profiles/factor_plan_device_asm.txt was recorded with.)
+static int run_factor_steps(mnk_ls* ls) {
+    mnk_ctx* ctx = ls->ctx;
+    const int64_t Np = ls->Np, ld = ls->ld, ldw = ls->ldw;
     const bool ldl = ls->algo == MNK_LDL;
     double* F = ls->fact.p;
-    {   // 96 KB of dynamic LDS: the attribute belongs to the (kernel, device) pair
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        MNK_HIP(hipGetDevice(&dev));
-        if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-            MNK_HIP(hipFuncSetAttribute((const void*)ppanel_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
-            MNK_HIP(hipFuncSetAttribute((const void*)ppanel_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
-            attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
+    FactorPlanIn in{Np, ldl, ls->algo_now, ls->lookahead != 0, mnk_ls_effective_nbo(ls), ls->pp_fuse_rows, ls->share, ls->small_tiles,
+                    ctx->num_cu, ctx->panel_cus};
+    FactorPlanShape shape = factor_plan_build(in, ls->steps);
+    if (shape.lookahead && ctx->sp == nullptr) {   // the streams are made with the first factorization that takes the look-ahead
+        int rc_s = mnk_ctx_ensure_panel_streams(ctx);   // schedule, and their CU split with them: that one is planned again
+        if (rc_s) return rc_s;
+        in.panel_cus = ctx->panel_cus;
+        shape = factor_plan_build(in, ls->steps);
+    }
+    if (shape.lookahead) {
+        const size_t nev = (size_t)shape.npanel + 1;
+        if (ctx->ev_panel.size() < nev) {
+            const size_t old = ctx->ev_panel.size();
+            ctx->ev_panel.resize(nev);
+            ctx->ev_next.resize(nev);
+            ctx->ev_next2.resize(nev);
+            ctx->ev_bdone.resize(nev);
+            for (size_t e = old; e < nev; ++e) {
+                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_panel[e], hipEventDisableTiming));
+                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_next[e], hipEventDisableTiming));
+                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_next2[e], hipEventDisableTiming));
+                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_bdone[e], hipEventDisableTiming));
+            }
+        }
+        if (ls->share != 0) {   // the counters of the shared tile queues: 8 ints per outer step
+            if (ls->tile_ctr.n < 8 * nev) {
+                int rc0 = ls->tile_ctr.alloc(8 * nev);
+                if (rc0) return rc0;
+            }
+            MNK_HIP(hipMemsetAsync(ls->tile_ctr.p, 0, 8 * nev * sizeof(int), ctx->stream));
         }
     }
-    constexpr int NBs = 4;  // 64-column blocks per persistent launch (8 was built and measured slower: 197 + 256 registers)
-    const int64_t ws = (int64_t)NBI * NBs;
+    if (ls->algo_now == 4) {   // 96 KB of dynamic LDS
+        static DynLdsAttr attr;
+        if (int rc_a = attr.set(PP_LDS_BYTES, ppanel_kernel<true, 4>, ppanel_kernel<false, 4>)) return rc_a;
+    }
+    const hipStream_t streams[3] = {ctx->stream, ctx->sp, ctx->su};   // FS_CALLER, FS_PANEL, FS_UPDATE_STREAM
+    hipEvent_t* const events[6] = {&ctx->ev_a, &ctx->ev_b, ctx->ev_panel.data(), ctx->ev_next.data(), ctx->ev_next2.data(),
+                                   ctx->ev_bdone.data()};   // FS_EV_A ... FS_EV_BDONE
     const int epoch16 = ls->epoch * 16;
-    bool waited = rest_ready == nullptr;
-    // columns in front of the next launch that it applies itself (ppanel_kernel's prologue)
-    const double* Vp = Vfirst;
-    int64_t ldv = ldvfirst;
-    int Kp = (int)Kfirst;
-    const bool fuse_mid = ls->pp_fuse_rows > 0 && Np - ko <= ls->pp_fuse_rows;
-    for (int64_t p = ko; p < kend; p += ws) {
-        const int nbk = (int)std::min<int64_t>(NBs, (kend - p) / NBI);
-        if (!waited && p + NBI * nbk > ko + rest_from) {
-            MNK_HIP(hipStreamWaitEvent(s, rest_ready, 0));
-            waited = true;
-        }
-        const unsigned grid = (unsigned)((Np - p) / NBI);
     unsigned long long* vmaxw = ls->bk.growth_word(ls);
-#define MNK_PP(LD, NBT)                                                                                              \
-    hipLaunchKernelGGL((ppanel_kernel<LD, NBT>), dim3(grid), dim3(256), PP_LDS_BYTES, s, F, ld, p, nbk, Np, ls->dblk.p, \
-                       ls->inv16.p, ls->dvec.p, ls->dinv.p, LD ? wbase : (double*)nullptr, LD ? ls->ldw : (int64_t)0,  \
-                       p - ko, ls->info_dev.p, ls->pivot_tol, ls->flag_p.p + p / NBI, epoch16, ls->debug_pp_missing, Vp,  \
-                       ldv, Kp, PpDag{nullptr, nullptr, 0, 0, 4, -1, 0, nullptr, vmaxw})
-        if (ldl) MNK_PP(true, 4);
-        else MNK_PP(false, 4);
-#undef MNK_PP
-        Vp = nullptr;
-        Kp = 0;
-        const int64_t p1 = p + NBI * nbk;
-        if (p1 >= kend) break;
-        const int64_t jj = (p1 - ko) / ws;    // launches of this outer panel that are finished
-        const int64_t w = ws * (jj & -jj);     // columns whose contribution is applied now
-        const int64_t pb = p1 - w;
-        const int64_t ncols = std::min<int64_t>(w, kend - p1);
-        if (fuse_mid && w == ws && ncols <= ws) {  // exactly the next launch's columns: it applies them itself
-            Vp = ldl ? wbase + (pb - ko) * ls->ldw : F + pb * ld;
-            ldv = ldl ? ls->ldw : ld;
-            Kp = (int)w;
-            continue;
+    for (const FactorStep& t : ls->steps) {
+        hipStream_t st = streams[t.stream];
+        double* wbase = ldl && t.whalf >= 0 ? ls->wbuf[t.whalf].p : nullptr;   // the W buffer the step writes ...
+        const int64_t wld = ldl ? ldw : 0, woff = t.col - t.wko;                //  ... and the step's first column in it
+        switch (t.kind) {
+        case FS_LEAF: {
+            double* dblk = ls->dblk.p + (t.col / NBI) * 4096;
+            double* inv16 = ls->inv16.p + (t.col / NBI) * 1024;
+            if (ldl)
+                hipLaunchKernelGGL(potrf64w_kernel<true>, dim3(1), dim3(64), 0, st, F, ld, (int64_t)t.col, dblk, inv16, ls->dvec.p,
+                                   ls->dinv.p, ls->info_dev.p, ls->pivot_tol, vmaxw);
+            else
+                hipLaunchKernelGGL(potrf64w_kernel<false>, dim3(1), dim3(64), 0, st, F, ld, (int64_t)t.col, dblk, inv16, ls->dvec.p,
+                                   ls->dinv.p, ls->info_dev.p, ls->pivot_tol, (unsigned long long*)nullptr);
+            break;
         }
-        if (!waited && p1 + ncols > ko + rest_from) {
-            MNK_HIP(hipStreamWaitEvent(s, rest_ready, 0));
-            waited = true;
-        }
-        const double* Wp = ldl ? wbase + p1 + (pb - ko) * ls->ldw : F + p1 + pb * ld;
-        int rc;
-        if (gemm_nt_lower_tiles(Np - p1, ncols) < SMALL_TILES_MID)
-            rc = launch_gemm_nt_lower_small(s, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + pb * ld, ld,
-                                            F + p1 + p1 * ld, ld, ls->info_dev.p);
-        else
-            rc = launch_gemm_nt(s, 2, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + pb * ld, ld, F + p1 + p1 * ld,
-                                ld, nullptr, nullptr, 0, ls->info_dev.p);
-        if (rc) return rc;
-    }
-    MNK_HIP(hipGetLastError());
-    return 0;
-}
-
-// (Vfirst, ldvfirst, Kfirst: panel_algo 4 only -- the Kfirst columns in front of the panel are applied to its first
-// 256 columns by the first persistent launch itself; V[row, k] = Vfirst[row + k * ldvfirst])
-static int factor_outer_panel(mnk_ls* ls, hipStream_t s, int64_t ko, int64_t kend, double* wbase,
-                              hipEvent_t rest_ready = nullptr, int64_t rest_from = 256, const double* Vfirst = nullptr,
-                              int64_t ldvfirst = 0, int64_t Kfirst = 0) {
-    if (ls->algo_now == 4)
-        return factor_outer_panel_pp(ls, s, ko, kend, wbase, rest_ready, rest_from, Vfirst, ldvfirst, Kfirst);
-    const int64_t Np = ls->Np, ld = ls->ld;
-    const bool ldl = ls->algo == MNK_LDL;
-    double* F = ls->fact.p;
-    bool waited = rest_ready == nullptr;
-    for (int64_t j = ko; j < kend; j += NBI) {
-        double* dblk = ls->dblk.p + (j / NBI) * 4096;
-        double* inv16 = ls->inv16.p + (j / NBI) * 1024;
-        if (ldl)
-            hipLaunchKernelGGL(potrf64w_kernel<true>, dim3(1), dim3(64), 0, s, F, ld, j, dblk, inv16, ls->dvec.p, ls->dinv.p,
-                               ls->info_dev.p, ls->pivot_tol, ls->bk.growth_word(ls));
-        else
-            hipLaunchKernelGGL(potrf64w_kernel<false>, dim3(1), dim3(64), 0, s, F, ld, j, dblk, inv16, ls->dvec.p, ls->dinv.p,
-                               ls->info_dev.p, ls->pivot_tol, (unsigned long long*)nullptr);
-        const int64_t M = Np - j - NBI;
-        if (M <= 0) break;
-        // 16-row strips per wave: one while the panel is short (more workgroups, shortest chain), two beyond
-        const bool two = M / 64 > 2 * (int64_t)ls->ctx->num_cu;
-        const unsigned grid = (unsigned)((M / (two ? 32 : 16) + 3) / 4);
-#define MNK_TRSM(LD, NS)                                                                                          \
-    hipLaunchKernelGGL((trsm64_mfma_kernel<LD, NS>), dim3(grid), dim3(256), 0, s, F, ld, j, Np, dblk, inv16,    \
-                       ls->dinv.p, LD ? wbase : (double*)nullptr, LD ? ls->ldw : (int64_t)0, j - ko, ls->info_dev.p,  \
-                       ls->bk.growth_word(ls))
-        if (ldl) { if (two) MNK_TRSM(true, 2); else MNK_TRSM(true, 1); }
-        else { if (two) MNK_TRSM(false, 2); else MNK_TRSM(false, 1); }
+        case FS_TRSM: {
+            double* dblk = ls->dblk.p + (t.col / NBI) * 4096;
+            double* inv16 = ls->inv16.p + (t.col / NBI) * 1024;
+            const int64_t M = Np - t.col - NBI;
+            const unsigned grid = (unsigned)((M / (16 * t.n) + 3) / 4);
+#define MNK_TRSM(LD, NS)                                                                                              \
+    hipLaunchKernelGGL((trsm64_mfma_kernel<LD, NS>), dim3(grid), dim3(256), 0, st, F, ld, (int64_t)t.col, Np, dblk, inv16, \
+                       ls->dinv.p, wbase, wld, woff, ls->info_dev.p, vmaxw)
+            if (ldl) { if (t.n == 2) MNK_TRSM(true, 2); else MNK_TRSM(true, 1); }
+            else { if (t.n == 2) MNK_TRSM(false, 2); else MNK_TRSM(false, 1); }
 #undef MNK_TRSM
-        const int64_t p1 = j + NBI;
-        if (p1 >= kend) break;
-        const int64_t jj = (p1 - ko) / NBI;            // blocks of this outer panel that are finished
-        const int64_t w = NBI * (jj & -jj);             // columns whose contribution is applied now
-        const int64_t p0 = p1 - w;
-        const int64_t ncols = std::min<int64_t>(w, kend - p1);
-        if (!waited && p1 + ncols > ko + rest_from) {  // first kernel that touches columns the caller delivers late
-            MNK_HIP(hipStreamWaitEvent(s, rest_ready, 0));
-            waited = true;
+            break;
         }
-        const double* Wp = ldl ? wbase + p1 + (p0 - ko) * ls->ldw : F + p1 + p0 * ld;
-        int rc;
-        if (gemm_nt_lower_tiles(Np - p1, ncols) < SMALL_TILES_MID)
-            rc = launch_gemm_nt_lower_small(s, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + p0 * ld, ld,
-                                            F + p1 + p1 * ld, ld, ls->info_dev.p);
-        else
-            rc = launch_gemm_nt(s, 2, Np - p1, ncols, w, Wp, ldl ? ls->ldw : ld, F + p1 + p0 * ld, ld,
-                                F + p1 + p1 * ld, ld, nullptr, nullptr, 0, ls->info_dev.p);
-        if (rc) return rc;
+        case FS_PPANEL: {
+            const unsigned grid = (unsigned)((Np - t.col) / NBI);
+            // columns in front of the launch that it applies itself: V[row, k] = Vp[row + k * ldv]
+            const double* Vp = t.K == 0 ? nullptr : ldl ? ls->wbuf[t.rhalf].p + (t.src - t.rko) * ldw : F + t.src * ld;
+            const int64_t ldv = t.K == 0 ? 0 : ldl ? ldw : ld;
+#define MNK_PP(LD, NBT)                                                                                                   \
+    hipLaunchKernelGGL((ppanel_kernel<LD, NBT>), dim3(grid), dim3(256), PP_LDS_BYTES, st, F, ld, (int64_t)t.col, (int)t.n, Np, \
+                       ls->dblk.p, ls->inv16.p, ls->dvec.p, ls->dinv.p, wbase, wld, woff, ls->info_dev.p, ls->pivot_tol,    \
+                       ls->flag_p.p + t.col / NBI, epoch16, ls->debug_pp_missing, Vp, ldv, (int)t.K,                          \
+                       PpDag{nullptr, nullptr, 0, 0, 4, -1, 0, nullptr, vmaxw})
+            if (ldl) MNK_PP(true, 4);
+            else MNK_PP(false, 4);
+#undef MNK_PP
+            break;
+        }
+        case FS_UPDATE: {
+            const double* B = F + t.col + (int64_t)t.src * ld;
+            const double* A = ldl ? ls->wbuf[t.rhalf].p + t.col + (t.src - t.rko) * ldw : B;
+            double* C = F + t.col + (int64_t)t.col * ld;
+            int rc;
+            if (t.variant == FS_SMALL)
+                rc = launch_gemm_nt_lower_small(st, t.rows, t.n, t.K, A, ldl ? ldw : ld, B, ld, C, ld, ls->info_dev.p);
+            else if (t.variant == FS_QUEUE)
+                rc = launch_gemm_nt_queue(st, t.rows, t.n, t.K, A, ldl ? ldw : ld, B, ld, C, ld, ls->tile_ctr.p + 8 * t.slot, t.cus,
+                                          ls->info_dev.p);
+            else
+                rc = launch_gemm_nt(st, 2, t.rows, t.n, t.K, A, ldl ? ldw : ld, B, ld, C, ld, nullptr, nullptr, 0, ls->info_dev.p);
+            if (rc) return rc;
+            break;
+        }
+        case FS_RECORD: MNK_HIP(hipEventRecord(events[t.event][t.index], st)); break;
+        case FS_WAIT: MNK_HIP(hipStreamWaitEvent(st, events[t.event][t.index], 0)); break;
+        }
     }
     MNK_HIP(hipGetLastError());
     return 0;
@@ -1111,14 +1095,8 @@ int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
 // The persistent pivot chain of the task-DAG schedule (dag.hip's host driver launches it beside the bulk kernel).
 int mnk_launch_pchain(mnk_ls* ls, hipStream_t sp, const mnk::PpDag& dag, int js_begin, int js_end, unsigned strips) {
     {   // 96 KB of dynamic LDS: the attribute belongs to the (kernel, device) pair
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        MNK_HIP(hipGetDevice(&dev));
-        if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-            MNK_HIP(hipFuncSetAttribute((const void*)pchain_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
-            MNK_HIP(hipFuncSetAttribute((const void*)pchain_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
-            attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
+        static DynLdsAttr attr;
+        if (int rc_a = attr.set(PC_LDS_BYTES, pchain_kernel<true>, pchain_kernel<false>)) return rc_a;
     }
     const bool ldl = ls->algo == MNK_LDL;
     const int epoch16 = ls->epoch * 16;
@@ -1151,14 +1129,8 @@ void mnk_pchain_fill_sys(mnk_ls* ls, void* rec_host, int* front, const int* af) 
 
 int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, void* table) {
     {   // 96 KB of dynamic LDS: the attribute belongs to the (kernel, device) pair
-        static std::atomic<uint64_t> attr_devs{0};
-        int dev = 0;
-        MNK_HIP(hipGetDevice(&dev));
-        if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-            MNK_HIP(hipFuncSetAttribute((const void*)pchain_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
-            MNK_HIP(hipFuncSetAttribute((const void*)pchain_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS_BYTES));
-            attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-        }
+        static DynLdsAttr attr;
+        if (int rc_a = attr.set(PC_LDS_BYTES, pchain_multi_kernel<true>, pchain_multi_kernel<false>)) return rc_a;
     }
     const mnk::PcSys* dst = static_cast<const mnk::PcSys*>(table);
     const bool ldl = v[0]->algo == MNK_LDL;
@@ -1169,6 +1141,31 @@ int mnk_launch_pchain_multi(mnk_ls* const* v, int n, hipStream_t sp, void* table
         hipLaunchKernelGGL(pchain_multi_kernel<false>, dim3((unsigned)(n * strips)), dim3(256), PC_LDS_BYTES, sp, dst, strips);
     MNK_HIP(hipGetLastError());
     return 0;
+}
+
+// The schedule of the factorization about to be enqueued: panel_algo, stepped down 5 -> 4 -> 1 where the higher one cannot run.
+// It acquires what schedule 5 needs on the way (streams, buffers), in this order.
+// The persistent kernels keep waiting workgroups resident.  Two of them from different contexts on the same CUs can
+// starve each other's diagonal strips (per-XCD dispatch order), so the persistent operations of one process take turns
+// on the device (mnk_persist_begin); a wait that expires anyway (another PROCESS) falls back (mnk_ls_fetch_info) and the
+// persistent schedule is tried again 16, then 64, 256, ... factorizations later (PersistBackoff: blocked_now).
+static int choose_schedule(mnk_ls* ls) {
+    mnk_ctx* ctx = ls->ctx;
+    const int64_t Np = ls->Np;
+    int algo = ls->panel_algo;
+    // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag_batch.hip)
+    const int64_t min_rows = mnk_batch_active() ? std::min<int64_t>(ls->dag_min_rows, 256) : ls->dag_min_rows;
+    if (algo == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) algo = 4;
+    if (algo == 5 && ctx->sp_dag == nullptr && mnk_ctx_ensure_dag(ctx) != 0) { (void)hipGetLastError(); algo = 4; }   // (released while idle)
+    if (algo == 5 && ctx->sp_dag == nullptr) algo = 4;
+    if (ls->pp.blocked_now() && algo >= 4) return 1;
+    // the task-DAG schedule's buffers (task list, progress words, V = L D): a device that cannot hold them keeps schedule 4
+    if (algo == 5 && mnk_ls_dag_prepare(ls) != 0) algo = 4;
+    if (algo == 5 && ls->plan.key.js2 < (Np + 255) / 256) {   // (the deep-band stream pair: made with the first such factorization)
+        if (mnk_ctx_ensure_dag2(ctx) != 0) (void)hipGetLastError();
+        if (ctx->sp_dag2 == nullptr) algo = 4;
+    }
+    return algo;
 }
 
 int mnk_ls_run_factorization(mnk_ls* ls) {
@@ -1184,25 +1181,9 @@ int mnk_ls_run_factorization(mnk_ls* ls) {
     ls->inv_done = 0;
     ls->t_fact_launch_ms = mnk_host_ms();
     { int rc_a = ls->verdict.arm_reject(ls, s); if (rc_a) return rc_a; }
-    // The persistent kernels keep waiting workgroups resident.  Two of them from different contexts on the same CUs can
-    // starve each other's diagonal strips (per-XCD dispatch order), so the persistent operations of one process take turns
-    // on the device (the arbiter below); a wait that expires anyway (another PROCESS) falls back (mnk_ls_fetch_info) and the
-    // persistent schedule is tried again 16, then 64, 256, ... factorizations later.
-    ls->algo_now = ls->panel_algo;
     ls->env_used = false;   // (the task-DAG schedule sets it when it launches with an envelope)
     ls->envh_used = false;
-    // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag_batch.hip)
-    const int64_t min_rows = mnk_batch_active() ? std::min<int64_t>(ls->dag_min_rows, 256) : ls->dag_min_rows;
-    if (ls->algo_now == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) ls->algo_now = 4;
-    if (ls->algo_now == 5 && ctx->sp_dag == nullptr && mnk_ctx_ensure_dag(ctx) != 0) { (void)hipGetLastError(); ls->algo_now = 4; }   // (released while idle)
-    if (ls->algo_now == 5 && ctx->sp_dag == nullptr) ls->algo_now = 4;
-    if (ls->pp.blocked_now() && ls->algo_now >= 4) ls->algo_now = 1;
-    // the task-DAG schedule's buffers (task list, progress words, V = L D): a device that cannot hold them keeps schedule 4
-    if (ls->algo_now == 5 && mnk_ls_dag_prepare(ls) != 0) ls->algo_now = 4;
-    if (ls->algo_now == 5 && ls->plan.key.js2 < (Np + 255) / 256) {   // (the deep-band stream pair: made with the first such factorization)
-        if (mnk_ctx_ensure_dag2(ctx) != 0) (void)hipGetLastError();
-        if (ctx->sp_dag2 == nullptr) ls->algo_now = 4;
-    }
+    ls->algo_now = choose_schedule(ls);
     // Persistent schedules of different contexts take turns on the device (common.h: mnk_persist_begin); round 3 sent every
     // solver to schedule 1 as soon as a second context was alive (12.4 instead of 9.3 ms at C3).
     // a batch of independent factorizations (dag_batch.hip: mnk_factorize_batch_begin / _end) launches them together later
@@ -1223,178 +1204,12 @@ int mnk_ls_run_factorization_now(mnk_ls* ls) {
 }
 
 static int run_factorization_body(mnk_ls* ls) {
-    mnk_ctx* ctx = ls->ctx;
-    hipStream_t s = ctx->stream;
-    const int64_t Np = ls->Np, ld = ls->ld;
-    const bool ldl = ls->algo == MNK_LDL;
-    double* F = ls->fact.p;
-    const int64_t NBO = mnk_ls_effective_nbo(ls);
+    hipStream_t s = ls->ctx->stream;
+    const int64_t Np = ls->Np;
     if (ls->algo_now != 5) MNK_HIP(hipMemsetAsync(ls->info_dev.p, 0, 2 * sizeof(int), s));   // (the task-DAG driver resets it with its flags)
-    // Outer panel boundaries.  Once the remaining matrix is small the factorization is bound by the panel
-    // chain, not by the update: narrower outer panels (TAIL_NBO) then drop the middle-level update and halve
-    // the depth of the (a) piece the chain waits for (measured: 355 -> ~300 us per 512 columns of the tail).
-    // The outer panels are TAIL_NBO wide once TAIL_ROWS rows (or fewer) remain: one persistent launch per panel with the
-    // fused prologue, no inner update (C3: 11.80 -> 11.71 ms).
-    constexpr int64_t TAIL_ROWS = 4096, TAIL_NBO = 256;
-    std::vector<int64_t> bnd{0};
-    for (int64_t pos = 0; pos < Np;) {
-        const bool tail = ls->lookahead && NBO < Np && Np - pos <= TAIL_ROWS && TAIL_NBO < NBO;
-        pos = std::min<int64_t>(pos + (tail ? TAIL_NBO : NBO), Np);
-        bnd.push_back(pos);
-    }
-    const int64_t npanel = (int64_t)bnd.size() - 1;
-    const bool la = ls->lookahead && npanel > 1;
-
-    if (ls->algo_now == 5) {
-        int rc = mnk_ls_run_factorization_dag(ls);
+    {
+        int rc = ls->algo_now == 5 ? mnk_ls_run_factorization_dag(ls) : run_factor_steps(ls);
         if (rc) return rc;
-    } else if (!la) {
-        for (int64_t ko = 0; ko < Np; ko += NBO) {
-            const int64_t kend = std::min<int64_t>(ko + NBO, Np);
-            int rc = factor_outer_panel(ls, s, ko, kend, ls->wbuf[0].p);
-            if (rc) return rc;
-            const int64_t Mt = Np - kend;
-            if (Mt > 0) {
-                const double* Wsrc = ldl ? ls->wbuf[0].p + kend : F + kend + ko * ld;
-                rc = launch_gemm_nt(s, 2, Mt, Mt, kend - ko, Wsrc, ldl ? ls->ldw : ld, F + kend + ko * ld, ld,
-                                    F + kend + kend * ld, ld, nullptr, nullptr, 0, ls->info_dev.p);
-                if (rc) return rc;
-            }
-        }
-    } else {
-        // look-ahead: panel stream sp (high priority) factors panel k+1 while the update
-        // stream su applies panel k to the rest of the trailing matrix.
-        // One CU partition for every size: a quarter of the CUs for the panel stream.  (A second pair with an
-        // eighth, for "update-bound" sizes, measured slower at every N once the panel stream's CUs join the
-        // trailing update: N = 30 000 156 vs 178 ms, N = 11 192 +0.5 ms per step taken on it.)
-        { int rc_s = mnk_ctx_ensure_panel_streams(ctx); if (rc_s) return rc_s; }   // (made with the first factorization that takes this schedule)
-        hipStream_t sp = ctx->sp, su = ctx->su;
-        if ((int64_t)ctx->ev_panel.size() < npanel + 1) {
-            const size_t old = ctx->ev_panel.size();
-            ctx->ev_panel.resize(npanel + 1);
-            ctx->ev_next.resize(npanel + 1);
-            ctx->ev_next2.resize(npanel + 1);
-            ctx->ev_bdone.resize(npanel + 1);
-            for (size_t e = old; e < ctx->ev_panel.size(); ++e) {
-                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_panel[e], hipEventDisableTiming));
-                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_next[e], hipEventDisableTiming));
-                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_next2[e], hipEventDisableTiming));
-                MNK_HIP(hipEventCreateWithFlags(&ctx->ev_bdone[e], hipEventDisableTiming));
-            }
-        }
-        // Work sharing: while the trailing update is the longer leg, the panel stream's CUs would
-        // idle once panel k+1 is factored; (b) is then launched as a tile queue on both streams
-        // (update stream right after (a), panel stream after the panel) and the two launches drain
-        // one counter.  Estimated leg lengths only decide whether the second launch is worth it.
-        const int pcus = ctx->panel_cus;
-        const int ucus = pcus > 0 ? ctx->num_cu - pcus : ctx->num_cu;
-        const bool share = ls->share != 0;
-        if (share) {
-            if (ls->tile_ctr.n < 8 * ((size_t)npanel + 1)) {
-                int rc0 = ls->tile_ctr.alloc(8 * ((size_t)npanel + 1));
-                if (rc0) return rc0;
-            }
-            MNK_HIP(hipMemsetAsync(ls->tile_ctr.p, 0, 8 * ((size_t)npanel + 1) * sizeof(int), s));
-        }
-        // Panel 0 has nothing to overlap with: it runs on the caller's stream, i.e. on the whole chip (its
-        // triangular solves and inner updates are throughput-bound at this height), before the fork.
-        int rc = factor_outer_panel(ls, s, 0, bnd[1], ls->wbuf[0].p);
-        if (rc) return rc;
-        MNK_HIP(hipEventRecord(ctx->ev_a, s));
-        MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_a, 0));
-        MNK_HIP(hipStreamWaitEvent(su, ctx->ev_a, 0));
-        MNK_HIP(hipEventRecord(ctx->ev_panel[0], sp));
-        for (int64_t k = 0; k + 1 < npanel; ++k) {
-            const int64_t ko = bnd[k], kend = bnd[k + 1];
-            const int64_t Mt = Np - kend;
-            if (Mt <= 0) break;
-            const int64_t nnext = bnd[k + 2] - kend;
-            double* wk = ls->wbuf[k & 1].p;
-            const double* Wsrc = ldl ? wk + kend : F + kend + ko * ld;
-            const int64_t ldws = ldl ? ls->ldw : ld;
-            const int64_t Kw = kend - ko;
-            // ev_panel[k] is recorded after panel k and after the panel stream's share of (b)_{k-1}
-            MNK_HIP(hipStreamWaitEvent(su, ctx->ev_panel[k], 0));
-            // (a) columns of the next outer panel, delivered in two pieces: the columns the panel stream starts on
-            // at once, then the remaining ones (needed only when those are finished)
-            auto update_a = [&](hipStream_t st, int64_t c0, int64_t c1) -> int {
-                const int64_t Mp = Mt - c0, Nn = c1 - c0;
-                double* Cp = F + (kend + c0) + (kend + c0) * ld;
-                if (gemm_nt_lower_tiles(Mp, Nn) < ls->small_tiles)
-                    return launch_gemm_nt_lower_small(st, Mp, Nn, Kw, Wsrc + c0, ldws, F + kend + c0 + ko * ld, ld, Cp,
-                                                      ld, ls->info_dev.p);
-                return launch_gemm_nt(st, 2, Mp, Nn, Kw, Wsrc + c0, ldws, F + kend + c0 + ko * ld, ld, Cp, ld, nullptr,
-                                      nullptr, 0, ls->info_dev.p);
-            };
-            // The first OWN_COLS columns of the next panel are updated on the PANEL stream itself, right behind
-            // panel k (no cross-stream hand-over before the next pivot block starts); the update stream delivers
-            // the other columns while they are being factored.
-            // Few rows left (the pivot chain is the critical path): the first persistent launch of the next panel applies
-            // panel k to its own 256 columns itself (ppanel_kernel's prologue) -- no (a) kernel and no cross-stream
-            // hand-over in front of the chain; the update stream delivers the other columns of the panel meanwhile.
-            const bool fuse_a = ls->algo_now == 4 && ls->pp_fuse_rows > 0 && Mt <= ls->pp_fuse_rows && Kw <= 512;
-            constexpr int64_t OWN_COLS = 128;
-            const bool own_first = !fuse_a && nnext > NBI;
-            const int64_t n1 = own_first ? std::min<int64_t>(OWN_COLS, nnext - NBI) : std::min<int64_t>(256, nnext);
-            const bool split_a = nnext > n1;
-            if (fuse_a) {
-                if (k > 0) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_bdone[k - 1], 0));  // (b)_{k-1} touched these columns
-                if (split_a) {
-                    rc = update_a(su, n1, nnext);
-                    if (rc) return rc;
-                    MNK_HIP(hipEventRecord(ctx->ev_next2[k], su));
-                }
-            } else if (own_first) {
-                if (k > 0) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_bdone[k - 1], 0));  // (b)_{k-1} touched these columns
-                rc = update_a(sp, 0, n1);
-                if (rc) return rc;
-                rc = update_a(su, n1, nnext);
-                if (rc) return rc;
-                MNK_HIP(hipEventRecord(ctx->ev_next2[k], su));
-            } else {   // (a next panel of one 64-column block: nothing to split)
-                rc = update_a(su, 0, nnext);
-                if (rc) return rc;
-                MNK_HIP(hipEventRecord(ctx->ev_next[k], su));
-            }
-            // (b) the rest of the trailing matrix
-            const int64_t Mb = Mt - nnext;
-            const int64_t Nb = Mb;
-            bool shared_b = false;
-            if (Mb > 0 && Nb > 0) {
-                const int ntiles = gemm_nt_lower_tiles(Mb, Nb);
-                // CU-us per 128x128xKw tile at ~80 % of the MFMA rate; ~55 us of panel stream per 64 columns
-                const double t_upd = ntiles * (68.0 * (double)Kw / 512.0) / ucus;
-                const double t_pan = 55.0 * (double)nnext / 64.0 * (pcus > 0 ? 64.0 / pcus : 1.0);
-                shared_b = share && pcus > 0 && (t_upd > t_pan || ls->share == 2);
-                if (shared_b)
-                    rc = launch_gemm_nt_queue(su, Mb, Nb, Kw, Wsrc + nnext, ldws, F + kend + nnext + ko * ld, ld,
-                                              F + (kend + nnext) + (kend + nnext) * ld, ld, ls->tile_ctr.p + 8 * k,
-                                              ucus, ls->info_dev.p);
-                else
-                    rc = launch_gemm_nt(su, 2, Mb, Nb, Kw, Wsrc + nnext, ldws, F + kend + nnext + ko * ld, ld,
-                                        F + (kend + nnext) + (kend + nnext) * ld, ld, nullptr, nullptr, 0,
-                                        ls->info_dev.p);
-                if (rc) return rc;
-            }
-            MNK_HIP(hipEventRecord(ctx->ev_bdone[k], su));
-            // panel k+1 on the panel stream, as soon as (a) is done
-            if (!own_first && !fuse_a) MNK_HIP(hipStreamWaitEvent(sp, ctx->ev_next[k], 0));
-            rc = factor_outer_panel(ls, sp, kend, kend + nnext, ls->wbuf[(k + 1) & 1].p,
-                                    split_a ? ctx->ev_next2[k] : nullptr, own_first ? n1 : 256,
-                                    fuse_a ? (ldl ? wk : F + ko * ld) : nullptr, ldws, fuse_a ? Kw : 0);
-            if (rc) return rc;
-            if (shared_b) {
-                rc = launch_gemm_nt_queue(sp, Mb, Nb, Kw, Wsrc + nnext, ldws, F + kend + nnext + ko * ld, ld,
-                                          F + (kend + nnext) + (kend + nnext) * ld, ld, ls->tile_ctr.p + 8 * k,
-                                          pcus, ls->info_dev.p);
-                if (rc) return rc;
-            }
-            MNK_HIP(hipEventRecord(ctx->ev_panel[k + 1], sp));
-        }
-        MNK_HIP(hipEventRecord(ctx->ev_a, sp));
-        MNK_HIP(hipEventRecord(ctx->ev_b, su));
-        MNK_HIP(hipStreamWaitEvent(s, ctx->ev_a, 0));
-        MNK_HIP(hipStreamWaitEvent(s, ctx->ev_b, 0));
     }
     // inverses of the diagonal blocks for the solves (batched, off the critical path of the panels); the task-DAG schedule
     // has already inverted the strip-columns below ls->inv_done on its bulk stream, under the chain's last steps

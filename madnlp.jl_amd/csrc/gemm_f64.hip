@@ -104,13 +104,8 @@ static int launch_batch_t(hipStream_t s, int64_t M, int64_t N, int64_t K, const 
     const int ntm = (int)((M + BM - 1) / BM), ntn = (int)((N + BN - 1) / BN);
     const size_t smem = 2 * tile_bk(WM, WN, WT) * ((BM + 16) + (BN + 16)) * sizeof(double);
     auto kern = gemm_nt_batch_kernel<WM, WN, WT, 0>;
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    MNK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-    }
+    static DynLdsAttr attr;
+    if (int rc = attr.set((int)smem, kern)) return rc;
     hipLaunchKernelGGL(kern, dim3(ntm * ntn, nbatch), dim3(64 * WM * WN), smem, s, M, N, K, recs, lda, ldb, ldc, ntm,
                        ntn < ntm ? ntn : ntm, 1);
     MNK_HIP(hipGetLastError());
@@ -146,14 +141,8 @@ static int launch_t(hipStream_t s, int64_t M, int64_t N, int64_t K, const double
     }
     const size_t smem = 2 * tile_bk(WM, WN, WT) * ((BM + 16) + (BN + 16)) * sizeof(double);
     auto kern = gemm_nt_kernel<WM, WN, WT, MODE, LDL_EPI>;
-    // the attribute belongs to the (kernel, device) pair: set it once per device of this process
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    MNK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-    }
+    static DynLdsAttr attr;
+    if (int rc = attr.set((int)smem, kern)) return rc;
     if (ntiles <= 0) return 0;
     hipLaunchKernelGGL(kern, dim3(ntiles), dim3(64 * WM * WN), smem, s, M, N, K, A, lda, B, ldb, C,
                        ldc, colscale, C2, ldc2, ntm, info_flag, /*tile_off=*/0, nc, tile_super_width());
@@ -210,12 +199,6 @@ int launch_gemm_nt_lower_small(hipStream_t s, int64_t M, int64_t N, int64_t K, c
     return launch_t<2, 2, 2, 2, false>(s, M, N, K, A, lda, B, ldb, C, ldc, nullptr, nullptr, 0, info_flag);
 }
 
-int gemm_nt_lower_tiles(int64_t M, int64_t N) {
-    const int ntm = (int)((M + 127) / 128), ntn = (int)((N + 127) / 128);
-    const int nc = ntn < ntm ? ntn : ntm;
-    return nc * ntm - nc * (nc - 1) / 2;
-}
-
 // Work-queue launch of the lower-tile update (mode 2, 128x128 tiles): as many workgroups as fit on `cus`
 // CUs pull tiles from counter[0..7] (zeroed by the caller before the first launch that shares them).
 int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
@@ -230,14 +213,8 @@ int launch_gemm_nt_queue(hipStream_t s, int64_t M, int64_t N, int64_t K, const d
     if (nwg > ntiles) nwg = ntiles;
     const size_t smem = 2 * tile_bk(2, 2, 4) * ((BM + 16) + (BM + 16)) * sizeof(double);
     auto kern = gemm_nt_queue_kernel<2, 2, 4, 2>;
-    // the attribute belongs to the (kernel, device) pair: set it once per device of this process
-    static std::atomic<uint64_t> attr_devs{0};
-    int dev = 0;
-    MNK_HIP(hipGetDevice(&dev));
-    if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-        MNK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-    }
+    static DynLdsAttr attr;
+    if (int rc = attr.set((int)smem, kern)) return rc;
     const int ntn_q = (int)((N + BM - 1) / BM);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), smem, s, M, N, K, A, lda, B, ldb, C, ldc, ntm, ntiles, counter,
                        info_flag, ntn_q < ntm ? ntn_q : ntm, tile_super_width());

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "dag_plan.h"
+#include "factor_plan.h"
 
 struct mnk_sc {
     mnk_ctx* ctx = nullptr;
@@ -340,6 +341,7 @@ struct mnk_ls {
     PersistBackoff pp;
     double stall_ms_total = 0.0; // host time between the launch of a factorization whose bounded wait expired and the moment the expiry was seen: what the fall-backs of this solver have cost (get_stat "stall_ms_total"; "stall_ms_process": all solvers)
     double t_fact_launch_ms = 0.0;   // host clock (ms) when the current factorization was enqueued
+    std::vector<mnk::FactorStep> steps;   // schedules 1 and 4: the steps of the current factorization (factor_plan.h), refilled by every one
     int64_t pp_fuse_rows = 4096; // > 0: once this many rows (or fewer) remain, persistent panel launches apply the columns in front of them themselves
     // task-DAG schedule (panel_algo = 5, dag.hip)
     DagPlan plan;

@@ -991,15 +991,9 @@ int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
         const int64_t t0 = (sc0 + 1) / 2, t1 = std::min<int64_t>(sc1, nsc) == nsc ? (ls->Np + 511) / 512 : sc1 / 2;
         if (t1 > t0) {
             const unsigned nt = (unsigned)(t1 - t0);
-            static std::atomic<uint64_t> attr_devs{0};
-            int dev = 0;
-            MNK_HIP(hipGetDevice(&dev));
             const int smem = 2 * 8 * ((128 + 16) + (128 + 16)) * (int)sizeof(double);
-            if (!(attr_devs.load(std::memory_order_relaxed) >> (dev & 63) & 1)) {
-                MNK_HIP(hipFuncSetAttribute((const void*)inv512_gemm_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-                MNK_HIP(hipFuncSetAttribute((const void*)inv512_gemm_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-                attr_devs.fetch_or(1ull << (dev & 63), std::memory_order_relaxed);
-            }
+            static DynLdsAttr attr;
+            if (int rc_a = attr.set(smem, inv512_gemm_kernel<1>, inv512_gemm_kernel<2>)) return rc_a;
             hipLaunchKernelGGL(inv512_assemble_kernel, dim3(nt, 512), dim3(512), 0, s, ls->linv256.p, ls->linv256t.p, ls->solves.linv512.p,
                                ls->solves.linv512t.p, ls->Np, (int)t0, ls->info_dev.p);
             hipLaunchKernelGGL(inv512_gemm_kernel<1>, dim3(nt, 4, 1), dim3(256), smem, s, ls->fact.p, ls->ld, ls->linv256.p, ls->linv256t.p,

@@ -535,7 +535,19 @@ def test_ipm_sparse_qp_cpu_vs_hip(ctx, case):
 def test_factorization_schedules_agree(ctx, N, alg, nbo, la):
     """Every blocking / look-ahead schedule must produce the same factor (to rounding) and the same
     solve: several outer panels, a ragged last panel, outer widths that are not multiples of the
-    256-column middle level, with and without the two-stream look-ahead."""
+    256-column middle level, with and without the two-stream look-ahead.  Schedule 4 (these orders are
+    inside the task-DAG schedule's window, where the default schedule reads none of these options)."""
+    _schedules_agree(ctx, N, alg, nbo, la, 4)
+
+
+@pytest.mark.parametrize("alg", [mj.CHOLESKY, mj.LDL])
+@pytest.mark.parametrize("nbo,la", [(128, False), (256, True), (512, True), (1024, False), (192, True)])
+def test_factorization_schedules_agree_one_launch_per_piece(ctx, alg, nbo, la):
+    """... and schedule 1 (leaf, triangular solve and update launches), the fallback of the persistent ones."""
+    _schedules_agree(ctx, 2500, alg, nbo, la, 1)
+
+
+def _schedules_agree(ctx, N, alg, nbo, la, panel_algo):
     rng = np.random.default_rng(N)
     R = rng.standard_normal((N, 96))
     A = np.asfortranarray(R @ R.T + np.diag(10.0 ** rng.uniform(-2, 3, N)))
@@ -545,9 +557,10 @@ def test_factorization_schedules_agree(ctx, N, alg, nbo, la):
         A[N - k:, N - k:] -= np.eye(k) * 5.0
         A = np.asfortranarray((A + A.T) / 2)
     dA = torch.from_numpy(A).cuda()  # column-major view of a symmetric matrix
-    M = mj.HipLinearSolver(dA, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=alg, outer_block=nbo, lookahead=la,
+    M = mj.HipLinearSolver(dA, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=alg, outer_block=nbo, lookahead=la, panel_algo=panel_algo,
                                                                 single_rows=0))  # force the multi-panel schedules
     M.factorize()
+    assert M.get_stat("panel_algo") == panel_algo
     ref_alg = CHOLESKY if alg == mj.CHOLESKY else BUNCHKAUFMAN
     ref = LapackCPUSolver(A, ref_alg).factorize()
     assert M.inertia() == ref.inertia()
@@ -582,8 +595,10 @@ def test_shared_tile_queue_schedule_is_bit_identical(ctx, alg, nbo, small):
     facs = []
     for share in (0, 1, 2, 2):  # off, adaptive, forced (every trailing update goes through the queue)
         M = mj.HipLinearSolver(dA, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=alg, outer_block=nbo,
-                                                                   share=share, small_tiles=small, single_rows=0))
+                                                                   share=share, small_tiles=small, single_rows=0,
+                                                                   panel_algo=4))   # (the look-ahead schedule reads these options)
         M.factorize()
+        assert M.get_stat("panel_algo") == 4
         Lf, d = M.get_factor()
         facs.append((np.tril(Lf).copy(), None if d is None else np.array(d)))
         inert = M.inertia()
@@ -597,19 +612,22 @@ def test_shared_tile_queue_schedule_is_bit_identical(ctx, alg, nbo, small):
 
 def test_repeated_factorizations_are_deterministic(ctx):
     """Refactorizing the same matrix (the IPM does it every iteration) gives bit-identical factors:
-    no race between the look-ahead streams, no stale state between calls."""
+    no race between the look-ahead streams, no stale state between calls.  The look-ahead schedules of
+    the persistent panel launches (4) and of one launch per piece (1)."""
     rng = np.random.default_rng(11)
     N = 3000
     R = rng.standard_normal((N, 64))
     A = np.asfortranarray(R @ R.T + N * np.eye(N))
-    M = mj.HipLinearSolver(A, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=mj.CHOLESKY, single_rows=0))
-    M.factorize()
-    L0, _ = M.get_factor()
-    for _ in range(4):
+    for panel_algo in (4, 1):
+        M = mj.HipLinearSolver(A, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=mj.CHOLESKY, single_rows=0, panel_algo=panel_algo))
         M.factorize()
-        L1, _ = M.get_factor()
-        assert np.array_equal(np.tril(L0), np.tril(L1))
-    M.close()
+        assert M.get_stat("panel_algo") == panel_algo
+        L0, _ = M.get_factor()
+        for _ in range(4):
+            M.factorize()
+            L1, _ = M.get_factor()
+            assert np.array_equal(np.tril(L0), np.tril(L1))
+        M.close()
 
 
 # --------------------------------------------------------------------------- persistent solve

@@ -32,6 +32,17 @@ CASES = [(N, alg, la, fuse) for N in (129, 257, 577, 640, 900, 1500, 2100)
 
 @pytest.mark.parametrize("N,alg,lookahead_on_small,fuse", CASES)
 def test_ill_conditioned_factorizations_match_lapack(ctx, N, alg, lookahead_on_small, fuse):
+    _matches_lapack(ctx, N, alg, lookahead_on_small, fuse)
+
+
+# From 1280 rows on the default schedule is the task-DAG one, which reads neither single_rows nor pp_fuse_rows: the look-ahead
+# cases of those orders once more under the schedule they are meant for.
+@pytest.mark.parametrize("N,alg,lookahead_on_small,fuse", [c for c in CASES if c[0] >= 1280 and c[2]])
+def test_ill_conditioned_factorizations_match_lapack_persistent_panels(ctx, N, alg, lookahead_on_small, fuse):
+    _matches_lapack(ctx, N, alg, lookahead_on_small, fuse, panel_algo=4)
+
+
+def _matches_lapack(ctx, N, alg, lookahead_on_small, fuse, panel_algo=None):
     rng = np.random.default_rng(N)  # N = 577 reproduces the matrix of the round-2 incident
     A = _spd(rng, N)
     quasi = alg == mj.LDL and N % 2 == 0
@@ -44,8 +55,11 @@ def test_ill_conditioned_factorizations_match_lapack(ctx, N, alg, lookahead_on_s
         M.set_option("single_rows", 0)  # the two-stream look-ahead schedule instead of one outer panel
     if fuse is not None:
         M.set_option("pp_fuse_rows", fuse)
+    if panel_algo is not None:
+        M.set_option("panel_algo", panel_algo)
     M.factorize()
     assert M.info == 0
+    assert panel_algo is None or M.get_stat("panel_algo") == panel_algo
     assert M.inertia() == ((N // 2, 0, N - N // 2) if quasi else (N, 0, 0))
     b = rng.standard_normal(N)
     x = M.solve_linear_system(b.copy())
