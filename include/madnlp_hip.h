@@ -293,7 +293,9 @@ int mnk_ls_bk_info(mnk_ls* ls, int* active, int* count, int32_t* perm, double* d
  * current factor (4: persistent panel kernel; 1: one launch per panel piece -- chosen automatically while more than
  * one context of this process lives on the device, or for good after a persistent panel gave up on a dependency),
  * "pp_fallbacks" = how many factorizations of this solver were redone for that reason.  Synchronizes when a
- * factorization is pending (the fallback is decided when `info` is read). */
+ * factorization is pending (the fallback is decided when `info` is read).  "solve_path" = how the solver's last solve ran
+ * (0: none yet, 1: one launch per 256-column step, 2: one launch over 256-column steps, 3: one launch over 512-column
+ * steps, 4: a system of a merged launch of a solve batch; csrc/solve_plan.h). */
 int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value);
 
 /* ----------------------------------------------------------- utilities ------ */
@@ -715,6 +717,22 @@ int mnk_debug_probe_schedule(int64_t N, int n, const int64_t* cols, int64_t* ord
  * Returns the number of steps, -1 on bad arguments. */
 int mnk_debug_factor_plan(int64_t Np, int ldl, int algo_now, int lookahead, int64_t outer_width, int64_t pp_fuse_rows, int share,
                           int small_tiles, int num_cu, int panel_cus, int32_t* out, int cap, int* shape);
+/* How solve! would run for a solver described by plain numbers (csrc/solve_plan.hip; host only, no device is opened): padded order Np
+ * (a multiple of 64), the context's CUs, and the flags of SolveShape (the factor is the pivoted tier's, options persistent_solve and
+ * solve512, the 512-row inverses exist, the context is a CU partition, an abort is pending, debug_ps_missing is set, solve_trace is
+ * on, LDL^T) plus option linv_mfma.  out[0] = the path as the statistic "solve_path" of mnk_ls_get_stat reports it (1: one launch
+ * per 256-column step, 2: one launch over 256-column steps, 3: one launch over 512-column steps; 4, a system of a merged launch of a
+ * solve batch, is never planned here; the statistic is 0 before the first solve), out[1] = the grid of a one-launch path (0:
+ * stepwise), out[2] = a solve batch may queue it, out[3] = a solver of this order gets the 512-row inverses with solve512,
+ * out[4] = the inverses of a batch of small factorizations come from one launch.  Returns 0, -1 on bad arguments. */
+int mnk_debug_solve_plan(int64_t Np, int num_cu, int pivoted, int persistent_opt, int solve512_opt, int have_linv512, int partitioned,
+                         int abort_raised, int debug_missing, int tracing, int ldl, int linv_mfma, int* out);
+/* The launches a solve batch makes of `n` queued solves (in queue order: solver identity, device, padded order, LDL^T or not and the
+ * CUs of its context): launch l runs the requests idx[begin[l] .. begin[l + 1]) with G[l] workgroups per system; a launch of one
+ * request is an ordinary solve (G[l] = 0).  begin holds n + 1, idx and G n entries.  Returns the number of launches, -1 on bad
+ * arguments. */
+int mnk_debug_solve_batch_groups(int n, const int64_t* solver_id, const int32_t* device, const int64_t* Np, const int32_t* ldl,
+                                 const int32_t* num_cu, int32_t* begin, int32_t* idx, int32_t* G);
 
 #ifdef __cplusplus
 }

@@ -236,7 +236,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             mnk::DagInst* st_inst = reinterpret_cast<mnk::DagInst*>(B.stage);
             char* st_pc = B.stage + (size_t)k * sizeof(mnk::DagInst);
             mnk::SmallSysRec* st_aux = reinterpret_cast<mnk::SmallSysRec*>(st_pc + (size_t)k * pc_bytes);
-            const bool batch_aux = l0->solves.linv_mfma && !l0->solves.solve512;   // (the other inverse kernels have no batched form)
+            const bool batch_aux = mnk::solve_inverses_batchable(l0->solves.linv_mfma != 0, l0->solves.solve512 != 0);
             for (int i = 0; i < k; ++i) {
                 mnk_ls* ls = g[r0 + i];
                 hin.push_back(mnk::dag_prepare_instance(ls, true));   // (batches of small systems run dense: their bulk tasks only accumulate band tiles)

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "dag_plan.h"
 #include "factor_plan.h"
+#include "solve_plan.h"
 
 struct mnk_sc {
     mnk_ctx* ctx = nullptr;
@@ -306,6 +307,7 @@ struct SolveState {
     int debug_ps_missing = -1; // option (tests): this workgroup of the persistent solve leaves at once (a peer that never became resident)
     mnk::DevBuf<double> linv512, linv512t, linv512tmp;
     mnk::DevBuf<unsigned long long> trace;  // diagnostics: 8 time stamps per 64-row block (option solve_trace)
+    int last_path = mnk::SOLVE_NONE;        // statistic "solve_path": how this solver's last solve ran (solve_plan.h: SolvePath), noted where the path is chosen
     int create();                            // the pinned abort word
     void destroy();
     int* abort_word() const { return abort; }   // what the solve kernels raise (the host reads it without a sync)

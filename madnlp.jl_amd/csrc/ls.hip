@@ -1289,24 +1289,21 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
             continue;
         }
         { int rc_q = mnk_solve_sync_deferred(ls); if (rc_q) return rc_q; }
-        MNK_HIP(hipMemsetAsync(w, 0, Np * sizeof(double), s));
-        MNK_HIP(mnk::h2d_copy(w, xk, N * sizeof(double), s));
-        int rc = mnk_ls_run_solve(ls, w);
+        auto solve_staged = [&]() -> int {   // the host's right-hand side, zero padded, through the work vector
+            MNK_HIP(hipMemsetAsync(w, 0, Np * sizeof(double), s));
+            MNK_HIP(mnk::h2d_copy(w, xk, N * sizeof(double), s));
+            return mnk_ls_run_solve(ls, w);
+        };
+        int rc = solve_staged();
         if (rc) return rc;
-        if (loc != MNK_DEVICE && ls->solves.persistent_solve) {
+        if (ls->solves.persistent_solve) {
             // The one-launch solve gives up (instead of hanging the device) if its workgroups cannot all become
             // resident, e.g. another process saturates the GPU with its own persistent kernels.  The host still
             // owns the right-hand side here: redo this and all later solves with one launch per step.
             MNK_HIP(mnk::stream_wait(s));
-            if (mnk_ls_take_solve_abort(ls)) {
-                MNK_HIP(hipMemsetAsync(w, 0, Np * sizeof(double), s));
-                MNK_HIP(mnk::h2d_copy(w, xk, N * sizeof(double), s));
-                rc = mnk_ls_run_solve(ls, w);
-                if (rc) return rc;
-            }
+            if (mnk_ls_take_solve_abort(ls) && (rc = solve_staged()) != 0) return rc;
         }
-        if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(xk, w, N * sizeof(double), hipMemcpyDeviceToDevice, s));
-        else MNK_HIP(mnk::d2h_copy(xk, w, N * sizeof(double), s));
+        MNK_HIP(mnk::d2h_copy(xk, w, N * sizeof(double), s));
     }
     return 0;
 }
@@ -1403,6 +1400,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     }
     if (!strcmp(key, "panel_algo")) { *value = ls->algo_now; return 0; }
     if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp.fallbacks; return 0; }
+    if (!strcmp(key, "solve_path")) { *value = ls->solves.last_path; return 0; }   // how the last solve ran (solve_plan.h: SolvePath; 0: none yet)
     // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
     if (!strcmp(key, "timeout_site")) { *value = ls->pp.last_site; return 0; }
     if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe.hits; return 0; }       // matrices rejected by the leading-block probe alone

@@ -708,6 +708,9 @@ __global__ void ps_set_sys_kernel(PsSys rec, PsSys* __restrict__ dst) { *dst = r
 // 4 sub .. 4 sub + 3, colq = lane >> 3: columns colq + 8 p, p < 4).
 // ================================================================================================
 constexpr int P5_RB = 32, P5_NBS = 16, P5_STEP = 512, P5_NQ = 32, P5_CW = 16;
+// the host's rules (solve_plan.h) speak of the same blocks and steps as the kernels
+static_assert(PS_MAXOWN == SP_MAXOWN && SB == SP_STEP256 && PS_NT / PS_NQ == SP_RB256, "solve_plan.h: the 256-column solve");
+static_assert(P5_RB == SP_RB512 && P5_STEP == SP_STEP512 && P5_NBS == SP_NBS512, "solve_plan.h: the 512-column solve");
 
 template <bool LDL>
 __global__ __launch_bounds__(PS_NT) void persistent_solve512_kernel(
@@ -977,8 +980,7 @@ int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1) {
     //   inv [A 0; C D] = [A^-1 0; -D^-1 C A^-1  D^-1],   T' = A^-T C' (stage 1),  X = -D^-1 T,  X' = -T' D^-T (stage 2)
     // (a 512 x 512 triangle inverted block by block with the scalar kernel above costs 35 dependent 64x64x16 products:
     // +0.63 ms on factorize! at C3, measured).
-    constexpr int64_t SOLVE512_MIN_ROWS = 4096;
-    if (ls->solves.solve512 && ls->Np >= SOLVE512_MIN_ROWS && ls->Np % 512 != 384 && !ls->solves.linv512.p) {
+    if (ls->solves.solve512 && solve512_wanted(ls->Np) && !ls->solves.linv512.p) {
         const size_t ntri = (size_t)((ls->Np + 511) / 512);
         if (ls->solves.linv512.alloc(ntri * 512 * 512) || ls->solves.linv512t.alloc(ntri * 512 * 512) || ls->solves.linv512tmp.alloc(ntri * 256 * 256)) {
             (void)hipGetLastError();
@@ -1047,38 +1049,87 @@ bool SolveState::take_abort() {
     return true;
 }
 
+// what the planner reads of a solver (solve_plan.h)
+static SolveShape solve_shape(const mnk_ls* ls) {
+    return SolveShape{ls->Np, ls->ctx->num_cu, ls->verdict.is_pivoted(), ls->solves.persistent_solve != 0, ls->solves.solve512 != 0,
+                      ls->solves.linv512.p != nullptr, ls->ctx->partitioned, ls->solves.abort_raised(), ls->solves.debug_ps_missing >= 0,
+                      ls->solves.trace.p != nullptr, ls->algo == MNK_LDL};
+}
+
+// the LDL^T or the Cholesky instance of one of the three one-launch solve kernels: same grid, same arguments
+template <class... P, class... A>
+static void launch_solve_kernel(bool ldl, void (*k_ldl)(P...), void (*k_chol)(P...), int grid, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(ldl ? k_ldl : k_chol, dim3((unsigned)grid), dim3(PS_NT), 0, s, args...);
+}
+
+// The one-launch solve the plan chose, on plan.G workgroups.  SOLVE_ONE_LAUNCH_256 reads `xin` and writes `xout` (`nio` entries: N
+// of the caller's vector or Np of xdev); SOLVE_ONE_LAUNCH_512 works in xdev[0:Np].
+static int solve_one_launch(mnk_ls* ls, const SolvePlan& plan, bool ldl, double* xdev, const double* xin, double* xout, int64_t nio) {
+    hipStream_t s = ls->ctx->stream;
+    const int64_t Np = ls->Np;
+    SolveState& st = ls->solves;
+    // The kernel needs all its workgroups resident at once (one per CU).  Two of them launched from different contexts
+    // could each grab part of the chip and wait for the rest forever, and the same holds next to a persistent
+    // factorization: the persistent operations of one process take turns on the device (common.h: mnk_persist_begin).
+    int rc = mnk_persist_begin(ls->ctx, s);
+    if (rc) return rc;
+    const int ps_near = PS_NEAR, ps_nap = 6;
+    double* pubs[2] = {xdev + 2 * Np, xdev + 6 * Np};
+    auto ensure_clean = [&](int b) {
+        if (st.reset_due(b))
+            hipLaunchKernelGGL(ps_reset_kernel, dim3((unsigned)((4 * Np + 255) / 256)), dim3(256), 0, s,
+                               reinterpret_cast<unsigned long long*>(pubs[b]), 4 * Np);
+    };
+    if (plan.path == SOLVE_ONE_LAUNCH_512) {
+        // steps of 512 columns, blocks of 32 rows (half the steps, the same two hops per step)
+        st.dirtied(0);
+        ensure_clean(0);
+        launch_solve_kernel(ldl, persistent_solve512_kernel<true>, persistent_solve512_kernel<false>, plan.G, s, ls->fact.p, ls->ld,
+                            st.linv512.p, st.linv512t.p, ls->dinv.p, xdev, pubs[0], Np, st.abort_word(), ls->info_dev.p, ps_near, ps_nap,
+                            st.ps_spin_limit, st.debug_ps_missing);
+        st.dirtied(0);
+    } else {
+        // two publication buffers: this solve polls `cur` (all sentinel) and fills `oth` with the sentinel for the next one
+        const int cur = st.poll_buffer(), oth = cur ^ 1;
+        ensure_clean(cur);
+        launch_solve_kernel(ldl, persistent_solve_kernel<true>, persistent_solve_kernel<false>, plan.G, s, ls->fact.p, ls->ld, ls->linv256.p,
+                            ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, st.abort_word(), ls->info_dev.p,
+                            st.trace.p, ps_near, ps_nap, st.ps_spin_limit, st.debug_ps_missing);
+        // (a test's "missing" workgroup does not clear its blocks either; a solve that gives up marks both buffers dirty: take_abort)
+        st.solve_queued(st.debug_ps_missing < 0);
+    }
+    rc = hipGetLastError() == hipSuccess ? 0 : -2;
+    return mnk_persist_end(ls->ctx, s, rc);
+}
+
 // xdev: the solver's work vector (10*Np doubles: x | y | two publication buffers of 4*Np).
 // xuser == NULL: on entry xdev[0:Np] = rhs (zero padded); on exit xdev[0:Np] = solution.
 // xuser != NULL: a device vector of N entries, rhs on entry, solution on exit; the one-launch solve reads and writes it
 // directly (ONE launch per solve: no padded staging copy, no reset kernel, no copy back), every other path stages through xdev.
+// Runs the way solve_plan_single says and notes it for the statistic "solve_path".
 int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     hipStream_t s = ls->ctx->stream;
     const int64_t Np = ls->Np, ld = ls->ld, N = ls->N;
-    const int ldl = ls->algo == MNK_LDL;
-    const int64_t nb64 = Np / 64;
-    const int G = (int)std::min<int64_t>(nb64, ls->ctx->num_cu);
-    // Bunch-Kaufman factor (bk.hip): P A P^T = L D L^T with 2x2 blocks in D -- gather, stepwise unit-lower sweeps,
-    // block-diagonal D^-1, scatter (a 2x2 block may straddle two 64-row blocks, which the one-launch solve's
-    // block ownership does not allow)
-    const bool bk = ls->verdict.is_pivoted();
-    const bool persistent = !bk && ls->solves.persistent_solve && G >= 1 && (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G);
-    const int64_t nb32 = Np / P5_RB;
-    const int G5 = (int)std::min<int64_t>(nb32, ls->ctx->num_cu);
-    const bool use512 = persistent && ls->solves.solve512 && ls->solves.linv512.p && (nb32 + G5 - 1) / G5 <= PS_MAXOWN && (G5 >= P5_NBS || nb32 <= G5);
-    const bool direct = persistent && !use512;
-    auto stage_in = [&]() -> int {
-        if (xuser != nullptr) hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, xdev, xuser, N, Np);
-        MNK_HIP(hipGetLastError());
-        return 0;
-    };
+    const SolveShape shape = solve_shape(ls);
+    const SolvePlan plan = solve_plan_single(shape);
+    ls->solves.last_path = plan.path;
+    const bool ldl = shape.ldl;
+    // the 256-column one-launch solve works on the caller's vector itself; every other path stages through xdev
+    if (plan.path == SOLVE_ONE_LAUNCH_256)
+        return xuser != nullptr ? solve_one_launch(ls, plan, ldl, xdev, xuser, xuser, N) : solve_one_launch(ls, plan, ldl, xdev, xdev, xdev, Np);
+    if (xuser != nullptr) hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, s, xdev, xuser, N, Np);
+    MNK_HIP(hipGetLastError());
     auto stage_out = [&]() -> int {
         if (xuser != nullptr) MNK_HIP(hipMemcpyAsync(xuser, xdev, N * sizeof(double), hipMemcpyDeviceToDevice, s));
         return 0;
     };
-    if (!direct) {
-        int rc = stage_in();
-        if (rc) return rc;
+    if (plan.path == SOLVE_ONE_LAUNCH_512) {
+        const int rc = solve_one_launch(ls, plan, ldl, xdev, nullptr, nullptr, 0);
+        return rc ? rc : stage_out();
     }
+    // SOLVE_STEPWISE.  Bunch-Kaufman factor (bk.hip): P A P^T = L D L^T with 2x2 blocks in D -- gather, stepwise unit-lower
+    // sweeps, block-diagonal D^-1, scatter
+    const bool bk = shape.pivoted;
     if (bk) {
         // (the permutation's scratch is the first publication buffer of the one-launch solve: it no longer holds the sentinel --
         // a later solve on the static-pivot tier must reset it before it polls it)
@@ -1086,58 +1137,7 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
         int rc = ls->bk.permute(ls, xdev, xdev + 2 * Np, true);
         if (rc) return rc;
     }
-    if (persistent) {
-        // The kernel needs all its workgroups resident at once (one per CU).  Two of them launched from different contexts
-        // could each grab part of the chip and wait for the rest forever, and the same holds next to a persistent
-        // factorization: the persistent operations of one process take turns on the device (common.h: mnk_persist_begin).
-        int rc = mnk_persist_begin(ls->ctx, s);
-        if (rc) return rc;
-        const int ps_near = PS_NEAR, ps_nap = 6;
-        double* pubs[2] = {xdev + 2 * Np, xdev + 6 * Np};
-        auto ensure_clean = [&](int b) {
-            if (ls->solves.reset_due(b))
-                hipLaunchKernelGGL(ps_reset_kernel, dim3((unsigned)((4 * Np + 255) / 256)), dim3(256), 0, s,
-                                   reinterpret_cast<unsigned long long*>(pubs[b]), 4 * Np);
-        };
-        if (use512) {
-            // steps of 512 columns, blocks of 32 rows (half the steps, the same two hops per step)
-            ls->solves.dirtied(0);
-            ensure_clean(0);
-            double* pub = pubs[0];
-            if (ldl)
-                hipLaunchKernelGGL(persistent_solve512_kernel<true>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->solves.linv512.p,
-                                   ls->solves.linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solves.abort_word(), ls->info_dev.p, ps_near, ps_nap,
-                                   ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
-            else
-                hipLaunchKernelGGL(persistent_solve512_kernel<false>, dim3(G5), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->solves.linv512.p,
-                                   ls->solves.linv512t.p, ls->dinv.p, xdev, pub, Np, ls->solves.abort_word(), ls->info_dev.p, ps_near, ps_nap,
-                                   ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
-            ls->solves.dirtied(0);
-            rc = hipGetLastError() == hipSuccess ? 0 : -2;
-            rc = mnk_persist_end(ls->ctx, s, rc);
-            return rc ? rc : stage_out();
-        }
-        // two publication buffers: this solve polls `cur` (all sentinel) and fills `oth` with the sentinel for the next one
-        const int cur = ls->solves.poll_buffer(), oth = cur ^ 1;
-        ensure_clean(cur);
-        const double* xin = xuser != nullptr ? xuser : xdev;
-        double* xout = xuser != nullptr ? xuser : xdev;
-        const int64_t nio = xuser != nullptr ? N : Np;
-        if (ldl)
-            hipLaunchKernelGGL(persistent_solve_kernel<true>, dim3(G), dim3(PS_NT), 0, s, ls->fact.p, ld, ls->linv256.p,
-                               ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solves.abort_word(), ls->info_dev.p,
-                               ls->solves.trace.p, ps_near, ps_nap, ls->solves.ps_spin_limit, ls->solves.debug_ps_missing);
-        else
-            hipLaunchKernelGGL(persistent_solve_kernel<false>, dim3(G), dim3(PS_NT), 0, s, ls->fact.p, ld,
-                               ls->linv256.p, ls->linv256t.p, ls->dinv.p, xin, xout, nio, pubs[cur], pubs[oth], Np, ls->solves.abort_word(),
-                               ls->info_dev.p, ls->solves.trace.p, ps_near, ps_nap, ls->solves.ps_spin_limit,
-                               ls->solves.debug_ps_missing);
-        // (a test's "missing" workgroup does not clear its blocks either; a solve that gives up marks both buffers dirty: take_abort)
-        ls->solves.solve_queued(ls->solves.debug_ps_missing < 0);
-        rc = hipGetLastError() == hipSuccess ? 0 : -2;
-        return mnk_persist_end(ls->ctx, s, rc);
-    }
-    double* b = xdev;       // forward: running right-hand side; backward: solution
+    double* b = xdev;      // forward: running right-hand side; backward: solution
     double* y = xdev + Np;  // forward: solution of L y = b (scaled by D^-1 for LDL); backward: running rhs
     const int64_t nsteps = (Np + SB - 1) / SB;
     for (int64_t k = 0; k < nsteps; ++k) {
@@ -1176,52 +1176,47 @@ int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Batches of independent solves (mnk_solve_batch_begin / _end): between the two calls the single-right-hand-side solves of
-// the calling thread on DEVICE vectors are queued; `end` runs them up to four systems per launch
-// (persistent_solve_multi_kernel).  Systems of one launch belong to different solvers (a solver's second right-hand side goes
-// into the next launch: its publication buffers are in use); solves that do not qualify (host vectors, several right-hand
-// sides, the pivoted tier, the stepwise solve) run at once as usual.
+// the calling thread on DEVICE vectors are queued; `end` runs them several systems per launch (persistent_solve_multi_kernel),
+// grouped by solve_batch_groups (solve_plan.h: the rules).  Solves that do not qualify (solve_batchable; host vectors, several
+// right-hand sides) run at once as usual.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 struct SolveReq { mnk_ls* ls; double* x; };
-struct SolveBatchState { int depth = 0; bool active = false; std::vector<SolveReq> pend; };
+// (pend: the queue; flushing, req, groups, launch: what a flush plans and runs from, kept for their capacity)
+struct SolveBatchState {
+    int depth = 0; bool active = false;
+    std::vector<SolveReq> pend, flushing, launch;
+    std::vector<SolveBatchReq> req;
+    SolveBatchGroups groups;
+};
 thread_local SolveBatchState t_sbatch;
 struct SolveBatchBuffers { mnk::DevBuf<char> sys; hipEvent_t ev = nullptr; };
 SolveBatchBuffers g_sbatch[64];
-constexpr int PS_BATCH_MAXQ = 32;
 }  // namespace
 
-static bool solve_eligible(const mnk_ls* ls) {
-    const int64_t nb64 = ls->Np / 64;
-    const int G = (int)std::min<int64_t>(nb64, ls->ctx->num_cu);
-    return !ls->verdict.is_pivoted() && ls->solves.persistent_solve && !(ls->solves.solve512 && ls->solves.linv512.p) && !ls->ctx->partitioned &&
-           (nb64 + G - 1) / G <= PS_MAXOWN && (G >= 4 || nb64 <= G) && !ls->solves.abort_raised() &&
-           ls->solves.debug_ps_missing < 0 && !ls->solves.trace.p;
-}
-
 bool mnk_solve_defer(mnk_ls* ls, double* xuser) {
-    if (!t_sbatch.active || !solve_eligible(ls)) return false;
+    if (!t_sbatch.active || !solve_batchable(solve_shape(ls))) return false;
     if (!ls->ev_defer && hipEventCreateWithFlags(&ls->ev_defer, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipEventRecord(ls->ev_defer, ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
     t_sbatch.pend.push_back({ls, xuser});
     return true;
 }
 
-// one launch: systems v[0..q) (distinct solvers of one device, order and algorithm)
-static int solve_batch_launch(const std::vector<SolveReq>& v) {
+// one launch: systems v[0..q) (distinct solvers of one device, order and algorithm), G workgroups each (solve_batch_groups)
+static int solve_batch_launch(const std::vector<SolveReq>& v, int G) {
     const int q = (int)v.size();
     mnk_ls* l0 = v[0].ls;
     mnk_ctx* c0 = l0->ctx;
     hipStream_t h = c0->stream;
     MNK_HIP(hipSetDevice(c0->device));
-    const int64_t Np = l0->Np, nb64 = Np / 64;
-    const int G = (int)std::min<int64_t>(nb64, c0->num_cu / q);
+    const int64_t Np = l0->Np;
     SolveBatchBuffers& B = g_sbatch[c0->device & 63];
     for (const SolveReq& r : v)
         if (r.ls->ctx->stream != h) MNK_HIP(hipStreamWaitEvent(h, r.ls->ev_defer, 0));
     int rc = mnk_persist_begin(c0, h);
     if (rc) return rc;
     auto body = [&]() -> int {
-        if (B.sys.n < sizeof(PsSys) * PS_BATCH_MAXQ && B.sys.alloc(sizeof(PsSys) * PS_BATCH_MAXQ)) return -2;
+        if (B.sys.n < sizeof(PsSys) * SP_BATCH_MAXQ && B.sys.alloc(sizeof(PsSys) * SP_BATCH_MAXQ)) return -2;
         if (!B.ev) MNK_HIP(hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
         PsSys* dsys = reinterpret_cast<PsSys*>(B.sys.p);
         for (int i = 0; i < q; ++i) {
@@ -1235,12 +1230,10 @@ static int solve_batch_launch(const std::vector<SolveReq>& v) {
                       ls->solves.abort_word(), ls->info_dev.p};
             hipLaunchKernelGGL(ps_set_sys_kernel, dim3(1), dim3(1), 0, h, rec, dsys + i);
             ls->solves.solve_queued(true);
+            ls->solves.last_path = SOLVE_MERGED;
         }
-        const bool ldl = l0->algo == MNK_LDL;
-        if (ldl)
-            hipLaunchKernelGGL(persistent_solve_multi_kernel<true>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->solves.ps_spin_limit);
-        else
-            hipLaunchKernelGGL(persistent_solve_multi_kernel<false>, dim3((unsigned)(q * G)), dim3(PS_NT), 0, h, dsys, G, Np, PS_NEAR, 6, l0->solves.ps_spin_limit);
+        launch_solve_kernel(l0->algo == MNK_LDL, persistent_solve_multi_kernel<true>, persistent_solve_multi_kernel<false>, q * G, h, dsys, G, Np,
+                            PS_NEAR, 6, l0->solves.ps_spin_limit);
         MNK_HIP(hipGetLastError());
         return 0;
     };
@@ -1258,32 +1251,21 @@ static int solve_batch_launch(const std::vector<SolveReq>& v) {
 }
 
 static int solve_batch_flush() {
-    std::vector<SolveReq> pend;
-    pend.swap(t_sbatch.pend);
-    // systems per launch: four for large systems (measured at N = 11 192: 2 -> 104.0, 4 -> 107.4, 8 -> 106.2 it/s of the C5
-    // step), as many as the CUs hold for small ones (a 512-row block has 8 blocks of 64 rows: 32 of them per launch)
+    // The queue leaves `pend` first (nothing below queues a solve or flushes again) and runs as the launches solve_batch_groups
+    // (solve_plan.h) makes of it: two or more systems in one merged launch, a single one as an ordinary solve.
+    SolveBatchState& S = t_sbatch;
+    S.flushing.clear();
+    S.flushing.swap(S.pend);
+    S.req.clear();
+    for (const SolveReq& r : S.flushing)
+        S.req.push_back({(int64_t)(intptr_t)r.ls, r.ls->ctx->device, r.ls->Np, r.ls->algo == MNK_LDL, r.ls->ctx->num_cu});
+    solve_batch_groups(S.req.data(), (int)S.req.size(), S.groups);
     int rc_all = 0;
-    while (!pend.empty()) {
-        mnk_ls* l0 = pend.front().ls;
-        const int64_t nb64 = l0->Np / 64;
-        const int g4 = (int)std::max<int64_t>(1, std::min<int64_t>(nb64, l0->ctx->num_cu / 4));   // workgroups of a system when four share the chip
-        const int maxq = std::max(1, std::min(PS_BATCH_MAXQ, l0->ctx->num_cu / g4));
-        std::vector<SolveReq> g, rest;
-        for (const SolveReq& r : pend) {
-            bool take = (int)g.size() < maxq && r.ls->ctx->device == l0->ctx->device && r.ls->Np == l0->Np && r.ls->algo == l0->algo;
-            for (const SolveReq& t : g) take = take && t.ls != r.ls;      // (one right-hand side per solver and launch)
-            for (const SolveReq& t : rest) take = take && t.ls != r.ls;   // (and a solver's right-hand sides keep their order)
-            if (take) {   // all workgroups of the launch resident, at most PS_MAXOWN blocks each
-                const int Gq = (int)std::min<int64_t>(nb64, l0->ctx->num_cu / ((int)g.size() + 1));
-                take = (Gq >= 4 || nb64 <= Gq) && (nb64 + Gq - 1) / Gq <= PS_MAXOWN;
-                take = take || g.empty();   // (the first one always goes: alone it is an ordinary solve)
-            }
-            (take ? g : rest).push_back(r);
-        }
-        pend.swap(rest);
-        int rc;
-        if (g.size() >= 2) rc = solve_batch_launch(g);
-        else rc = mnk_ls_run_solve(g[0].ls, g[0].ls->xwork.p, g[0].x);
+    for (int l = 0; l < S.groups.launches(); ++l) {
+        std::vector<SolveReq>& v = S.launch;
+        v.clear();
+        for (int32_t k = S.groups.begin[l]; k < S.groups.begin[l + 1]; ++k) v.push_back(S.flushing[S.groups.idx[k]]);
+        const int rc = v.size() >= 2 ? solve_batch_launch(v, S.groups.G[l]) : mnk_ls_run_solve(v[0].ls, v[0].ls->xwork.p, v[0].x);
         if (rc && !rc_all) rc_all = rc;
     }
     return rc_all;

@@ -218,6 +218,11 @@ def test_solves_return_the_dyadic_solution(ctx, n):
         with mj.solve_batch():
             M.solve_linear_system(xb)
         M.check_solve()
+        try:   # a pivoted factor is solved stepwise, inside a batch too (None: a build of the library without the statistic)
+            path = M.get_stat("solve_path")
+        except mj.HipError:
+            path = None
+        assert path in (1, None), path
         assert torch.equal(xb.cpu(), torch.from_numpy(c.x)), f"N={n} solve inside a solve batch"
     finally:
         M.close()

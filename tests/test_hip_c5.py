@@ -216,6 +216,15 @@ def test_batch_with_mixed_orders_and_a_forgotten_end():
     ctx.close()
 
 
+def _solve_path(M):
+    """Statistic "solve_path" (csrc/solve_plan.h: 1 stepwise, 2 one launch over 256-column steps, 3 over 512-column steps, 4 a system
+    of a merged launch), or None from a build of the library that does not report it (A/B runs through MNK_LIBPATH)."""
+    try:
+        return M.get_stat("solve_path")
+    except mj.HipError:
+        return None
+
+
 @pytest.mark.parametrize("nctx", [1, 2])
 def test_batched_solves_are_bit_identical_to_lone_ones(nctx):
     """mnk_solve_batch_begin / _end: the single-right-hand-side solves of a block on device vectors are queued and run up to
@@ -237,6 +246,7 @@ def test_batched_solves_are_bit_identical_to_lone_ones(nctx):
             din["x"].copy_(din["rhs"])
             kh.linear_solver.solve_linear_system(din["x"])
             kh.linear_solver.check_solve()
+            assert _solve_path(kh.linear_solver) in (2, None)
             lone.append(din["x"].clone())
     torch.cuda.synchronize()
     rhs2 = insts[0][3]["rhs"] * 3.0 + 1.0
@@ -260,6 +270,11 @@ def test_batched_solves_are_bit_identical_to_lone_ones(nctx):
                 insts[0][1].linear_solver.solve_linear_system(x2)
         for (_, kh, st, din) in insts:
             kh.linear_solver.check_solve()
+        # Merged launches of four (instances 0-3) and of two (4, 5).  The second right-hand side of instance 0 arrives while its
+        # first is queued: its solver (early rejection armed, as in every KKT handle) looks at the factorization's verdict first,
+        # which runs what is queued for it; the second one is then alone in the queue and runs as an ordinary one-launch solve.
+        paths = [_solve_path(kh.linear_solver) for (_, kh, _, _) in insts]
+        assert paths in ([2, 4, 4, 4, 4, 4], [None] * 6), (rnd, paths)
         torch.cuda.synchronize()
         for i, (P, kh, st, din) in enumerate(insts):
             assert torch.equal(din["x"], lone[i]), (rnd, i)
@@ -306,6 +321,8 @@ def test_batched_solves_of_small_and_mixed_systems():
             xh = sols[1].solve_linear_system(rhs[1].cpu().numpy().copy())     # host vector: at once, behind solver 1's queued solve
         for M in sols:
             M.check_solve()
+        # merged launches of three and of two; solver 1's host vector came last for it, an ordinary one-launch solve
+        assert [_solve_path(M) for M in sols] in ([4, 2, 4, 4, 4], [None] * 5)
         st.synchronize()
         for x, r in zip(xs, refs):
             assert torch.equal(x, r)

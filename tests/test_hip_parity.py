@@ -631,8 +631,17 @@ def test_repeated_factorizations_are_deterministic(ctx):
 
 
 # --------------------------------------------------------------------------- persistent solve
+def _solve_path(M):
+    """Statistic "solve_path" (csrc/solve_plan.h: 1 stepwise, 2 one launch over 256-column steps, 3 over 512-column steps, 4 a system
+    of a merged launch), or None from a build of the library that does not report it (A/B runs through MNK_LIBPATH)."""
+    try:
+        return M.get_stat("solve_path")
+    except mj.HipError:
+        return None
+
+
 @pytest.mark.parametrize("alg", [mj.CHOLESKY, mj.LDL])
-@pytest.mark.parametrize("N", [64, 200, 1000, 3333, 6000])
+@pytest.mark.parametrize("N", [64, 200, 320, 1000, 3333, 6000])
 def test_persistent_solve_matches_stepwise_solve(ctx, alg, N):
     """The one-launch solve (workgroups exchanging block results through polled global values) and the
     one-launch-per-step solve apply the same operators (explicit 256x256 diagonal inverses, panel GEMVs) with
@@ -650,7 +659,9 @@ def test_persistent_solve_matches_stepwise_solve(ctx, alg, N):
     for persistent in (True, False):
         M = mj.HipLinearSolver(A, ctx=ctx, opt=mj.HipSolverOptions(lapack_algorithm=alg, persistent_solve=persistent))
         M.factorize()
+        assert _solve_path(M) in (0, None)
         x = M.solve_linear_system(b.copy())
+        assert _solve_path(M) in (2 if persistent else 1, None), (persistent, _solve_path(M))   # (each side took the path it names)
         nrm = np.abs(A).sum(axis=1).max()
         res = np.abs(A @ x - b).max() / (nrm * np.abs(x).max() + np.abs(b).max())
         assert res <= 1e-13, (persistent, res)

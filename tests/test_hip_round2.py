@@ -116,6 +116,15 @@ def test_c3_size_factorization_vs_lapack(ctx, alg):
 
 
 # --------------------------------------------------------------------------- persistent solve: give-up path
+def _solve_path(M):
+    """Statistic "solve_path" (csrc/solve_plan.h: 1 stepwise, 2 one launch over 256-column steps, 3 over 512-column steps, 4 a system
+    of a merged launch), or None from a build of the library that does not report it (A/B runs through MNK_LIBPATH)."""
+    try:
+        return M.get_stat("solve_path")
+    except mj.HipError:
+        return None
+
+
 def _spd(rng, N):
     R = rng.standard_normal((N, 64))
     return np.asfortranarray(R @ R.T + N * np.eye(N))
@@ -135,10 +144,13 @@ def test_persistent_solve_abort_falls_back_to_stepwise_on_host_path(ctx, alg):
     x_ok = M.solve_linear_system(b.copy())
     M.set_option("ps_spin_limit", 2048)
     M.set_option("debug_ps_missing", 5)
+    assert _solve_path(M) in (2, None)
     x = M.solve_linear_system(b.copy())      # aborts inside, redone stepwise
+    assert _solve_path(M) in (1, None)
     assert np.abs(A @ x - b).max() <= 1e-10 * N
     np.testing.assert_allclose(x, x_ok, rtol=0, atol=1e-12 * np.abs(x_ok).max() * 10)
     x2 = M.solve_linear_system(b.copy())     # persistent_solve is off now: no further abort
+    assert _solve_path(M) in (1, None)
     np.testing.assert_array_equal(x2, x)
     M.close()
 
@@ -162,6 +174,7 @@ def test_persistent_solve_abort_is_reported_to_device_resident_callers(ctx):
     xd = torch.from_numpy(b).cuda()
     M.solve_linear_system(xd)                 # stepwise from here on
     M.check_solve()
+    assert _solve_path(M) in (1, None)
     assert np.abs(A @ xd.cpu().numpy() - b).max() <= 1e-10 * N
     M.close()
 
@@ -192,6 +205,7 @@ def test_solve_kkt_redoes_an_aborted_persistent_solve(ctx):
     kh.solve_kkt_device(bh)                  # the persistent solve inside gives up; redone stepwise in the same call
     assert np.abs(bh.values - good).max() <= 1e-10 * np.abs(good).max()
     kh.linear_solver.check_solve()           # nothing left pending
+    assert _solve_path(kh.linear_solver) in (1, None)
     kh.close()
 
 
@@ -705,7 +719,7 @@ def test_condensed_systems_do_not_pay_for_the_pivoted_tier(ctx):
     k.close()
 
 
-@pytest.mark.parametrize("N,alg", [(4096, "CHOLESKY"), (5000, "LDL"), (6100, "LDL"), (11192, "LDL")])
+@pytest.mark.parametrize("N,alg", [(3968, "LDL"), (4096, "CHOLESKY"), (5000, "LDL"), (6100, "LDL"), (11192, "LDL")])
 def test_solve_with_512_column_steps_matches_the_256_column_solve(ctx, N, alg):
     """Option solve512: the one-launch solve with 32-row blocks, 512-column steps and 512 x 512 explicit inverses assembled from
     the 256 x 256 ones on the MFMA tile kernel (half the steps per sweep).  Same solution as the default solve to rounding,
@@ -727,6 +741,8 @@ def test_solve_with_512_column_steps_matches_the_256_column_solve(ctx, N, alg):
         ls.factorize()
         ls.solve_linear_system(x)
         ctx.synchronize()
+        # (N = 3968: fewer than 4096 rows, and a 384-row last triangle: the option changes nothing there)
+        assert _solve_path(ls) in (3 if s512 and N != 3968 else 2, None), (s512, _solve_path(ls))
         xs.append(x.cpu().numpy())
         ls.close()
     An = torch.linalg.matrix_norm(A, ord=float("inf")).item()
