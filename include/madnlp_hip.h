@@ -655,6 +655,20 @@ int mnk_schur_assemble(mnk_schur* h, const double* hess, const double* jac, cons
 void* mnk_schur_s0_buffer(mnk_schur* h);
 int mnk_schur_get_block(mnk_schur* h, int64_t k, double* A_kk, double* C_dk, double* S0);
 int mnk_schur_solve(mnk_schur* h, double* rhs_k, double* rhs_d, int loc);
+/* Long inequality rows.  The source list of an inequality row holds one term per pair of its COO entries: it grows with the square
+ * of the row's length (a second-stage constraint that touches all of 400 design variables: 160 000 terms per row).  A row with MORE
+ * than `row_entries` COO entries (duplicates counted) therefore adds no pairs: mnk_schur_assemble stages the entries of such rows
+ * into dense zero-padded operands (duplicates summed in COO order) and adds J' D J of them to A_k, C_dk and S0 as weighted Gram
+ * products on the fp64 matrix cores, behind the source lists' kernel.  Every destination entry is owned by one workgroup and summed
+ * in a fixed order: the bits depend on the structure and the values alone.  A problem whose inequality rows all have at most
+ * `row_entries` entries keeps the bits of the source lists.
+ *   mnk_schur_set_gram_threshold  the threshold of the NEXT mnk_schur_set_structure; negative: the built-in default (64),
+ *                                 INT64_MAX: never (every row keeps its pairs)
+ *   mnk_schur_assembly_stats      of the structure in force: out[0] = terms of the source lists, out[1] = their segments (touched
+ *                                 entries), out[2] = long rows over the local scenarios, out[3] = doubles of the staging operands,
+ *                                 out[4] = the threshold in force; cap >= 5 */
+int mnk_schur_set_gram_threshold(mnk_schur* h, int64_t row_entries);
+int mnk_schur_assembly_stats(mnk_schur* h, int64_t* out, int cap);
 
 /* Diagnostics: with option "solve_trace" = 1 the persistent solve kernel stamps the forward sweep's critical
  * path (8 x 100 MHz timer values per 64-row block); this copies them out (n = number of uint64 to copy). */
@@ -733,6 +747,15 @@ int mnk_debug_solve_plan(int64_t Np, int num_cu, int pivoted, int persistent_opt
  * arguments. */
 int mnk_debug_solve_batch_groups(int n, const int64_t* solver_id, const int32_t* device, const int64_t* Np, const int32_t* ldl,
                                  const int32_t* num_cu, int32_t* begin, int32_t* idx, int32_t* G);
+/* What mnk_schur_set_structure would plan for a stage of `ns_local` scenarios of block order `blk` and `nd` design variables
+ * (csrc/schur_plan.hip; host only, no device is opened): the pattern arguments of mnk_schur_set_structure, then the stage's three
+ * numbers and the Gram row threshold T (negative: the default, INT64_MAX: never).  Runs the same checks and fills out[0..4] as
+ * mnk_schur_assembly_stats does; cap >= 5.  Returns 0, or a negative value with the error string set. */
+int mnk_debug_schur_assembly_plan(int64_t n, int64_t m, int64_t nv, int64_t nc, int64_t nnzh, const int32_t* hess_I,
+                                  const int32_t* hess_J, int64_t nnzj, const int32_t* jac_I, const int32_t* jac_J, int64_t n_ineq,
+                                  const int64_t* ind_ineq, int64_t n_eq, const int64_t* ind_eq, int index_base, int64_t ns_global,
+                                  const int64_t* local_scen, int own_design, int64_t ns_local, int64_t blk, int64_t nd, int64_t T,
+                                  int64_t* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -764,11 +764,15 @@ end
 Once per system: the COO patterns (1-based, as the callbacks give them) of the Lagrangian Hessian and of the Jacobian (row =
 constraint), the inequality rows in slack order and the equality rows.  The library checks the two-stage layout (what
 `_build_schur_symbolic` checks, schur.jl:140-236) and builds the source list of every touched entry of `A_k` / `C_dk` / `S0`.
+An inequality row with more than `gram_row_threshold` COO entries adds no pairs to the lists: its condensation runs as weighted
+Gram products on the matrix cores (`mnk_schur_set_gram_threshold`; negative: the library's default, `typemax(Int64)`: never).
 """
 function set_structure!(st::HipSchurStage, n::Integer, m::Integer, nv::Integer, nc::Integer, hess_I::Vector{Int32},
                         hess_J::Vector{Int32}, jac_I::Vector{Int32}, jac_J::Vector{Int32}, ind_ineq::Vector{Int64},
                         ind_eq::Vector{Int64}; ns_global::Integer = st.ns_local, local_scen::Union{Nothing, Vector{Int64}} = nothing,
-                        own_design::Bool = true)
+                        own_design::Bool = true, gram_row_threshold::Integer = -1)
+    rc = ccall((:mnk_schur_set_gram_threshold, libmadnlp_hip), Cint, (Ptr{Cvoid}, Int64), st.handle, gram_row_threshold)
+    check(rc, SymbolicException)
     rc = ccall((:mnk_schur_set_structure, libmadnlp_hip), Cint,
                (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int64},
                 Int64, Ptr{Int64}, Cint, Int64, Ptr{Int64}, Cint),
@@ -881,6 +885,7 @@ function MadNLP.create_kkt_system(
     ::Type{HipSchurComplementKKTSystem}, cb::SparseCallback{T, VT}, linear_solver::Type;
     opt_linear_solver = default_options(linear_solver), hessian_approximation = ExactHessian, qn_options = QuasiNewtonOptions(),
     schur_ns::Int = 0, schur_nv::Int = 0, schur_nd::Int = 0, schur_nc::Int = 0, device::Integer = 0,
+    schur_gram_row_threshold::Int = -1,
 ) where {T <: Float64, VT <: Vector{T}}
     inner = MadNLP.create_kkt_system(MadNLP.SchurComplementKKTSystem, cb, MadNLP.LapackCPUSolver;
                                      hessian_approximation = hessian_approximation, qn_options = qn_options,
@@ -894,7 +899,8 @@ function MadNLP.create_kkt_system(
     # the index maps of the scatter live in the library (built from the COO patterns the callbacks gave; jt_coo is J': I = variable)
     set_structure!(stage, MadNLP.num_variables(inner), length(inner.du_diag), inner.nv, inner.nc,
                    Vector{Int32}(inner.hess_raw.I), Vector{Int32}(inner.hess_raw.J), Vector{Int32}(inner.jt_coo.J),
-                   Vector{Int32}(inner.jt_coo.I), Vector{Int64}(inner.ind_ineq), Vector{Int64}(inner.ind_eq))
+                   Vector{Int32}(inner.jt_coo.I), Vector{Int64}(inner.ind_ineq), Vector{Int64}(inner.ind_eq);
+                   gram_row_threshold = schur_gram_row_threshold)
     return HipSchurComplementKKTSystem(inner, stage, HipSchurDesignSolver{T}(stage, Sdev), zeros(T, inner.blk_size, inner.ns))
 end
 

@@ -18,7 +18,9 @@
 // all-reduce of nd doubles (mnk_schur_forward's contribution).  The library itself does no communication.
 #include <vector>
 
+#include "gemm_tile.h"
 #include "ls.h"
+#include "schur_plan.h"
 
 struct mnk_schur {
     mnk_ctx* ctx = nullptr;
@@ -59,7 +61,16 @@ struct mnk_schur {
         mnk::DevBuf<int32_t> src_a, src_b, src_w;
         mnk::DevBuf<int64_t> ind_ineq;          // constraint row of slack p
         mnk::DevBuf<double> D, S0, vals;        // n_ineq | nd x nd | staging of host inputs: hess | jac | pr_diag | du_diag
+        // long inequality rows (more than T COO entries; schur_plan.h): no pairs -- their entries are staged into dense zero-padded
+        // operands and condensed by three weighted Gram products on the matrix cores behind schur_assemble_kernel
+        int64_t stats[5] = {0, 0, 0, 0, 0};     // mnk_schur_assembly_stats
+        int64_t long_rows = 0, nvp = 0, ndp = 0, Kp = 0, nslot = 0, nchunk = 0;
+        mnk::DevBuf<int64_t> slot_dst;          // nslot: offset into W (and DW)
+        mnk::DevBuf<int32_t> slot_ptr, slot_src, slot_p;   // nslot + 1 | COO entries of the slots | slack index of a slot's row
+        mnk::DevBuf<double> W, DW;              // [Wv_0 .. Wv_ns-1 (nvp x Kp each) | Wd_0 .. Wd_ns-1 (ndp x Kp each)] and its twin D W
+        mnk::DevBuf<double> P;                  // nchunk x (nd x nd): the partial sums of the S0 product, one per K chunk
     } as;
+    int64_t gram_T = -1;                        // Gram row threshold of the next mnk_schur_set_structure (negative: the default)
 };
 
 namespace mnk {
@@ -184,6 +195,77 @@ __global__ void schur_assemble_kernel(int64_t nseg, const int64_t* __restrict__ 
     if (d < sizeA) A[d] = acc;
     else if (d < sizeA + sizeC) Cb[d - sizeA] = acc;
     else S0[d - sizeA - sizeC] = acc;
+}
+
+// ---- long inequality rows: J' D J as weighted Gram products (schur_plan.h) ----
+// One thread per staging slot = distinct (long row, column): the sum of its COO entries in COO order into W, D[row] times the sum
+// into the twin.  The padding of both buffers was zeroed once (mnk_schur_set_structure) and is never written.
+__global__ void schur_gram_stage_kernel(int64_t nslot, const int64_t* __restrict__ slot_dst, const int32_t* __restrict__ slot_ptr,
+                                        const int32_t* __restrict__ slot_src, const int32_t* __restrict__ slot_p,
+                                        const double* __restrict__ jac, const double* __restrict__ D, double* __restrict__ W,
+                                        double* __restrict__ DW) {
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (t >= nslot) return;
+    double w = 0.0;
+    for (int32_t q = slot_ptr[t]; q < slot_ptr[t + 1]; ++q) w = __dadd_rn(w, jac[slot_src[q]]);
+    const int64_t d = slot_dst[t];
+    W[d] = w;
+    DW[d] = __dmul_rn(D[slot_p[t]], w);
+}
+
+// dst_y (+)= W_y DW_y' for the batch member y = blockIdx.y, one 64 x 64 tile (blockIdx.x; 2 x 2 waves of 32 x 32) per workgroup:
+// W_y = W + y * strideW (element (c, k) at c + k * ldw, rows padded to 64), DW_y likewise, K = 16 * nk long rows (the last member:
+// 16 * nk_last).  The K-loop is gemm_nt_mainloop on the padded operands (no bounds checks); the epilogue touches rows < rows and
+// columns < cols of the unpadded destination only.  add: dst = dst + acc, rounded once (the destination holds what
+// schur_assemble_kernel wrote); else dst = acc (a partial sum of the S0 product).  One workgroup owns a destination tile and sums
+// its K range front to back: the bits depend on the structure and the values alone.
+constexpr int GRAM_WM = 2, GRAM_WN = 2, GRAM_WT = 2, GRAM_BK = (int)SCHUR_GRAM_BK;
+constexpr int GRAM_TILE = 16 * GRAM_WT * GRAM_WM;
+constexpr int GRAM_LDS_BYTES = 2 * 2 * GRAM_BK * (GRAM_TILE + 16) * 8;
+static_assert(GRAM_TILE == SCHUR_GRAM_TILE && 16 * GRAM_WT * GRAM_WN == SCHUR_GRAM_TILE, "the planner pads to the kernel's tile");
+constexpr int GRAM_S0_CHUNK = 32;   // k-tiles (of 16 long rows) per partial sum of the S0 product
+__global__ __launch_bounds__(64 * GRAM_WM * GRAM_WN) void schur_gram_kernel(const double* __restrict__ W, int64_t ldw, int64_t strideW,
+                                                                            const double* __restrict__ DW, int64_t lddw, int64_t strideDW,
+                                                                            int nk, int nk_last, double* dst, int64_t ldd, int64_t strideD,
+                                                                            int64_t rows, int64_t cols, int ntm, int add) {
+    __shared__ __attribute__((aligned(16))) char smem[GRAM_LDS_BYTES];
+    const int tid = threadIdx.x;
+    const int tm = (int)blockIdx.x % ntm, tn = (int)blockIdx.x / ntm;
+    const int64_t y = blockIdx.y;
+    const int64_t row0 = (int64_t)tm * GRAM_TILE, col0 = (int64_t)tn * GRAM_TILE;
+    v4f64 acc[GRAM_WT][GRAM_WT];
+#pragma unroll
+    for (int i = 0; i < GRAM_WT; ++i)
+#pragma unroll
+        for (int j = 0; j < GRAM_WT; ++j) acc[i][j] = v4f64{0.0, 0.0, 0.0, 0.0};
+    (void)gemm_nt_mainloop<GRAM_WM, GRAM_WN, GRAM_WT, GRAM_BK>(acc, W + y * strideW + row0, ldw, DW + y * strideDW + col0, lddw,
+                                                                y + 1 == (int64_t)gridDim.y ? nk_last : nk, smem, tid);
+    // acc[ni][mi] register r of lane (l15, l4) of wave (wm, wn): row wm*32 + mi*16 + l15, column wn*32 + ni*16 + l4 + 4r (gemm_tile.h)
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave % GRAM_WM, wn = wave / GRAM_WM, l15 = lane & 15, l4 = lane >> 4;
+    double* D0 = dst + y * strideD;
+#pragma unroll
+    for (int ni = 0; ni < GRAM_WT; ++ni)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t col = col0 + wn * 16 * GRAM_WT + ni * 16 + l4 + 4 * r;
+            if (col >= cols) continue;
+#pragma unroll
+            for (int mi = 0; mi < GRAM_WT; ++mi) {
+                const int64_t row = row0 + wm * 16 * GRAM_WT + mi * 16 + l15;
+                if (row >= rows) continue;
+                double* p = D0 + row + col * ldd;
+                *p = add ? __dadd_rn(*p, acc[ni][mi][r]) : acc[ni][mi][r];
+            }
+        }
+}
+// S0 = (((S0 + P_0) + P_1) + ...): the partial sums of the S0 product in chunk order, every addition rounded on its own
+__global__ void schur_gram_reduce_kernel(double* __restrict__ S0, const double* __restrict__ P, int64_t nchunk, int64_t n) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double v = S0[i];
+    for (int64_t c = 0; c < nchunk; ++c) v = __dadd_rn(v, P[c * n + i]);
+    S0[i] = v;
 }
 }  // namespace mnk
 
@@ -488,148 +570,61 @@ int mnk_schur_backward(mnk_schur* h, double* rhs_k, const double* x_d) {
     return schur_check_solves(h, true, false);
 }
 
-// A device buffer of nd x nd doubles owned by the handle: `S_out` of mnk_schur_build_local and `S` of mnk_schur_factorize_s for
-// callers that keep no device memory themselves (the Julia glue's host-driven KKT system, julia/MadNLPHIP.jl).
+// The Gram row threshold of the next mnk_schur_set_structure and the numbers of the structure in force (schur_plan.h).
+int mnk_schur_set_gram_threshold(mnk_schur* h, int64_t row_entries) {
+    MNK_REQUIRE(h, "mnk_schur_set_gram_threshold: NULL handle");
+    h->gram_T = row_entries < 0 ? -1 : row_entries;
+    return 0;
+}
+
+int mnk_schur_assembly_stats(mnk_schur* h, int64_t* out, int cap) {
+    MNK_REQUIRE(h && h->as.have, "mnk_schur_assembly_stats: call mnk_schur_set_structure first");
+    MNK_REQUIRE(out && cap >= 5, "mnk_schur_assembly_stats: out needs room for five numbers");
+    std::copy(h->as.stats, h->as.stats + 5, out);
+    return 0;
+}
+
+// The lists come from the host-only planner (schur_plan.hip); this uploads them and zeroes the staging operands of the long rows.
 int mnk_schur_set_structure(mnk_schur* h, int64_t n, int64_t m, int64_t nv, int64_t nc, int64_t nnzh, const int32_t* hess_I,
                             const int32_t* hess_J, int64_t nnzj, const int32_t* jac_I, const int32_t* jac_J, int64_t n_ineq,
                             const int64_t* ind_ineq, int64_t n_eq, const int64_t* ind_eq, int index_base, int64_t ns_global,
                             const int64_t* local_scen, int own_design) {
     MNK_REQUIRE(h, "mnk_schur_set_structure: NULL handle");
-    MNK_REQUIRE(index_base == 0 || index_base == 1, "mnk_schur_set_structure: index_base must be 0 or 1");
-    MNK_REQUIRE((nnzh == 0 || (hess_I && hess_J)) && (nnzj == 0 || (jac_I && jac_J)) && (n_ineq == 0 || ind_ineq) && (n_eq == 0 || ind_eq),
-                "mnk_schur_set_structure: NULL pattern");
-    const int64_t ns = local_scen ? ns_global : h->ns, nd = h->nd, blk = h->blk;
-    MNK_REQUIRE(ns >= h->ns && nv > 0 && nc >= 0, "mnk_schur_set_structure: bad dimensions");
-    MNK_REQUIRE(n == ns * nv + nd && m == ns * nc, "mnk_schur_set_structure: n, m do not match ns * nv + nd, ns * nc");
-    MNK_REQUIRE(n_eq + n_ineq == m && n_eq % std::max<int64_t>(ns, 1) == 0 && n_ineq % std::max<int64_t>(ns, 1) == 0,
-                "mnk_schur_set_structure: the scenarios have different numbers of equality / inequality constraints");
-    const int64_t nc_eq = ns > 0 ? n_eq / ns : 0;
-    MNK_REQUIRE(blk == nv + nc_eq, "mnk_schur_set_structure: the stage's block order is not nv + (equality rows per scenario)");
-    MNK_REQUIRE(nnzh < 2000000000 && nnzj < 2000000000 && n + n_ineq < 2000000000, "mnk_schur_set_structure: structure exceeds int32 range");
+    const int64_t nd = h->nd;
+    const SchurPatterns in{h->ns, h->blk, nd, n, m, nv, nc, nnzh, hess_I, hess_J, nnzj, jac_I, jac_J, n_ineq, ind_ineq,
+                           n_eq, ind_eq, index_base, ns_global, local_scen, own_design, h->gram_T};
+    SchurAssemblyPlan plan;
+    const char* err = schur_assembly_plan(in, plan);
+    MNK_REQUIRE(!err, err);
+    MNK_REQUIRE(plan.long_rows == 0 || (h->ns <= 65535 && h->ns * plan.Kp / GRAM_BK <= (int64_t)65535 * GRAM_S0_CHUNK),
+                "mnk_schur_set_structure: too many local scenarios / long rows for the Gram products' grids");
     MNK_HIP(hipSetDevice(h->ctx->device));
-    const int64_t off = ns * nv;
-    // global scenario -> local block (or -1)
-    std::vector<int64_t> loc_of(ns, -1);
-    for (int64_t i = 0; i < h->ns; ++i) {
-        const int64_t g = local_scen ? local_scen[i] : i;
-        MNK_REQUIRE(g >= 0 && g < ns && loc_of[g] < 0, "mnk_schur_set_structure: bad local scenario list");
-        loc_of[g] = i;
-    }
-    // equality rows: local index = rank among the scenario's equality rows (ascending); inequality rows: slack index
-    std::vector<int64_t> eq_local(m, -1), slack_of(m, -1);
-    {
-        std::vector<int64_t> eq_sorted(ind_eq, ind_eq + n_eq);
-        for (auto& r : eq_sorted) r -= index_base;
-        std::sort(eq_sorted.begin(), eq_sorted.end());
-        std::vector<int64_t> cnt(ns, 0);
-        for (int64_t r : eq_sorted) {
-            MNK_REQUIRE(r >= 0 && r < m, "mnk_schur_set_structure: equality index out of range");
-            const int64_t k = nc > 0 ? r / nc : 0;
-            eq_local[r] = cnt[k]++;
-        }
-        for (int64_t k = 0; k < ns; ++k)
-            MNK_REQUIRE(cnt[k] == nc_eq, "mnk_schur_set_structure: the scenarios have different numbers of equality / inequality constraints");
-        for (int64_t p = 0; p < n_ineq; ++p) {
-            const int64_t r = ind_ineq[p] - index_base;
-            MNK_REQUIRE(r >= 0 && r < m && eq_local[r] < 0 && slack_of[r] < 0, "mnk_schur_set_structure: bad inequality index");
-            slack_of[r] = p;
-        }
-    }
-    auto scen = [&](int64_t var) -> int64_t { return var < off ? var / nv : -1; };
-    struct Src { int64_t dst; int8_t kind; int32_t a, b, w; };
-    std::vector<Src> src;
-    const int64_t sizeA = h->ns * blk * blk, sizeC = h->ns * nd * blk;
-    auto putA = [&](int64_t kl, int64_t r, int64_t c, int8_t kind, int64_t a, int64_t b = 0, int64_t w = 0) {
-        src.push_back(Src{kl * blk * blk + r + c * blk, kind, (int32_t)a, (int32_t)b, (int32_t)w});
-    };
-    auto putC = [&](int64_t kl, int64_t d, int64_t c, int8_t kind, int64_t a, int64_t b = 0, int64_t w = 0) {
-        src.push_back(Src{sizeA + kl * nd * blk + d + c * nd, kind, (int32_t)a, (int32_t)b, (int32_t)w});
-    };
-    auto putS = [&](int64_t r, int64_t c, int8_t kind, int64_t a, int64_t b = 0, int64_t w = 0) {
-        src.push_back(Src{sizeA + sizeC + r + c * nd, kind, (int32_t)a, (int32_t)b, (int32_t)w});
-    };
-    // Hessian entries (forced to the lower triangle, matrixtools.jl:129-137): scenario block, coupling block, design block
-    for (int64_t e = 0; e < nnzh; ++e) {
-        int64_t i = hess_I[e] - index_base, j = hess_J[e] - index_base;
-        MNK_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "mnk_schur_set_structure: Hessian index out of range");
-        if (j > i) std::swap(i, j);
-        const int64_t si = scen(i), sj = scen(j);
-        if (si >= 0 && sj >= 0) {
-            MNK_REQUIRE(si == sj, "mnk_schur_set_structure: a Hessian entry couples two scenarios");
-            const int64_t kl = loc_of[si];
-            if (kl < 0) continue;
-            const int64_t li = i - si * nv, lj = j - sj * nv;
-            putA(kl, li, lj, 0, e);
-            if (li != lj) putA(kl, lj, li, 0, e);
-        } else if (si < 0 && sj < 0) {
-            if (!own_design) continue;
-            putS(i - off, j - off, 0, e);
-            if (i != j) putS(j - off, i - off, 0, e);
-        } else {   // (lower triangle: the design variable is the row)
-            const int64_t kl = loc_of[sj];
-            if (kl >= 0) putC(kl, i - off, j - sj * nv, 0, e);
-        }
-    }
-    // diagonal terms
-    for (int64_t k = 0; k < ns; ++k) {
-        const int64_t kl = loc_of[k];
-        if (kl < 0) continue;
-        for (int64_t j = 0; j < nv; ++j) putA(kl, j, j, 2, k * nv + j);
-    }
-    for (int64_t r = 0; r < m; ++r)
-        if (eq_local[r] >= 0 && loc_of[r / nc] >= 0) putA(loc_of[r / nc], nv + eq_local[r], nv + eq_local[r], 3, r);
-    if (own_design)
-        for (int64_t j = 0; j < nd; ++j) putS(j, j, 2, off + j);
-    // Jacobian entries of equality rows; the entries of every inequality row in COO order
-    std::vector<std::vector<std::pair<int32_t, int64_t>>> row_entries(m);
-    for (int64_t e = 0; e < nnzj; ++e) {
-        const int64_t r = jac_I[e] - index_base, c = jac_J[e] - index_base;
-        MNK_REQUIRE(r >= 0 && r < m && c >= 0 && c < n, "mnk_schur_set_structure: Jacobian index out of range");
-        const int64_t k = r / nc;
-        MNK_REQUIRE(c >= off || c / nv == k, "mnk_schur_set_structure: a constraint reaches the variables of another scenario");
-        const int64_t kl = loc_of[k];
-        if (kl < 0) continue;
-        if (eq_local[r] >= 0) {
-            const int64_t li = eq_local[r];
-            if (c < off) { putA(kl, nv + li, c - k * nv, 1, e); putA(kl, c - k * nv, nv + li, 1, e); }
-            else putC(kl, c - off, nv + li, 1, e);
-        } else {
-            row_entries[r].push_back({(int32_t)e, c});
-        }
-    }
-    // inequality rows: J' D J over A_k, C_dk and S0, one pair of entries at a time (_scatter_quad_add!, schur.jl:966-972)
-    for (int64_t p = 0; p < n_ineq; ++p) {
-        const int64_t r = ind_ineq[p] - index_base, k = r / nc, kl = loc_of[k];
-        if (kl < 0) continue;
-        const auto& ents = row_entries[r];
-        for (const auto& e1 : ents)
-            for (const auto& e2 : ents) {
-                const int64_t c1 = e1.second, c2 = e2.second;
-                if (c1 < off && c2 < off) putA(kl, c1 - k * nv, c2 - k * nv, 4, e1.first, e2.first, p);
-                else if (c1 >= off && c2 < off) putC(kl, c1 - off, c2 - k * nv, 4, e1.first, e2.first, p);
-                else if (c1 >= off && c2 >= off) putS(c1 - off, c2 - off, 4, e1.first, e2.first, p);
-            }
-    }
-    MNK_REQUIRE(src.size() < (size_t)2000000000, "mnk_schur_set_structure: too many assembly terms");
-    std::stable_sort(src.begin(), src.end(), [](const Src& x, const Src& y) { return x.dst < y.dst; });
-    std::vector<int64_t> seg_dst;
-    std::vector<int32_t> seg_ptr, sa(src.size()), sb(src.size()), sw(src.size());
-    std::vector<int8_t> kind(src.size());
-    for (size_t q = 0; q < src.size(); ++q) {
-        if (q == 0 || src[q].dst != src[q - 1].dst) { seg_dst.push_back(src[q].dst); seg_ptr.push_back((int32_t)q); }
-        kind[q] = src[q].kind; sa[q] = src[q].a; sb[q] = src[q].b; sw[q] = src[q].w;
-    }
-    seg_ptr.push_back((int32_t)src.size());
     auto& as = h->as;
     as.have = false;
     as.n = n; as.m = m; as.nv = nv; as.nc = nc; as.nnzh = nnzh; as.nnzj = nnzj; as.n_ineq = n_ineq;
-    as.nseg = (int64_t)seg_dst.size(); as.nsrc = (int64_t)src.size();
-    std::vector<int64_t> ineq0(n_ineq);
-    for (int64_t p = 0; p < n_ineq; ++p) ineq0[p] = ind_ineq[p] - index_base;
+    as.nseg = plan.nseg(); as.nsrc = plan.nsrc();
+    plan.stats(as.stats);
+    as.long_rows = plan.long_rows; as.nvp = plan.nvp; as.ndp = plan.ndp; as.Kp = plan.Kp;
+    as.nslot = (int64_t)plan.slot_dst.size();
+    as.nchunk = (h->ns * plan.Kp / GRAM_BK + GRAM_S0_CHUNK - 1) / GRAM_S0_CHUNK;
     hipStream_t st = h->ctx->stream;
-    int rc = as.seg_dst.upload(seg_dst, st) | as.seg_ptr.upload(seg_ptr, st) | as.src_kind.upload(kind, st) | as.src_a.upload(sa, st) |
-             as.src_b.upload(sb, st) | as.src_w.upload(sw, st) | as.ind_ineq.upload(ineq0, st) | as.D.alloc((size_t)std::max<int64_t>(n_ineq, 1)) |
-             as.S0.alloc((size_t)nd * nd + 8) | as.vals.alloc((size_t)(nnzh + nnzj + n + n_ineq + m) + 8);
+    int rc = as.seg_dst.upload(plan.seg_dst, st) | as.seg_ptr.upload(plan.seg_ptr, st) | as.src_kind.upload(plan.kind, st) |
+             as.src_a.upload(plan.a, st) | as.src_b.upload(plan.b, st) | as.src_w.upload(plan.w, st) | as.ind_ineq.upload(plan.ineq0, st) |
+             as.D.alloc((size_t)std::max<int64_t>(n_ineq, 1)) | as.S0.alloc((size_t)nd * nd + 8) |
+             as.vals.alloc((size_t)(nnzh + nnzj + n + n_ineq + m) + 8);
+    if (!rc && as.long_rows > 0) {
+        const size_t nw = (size_t)(plan.size_wv() + plan.size_wd());
+        rc = as.slot_dst.upload(plan.slot_dst, st) | as.slot_ptr.upload(plan.slot_ptr, st) | as.slot_src.upload(plan.slot_src, st) |
+             as.slot_p.upload(plan.slot_p, st) | as.W.alloc(nw + 8) | as.DW.alloc(nw + 8) | as.P.alloc((size_t)as.nchunk * nd * nd + 8);
+        if (!rc) {   // the padding never changes: zeroed once
+            MNK_HIP(hipMemsetAsync(as.W.p, 0, (nw + 8) * sizeof(double), st));
+            MNK_HIP(hipMemsetAsync(as.DW.p, 0, (nw + 8) * sizeof(double), st));
+            MNK_HIP(mnk::stream_wait(st));
+        }
+    } else if (!rc) {
+        as.slot_dst.release(); as.slot_ptr.release(); as.slot_src.release(); as.slot_p.release();
+        as.W.release(); as.DW.release(); as.P.release();
+    }
     if (rc) { (void)hipGetLastError(); set_error("mnk_schur_set_structure: out of device memory"); return -2; }
     as.have = true;
     return 0;
@@ -660,6 +655,30 @@ int mnk_schur_assemble(mnk_schur* h, const double* hess, const double* jac, cons
         hipLaunchKernelGGL(mnk::schur_assemble_kernel, dim3((unsigned)((as.nseg + 255) / 256)), dim3(256), 0, s, as.nseg, as.seg_dst.p, as.seg_ptr.p,
                            as.src_kind.p, as.src_a.p, as.src_b.p, as.src_w.p, hess, jac, pr_diag, du_diag, as.D.p, h->A.p, sizeA, h->C.p, sizeC,
                            as.S0.p);
+    if (as.long_rows > 0) {   // J' D J of the long rows, added behind the segments' `=` on the same stream
+        const double* Wv = as.W.p;
+        const double* DWv = as.DW.p;
+        const int64_t sizeWv = h->ns * as.nvp * as.Kp, nv = as.nv, nd = h->nd, nvp = as.nvp, ndp = as.ndp, Kp = as.Kp;
+        const double* Wd = Wv + sizeWv;
+        const double* DWd = DWv + sizeWv;
+        const int tv = (int)(nvp / GRAM_TILE), td = (int)(ndp / GRAM_TILE), nk = (int)(Kp / GRAM_BK);
+        const dim3 blkdim(64 * GRAM_WM * GRAM_WN);
+        hipLaunchKernelGGL(mnk::schur_gram_stage_kernel, dim3((unsigned)((as.nslot + 255) / 256)), dim3(256), 0, s, as.nslot, as.slot_dst.p,
+                           as.slot_ptr.p, as.slot_src.p, as.slot_p.p, jac, as.D.p, as.W.p, as.DW.p);
+        // A_k[0:nv, 0:nv] += Wv_k DWv_k'  |  C_dk[0:nd, 0:nv] += Wd_k DWv_k'   (blockIdx.y = local scenario)
+        hipLaunchKernelGGL(mnk::schur_gram_kernel, dim3((unsigned)(tv * tv), (unsigned)h->ns), blkdim, 0, s, Wv, nvp, nvp * Kp, DWv, nvp,
+                           nvp * Kp, nk, nk, h->A.p, h->blk, h->blk * h->blk, nv, nv, tv, 1);
+        hipLaunchKernelGGL(mnk::schur_gram_kernel, dim3((unsigned)(td * tv), (unsigned)h->ns), blkdim, 0, s, Wd, ndp, ndp * Kp, DWv, nvp,
+                           nvp * Kp, nk, nk, h->C.p, nd, nd * h->blk, nd, nv, td, 1);
+        // S0 += Wd_all DWd_all' over the long rows of all local scenarios in local order: partial sums over chunks of
+        // GRAM_S0_CHUNK k-tiles (blockIdx.y = chunk), added to S0 in chunk order
+        const int nk_all = (int)(h->ns * Kp / GRAM_BK), nk_last = nk_all - (int)(as.nchunk - 1) * GRAM_S0_CHUNK;
+        const int64_t cstride = (int64_t)GRAM_S0_CHUNK * GRAM_BK * ndp;
+        hipLaunchKernelGGL(mnk::schur_gram_kernel, dim3((unsigned)(td * td), (unsigned)as.nchunk), blkdim, 0, s, Wd, ndp, cstride, DWd, ndp,
+                           cstride, GRAM_S0_CHUNK, nk_last, as.P.p, nd, nd * nd, nd, nd, td, 0);
+        hipLaunchKernelGGL(mnk::schur_gram_reduce_kernel, dim3((unsigned)((nd * nd + 255) / 256)), dim3(256), 0, s, as.S0.p, as.P.p, as.nchunk,
+                           nd * nd);
+    }
     MNK_HIP(hipGetLastError());
     h->built = false;
     return 0;
@@ -678,6 +697,8 @@ int mnk_schur_get_block(mnk_schur* h, int64_t k, double* A_kk, double* C_dk, dou
     return 0;
 }
 
+// A device buffer of nd x nd doubles owned by the handle: `S_out` of mnk_schur_build_local and `S` of mnk_schur_factorize_s for
+// callers that keep no device memory themselves (the Julia glue's host-driven KKT system, julia/MadNLPHIP.jl).
 void* mnk_schur_s_buffer(mnk_schur* h) {
     if (!h) return nullptr;
     (void)hipSetDevice(h->ctx->device);

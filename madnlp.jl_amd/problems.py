@@ -840,7 +840,8 @@ def random_twostage_qp(ns=8, nv=40, nd=12, nc=10, nc_eq=4, seed=0, density_v=0.4
     """A larger `TwoStageQPModel` with the first `nc_eq` constraints of every scenario equalities and the rest two-sided
     inequalities around a strictly feasible point (so that both kinds of rows of the Schur system's blocks are exercised).
     `density_v` / `density_d`: fraction of nonzeros in a constraint row's recourse / design part (the condensation of an
-    inequality row costs the SQUARE of its length in the reference's pair lists: large instances need sparse rows)."""
+    inequality row costs the SQUARE of its length in the reference's pair lists; the HIP system condenses rows of more than
+    `gram_row_threshold` entries as Gram products instead, so dense rows are fine there)."""
     rng = np.random.default_rng(seed)
     hess_v = rng.uniform(0.5, 4.0, (nv, ns))
     hess_d = rng.uniform(0.5, 4.0, nd)

@@ -15,6 +15,9 @@ from . import _lib as L
 from .linear_solver import BUNCHKAUFMAN, _ALGO, _LIVE_OBJECTS, FactorizationException, HipContext, SolveException
 
 
+GRAM_NEVER = 2 ** 63 - 1   # `gram_row_threshold`: no inequality row is long (INT64_MAX of mnk_schur_set_gram_threshold)
+
+
 def shard(ns: int, rank: int, world: int):
     """Global scenario indices owned by `rank` (round-robin, as the C5 instance partition)."""
     return list(range(rank, ns, world))
@@ -56,10 +59,15 @@ class SchurDenseStage:
         self._assembled = False
 
     # ---- device-side assembly (mnk_schur_set_structure / mnk_schur_assemble)
-    def set_structure(self, n, m, nv, nc, hess_I, hess_J, jac_I, jac_J, ind_ineq, ind_eq, ns_global=None, local_scen=None, own_design=True):
+    def set_structure(self, n, m, nv, nc, hess_I, hess_J, jac_I, jac_J, ind_ineq, ind_eq, ns_global=None, local_scen=None, own_design=True,
+                      gram_row_threshold=None):
         """Once: the COO patterns (0-based) from which the library builds, per touched entry of A_k / C_dk / S0, the list of its
         sources in the reference's scatter order (schur.jl:935-972).  Raises ValueError where the reference's
-        `_build_schur_symbolic` throws (:140-236)."""
+        `_build_schur_symbolic` throws (:140-236).  `gram_row_threshold`: an inequality row with more COO entries than this adds
+        no pairs to the lists -- its condensation runs as weighted Gram products on the matrix cores (`mnk_schur_set_gram_threshold`;
+        None: the library's default, `GRAM_NEVER`: every row keeps its pairs)."""
+        L.check(L.lib().mnk_schur_set_gram_threshold(self._h, -1 if gram_row_threshold is None else int(gram_row_threshold)),
+                "mnk_schur_set_gram_threshold")
         hI, hJ = (np.ascontiguousarray(a, dtype=np.int32) for a in (hess_I, hess_J))
         jI, jJ = (np.ascontiguousarray(a, dtype=np.int32) for a in (jac_I, jac_J))
         ii, ie = (np.ascontiguousarray(a, dtype=np.int64) for a in (ind_ineq, ind_eq))
@@ -71,6 +79,13 @@ class SchurDenseStage:
         if rc:
             raise ValueError(L.lib().mnk_last_error_string().decode())
         self._assembled = False
+
+    def assembly_stats(self):
+        """(terms of the source lists, their segments, long rows over the local scenarios, doubles of the Gram staging operands,
+        the Gram row threshold in force) of the structure in force (`mnk_schur_assembly_stats`)."""
+        out = (C.c_int64 * 5)()
+        L.check(L.lib().mnk_schur_assembly_stats(self._h, out, 5), "mnk_schur_assembly_stats")
+        return tuple(int(v) for v in out)
 
     def assemble(self, hess, jac, pr_diag, du_diag):
         """`build_kkt!`'s scatter (reference :935-972) on the device: A_k, C_dk of every local scenario and S0 from the callbacks'

@@ -96,7 +96,7 @@ class SchurComplementKKTSystem(_KKTCommon):
 
     device_assembly = True     # False: the host assembly of rounds 4-5 (diagnostic A/B runs)
 
-    def __init__(self, n, m, jac_I, jac_J, hess_I, hess_J, ind_ineq, ind_eq, ind_lb, ind_ub, ns, nv, nd, nc, ctx=None):
+    def __init__(self, n, m, jac_I, jac_J, hess_I, hess_J, ind_ineq, ind_eq, ind_lb, ind_ub, ns, nv, nd, nc, ctx=None, gram_row_threshold=None):
         import torch
         self.torch = torch
         sym = build_schur_symbolic(n, m, ns, nv, nd, nc, hess_I, hess_J, jac_I, jac_J, ind_eq, ind_ineq)
@@ -128,8 +128,10 @@ class SchurComplementKKTSystem(_KKTCommon):
         zC = [np.zeros((nd, self.blk)) for _ in range(ns)]
         self.stage = SchurDenseStage(zA, zC, np.eye(nd), nd, self.blk, ctx=self.ctx)
         # the index maps of `_build_schur_symbolic` (reference :460-700) live in the library: one source list per touched entry of
-        # A_k / C_dk / S0, built from the COO patterns once
-        self.stage.set_structure(n, m, nv, nc, self.hess_I, self.hess_J, self.jac_I, self.jac_J, self.ind_ineq, self.ind_eq)
+        # A_k / C_dk / S0, built from the COO patterns once; inequality rows with more than `gram_row_threshold` entries are condensed
+        # as Gram products on the matrix cores instead (None: the library's default)
+        self.stage.set_structure(n, m, nv, nc, self.hess_I, self.hess_J, self.jac_I, self.jac_J, self.ind_ineq, self.ind_eq,
+                                 gram_row_threshold=gram_row_threshold)
         self.aug_com = self.stage.S
         self.linear_solver = _DesignSolver(self.stage)
         self._order = nd
