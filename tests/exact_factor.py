@@ -58,10 +58,9 @@ class ExactCase:
         return int(bad[0]) + 1 if len(bad) else 0
 
 
-def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool = True, per_row: int = 6,
-               exponents: tuple = (-2, 3)) -> ExactCase:
-    """`breakdowns`: {column: new d_k}.  `positive`: every other pivot > 0 (else random signs).  `exponents`: the range
-    (inclusive) of e in |d_k| = 4^e."""
+def draw_factors(n: int, seed: int, breakdowns: dict | None = None, positive: bool = True, per_row: int = 6,
+                 exponents: tuple = (-2, 3)):
+    """(N sparse, d) of make_exact, without the dense A (orders at which forming it on the host is too slow)."""
     rng = np.random.default_rng(seed)
     src = rng.random(n) < 0.5
     src[0] = True
@@ -86,6 +85,14 @@ def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool
         d *= rng.choice([-1.0, 1.0], size=n)
     for k, v in (breakdowns or {}).items():
         d[k] = v
+    return Nmat, d
+
+
+def make_exact(n: int, seed: int, breakdowns: dict | None = None, positive: bool = True, per_row: int = 6,
+               exponents: tuple = (-2, 3)) -> ExactCase:
+    """`breakdowns`: {column: new d_k}.  `positive`: every other pivot > 0 (else random signs).  `exponents`: the range
+    (inclusive) of e in |d_k| = 4^e."""
+    Nmat, d = draw_factors(n, seed, breakdowns, positive, per_row, exponents)
     M = sp.identity(n, format="csc") + Nmat
     A = (M @ sp.diags(d) @ M.T).toarray()
     return ExactCase(n, Nmat, d, np.asfortranarray(A))
