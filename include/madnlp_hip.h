@@ -260,7 +260,12 @@ int mnk_ls_solve_batch(int n, mnk_ls* const* ls, double* const* x, int loc);
 int mnk_ls_inertia(mnk_ls* ls, int64_t* num_pos, int64_t* num_zero, int64_t* num_neg);
 /* solve_linear_system!(M, x) `lapack_common.jl:75-81` (dpotrs / dsytrs): in place,
  * nrhs right-hand sides with leading dimension ldx (the reference loops over
- * columns, `src/LinearSolvers/linearsolvers.jl:102-110`). */
+ * columns, `src/LinearSolvers/linearsolvers.jl:102-110`).  So does this call, one single-vector solve per column, unless
+ * option multi_rhs_min is positive, nrhs >= multi_rhs_min and the factor is the static-pivot tier's (CHOLESKY / LDL, not
+ * pivoted): then the columns go through both sweeps in chunks of 64 on the fp64 matrix cores, one pass over the factor per
+ * chunk and sweep (statistics "solve_path" = 5, "solve_rhs_chunks"; csrc/solve_multi.hip).  The blocked results are those of
+ * the same factor with the sums grouped differently, not the bits of the column loop; a column's bits do not depend on nrhs,
+ * on its position in x or on the other columns.  Rows >= N of a strided x and columns >= nrhs are never written. */
 int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc);
 /* Status of the solves enqueued so far, for callers whose vectors live on the device (loc = MNK_DEVICE):
  * synchronizes the context stream; 0 if every solve completed, -3 if a one-launch ("persistent") solve gave
@@ -741,6 +746,14 @@ int mnk_debug_factor_plan(int64_t Np, int ldl, int algo_now, int lookahead, int6
  * out[4] = the inverses of a batch of small factorizations come from one launch.  Returns 0, -1 on bad arguments. */
 int mnk_debug_solve_plan(int64_t Np, int num_cu, int pivoted, int persistent_opt, int solve512_opt, int have_linv512, int partitioned,
                          int abort_raised, int debug_missing, int tracing, int ldl, int linv_mfma, int* out);
+/* ... and a solve of `nrhs` right-hand sides with option multi_rhs_min (the same shape arguments, without linv_mfma): out[0] = the
+ * path -- 5 (blocked, csrc/solve_multi.hip) exactly when the factor is not pivoted, multi_rhs_min > 0 and nrhs >= multi_rhs_min,
+ * otherwise the path of every column of the column loop as mnk_debug_solve_plan gives it --, out[1] = the chunk width W (right-hand
+ * sides per pass over the factor), out[2] = the chunks, out[3] = the padded width of the last chunk's working block (a multiple
+ * of 16), out[4] = the grid of the column loop's one-launch path; out[1..3] are 0 for the column loop.  Returns 0, -1 on bad
+ * arguments. */
+int mnk_debug_solve_plan_multi(int64_t Np, int num_cu, int pivoted, int persistent_opt, int solve512_opt, int have_linv512, int partitioned,
+                               int abort_raised, int debug_missing, int tracing, int ldl, int64_t nrhs, int64_t multi_rhs_min, int* out);
 /* The launches a solve batch makes of `n` queued solves (in queue order: solver identity, device, padded order, LDL^T or not and the
  * CUs of its context): launch l runs the requests idx[begin[l] .. begin[l + 1]) with G[l] workgroups per system; a launch of one
  * request is an ordinary solve (G[l] = 0).  begin holds n + 1, idx and G n entries.  Returns the number of launches, -1 on bad

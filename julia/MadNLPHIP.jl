@@ -85,6 +85,8 @@ end
     panel_algo::Int = 5             # 5: task-DAG schedule (persistent pivot chain + persistent bulk kernel); 4: persistent panel
                                     # kernel per 256 columns + one trailing update per outer panel; 1: one launch per piece (set 1
                                     # when several processes share the GPU: 4 and 5 keep waiting workgroups resident)
+    multi_rhs_min::Int = 4          # Matrix right-hand sides with this many columns or more are solved blocked on the matrix
+                                    # cores (static-pivot factor; statistic solve_path = 5); 0: never, one solve per column
     bk_fallback::Bool = true        # BUNCHKAUFMAN: refactor with 1x1/2x2 Bunch-Kaufman pivoting when the static-pivot
                                     # LDL^T breaks down (false: report the breakdown as num_zero, the IPM regularizes)
 end
@@ -160,6 +162,7 @@ function HipLinearSolver(A::MT; opt = HipSolverOptions(), logger = MadNLPLogger(
     set_option!(h[], "persistent_solve", opt.persistent_solve)
     set_option!(h[], "single_rows", opt.single_rows)
     set_option!(h[], "panel_algo", opt.panel_algo)
+    set_option!(h[], "multi_rhs_min", opt.multi_rhs_min)
     set_option!(h[], "bk_fallback", opt.bk_fallback)
     M = HipLinearSolver{Float64, MT}(A, h[], ctx, n, Ref{Cint}(0), opt, logger)
     finalizer(M) do m
@@ -260,6 +263,15 @@ function MadNLP.solve_linear_system!(M::HipLinearSolver, x::Vector{Float64})
                M.handle, x, 1, length(x), MNK_HOST)
     check(rc, SolveException)
     return x
+end
+# Matrix right-hand sides in ONE call: from `multi_rhs_min` columns on the library solves them blocked (one pass over the factor per
+# 64 columns and sweep), below that it loops over the columns itself -- either way without the reference's per-column fallback
+# (src/LinearSolvers/linearsolvers.jl:102-110), which would cross the bus once per column.
+function MadNLP.solve_linear_system!(M::HipLinearSolver, X::Matrix{Float64})
+    rc = ccall((:mnk_ls_solve, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64, Int64, Cint),
+               M.handle, X, size(X, 2), stride(X, 2), MNK_HOST)
+    check(rc, SolveException)
+    return X
 end
 
 """

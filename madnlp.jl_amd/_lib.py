@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of another commit's build of the same ABI (tools/leaf_ab.py, tools/README.md); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_plan.hip", "schur_plan.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip"]
 HEADERS = ["common.h", "ls.h", "dag_plan.h", "factor_plan.h", "solve_plan.h", "schur_plan.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "ipm_handle.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
@@ -257,6 +257,7 @@ SIGNATURES = {
     "mnk_debug_probe_schedule": (C.c_int, [C.c_int64, C.c_int, _vp, _vp]),
     "mnk_debug_factor_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64] + [C.c_int] * 4 + [_vp, C.c_int, _vp]),
     "mnk_debug_solve_plan": (C.c_int, [C.c_int64] + [C.c_int] * 11 + [_vp]),
+    "mnk_debug_solve_plan_multi": (C.c_int, [C.c_int64] + [C.c_int] * 10 + [C.c_int64, C.c_int64, _vp]),
     "mnk_debug_solve_batch_groups": (C.c_int, [C.c_int] + [_vp] * 8),
     "mnk_debug_schur_assembly_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp,
                                                 C.c_int64, _vp, C.c_int64, _vp, C.c_int, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int64,

@@ -308,6 +308,8 @@ struct SolveState {
     mnk::DevBuf<double> linv512, linv512t, linv512tmp;
     mnk::DevBuf<unsigned long long> trace;  // diagnostics: 8 time stamps per 64-row block (option solve_trace)
     int last_path = mnk::SOLVE_NONE;        // statistic "solve_path": how this solver's last solve ran (solve_plan.h: SolvePath), noted where the path is chosen
+    int64_t multi_rhs_min = 4;              // option: solves of this many right-hand sides or more run blocked (SOLVE_BLOCKED, solve_multi.hip); 0: never.  Default: the smallest count from which the blocked path beat the column loop at N = 2048 and N = 11 192 (profiles/solve_multi_ab.json)
+    int last_rhs_chunks = 0;                // statistic "solve_rhs_chunks": passes over the factor per sweep of the last blocked solve
     int create();                            // the pinned abort word
     void destroy();
     int* abort_word() const { return abort; }   // what the solve kernels raise (the host reads it without a sync)
@@ -336,6 +338,7 @@ struct mnk_ls {
     int64_t single_rows = 2560;  // systems up to this (padded) order are factored as ONE outer panel on the whole chip (with the fused tail panels the look-ahead schedule wins from N = 3072 on: 2.12 vs 2.34 ms at 4096)
     mnk::DevBuf<int> tile_ctr;  // one work-queue counter per outer step
     mnk::DevBuf<double> fact, wbuf[2], linv, dblk, inv16, linv256, linv256t, dvec, dinv, xwork;
+    mnk::DevBuf<double> xmulti;   // the blocked solve's two working blocks and its staging block (solve_multi.hip), allocated by the first blocked solve
     SpareFill spare;   // the second factor buffer of sparse sources and its background zero-fill
     int epoch = 0;    // value the hand-off flags of the current factorization carry
     mnk::DevBuf<int> flag_p;
@@ -423,6 +426,9 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls);   // dag.hip: the task-DAG schedul
 int mnk_ls_dag_prepare(mnk_ls* ls);             // dag.hip: its buffers (0: ready; otherwise the device cannot hold them -> schedule 4)
 int mnk_launch_pchain(mnk_ls* ls, hipStream_t sp, const mnk::PpDag& dag, int js_begin, int js_end, unsigned strips);  // factor.hip
 int mnk_ls_run_solve(mnk_ls* ls, double* xdev /* the solver's work vector */, double* xuser = nullptr /* N entries on the device, or NULL: xdev holds the padded rhs */);
+mnk::SolveShape mnk_ls_solve_shape(const mnk_ls* ls);   // solve.hip: what the planner reads of a solver (solve_plan.h)
+mnk::SolveMultiPlan mnk_ls_plan_multi(const mnk_ls* ls, int64_t nrhs);   // solve_multi.hip: solve_plan_multi for this solver and its option multi_rhs_min
+int mnk_ls_run_solve_multi(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc, const mnk::SolveMultiPlan& mp);   // solve_multi.hip: the blocked solve (mp.path == SOLVE_BLOCKED)
 int mnk_ls_build_inverses(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);  // 256x256 triangles of the strip-columns [sc0, sc1)
 int mnk_ls_invert_blocks(mnk_ls* ls, hipStream_t s, int64_t sc0, int64_t sc1);   // 64x64 blocks + 256x256 triangles
 // Right-side triangular solve of `nrows` free-standing rows (multiple of 16) against the factored diagonal block that

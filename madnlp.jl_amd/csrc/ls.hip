@@ -710,6 +710,11 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     }
     if (!strcmp(key, "solve512")) { ls->solves.solve512 = value != 0; return 0; }   // 512-column steps of the one-launch solve
     if (!strcmp(key, "linv_mfma")) { ls->solves.linv_mfma = value != 0.0; return 0; }
+    if (!strcmp(key, "multi_rhs_min")) {   // solves of this many right-hand sides or more run blocked on the matrix cores (static-pivot tier); 0: never
+        MNK_REQUIRE(value >= 0.0, "multi_rhs_min must be 0 (never) or a positive count of right-hand sides");
+        ls->solves.multi_rhs_min = (int64_t)value;
+        return 0;
+    }
     if (!strcmp(key, "prefill")) { ls->spare.prefill = value != 0; return 0; }   // background zero-fill into a second factor buffer
     if (!strcmp(key, "single_rows")) {  // systems up to this order: one outer panel, no look-ahead (0: never)
         ls->single_rows = (int64_t)value;
@@ -1275,6 +1280,9 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
                   "again (persistent_solve is now off for this solver)");
         return -3;
     }
+    // from option multi_rhs_min right-hand sides on, a static-pivot factor solves them blocked (never queued in a solve batch)
+    const mnk::SolveMultiPlan mp = mnk_ls_plan_multi(ls, nrhs);
+    if (mp.path == mnk::SOLVE_BLOCKED) return mnk_ls_run_solve_multi(ls, x, nrhs, ldx, loc, mp);
     hipStream_t s = ls->ctx->stream;
     const int64_t N = ls->N, Np = ls->Np;
     double* w = ls->xwork.p;
@@ -1401,6 +1409,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "panel_algo")) { *value = ls->algo_now; return 0; }
     if (!strcmp(key, "pp_fallbacks")) { *value = ls->pp.fallbacks; return 0; }
     if (!strcmp(key, "solve_path")) { *value = ls->solves.last_path; return 0; }   // how the last solve ran (solve_plan.h: SolvePath; 0: none yet)
+    if (!strcmp(key, "solve_rhs_chunks")) { *value = ls->solves.last_rhs_chunks; return 0; }   // passes over the factor per sweep of the last blocked solve (solve_path 5; 0: none yet)
     // which bounded device-side wait expired last (info = -7): 1 bulk task / operand rows, 2 bulk task / chunk order, 4 chain strip / diagonal block, 5 chain strip / bulk kernel's rows or band tiles; 0: none
     if (!strcmp(key, "timeout_site")) { *value = ls->pp.last_site; return 0; }
     if (!strcmp(key, "probe_hits")) { *value = (double)ls->probe.hits; return 0; }       // matrices rejected by the leading-block probe alone

@@ -1050,7 +1050,7 @@ bool SolveState::take_abort() {
 }
 
 // what the planner reads of a solver (solve_plan.h)
-static SolveShape solve_shape(const mnk_ls* ls) {
+SolveShape mnk_ls_solve_shape(const mnk_ls* ls) {
     return SolveShape{ls->Np, ls->ctx->num_cu, ls->verdict.is_pivoted(), ls->solves.persistent_solve != 0, ls->solves.solve512 != 0,
                       ls->solves.linv512.p != nullptr, ls->ctx->partitioned, ls->solves.abort_raised(), ls->solves.debug_ps_missing >= 0,
                       ls->solves.trace.p != nullptr, ls->algo == MNK_LDL};
@@ -1110,7 +1110,7 @@ static int solve_one_launch(mnk_ls* ls, const SolvePlan& plan, bool ldl, double*
 int mnk_ls_run_solve(mnk_ls* ls, double* xdev, double* xuser) {
     hipStream_t s = ls->ctx->stream;
     const int64_t Np = ls->Np, ld = ls->ld, N = ls->N;
-    const SolveShape shape = solve_shape(ls);
+    const SolveShape shape = mnk_ls_solve_shape(ls);
     const SolvePlan plan = solve_plan_single(shape);
     ls->solves.last_path = plan.path;
     const bool ldl = shape.ldl;
@@ -1195,7 +1195,7 @@ SolveBatchBuffers g_sbatch[64];
 }  // namespace
 
 bool mnk_solve_defer(mnk_ls* ls, double* xuser) {
-    if (!t_sbatch.active || !solve_batchable(solve_shape(ls))) return false;
+    if (!t_sbatch.active || !solve_batchable(mnk_ls_solve_shape(ls))) return false;
     if (!ls->ev_defer && hipEventCreateWithFlags(&ls->ev_defer, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipEventRecord(ls->ev_defer, ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
     t_sbatch.pend.push_back({ls, xuser});

@@ -1,14 +1,16 @@
-// The planner of solve!: which of its four ways a solve runs, the grid of a one-launch solve, whether a solver gets the 512-row
+// The planner of solve!: which of its five ways a solve runs, the grid of a one-launch solve, whether a solver gets the 512-row
 // inverses, and how the queued solves of a batch are grouped into launches.  Host only and plain C++ -- no HIP header, no runtime
 // call, no kernel -- so the unit (solve_plan.hip) also compiles with a host compiler and runs under its sanitizers
 // (tools/solve_plan_check.cpp), and a CPU test checks the rules (tests/test_solve_plan_cpu.py).  The executor that fills a
 // SolveShape from a solver and launches what the plan says is in solve.hip (mnk_ls_run_solve, solve_batch_flush).
 //
-// The four ways (the statistic "solve_path" of mnk_ls_get_stat reports the one a solver's last solve took):
+// The five ways (the statistic "solve_path" of mnk_ls_get_stat reports the one a solver's last solve took):
 //   SOLVE_STEPWISE         one launch per 256-column step; always possible, and the only way for a pivoted (Bunch-Kaufman) factor
 //   SOLVE_ONE_LAUNCH_256   both sweeps in one launch, 64-row blocks, 256-column steps
 //   SOLVE_ONE_LAUNCH_512   ... 32-row blocks, 512-column steps (option solve512, needs the 512-row inverses)
 //   SOLVE_MERGED           a system of a merged launch of a solve batch (the 256-column body, G workgroups per system)
+//   SOLVE_BLOCKED          several right-hand sides at once, a chunk of SP_MULTI_W of them per pass over the factor (solve_multi.hip;
+//                          static-pivot tier, from option multi_rhs_min right-hand sides on: solve_plan_multi)
 //
 // THE RESIDENCY AND OWNERSHIP RULE of the one-launch solves (solve_grid): the blocks of the right-hand side are owned round-robin
 // by G = min(blocks, CUs available) workgroups, which wait for each other and so must all be resident (G <= CUs, one per CU);
@@ -29,9 +31,12 @@ constexpr int SP_BATCH_MAXQ = 32;                  // systems of a merged launch
 constexpr int SP_BATCH_LARGE_Q = 4;                // ... of large systems: four side by side share the chip's bandwidth best (see solve_batch_groups)
 constexpr int64_t SOLVE512_MIN_ROWS = 4096;        // smaller systems never get the 512-row inverses
 
-enum SolvePath : int32_t { SOLVE_NONE = 0, SOLVE_STEPWISE = 1, SOLVE_ONE_LAUNCH_256 = 2, SOLVE_ONE_LAUNCH_512 = 3, SOLVE_MERGED = 4 };
+constexpr int SP_MULTI_W = 64;                     // blocked solve: right-hand sides per pass over the factor (four MFMA tiles of 16)
+constexpr int SP_MULTI_TILE = 16;                  // ... the last chunk is padded to a multiple of this (the MFMA tile edge)
 
-// What the rules read of a solver, and nothing else (solve.hip: solve_shape fills it).
+enum SolvePath : int32_t { SOLVE_NONE = 0, SOLVE_STEPWISE = 1, SOLVE_ONE_LAUNCH_256 = 2, SOLVE_ONE_LAUNCH_512 = 3, SOLVE_MERGED = 4, SOLVE_BLOCKED = 5 };
+
+// What the rules read of a solver, and nothing else (solve.hip: mnk_ls_solve_shape fills it).
 struct SolveShape {
     int64_t Np;            // padded order (a multiple of 64)
     int num_cu;            // CUs of the solver's context
@@ -52,6 +57,12 @@ struct SolvePlan { int32_t path, G; };   // SolvePath and, for a one-launch path
 int solve_grid(int64_t blocks, int cus, int nbs);
 // How one solve of this solver runs outside a merged launch.
 SolvePlan solve_plan_single(const SolveShape& s);
+// How a solve of `nrhs` right-hand sides runs.  SOLVE_BLOCKED exactly when the factor is not pivoted, multi_rhs_min > 0 and
+// nrhs >= multi_rhs_min: then W = SP_MULTI_W, `chunks` passes over the factor per sweep and `last_padded` = the width of the last
+// chunk's working block (a multiple of SP_MULTI_TILE).  Otherwise the column loop: path and G are solve_plan_single's for every
+// column, W = chunks = last_padded = 0.  (Nothing else of the shape matters: the blocked solve waits for no workgroup.)
+struct SolveMultiPlan { int32_t path, G, W, chunks, last_padded; };
+SolveMultiPlan solve_plan_multi(const SolveShape& s, int64_t nrhs, int64_t multi_rhs_min);
 // A solver of this order gets the 512-row inverses (with option solve512): from SOLVE512_MIN_ROWS rows on, and not where the last
 // 512-row triangle would end in a partial 256-row block (Np % 512 == 384: inv512_gemm_kernel multiplies whole 256-row blocks).
 bool solve512_wanted(int64_t Np);

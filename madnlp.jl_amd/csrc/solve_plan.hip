@@ -23,6 +23,15 @@ SolvePlan solve_plan_single(const SolveShape& s) {
     return G5 != 0 ? SolvePlan{SOLVE_ONE_LAUNCH_512, G5} : SolvePlan{SOLVE_ONE_LAUNCH_256, G};
 }
 
+SolveMultiPlan solve_plan_multi(const SolveShape& s, int64_t nrhs, int64_t multi_rhs_min) {
+    if (s.pivoted || multi_rhs_min <= 0 || nrhs < multi_rhs_min) {
+        const SolvePlan p = solve_plan_single(s);
+        return {p.path, p.G, 0, 0, 0};
+    }
+    const int64_t chunks = (nrhs + SP_MULTI_W - 1) / SP_MULTI_W, last = nrhs - (chunks - 1) * SP_MULTI_W;
+    return {SOLVE_BLOCKED, 0, SP_MULTI_W, (int32_t)chunks, (int32_t)((last + SP_MULTI_TILE - 1) / SP_MULTI_TILE * SP_MULTI_TILE)};
+}
+
 bool solve_batchable(const SolveShape& s) {
     // (only the 256-column body has a multi-system kernel: a solver with the 512-row inverses keeps to launches of its own, whether
     // or not its own plan would take the 512-column path)
@@ -78,6 +87,21 @@ extern "C" int mnk_debug_solve_plan(int64_t Np, int num_cu, int pivoted, int per
     out[2] = mnk::solve_batchable(s) ? 1 : 0;
     out[3] = mnk::solve512_wanted(Np) ? 1 : 0;
     out[4] = mnk::solve_inverses_batchable(linv_mfma != 0, solve512_opt != 0) ? 1 : 0;
+    return 0;
+}
+
+extern "C" int mnk_debug_solve_plan_multi(int64_t Np, int num_cu, int pivoted, int persistent_opt, int solve512_opt, int have_linv512,
+                                          int partitioned, int abort_raised, int debug_missing, int tracing, int ldl, int64_t nrhs,
+                                          int64_t multi_rhs_min, int* out) {
+    if (Np <= 0 || Np % 64 != 0 || num_cu <= 0 || nrhs < 1 || nrhs > (int64_t)1 << 40 || out == nullptr) return -1;
+    const mnk::SolveShape s{Np, num_cu, pivoted != 0, persistent_opt != 0, solve512_opt != 0, have_linv512 != 0, partitioned != 0,
+                            abort_raised != 0, debug_missing != 0, tracing != 0, ldl != 0};
+    const mnk::SolveMultiPlan p = mnk::solve_plan_multi(s, nrhs, multi_rhs_min);
+    out[0] = p.path;
+    out[1] = p.W;
+    out[2] = p.chunks;
+    out[3] = p.last_padded;
+    out[4] = p.G;
     return 0;
 }
 

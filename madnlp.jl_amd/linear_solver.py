@@ -167,6 +167,8 @@ class HipSolverOptions:
     panel_algo: int = 5      # 5: task-DAG schedule (persistent pivot chain + persistent bulk kernel); 4: persistent panel
                              # kernel per 256 columns + one trailing update per outer panel; 1: one launch per piece.
                              # 4 and 5 keep waiting workgroups resident: set 1 when several PROCESSES share the GPU
+    multi_rhs_min: int = 4   # matrix right-hand sides with this many columns or more are solved blocked on the matrix cores
+                             # (CHOLESKY / LDL, static-pivot factor; `solve_path` 5); 0: never, always one solve per column
 
 
 class HipLinearSolver:
@@ -197,7 +199,8 @@ class HipLinearSolver:
         settings = [("pivot_tol", self.opt.pivot_tol), ("outer_block", self.opt.outer_block),
                     ("lookahead", float(self.opt.lookahead)), ("share", float(self.opt.share)),
                     ("small_tiles", float(self.opt.small_tiles)), ("persistent_solve", float(self.opt.persistent_solve)),
-                    ("single_rows", float(self.opt.single_rows)), ("panel_algo", float(self.opt.panel_algo))]
+                    ("single_rows", float(self.opt.single_rows)), ("panel_algo", float(self.opt.panel_algo)),
+                    ("multi_rhs_min", float(self.opt.multi_rhs_min))]
         for key, val in settings:
             L.check(L.lib().mnk_ls_set_option(self._h, key.encode(), float(val)), "mnk_ls_set_option")
         self.info = 0

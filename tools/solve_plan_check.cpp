@@ -5,7 +5,8 @@
 //       madnlp.jl_amd/csrc/solve_plan.hip tools/solve_plan_check.cpp -o /tmp/solve_plan_check && /tmp/solve_plan_check
 //
 // Runs the grids of tests/test_solve_plan_cpu.py -- every single plan (orders x CUs x every combination of the flags) through
-// solve_plan_single / solve_batchable and through the host-only entry mnk_debug_solve_plan, and a few thousand random queues (up to 40
+// solve_plan_single / solve_batchable and through the host-only entry mnk_debug_solve_plan, the rule of the blocked solve for several
+// right-hand sides (solve_plan_multi / mnk_debug_solve_plan_multi) over counts and thresholds, and a few thousand random queues (up to 40
 // requests of up to 8 solvers on 2 devices; a generator of its own, not the test's) through solve_batch_groups and
 // mnk_debug_solve_batch_groups -- checks what the kernels need of every plan and every launch, that the entries return what the
 // planner built and write nothing behind their arrays, and prints the counts and one FNV-1a hash over everything planned, to compare
@@ -60,6 +61,24 @@ int main() {
                 CHECK(out[0] == p.path && out[1] == p.G && out[2] == (batchable ? 1 : 0) && out[3] == (solve512_wanted(Np) ? 1 : 0));
                 CHECK(out[4] == (solve_inverses_batchable(bit(0), bit(2)) ? 1 : 0) && out[5] == -77);
                 mix(p.path); mix(p.G); mix(out[2]); mix(out[3]);
+                // several right-hand sides: blocked exactly when not pivoted, multi_rhs_min > 0 and nrhs >= multi_rhs_min; the chunks
+                // cover nrhs, the last one padded to the MFMA tile; otherwise every column as planned above
+                if (bits % 8 <= 1)   // (only `pivoted` of the flags may matter: both values, one in four of the other combinations)
+                    for (int64_t nrhs : {1, 3, 4, 15, 16, 17, 63, 64, 65, 130, 1000})
+                        for (int64_t mn : {0, 2, 4, 16, 64, 65}) {
+                            const SolveMultiPlan m = solve_plan_multi(s, nrhs, mn);
+                            const bool blocked = !s.pivoted && mn > 0 && nrhs >= mn;
+                            CHECK((m.path == SOLVE_BLOCKED) == blocked);
+                            if (blocked) {
+                                const int64_t last = nrhs - (int64_t)(m.chunks - 1) * m.W;
+                                CHECK(m.W == SP_MULTI_W && m.G == 0 && m.chunks >= 1 && last >= 1 && last <= m.W);
+                                CHECK(m.last_padded >= last && m.last_padded - last < SP_MULTI_TILE && m.last_padded % SP_MULTI_TILE == 0 && m.last_padded <= m.W);
+                            } else CHECK(m.path == p.path && m.G == p.G && m.W == 0 && m.chunks == 0 && m.last_padded == 0);
+                            int om[6] = {-77, -77, -77, -77, -77, -77};
+                            CHECK(mnk_debug_solve_plan_multi(Np, cu, bit(0), bit(1), bit(2), bit(3), bit(4), bit(5), bit(6), bit(7), bit(8), nrhs, mn, om) == 0);
+                            CHECK(om[0] == m.path && om[1] == m.W && om[2] == m.chunks && om[3] == m.last_padded && om[4] == m.G && om[5] == -77);
+                            mix(m.path); mix(m.chunks); mix(m.last_padded);
+                        }
                 ++nplans;
             }
 
@@ -120,6 +139,8 @@ int main() {
     int out[5];
     CHECK(mnk_debug_solve_plan(100, 256, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1, out) == -1);
     CHECK(mnk_debug_solve_plan(512, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1, out) == -1);
+    CHECK(mnk_debug_solve_plan_multi(512, 256, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 4, out) == -1);
+    CHECK(mnk_debug_solve_plan_multi(500, 256, 0, 1, 0, 0, 0, 0, 0, 0, 0, 8, 4, out) == -1);
     CHECK(mnk_debug_solve_batch_groups(-1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == -1);
     std::printf("solve_plan_check: %ld plans, %ld queues, %ld launches, hash %016llx, all checks passed\n", nplans, nqueues, nlaunches,
                 (unsigned long long)g_hash);
