@@ -691,6 +691,17 @@ int mnk_ls_debug_dag_state(mnk_ls* ls, int* flags, int64_t nflags, int* chain, i
  * arithmetic (no device needed); the task-DAG schedule sizes its bulk kernel with it: 672 beside the 16-CU chain of a 256-CU
  * part, not 3 x 240 (workgroups placed in mid-kernel were the schedule's rare time-out). */
 int mnk_debug_grid_at_launch(int cu_first, int num_cu, int first, int per_cu);
+/* Which CU-mask bits the two streams of a CU-masked pair get on a device of `num_cu` CUs (csrc/stream_plan.hip; host only, no device
+ * is opened).  kind: 0 the task-DAG schedule's pivot chain | bulk kernel, 1 its deep band, 2 the second chain partition | bulk
+ * stream of batches, 3 the chains of a round of small systems (arg = their CUs) | the rest, 4 the look-ahead pair of the
+ * launch-per-panel schedules (arg = the panel stream's CUs; negative: the default); dag_cus / dag_cus2 = the chain CUs of kinds 0
+ * and 1.  split = {chain_first, chain_count, rest_first, rest_count}; chain_mask / rest_mask receive the (num_cu + 31) / 32 mask
+ * words of the two streams.  Returns 1, 0 where no such pair is made (split and masks are zero then), -1 on bad arguments. */
+int mnk_debug_stream_split(int kind, int num_cu, int dag_cus, int dag_cus2, int arg, int* split, int32_t* chain_mask, int32_t* rest_mask);
+/* Rounds of a batch of small factorizations of `strips` 64-row strips each (host only): out[0] = the CUs the bulk kernel keeps at
+ * least (0 without bulk tasks), out[1] = the systems of a round at most (< 2: no round), out[2] = the CUs of the chains' partition
+ * for a round of k systems.  Returns 0, -1 on bad arguments. */
+int mnk_debug_small_rounds(int strips, int num_cu, int has_bulk, int k, int* out);
 /* Diagnostics (bench.py `clocks`): the shader clock the chip sustains under fp64 MFMA load right now, MHz (s_memtime against the
  * 100 MHz s_memrealtime over the second of two ~2.5 ms launches of MFMAs on every CU, on the context's stream). */
 int mnk_debug_shader_clock(mnk_ctx* ctx, double* mhz);

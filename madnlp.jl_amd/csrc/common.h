@@ -76,13 +76,13 @@ struct DynLdsAttr {
 // runtime is synchronizing -- seen with four host threads driving four solvers (a solver freed on one thread, a chain
 // waiting 2.5 s for its bulk kernel on another: info = -7, schedule 1).  Frees issued by code outside this library
 // (another allocator in the process) are outside this lock: INTEGRATION.md section 0.
-std::recursive_mutex& launch_mutex();   // ls.hip
+std::recursive_mutex& launch_mutex();   // ctx.hip
 // Called with the lock held, in front of a runtime call that waits for the device to go idle (hipFree, hipHostFree, stream
 // destruction): waits until the last persistent operation of this process has completed.  The lock only keeps such a call
 // from falling BETWEEN the launches of a group; a group that is launched but not yet fully RUNNING is just as exposed --
 // stress runs with six host threads still lost a factorization to a 2.6 s stall (a chain strip waiting for a bulk kernel
 // that had been launched, at the moment another thread destroyed its solver) until frees also waited for the groups in flight.
-void quiesce_persistent();              // ls.hip
+void quiesce_persistent();              // ctx.hip
 struct LaunchLock {
     LaunchLock() { launch_mutex().lock(); }
     ~LaunchLock() { launch_mutex().unlock(); }
@@ -187,37 +187,26 @@ struct mnk_ctx {
     // look-ahead of the factorization: panel stream (high priority), update stream, fork/join events
     hipStream_t sp = nullptr, su = nullptr;
     int panel_cus = 0;  // > 0: sp is restricted to this many CUs and su to the others (CU masks)
-    // task-DAG schedule (dag.hip): the pivot chain needs only a few CUs, the persistent bulk kernel gets all the others
-    hipStream_t sp_dag = nullptr, su_dag = nullptr;
-    hipStream_t sp_dagB = nullptr, su_dagB = nullptr;   // batches (dag_batch.hip): a second chain partition (the next dag_cus mask bits) and a bulk stream on the CUs outside both
-    bool shared_dag_streams = false;   // the four task-DAG streams belong to the device's shared set (ls.hip), not to this context
-    int dag_cus = 0;    // > 0: sp_dag is restricted to this many CUs and su_dag to the others
-    // ... and a third pair for its second phase, where every remaining row is in the chain's band (one CU per 64 rows)
-    hipStream_t sp_dag2 = nullptr, su_dag2 = nullptr;
-    int dag_cus2 = 0;
+    // task-DAG schedule (dag.hip): chain CUs of the device's shared pairs PAIR_DAG and PAIR_DEEP (stream_plan.h; 0: no such pair).
+    // The streams themselves belong to the per-device owner in ctx.hip: mnk_ctx_stream_pair at the point of use.
+    int dag_cus = 0, dag_cus2 = 0;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    hipStream_t s_fill = nullptr;   // background zero-fill of the spare factor buffer (SpareFill, ls.h), created on first use
+    hipStream_t s_fill = nullptr;   // background zero-fill of the spare factor buffer (mnk_ctx_fill_stream), created on first use
     std::vector<hipEvent_t> ev_panel, ev_next, ev_next2, ev_bdone;
-    int num_cu = 256;   // CUs this context may use (the whole device, or its partition)
-    int cu_first = 0;   // first CU-mask bit of the partition
-    int total_cu = 256; // CUs of the device
-    bool partitioned = false;
-    void* persist_slot = nullptr;   // partitioned contexts: their own arbiter slot (ls.hip: mnk_persist_begin)
+    int num_cu = 256;   // CUs of the device
     // Handles created on this context (solvers, KKT systems).  Garbage-collected hosts (Julia) run finalizers
     // in no particular order: destroying a context that still has children only marks it released, and the
     // last child to go frees it (mnk_ctx_child_gone).
     int children = 0;
     bool released = false;
 };
-int mnk_masked_stream_pair(mnk_ctx* ctx, int chain_cus, hipStream_t* sp, hipStream_t* su);   // ls.hip
-// CU-masked streams that are made when a caller first needs them (every one is a hardware queue of the device): ls.hip
+// CU-masked streams are made when a caller first needs them (every one is a hardware queue of the device): ctx.hip
+int mnk_ctx_stream_pair(mnk_ctx* ctx, int kind, int arg, hipStream_t* sp, hipStream_t* su);   // a shared pair (StreamPairKind, stream_plan.h); *sp == nullptr: none
 int mnk_ctx_ensure_panel_streams(mnk_ctx* ctx);   // ctx->sp / su: look-ahead streams of the launch-per-panel schedules
-int mnk_ctx_ensure_dag(mnk_ctx* ctx);             // ctx->sp_dag / su_dag again after mnk_release_idle_streams took them
-int mnk_ctx_ensure_dag2(mnk_ctx* ctx);            // ctx->sp_dag2 / su_dag2: deep-band pair of the task-DAG schedule
-int mnk_ctx_ensure_batch_streams(mnk_ctx* ctx);   // ctx->sp_dagB / su_dagB: second chain partition + bulk stream of batches
+hipStream_t mnk_ctx_fill_stream(mnk_ctx* ctx);    // ctx->s_fill
 int mnk_solve_warmup(hipStream_t s);               // solve.hip: first (no-op) launch of the inverse kernel that needs scratch
-int mnk_ctx_bulk_wgs(const mnk_ctx* ctx, int first, int per_cu);   // ls.hip: workgroups the mask {CUs first.. of the context} holds AT ONCE
 int mnk_dag_warmup(hipStream_t* streams, int n, int nwg);   // dag.hip: first (empty) launch of the bulk kernels on these streams
+void mnk_batch_stream_gone(int device, hipStream_t s);      // dag_batch.hip: no per-device event of the batches stays behind on this stream
 int mnk_live_contexts(int device);  // contexts alive on this device in this process
 // Device arbiter of the PERSISTENT kernels (task-DAG schedule, persistent panel launches, one-launch solve): their waiting
 // workgroups stay resident, so two of them from different contexts must never share the chip (each could hold CUs the
@@ -225,8 +214,7 @@ int mnk_live_contexts(int device);  // contexts alive on this device in this pro
 // the previous persistent operation of ANY context of this process on the device, `end` records its own completion --
 // the operations run back to back at full speed, in the order they were enqueued, whatever stream they come from
 // (reference behaviour: distinct solver instances are driven concurrently, src/KKT/Schur/schur.jl:953).  `begin` returns
-// with the arbiter's mutex held; `end` releases it (enqueue order = execution order).  Contexts confined to a CU
-// partition arbitrate among themselves only.
+// with the arbiter's mutex held; `end` releases it (enqueue order = execution order).
 int mnk_persist_begin(mnk_ctx* ctx, hipStream_t s);
 int mnk_persist_end(mnk_ctx* ctx, hipStream_t s, int rc);   // returns rc (or the error of its own event record)
 void mnk_ctx_child_added(mnk_ctx* ctx);

@@ -856,7 +856,7 @@ using namespace mnk;
 // resident that could wait for them.  Without it the first real factorization of a process launches a pivot chain that
 // spins for a bulk kernel the runtime is still setting up -- normally microseconds, but seen to exceed the bound of the
 // device-side waits (info = -7, schedule 1 for the next 16 factorizations: round 3 met it in 2 of ~150 bench processes, this
-// round in 1 of 8 runs of tools/dag_time.py).  Called once per device when its task-DAG streams are created (ls.hip).
+// round in 1 of 8 runs of tools/dag_time.py).  Called once per device when its task-DAG streams are created (ctx.hip).
 int mnk_dag_warmup(hipStream_t* streams, int n, int nwg) {
     static mnk::DevBuf<int> ctr;   // (process lifetime)
     if (!ctr.p) {
@@ -903,15 +903,6 @@ long mnk_ls_dag_spin_limit(const mnk_ls* ls) {
     // whole redo plus 16 / 64 / 256 factorizations on the slow schedule -- the floor is the old 1 s there
     const double floor_polls = mnk_live_contexts(ls->ctx->device) > 1 ? 5880000.0 : 588000.0;
     return (long)std::min(16777216.0, std::max(floor_polls, polls));
-}
-
-// XCDs that have a CU among the CUs [first, num_cu) of the context (mask bit b is a CU of XCD b % 8: ls.hip)
-static int bulk_xcds(const mnk_ctx* c, int first) {
-    bool has[8] = {false, false, false, false, false, false, false, false};
-    for (int b = std::max(first, 0); b < c->num_cu; ++b) has[(c->cu_first + b) % 8] = true;
-    int n = 0;
-    for (bool x : has) n += x ? 1 : 0;
-    return n;
 }
 
 // ---- DagPlan (ls.h): the sizes of its device words ----
@@ -992,7 +983,7 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         const int part[3] = {0, h.n1, h.size()}, chain_cus[2] = {ctx->dag_cus, ctx->dag_cus2};
         bool may_queue[2];
         for (int ph = 0; ph < 2; ++ph)
-            may_queue[ph] = queues && part[ph + 1] - part[ph] >= mnk_ctx_bulk_wgs(ctx, chain_cus[ph], 3) && bulk_xcds(ctx, chain_cus[ph]) == mnk::DAG_NQ;
+            may_queue[ph] = queues && part[ph + 1] - part[ph] >= mnk::grid_at_launch(0, ctx->num_cu, chain_cus[ph], 3) && mnk::bulk_xcds(0, ctx->num_cu, chain_cus[ph]) == mnk::DAG_NQ;
         const mnk::DagDealtList dev_list = mnk::dag_deal_list(h, mnk::DAG_NQ, ls->dag_gang, may_queue);
         std::vector<int> qoff(32, 0);   // (16 per phase)
         for (int ph = 0; ph < 2; ++ph) {
@@ -1063,10 +1054,11 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         // no difference: 4 / 5 / 6 per CU 9.63-9.67 vs 9.64-9.68 ms)
         const int ph = (int)(counter - qctr), nq = ls->plan.nq[ph];
         // (per-XCD queues: every queue needs workgroups of its own XCD -- the grid the list was dealt for, see mnk_ls_dag_prepare)
-        MNK_REQUIRE(nq == 0 || (ntask >= mnk_ctx_bulk_wgs(ctx, chain_cus, 3) && bulk_xcds(ctx, chain_cus) == nq),
+        const int bulk_wgs = mnk::grid_at_launch(0, ctx->num_cu, chain_cus, 3);
+        MNK_REQUIRE(nq == 0 || (ntask >= bulk_wgs && mnk::bulk_xcds(0, ctx->num_cu, chain_cus) == nq),
                     "task-DAG schedule: the bulk grid does not cover the XCDs the task list was dealt for");
         rc = mnk::launch_dag_bulk_single(su, ldl, inst, ls->plan.tasks.p + 4 * (size_t)task0, ntask, ntile, counter, spin_limit,
-                                  std::min(ntask, mnk_ctx_bulk_wgs(ctx, chain_cus, 3)), trace ? trace + 8 * (size_t)task0 : nullptr,
+                                  std::min(ntask, bulk_wgs), trace ? trace + 8 * (size_t)task0 : nullptr,
                                   trace ? trace + (size_t)ntasks * 8 + 4096 * 8 + (task0 > 0 ? 512 * 8 : 0) : nullptr,
                                   ls->plan.qoff.p + 16 * ph, ls->plan.qheads.p + ph * mnk::DAG_QHEAD_WORDS, nq);
         if (rc) return rc;
@@ -1095,16 +1087,21 @@ int mnk_ls_run_factorization_dag(mnk_ls* ls) {
         MNK_HIP(hipStreamWaitEvent(s, ctx->ev_b, 0));
         return 0;
     };
+    // (the pairs are there: mnk_ls_run_factorization asked for them when it settled on this schedule)
+    hipStream_t sp = nullptr, su = nullptr;
     if (js2 > 0) {
-        int rc = phase(ctx->sp_dag, ctx->su_dag, ctx->dag_cus, 0, ntasks1, qctr, 0, std::min(js2, nsc),
-                       (unsigned)std::min<int64_t>(ls->dag_band, Np / NBI));
+        int rc = mnk_ctx_stream_pair(ctx, mnk::PAIR_DAG, 0, &sp, &su);
+        if (rc) return rc;
+        MNK_REQUIRE(sp != nullptr, "task-DAG schedule: the chain and bulk streams are missing");
+        rc = phase(sp, su, ctx->dag_cus, 0, ntasks1, qctr, 0, std::min(js2, nsc), (unsigned)std::min<int64_t>(ls->dag_band, Np / NBI));
         if (rc) return rc;
     }
     if (js2 < nsc) {
         const int64_t rows2 = Np - 256 * (int64_t)js2;
-        MNK_REQUIRE(ctx->sp_dag2 != nullptr, "task-DAG schedule: the deep-band streams are missing");   // (mnk_ls_run_factorization made them)
-        int rc = phase(ctx->sp_dag2, ctx->su_dag2, ctx->dag_cus2, ntasks1, ntasks - ntasks1,
-                       qctr + 1, js2, nsc, (unsigned)(rows2 / NBI));
+        int rc = mnk_ctx_stream_pair(ctx, mnk::PAIR_DEEP, 0, &sp, &su);
+        if (rc) return rc;
+        MNK_REQUIRE(sp != nullptr, "task-DAG schedule: the deep-band streams are missing");
+        rc = phase(sp, su, ctx->dag_cus2, ntasks1, ntasks - ntasks1, qctr + 1, js2, nsc, (unsigned)(rows2 / NBI));
         if (rc) return rc;
     }
     return 0;

@@ -28,7 +28,8 @@ struct BatchBuffers {   // per device, reused from batch to batch (guarded by th
     mnk::DevBuf<char> insts, pcsys, aux;
     char* stage = nullptr;        // pinned host memory: the records of one batch (instances | chain table | small-system records)
     size_t stage_bytes = 0;
-    hipEvent_t stage_ev = nullptr;   // recorded behind the last upload from `stage`
+    hipEvent_t stage_ev = nullptr;   // recorded behind the last upload from `stage` ...
+    hipStream_t stage_on = nullptr;  // ... on this stream, which it must not outlive (mnk_batch_stream_gone)
     int ntile = 0, ninst = 0, period = 0, ntasks = 0;   // what `tasks` was merged for: ntile, the instances, their shift ...
     DagPlan::Key key;                                   // ... and the plan of the group's first solver
     bool holds(int ntile_, int ninst_, int period_, const DagPlan::Key& k) const {
@@ -60,14 +61,26 @@ BatchBuffers g_batch[64];
 
 bool mnk_batch_active() { return t_batch.active; }
 
+// ctx.hip calls this (launch mutex held) before it gives up a context's stream: the per-device staging event must not outlive the
+// stream it was recorded on -- in a process whose contexts come and go hipEventSynchronize(stage_ev) answered "operation not permitted
+// when stream is capturing" (nothing captures here; supposedly the destroyed stream behind the event) in every later round.
+void mnk_batch_stream_gone(int device, hipStream_t s) {
+    BatchBuffers& B = g_batch[device & 63];
+    if (B.stage_ev == nullptr || B.stage_on != s) return;
+    (void)hipEventSynchronize(B.stage_ev);
+    (void)hipEventDestroy(B.stage_ev);
+    B.stage_ev = nullptr;
+}
+
 bool mnk_batch_defer(mnk_ls* ls) {
     if (!t_batch.active) return false;
     const int nsc = (int)((ls->Np + 255) / 256);
     // (two merged launches: the large-system mode of the schedule -- band + bulk + two alternating chains -- and the small
     // one, every row in the chain's band, many chains side by side; a second phase in mid-factorization is simply run now)
-    if (ls->algo_now != 5 || (ls->plan.key.js2 != nsc && ls->plan.key.js2 != 0) || ls->dag_trace_on || ls->ctx->partitioned) return false;
-    if (mnk_ctx_ensure_batch_streams(ls->ctx) != 0) (void)hipGetLastError();   // (made with the first batch of a process)
-    if (!ls->ctx->sp_dagB) return false;
+    if (ls->algo_now != 5 || (ls->plan.key.js2 != nsc && ls->plan.key.js2 != 0) || ls->dag_trace_on) return false;
+    hipStream_t spB = nullptr, suB = nullptr;
+    if (mnk_ctx_stream_pair(ls->ctx, mnk::PAIR_BATCH, 0, &spB, &suB) != 0) (void)hipGetLastError();   // (made with the first batch of a process)
+    if (!spB) return false;
     if (!ls->ev_defer && hipEventCreateWithFlags(&ls->ev_defer, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipEventRecord(ls->ev_defer, ls->ctx->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
     ls->deferred = true;
@@ -117,13 +130,18 @@ static int batch_run_group(std::vector<mnk_ls*>& g) {
             mnk::dag_reset_member(h, ls, hin.back(), insts_dev + (hin.size() - 1));
         }
         MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
-        hipStream_t sp[2] = {c0->sp_dag, c0->sp_dagB}, su = c0->su_dagB;
+        // two chain partitions (the chain stream of PAIR_DAG, whose bulk stream idles here, and PAIR_BATCH's) and the bulk stream outside both
+        hipStream_t sp[2] = {nullptr, nullptr}, su_dag = nullptr, su = nullptr;
+        r = mnk_ctx_stream_pair(c0, mnk::PAIR_DAG, 0, &sp[0], &su_dag);
+        if (!r) r = mnk_ctx_stream_pair(c0, mnk::PAIR_BATCH, 0, &sp[1], &su);
+        if (r) return r;
+        MNK_REQUIRE(sp[0] && sp[1], "factorize batch: the chain and bulk streams are missing");   // (mnk_batch_defer saw them)
         MNK_HIP(hipEventRecord(B.ev[0], h));
         MNK_HIP(hipStreamWaitEvent(sp[0], B.ev[0], 0));
         MNK_HIP(hipStreamWaitEvent(sp[1], B.ev[0], 0));
         MNK_HIP(hipStreamWaitEvent(su, B.ev[0], 0));
         const unsigned strips = (unsigned)std::min<int64_t>(l0->dag_band, Np / NBI);
-        const int bulk_wgs = mnk_ctx_bulk_wgs(c0, 2 * c0->dag_cus, 3);   // (the grid that is resident at launch: see ls.hip)
+        const int bulk_wgs = mnk::grid_at_launch(0, c0->num_cu, 2 * c0->dag_cus, 3);   // (the grid that is resident at launch: stream_plan.hip)
         // Launch order: the first two chains, THEN the bulk kernel, then everything else -- the host needs ~3 ms for the
         // 4 x ninst launches of the chains' streams (measured: the bulk kernel used to start 3 ms after the first chain,
         // 2 % of a 16-instance step).  Per chain stream: chain i, its inverses for the solves and its inertia / info words
@@ -180,17 +198,8 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
     const bool ldl = l0->algo == MNK_LDL;
     const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256), strips = (int)(Np / NBI);
     const int ntasks1 = l0->plan.list.size();   // (single phase: all tasks)
-    const int bulk_min = ntasks1 > 0 ? std::max(32, c0->num_cu / 4) : 0;
-    // The chains' CU partition is a multiple of 32 CUs: every workgroup of the chain launch must be RESIDENT (one per CU), and
-    // the dispatcher places them all only when the mask gives every shader engine of every XCD the same number of CUs --
-    // 8 XCDs x 4 SEs = 32 (tools/hip/mask_resident.hip: masks of 32 / 64 / 96 / 192 / 256 bits hold as many 96-KB workgroups
-    // as they have bits; 40, 48, 56, 72, 104, 176 do not, e.g. 34 workgroups on a 40-bit mask: 32 resident -- five 34-strip
-    // systems on 176 CUs stalled into the schedule's time-out).
-    // (... and of 64, so that a process ends up with three such stream pairs at most: every masked stream is a hardware queue,
-    // and the device runs only so many of them side by side -- ls.hip, ctx_create_common)
-    auto chain_cus_for = [&](int k) { return std::min(c0->num_cu, (k * strips + 63) / 64 * 64); };
-    int kmax = std::min(32, (c0->num_cu - bulk_min) / strips);
-    while (kmax > 1 && chain_cus_for(kmax) > c0->num_cu - bulk_min) --kmax;
+    // (chain partitions of a round and the most systems it takes beside the bulk kernel's CUs: stream_plan.hip)
+    const int kmax = mnk::small_rounds(strips, c0->num_cu, ntasks1 > 0).kmax;
     if (kmax < 2) {   // (no room for two chains: one after the other, as without a batch)
         for (mnk_ls* ls : g) {
             ls->deferred = false;
@@ -205,8 +214,10 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
     for (size_t r0 = 0; r0 < g.size(); r0 += (size_t)kmax) {
         const int k = (int)std::min<size_t>(kmax, g.size() - r0);
         hipStream_t sp = nullptr, su = nullptr;
-        int rc = mnk_masked_stream_pair(c0, chain_cus_for(k), &sp, &su);
+        const int chain_cus = mnk::small_chain_cus(k, strips, c0->num_cu);
+        int rc = mnk_ctx_stream_pair(c0, mnk::PAIR_SMALL, chain_cus, &sp, &su);
         if (rc) return rc;
+        MNK_REQUIRE(sp != nullptr, "factorize batch: bad size of the chains' CU partition");
         if (ntasks1 > 0 && su == nullptr) { set_error("factorize batch: no CUs left for the bulk kernel"); return -1; }
         rc = mnk_persist_begin(c0, h);
         if (rc) return rc;
@@ -248,6 +259,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             MNK_HIP(hipMemcpyAsync(B.pcsys.p, st_pc, (size_t)k * pc_bytes, hipMemcpyHostToDevice, h));
             MNK_HIP(hipMemcpyAsync(B.aux.p, st_aux, (size_t)k * sizeof(mnk::SmallSysRec), hipMemcpyHostToDevice, h));
             MNK_HIP(hipEventRecord(B.stage_ev, h));
+            B.stage_on = h;
             const mnk::SmallSysRec* aux_dev = reinterpret_cast<const mnk::SmallSysRec*>(B.aux.p);
             mnk::dag_reset_round(h, Np, aux_dev, k);
             MNK_HIP(hipMemsetAsync(B.qctr.p, 0, 4 * sizeof(int), h));
@@ -258,7 +270,7 @@ static int batch_run_group_small(std::vector<mnk_ls*>& g) {
             r = mnk_launch_pchain_multi(g.data() + r0, k, sp, B.pcsys.p);
             if (r) return r;
             if (ntasks1 > 0) {
-                const int bulk_wgs = mnk_ctx_bulk_wgs(c0, chain_cus_for(k), 3);
+                const int bulk_wgs = mnk::grid_at_launch(0, c0->num_cu, chain_cus, 3);
                 r = mnk::launch_dag_bulk_merged(su, ldl, insts_dev, B.tasks.p, B.ntasks, ntile, B.qctr.p, mnk_ls_dag_spin_limit(l0),
                                                 std::min(B.ntasks, bulk_wgs));
                 if (r) return r;

@@ -1156,14 +1156,15 @@ static int choose_schedule(mnk_ls* ls) {
     // (inside an open batch small systems take the task-DAG schedule too: their pivot chains run side by side, dag_batch.hip)
     const int64_t min_rows = mnk_batch_active() ? std::min<int64_t>(ls->dag_min_rows, 256) : ls->dag_min_rows;
     if (algo == 5 && (ctx->dag_cus < ls->dag_band || !ls->lookahead || Np < min_rows || Np > ls->dag_max_rows)) algo = 4;
-    if (algo == 5 && ctx->sp_dag == nullptr && mnk_ctx_ensure_dag(ctx) != 0) { (void)hipGetLastError(); algo = 4; }   // (released while idle)
-    if (algo == 5 && ctx->sp_dag == nullptr) algo = 4;
+    hipStream_t sp = nullptr, su = nullptr;
+    if (algo == 5 && mnk_ctx_stream_pair(ctx, PAIR_DAG, 0, &sp, &su) != 0) (void)hipGetLastError();   // (made again here after a release while idle)
+    if (algo == 5 && sp == nullptr) algo = 4;
     if (ls->pp.blocked_now() && algo >= 4) return 1;
     // the task-DAG schedule's buffers (task list, progress words, V = L D): a device that cannot hold them keeps schedule 4
     if (algo == 5 && mnk_ls_dag_prepare(ls) != 0) algo = 4;
     if (algo == 5 && ls->plan.key.js2 < (Np + 255) / 256) {   // (the deep-band stream pair: made with the first such factorization)
-        if (mnk_ctx_ensure_dag2(ctx) != 0) (void)hipGetLastError();
-        if (ctx->sp_dag2 == nullptr) algo = 4;
+        if (mnk_ctx_stream_pair(ctx, PAIR_DEEP, 0, &sp, &su) != 0) (void)hipGetLastError();
+        if (sp == nullptr) algo = 4;
     }
     return algo;
 }

@@ -10,6 +10,7 @@
 #include "dag_plan.h"
 #include "factor_plan.h"
 #include "solve_plan.h"
+#include "stream_plan.h"
 
 struct mnk_sc {
     mnk_ctx* ctx = nullptr;

@@ -4,8 +4,6 @@
 // solve entry points.  See include/madnlp_hip.h for the per-function citations.
 #include <cstdarg>
 #include <cstdlib>
-#include <atomic>
-#include <map>
 #include <mutex>
 
 #include <cfloat>
@@ -116,474 +114,10 @@ __global__ __launch_bounds__(256) void copy_lower_kernel(double* __restrict__ F,
 
 using namespace mnk;
 
-static std::mutex g_ctx_mutex;
-static std::atomic<int> g_live_ctx[64];
-static std::vector<mnk_ctx*> g_ctx_list[64];   // live whole-device contexts per device (g_ctx_mutex): mnk_release_idle_streams
-
-int mnk_live_contexts(int device) { return g_live_ctx[device & 63].load(std::memory_order_relaxed); }
-
-std::recursive_mutex& mnk::launch_mutex() {
-    static std::recursive_mutex m;
-    return m;
-}
-
-// ---- device arbiter of the persistent kernels (common.h) ----
-namespace {
-struct PersistSlot {   // (guarded by mnk::launch_mutex(): recursive -- a factorization that is redone inside mnk_ls_fetch_info re-enters on the same thread)
-    hipEvent_t last = nullptr;
-    bool recorded = false;
-};
-PersistSlot g_persist[64];
-PersistSlot& persist_slot_of(mnk_ctx* ctx) {
-    if (!ctx->partitioned) return g_persist[ctx->device & 63];
-    if (ctx->persist_slot == nullptr) ctx->persist_slot = new PersistSlot();   // (created before the context is shared between threads: mnk_ctx_create_partition)
-    return *static_cast<PersistSlot*>(ctx->persist_slot);
-}
-}  // namespace
-
-void mnk::quiesce_persistent() {
-    int cur = 0;
-    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-    for (int d = 0; d < 64; ++d) {
-        PersistSlot& ps = g_persist[d];
-        if (ps.last == nullptr || !ps.recorded) continue;
-        (void)hipSetDevice(d);
-        (void)hipEventSynchronize(ps.last);
-    }
-    if (have_cur) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
-
-int mnk_persist_begin(mnk_ctx* ctx, hipStream_t s) {
-    PersistSlot& ps = persist_slot_of(ctx);
-    mnk::launch_mutex().lock();
-    if (ps.last == nullptr && hipEventCreateWithFlags(&ps.last, hipEventDisableTiming) != hipSuccess) {
-        ps.last = nullptr;
-        mnk::launch_mutex().unlock();
-        mnk::set_error("mnk_persist_begin: hipEventCreate failed");
-        return -2;
-    }
-    if (ps.recorded && hipStreamWaitEvent(s, ps.last, 0) != hipSuccess) {
-        mnk::launch_mutex().unlock();
-        mnk::set_error("mnk_persist_begin: hipStreamWaitEvent failed");
-        return -2;
-    }
-    return 0;
-}
-
-int mnk_persist_end(mnk_ctx* ctx, hipStream_t s, int rc) {
-    PersistSlot& ps = persist_slot_of(ctx);
-    if (hipEventRecord(ps.last, s) == hipSuccess) ps.recorded = true;
-    else if (rc == 0) { mnk::set_error("mnk_persist_end: hipEventRecord failed"); rc = -2; }
-    mnk::launch_mutex().unlock();
-    return rc;
-}
-
-// ---- CU-masked streams the whole-device contexts of a process share per device ----
-namespace {
-struct DagStreams { hipStream_t sp = nullptr, su = nullptr, sp2 = nullptr, su2 = nullptr, spB = nullptr, suB = nullptr; int cus = 0; bool made = false; };
-DagStreams g_dag_streams[64];
-struct MaskedPair { hipStream_t sp = nullptr, su = nullptr; };
-std::map<std::pair<int, int>, MaskedPair> g_pair_cache;   // (device, chain CUs) -> pair (mnk_masked_stream_pair)
-}  // namespace
-
-// Destroys the masked streams of `device` that are shared between contexts -- the deep-band, batch and small-batch pairs, the
-// look-ahead pairs of the live contexts, and with `primary` the task-DAG schedule's first pair as well -- and forgets them in
-// every live context: each is made again by the first operation that needs it (mnk_ctx_ensure_*).  Why: every CU-masked stream
-// is a hardware queue, the device runs only so many of them side by side -- ALL PROCESSES TOGETHER -- and a process that
-// merely holds a dozen idle ones was seen to keep ANOTHER process' pivot chain and bulk kernel from being scheduled together
-// (tools/parent_child_probe.py).  Caller holds the launch mutex; nothing persistent is in flight.
-static void release_shared_streams_locked(int device, bool primary) {
-    mnk::quiesce_persistent();
-    (void)hipSetDevice(device);
-    std::lock_guard<std::mutex> lk(g_ctx_mutex);
-    DagStreams& d = g_dag_streams[device & 63];
-    auto kill = [](hipStream_t& st) { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; } };
-    kill(d.sp2); kill(d.su2); kill(d.spB); kill(d.suB);
-    if (primary) { kill(d.sp); kill(d.su); d.made = false; d.cus = 0; }
-    for (auto it = g_pair_cache.begin(); it != g_pair_cache.end();) {
-        if (it->first.first == device) { kill(it->second.sp); kill(it->second.su); it = g_pair_cache.erase(it); }
-        else ++it;
-    }
-    for (mnk_ctx* c : g_ctx_list[device & 63]) {
-        if (!c->shared_dag_streams) continue;
-        c->sp_dag2 = c->su_dag2 = c->sp_dagB = c->su_dagB = nullptr;
-        if (primary) c->sp_dag = c->su_dag = nullptr;
-        kill(c->sp); kill(c->su);
-    }
-    (void)hipGetLastError();
-}
-
-static void ctx_free(mnk_ctx* c) {
-    mnk::LaunchLock lock;   // (stream / event destruction may synchronize)
-    mnk::quiesce_persistent();
-    (void)hipSetDevice(c->device);
-    const int live_left = g_live_ctx[c->device & 63].fetch_sub(1, std::memory_order_relaxed) - 1;
-    {
-        std::lock_guard<std::mutex> lk(g_ctx_mutex);
-        auto& v = g_ctx_list[c->device & 63];
-        v.erase(std::remove(v.begin(), v.end(), c), v.end());
-    }
-    // the last context of a device: the process keeps no CU-masked stream (= hardware queue) of that device behind
-    if (live_left <= 0 && !c->partitioned) release_shared_streams_locked(c->device, true);
-    if (c->ev_a) (void)hipEventDestroy(c->ev_a);
-    if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-    for (hipEvent_t e : c->ev_panel) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_next) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_next2) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_bdone) (void)hipEventDestroy(e);
-    if (c->sp) (void)hipStreamDestroy(c->sp);
-    if (c->su) (void)hipStreamDestroy(c->su);
-    if (!c->shared_dag_streams) {   // (the per-device set of the whole-device contexts lives as long as the process)
-        if (c->sp_dag) (void)hipStreamDestroy(c->sp_dag);
-        if (c->su_dag) (void)hipStreamDestroy(c->su_dag);
-        if (c->sp_dag2) (void)hipStreamDestroy(c->sp_dag2);
-        if (c->su_dag2) (void)hipStreamDestroy(c->su_dag2);
-        if (c->sp_dagB) (void)hipStreamDestroy(c->sp_dagB);
-        if (c->su_dagB) (void)hipStreamDestroy(c->su_dagB);
-    }
-    if (c->s_fill) (void)hipStreamDestroy(c->s_fill);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->persist_slot) {
-        PersistSlot* ps = static_cast<PersistSlot*>(c->persist_slot);
-        if (ps->last) (void)hipEventDestroy(ps->last);
-        delete ps;
-    }
-    delete c;
-}
-
-void mnk_ctx_child_added(mnk_ctx* ctx) {
-    if (!ctx) return;
-    std::lock_guard<std::mutex> lock(g_ctx_mutex);
-    ++ctx->children;
-}
-
-void mnk_ctx_child_gone(mnk_ctx* ctx) {
-    if (!ctx) return;
-    bool free_now = false;
-    {
-        std::lock_guard<std::mutex> lock(g_ctx_mutex);
-        --ctx->children;
-        free_now = ctx->released && ctx->children <= 0;
-    }
-    if (free_now) ctx_free(ctx);
-}
-
 extern "C" {
 
 int mnk_version(void) { return MNK_VERSION; }
 const char* mnk_last_error_string(void) { return g_err.c_str(); }
-
-// A stream restricted to the listed CU-mask bits (bit b is CU b/8 of XCD b%8 on this part).
-static bool make_masked_stream(int num_cu_total, const int* bits, int count, hipStream_t& out) {
-    const int words = (num_cu_total + 31) / 32;
-    std::vector<uint32_t> m(words, 0u);
-    for (int i = 0; i < count; ++i)
-        if (bits[i] >= 0 && bits[i] < num_cu_total) m[bits[i] / 32] |= 1u << (bits[i] % 32);
-    if (hipExtStreamCreateWithCUMask(&out, (uint32_t)words, m.data()) == hipSuccess) return true;
-    (void)hipGetLastError();
-    out = nullptr;
-    return false;
-}
-
-}  // extern "C"
-// The CU-masked stream pairs of the task-DAG schedule that whole-device contexts share per device (process lifetime).  Only
-// the first pair (pivot chain | bulk kernel) is made with the first context; the others when a caller first needs them --
-// every masked stream is a hardware queue (see ctx_create_common).
-namespace {
-std::vector<int> ctx_bits(const mnk_ctx* c) {
-    std::vector<int> bits;
-    for (int b = 0; b < c->num_cu; ++b) bits.push_back(c->cu_first + b);
-    return bits;
-}
-}  // namespace
-
-// Size of a persistent grid on the CUs [first, num_cu) of the context (`per_cu` workgroups fit on a CU): the number of
-// workgroups the hardware places AT LAUNCH.  The dispatcher deals the workgroups of a grid out evenly -- XCD by XCD, and
-// inside an XCD shader engine by shader engine (mask bit b is CU b / 8 of XCD b % 8, shader engine (b / 8) % 4) -- whatever
-// the mask left of an engine, so the engine with the fewest CUs bounds what is resident at once: 16 chain CUs take one CU
-// from engines 0 and 1 of every XCD, which then hold 7 x 3 = 21 workgroups each, and of a grid of 3 x 240 = 720 exactly
-// 32 x 21 = 672 start (seen in round 4 with a build whose bulk workgroups recorded their CU -- removed, record in
-// profiles/r04_stall_captures.md: 21 / 21 / 22 / 21-22 workgroups per engine, 35 CUs of engines 2 and 3 holding two).  The others are placed LATER, in mid-kernel, when the hardware finds room -- and a workgroup
-// placed in mid-kernel is what the one-in-~3000 time-out of the task-DAG schedule was: in both captured
-// events 6 resp. 12 workgroups with block ids 672..686 had all just been started, within 0.2 ms of each other, took a task
-// each, and then did nothing for the ~965 ms until the time-out sent the others home -- at which point each ran its whole
-// task at the usual 13 us per tile column.  Tasks they held were ones the pivot chain needed.  (They were never in a wait of
-// their own, and polling with a back-off changed nothing.  Why the hardware stalls them is not known; a persistent grid
-// simply must not exceed what is co-resident at launch.)  Those workgroups did 0.9 % of the tasks.
-extern "C" int mnk_debug_grid_at_launch(int cu_first, int num_cu, int first, int per_cu) {
-    int per_engine[32] = {0};
-    for (int b = std::max(first, 0); b < num_cu; ++b) {
-        const int bit = cu_first + b;
-        ++per_engine[(bit % 8) * 4 + (bit / 8) % 4];
-    }
-    int engines = 0, least = INT_MAX;
-    for (int e = 0; e < 32; ++e)
-        if (per_engine[e] > 0) { ++engines; least = std::min(least, per_engine[e]); }
-    return engines > 0 ? per_cu * least * engines : per_cu;
-}
-int mnk_ctx_bulk_wgs(const mnk_ctx* c, int first, int per_cu) { return mnk_debug_grid_at_launch(c->cu_first, c->num_cu, first, per_cu); }
-
-// the deep-band pair (every row of a small system in the chain's band: dag_cus2 chain CUs | the others)
-int mnk_ctx_ensure_dag2(mnk_ctx* c) {
-    if (c->sp_dag2 != nullptr || c->dag_cus2 <= 0 || !c->shared_dag_streams) return 0;
-    mnk::LaunchLock lock;   // (stream creation may synchronize the device)
-    std::lock_guard<std::mutex> lk(g_ctx_mutex);
-    DagStreams& d = g_dag_streams[c->device & 63];
-    if (d.sp2 == nullptr) {
-        mnk::quiesce_persistent();
-        MNK_HIP(hipSetDevice(c->device));
-        const std::vector<int> bits = ctx_bits(c);
-        if (!(make_masked_stream(c->total_cu, bits.data(), c->dag_cus2, d.sp2) &&
-              make_masked_stream(c->total_cu, bits.data() + c->dag_cus2, c->num_cu - c->dag_cus2, d.su2))) {
-            if (d.sp2) (void)hipStreamDestroy(d.sp2);
-            d.sp2 = d.su2 = nullptr;
-            return -2;
-        }
-        hipStream_t warm[1] = {d.su2};
-        if (mnk_dag_warmup(warm, 1, 3 * c->num_cu) != 0) (void)hipGetLastError();
-        if (mnk_solve_warmup(d.su2) != 0) (void)hipGetLastError();
-    }
-    c->sp_dag2 = d.sp2; c->su_dag2 = d.su2;
-    return 0;
-}
-
-// batches of independent factorizations: a second chain partition and a bulk stream on the CUs outside both
-int mnk_ctx_ensure_batch_streams(mnk_ctx* c) {
-    if (c->sp_dagB != nullptr || c->dag_cus <= 0 || !c->shared_dag_streams || 2 * c->dag_cus + 32 > c->num_cu) return 0;
-    mnk::LaunchLock lock;
-    std::lock_guard<std::mutex> lk(g_ctx_mutex);
-    DagStreams& d = g_dag_streams[c->device & 63];
-    if (d.spB == nullptr) {
-        mnk::quiesce_persistent();
-        MNK_HIP(hipSetDevice(c->device));
-        const std::vector<int> bits = ctx_bits(c);
-        if (!(make_masked_stream(c->total_cu, bits.data() + c->dag_cus, c->dag_cus, d.spB) &&
-              make_masked_stream(c->total_cu, bits.data() + 2 * c->dag_cus, c->num_cu - 2 * c->dag_cus, d.suB))) {
-            if (d.spB) (void)hipStreamDestroy(d.spB);
-            d.spB = d.suB = nullptr;
-            return -2;
-        }
-        hipStream_t warm[1] = {d.suB};
-        if (mnk_dag_warmup(warm, 1, 3 * c->num_cu) != 0) (void)hipGetLastError();
-        for (hipStream_t w : {d.suB, d.spB})
-            if (mnk_solve_warmup(w) != 0) (void)hipGetLastError();
-    }
-    c->sp_dagB = d.spB; c->su_dagB = d.suB;
-    return 0;
-}
-
-// the task-DAG schedule's first pair (pivot chain | bulk kernel) after mnk_release_idle_streams has taken it away
-int mnk_ctx_ensure_dag(mnk_ctx* c) {
-    if (c->sp_dag != nullptr || c->dag_cus <= 0 || !c->shared_dag_streams) return 0;
-    mnk::LaunchLock lock;
-    std::lock_guard<std::mutex> lk(g_ctx_mutex);
-    DagStreams& d = g_dag_streams[c->device & 63];
-    if (d.sp == nullptr) {
-        mnk::quiesce_persistent();
-        MNK_HIP(hipSetDevice(c->device));
-        const std::vector<int> bits = ctx_bits(c);
-        if (!(make_masked_stream(c->total_cu, bits.data(), c->dag_cus, d.sp) &&
-              make_masked_stream(c->total_cu, bits.data() + c->dag_cus, c->num_cu - c->dag_cus, d.su))) {
-            if (d.sp) (void)hipStreamDestroy(d.sp);
-            d.sp = d.su = nullptr;
-            return -2;
-        }
-        d.cus = c->dag_cus; d.made = true;
-        hipStream_t warm[1] = {d.su};
-        if (mnk_dag_warmup(warm, 1, 3 * c->num_cu) != 0) (void)hipGetLastError();
-        for (hipStream_t w : {d.su, d.sp})
-            if (mnk_solve_warmup(w) != 0) (void)hipGetLastError();
-    }
-    c->sp_dag = d.sp; c->su_dag = d.su;
-    return 0;
-}
-
-extern "C" int mnk_release_idle_streams(int device) {
-    MNK_REQUIRE(device >= 0 && device < 64, "mnk_release_idle_streams: bad device");
-    mnk::LaunchLock lock;   // (no persistent group is being launched; the ones in flight are waited for)
-    release_shared_streams_locked(device, true);
-    return 0;
-}
-
-// the look-ahead streams of the launch-per-panel schedules (1, 4): a quarter of the CUs for the panel stream, the rest for the
-// update stream (measured, profiles/; MNK_PANEL_CUS overrides); stream priorities where masks are not to be had
-int mnk_ctx_ensure_panel_streams(mnk_ctx* c) {
-    if (c->sp != nullptr) return 0;
-    mnk::LaunchLock lock;
-    mnk::quiesce_persistent();
-    MNK_HIP(hipSetDevice(c->device));
-    const std::vector<int> bits = ctx_bits(c);
-    auto make_pair = [&](int want) -> bool {
-        if (want <= 0 || want >= c->num_cu) return false;
-        if (make_masked_stream(c->total_cu, bits.data(), want, c->sp) &&
-            make_masked_stream(c->total_cu, bits.data() + want, c->num_cu - want, c->su))
-            return true;
-        if (c->sp) { (void)hipStreamDestroy(c->sp); c->sp = nullptr; }
-        c->su = nullptr;
-        return false;
-    };
-    if (const char* e = getenv("MNK_PANEL_CUS")) {
-        const int want = atoi(e);
-        if (make_pair(want)) c->panel_cus = want;
-    } else if (c->num_cu >= 16) {
-        const int q4 = std::max(4, c->num_cu / 4);
-        if (make_pair(q4)) c->panel_cus = q4;
-    }
-    if (!c->sp) {
-        int prio_lo = 0, prio_hi = 0;  // numerically lower = higher priority
-        MNK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        MNK_HIP(hipStreamCreateWithPriority(&c->sp, hipStreamNonBlocking, prio_hi));
-        MNK_HIP(hipStreamCreateWithPriority(&c->su, hipStreamNonBlocking, prio_lo));
-    }
-    return 0;
-}
-
-extern "C" {
-// `part_first/part_count` confine the context to a contiguous range of CU-mask bits.  Kept for experiments
-// only (no public entry point): partitions run MFMA-bound kernels side by side at full rate, but the
-// latency-bound panel chain of one instance slows ~2x next to the updates of the others -- every partition
-// has CUs on every XCD and shares all L2s, and masks that differ between XCDs are not honoured
-// (tools/cumask_probe.hip, tools/partition_probe.py) -- so 16 instances per GPU run faster time-sharing the
-// whole chip (bench.py --batch) than on 2/4/8 partitions (72 vs 58/45/26 it/s).
-static int ctx_create_common(int device, void* stream, int part_first, int part_count, mnk_ctx** out) {
-    MNK_REQUIRE(out != nullptr, "mnk_ctx_create: out is NULL");
-    mnk::LaunchLock lock;   // (stream / event creation: not between two launches of another thread's persistent group)
-    int ndev = 0;
-    MNK_HIP(hipGetDeviceCount(&ndev));
-    MNK_REQUIRE(device >= 0 && device < ndev, "mnk_ctx_create: no such device");
-    MNK_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    MNK_HIP(hipGetDeviceProperties(&prop, device));
-    const int total = prop.multiProcessorCount;
-    const bool part = part_count > 0;
-    if (part)
-        MNK_REQUIRE(part_first >= 0 && part_count >= 16 && part_first + part_count <= total && stream == nullptr,
-                    "mnk_ctx_create_partition: need 16 <= cu_count, the range inside the device, and a library-owned stream");
-    mnk_ctx* c = new mnk_ctx();
-    c->device = device;
-    c->cu_first = part ? part_first : 0;
-    c->partitioned = part;
-    c->total_cu = total;
-    c->num_cu = part ? part_count : total;
-    // The CU-mask bits this context owns: a contiguous range (bits are dealt round-robin over the XCDs, so every
-    // XCD contributes the same number of CUs).  Masks that differ between XCDs are not honoured by the runtime
-    // (tools/cumask_probe.hip: a strided mask runs on all 256 CUs), so partitions cannot be whole XCDs.
-    std::vector<int> bits;
-    for (int b = 0; b < c->num_cu; ++b) bits.push_back(c->cu_first + b);
-    if (stream) {
-        c->stream = (hipStream_t)stream;
-    } else if (part) {
-        if (!make_masked_stream(total, bits.data(), part_count, c->stream)) {
-            delete c;
-            set_error("mnk_ctx_create_partition: CU-masked streams are not available on this device");
-            return -2;
-        }
-        c->own_stream = true;
-    } else {
-        MNK_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        c->own_stream = true;
-    }
-    // (The look-ahead streams of the launch-per-panel schedules are created when such a schedule first runs:
-    // mnk_ctx_ensure_panel_streams.  Every CU-masked stream is a hardware queue of its own, and the hardware runs only so
-    // many queues of a device side by side -- all processes together: with four idle contexts in a PARENT process, each
-    // holding its masked pair, a child's chain and bulk kernels were no longer scheduled together and every run of
-    // tools/parent_child_probe.py lost factorizations to their bounded waits; without the pairs, none.)
-    auto make_pair = [&](int want, hipStream_t& sp, hipStream_t& su) -> bool {
-        if (want <= 0 || want >= c->num_cu) return false;
-        if (make_masked_stream(total, bits.data(), want, sp) &&
-            make_masked_stream(total, bits.data() + want, c->num_cu - want, su))
-            return true;
-        if (sp) { (void)hipStreamDestroy(sp); sp = nullptr; }
-        su = nullptr;
-        return false;
-    };
-    // second pair for the task-DAG schedule: a handful of CUs for the pivot chain (two per XCD), the rest for the bulk kernel.
-    // Whole-device contexts SHARE these four streams per device: the persistent operations of a process take turns on the
-    // device anyway (mnk_persist_begin), and every stream more is one more client of the runtime's few hardware queues -- two
-    // streams whose kernels must run side by side (chain and bulk) must not end up multiplexed behind a third one.
-    if (c->num_cu >= 64) {
-        DagStreams own;
-        std::lock_guard<std::mutex> lock(g_ctx_mutex);
-        DagStreams& d = part ? own : g_dag_streams[device & 63];
-        if (!d.made) {
-            const int want = getenv("MNK_DAG_CUS") ? atoi(getenv("MNK_DAG_CUS")) : 16;
-            if (make_pair(want, d.sp, d.su)) d.cus = want;
-            d.made = true;
-            hipStream_t warm[1] = {d.su};
-            if (mnk_dag_warmup(warm, 1, 3 * c->num_cu) != 0) (void)hipGetLastError();   // (best effort)
-            for (hipStream_t w : {d.su, d.sp})              // (where the inverses for the solves are launched)
-                if (w != nullptr && mnk_solve_warmup(w) != 0) (void)hipGetLastError();
-        }
-        if (!part) g_ctx_list[device & 63].push_back(c);
-        c->sp_dag = d.sp; c->su_dag = d.su; c->dag_cus = d.cus;
-        c->dag_cus2 = d.cus > 0 ? (getenv("MNK_DAG_CUS2") ? atoi(getenv("MNK_DAG_CUS2")) : 96) : 0;   // (its streams: mnk_ctx_ensure_dag2)
-        if (c->dag_cus2 <= 0 || c->dag_cus2 >= c->num_cu) c->dag_cus2 = 0;
-        c->shared_dag_streams = !part;
-        if (part) {   // (a partition's streams are its own: made now, destroyed with it)
-            if (c->dag_cus2 > 0 && !make_pair(c->dag_cus2, c->sp_dag2, c->su_dag2)) c->dag_cus2 = 0;
-        }
-    }
-    MNK_HIP(hipEventCreateWithFlags(&c->ev_a, hipEventDisableTiming));
-    MNK_HIP(hipEventCreateWithFlags(&c->ev_b, hipEventDisableTiming));
-    if (mnk_solve_warmup(c->stream) != 0) (void)hipGetLastError();   // (the context's own stream runs the last inverses of every factorization)
-    g_live_ctx[device & 63].fetch_add(1, std::memory_order_relaxed);
-    *out = c;
-    return 0;
-}
-
-int mnk_ctx_create(int device, void* stream, mnk_ctx** out) { return ctx_create_common(device, stream, 0, 0, out); }
-
-}  // extern "C"
-// A pair of CU-masked streams of the whole device: `sp` on the first `chain_cus` mask bits, `su` on all the others (nullptr
-// when none are left); cached per device and size until mnk_release_idle_streams / the device's last context goes (masked
-// streams are hardware queues).
-int mnk_masked_stream_pair(mnk_ctx* ctx, int chain_cus, hipStream_t* sp, hipStream_t* su) {
-    mnk::LaunchLock lock;
-    MNK_REQUIRE(!ctx->partitioned && chain_cus > 0 && chain_cus <= ctx->total_cu, "mnk_masked_stream_pair: bad size");
-    MaskedPair& p = g_pair_cache[{ctx->device, chain_cus}];
-    if (p.sp == nullptr) {
-        std::vector<int> bits;
-        for (int b = 0; b < ctx->total_cu; ++b) bits.push_back(b);
-        if (!make_masked_stream(ctx->total_cu, bits.data(), chain_cus, p.sp)) { set_error("mnk_masked_stream_pair: CU-masked streams are not available"); return -2; }
-        if (chain_cus < ctx->total_cu && !make_masked_stream(ctx->total_cu, bits.data() + chain_cus, ctx->total_cu - chain_cus, p.su)) {
-            (void)hipStreamDestroy(p.sp);
-            p.sp = nullptr;
-            set_error("mnk_masked_stream_pair: CU-masked streams are not available");
-            return -2;
-        }
-        if (p.su != nullptr) {   // (first launches of the kernels that need scratch: see mnk_dag_warmup)
-            hipStream_t w[1] = {p.su};
-            if (mnk_dag_warmup(w, 1, 3 * ctx->num_cu) != 0) (void)hipGetLastError();
-        }
-    }
-    *sp = p.sp;
-    *su = p.su;
-    return 0;
-}
-extern "C" {
-
-int mnk_ctx_destroy(mnk_ctx* c) {
-    if (!c) return 0;
-    {
-        std::lock_guard<std::mutex> lock(g_ctx_mutex);
-        if (c->children > 0) {  // a solver / KKT handle still points here: the last of them frees the context
-            c->released = true;
-            return 0;
-        }
-    }
-    ctx_free(c);
-    return 0;
-}
-
-
-int mnk_ctx_synchronize(mnk_ctx* c) {
-    MNK_REQUIRE(c != nullptr, "ctx is NULL");
-    MNK_HIP(mnk::stream_wait(c->stream));
-    return 0;
-}
-
-void* mnk_ctx_stream(mnk_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int mnk_ls_create(mnk_ctx* ctx, int64_t N, int algo, mnk_ls** out) {
     MNK_REQUIRE(ctx && out, "mnk_ls_create: NULL argument");
@@ -863,7 +397,7 @@ int SpareFill::acquire(mnk_ls* ls) {
     if (pre && !buf.p) {
         // second factor buffer, events, side stream; if any of it cannot be had the fill stays in line
         if (buf.alloc(ls->fact.n) != 0) { (void)hipGetLastError(); prefill = 0; pre = false; }
-        if (pre && !ctx->s_fill && hipStreamCreateWithFlags(&ctx->s_fill, hipStreamNonBlocking) != hipSuccess) { prefill = 0; pre = false; }
+        if (pre && mnk_ctx_fill_stream(ctx) == nullptr) { prefill = 0; pre = false; }
         if (pre && (hipEventCreateWithFlags(&ev_zeroed, hipEventDisableTiming) != hipSuccess ||
                     hipEventCreateWithFlags(&ev_free, hipEventDisableTiming) != hipSuccess)) { prefill = 0; pre = false; }
         if (pre) MNK_HIP(hipMemsetAsync(buf.p, 0, buf.n * sizeof(double), s));  // (slack behind the matrix)
@@ -1425,7 +959,7 @@ int mnk_ls_get_stat(mnk_ls* ls, const char* key, double* value) {
     if (!strcmp(key, "evd_sweeps")) { *value = ls->alt ? ls->alt->stat(key) : 0.0; return 0; }   // EVD: block Jacobi sweeps of the last factorization
     if (!strcmp(key, "bk_panel_multi")) { *value = ls->bk.multi_last() ? 1.0 : 0.0; return 0; }
     if (!strcmp(key, "bk_mw_fallbacks")) { *value = ls->bk.mw_fallbacks(); return 0; }
-    if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk_ctx_bulk_wgs(ls->ctx, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain
+    if (!strcmp(key, "dag_bulk_wgs")) { *value = ls->ctx->dag_cus > 0 ? mnk::grid_at_launch(0, ls->ctx->num_cu, ls->ctx->dag_cus, 3) : 0; return 0; }   // grid of the bulk kernel beside the 16-CU chain
     if (!strcmp(key, "dag_ntasks")) { *value = ls->plan.list.size(); return 0; }    // task-DAG schedule: bulk tasks, ...
     if (!strcmp(key, "dag_ntasks1")) { *value = ls->plan.list.n1; return 0; }  // ... of them in the first phase, ...
     if (!strcmp(key, "dag_js2")) { *value = ls->plan.key.js2; return 0; }          // ... first strip-column of the second phase

@@ -1052,7 +1052,7 @@ bool SolveState::take_abort() {
 // what the planner reads of a solver (solve_plan.h)
 SolveShape mnk_ls_solve_shape(const mnk_ls* ls) {
     return SolveShape{ls->Np, ls->ctx->num_cu, ls->verdict.is_pivoted(), ls->solves.persistent_solve != 0, ls->solves.solve512 != 0,
-                      ls->solves.linv512.p != nullptr, ls->ctx->partitioned, ls->solves.abort_raised(), ls->solves.debug_ps_missing >= 0,
+                      ls->solves.linv512.p != nullptr, false, ls->solves.abort_raised(), ls->solves.debug_ps_missing >= 0,
                       ls->solves.trace.p != nullptr, ls->algo == MNK_LDL};
 }
 

@@ -44,7 +44,7 @@ struct SolveShape {
     bool persistent_opt;   // option persistent_solve (off, too, once a one-launch solve of this solver gave up)
     bool solve512_opt;     // option solve512
     bool have_linv512;     // the 512-row inverses exist
-    bool partitioned;      // the context runs on a CU partition of the device
+    bool partitioned;      // the context runs on a CU partition of the device (no entry point creates such a context today: always false)
     bool abort_raised;     // a one-launch solve gave up and nobody has answered it yet
     bool debug_missing;    // option debug_ps_missing is set (tests)
     bool tracing;          // option solve_trace

@@ -131,7 +131,7 @@ def test_merged_queue_of_a_batch(ntile, chunk, band_tiles, js2, taper0, ninst, p
 
 
 def test_persistent_grids_are_sized_by_what_is_placed_at_launch():
-    """`mnk_debug_grid_at_launch` (host arithmetic behind the bulk kernel's grid, csrc/ls.hip): the dispatcher deals a grid out
+    """`mnk_debug_grid_at_launch` (host arithmetic behind the bulk kernel's grid, csrc/stream_plan.hip): the dispatcher deals a grid out
     evenly per (XCD, shader engine) -- mask bit b is XCD b % 8, engine (b / 8) % 4 -- so the engine with the fewest CUs under the
     mask bounds what starts at launch.  Workgroups placed later, in mid-kernel, were the rare time-out of the task-DAG schedule
     (DESIGN.md section 8 item -1)."""

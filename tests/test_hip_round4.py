@@ -456,8 +456,8 @@ def test_time_out_of_the_task_dag_schedule_with_a_sparse_source_is_redone_on_a_c
 @pytest.mark.gpu
 def test_every_workgroup_of_the_bulk_grid_is_resident_at_launch(ctx):
     """A persistent grid must not exceed what the hardware places at launch: workgroups the dispatcher starts in mid-kernel
-    were what the one-in-~3000 time-out of the task-DAG schedule came from (csrc/ls.hip
-    mnk_ctx_bulk_wgs).  With the 16-CU chain mask two shader engines of every XCD keep 7 of their 8 CUs, and the grid is
+    were what the one-in-~3000 time-out of the task-DAG schedule came from (csrc/stream_plan.hip
+    grid_at_launch).  With the 16-CU chain mask two shader engines of every XCD keep 7 of their 8 CUs, and the grid is
     3 x 7 x 32 = 672 -- not 3 x 240.  Checked on the device with the schedule's own per-workgroup statistics (option
     dag_trace): every workgroup of the grid takes its first task within 2 ms of the first one (the late ones of the old
     grid started 3.6 and 7 ms into the 9 ms kernel, or never), every one works, and no slot beyond the grid is used."""
