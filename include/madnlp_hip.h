@@ -403,9 +403,21 @@ int mnk_ipm_get_norms(mnk_ipm* ipm, const double* c, int64_t m, double* out /* [
 /* Batch mode: between mnk_ipm_batch_begin and mnk_ipm_batch_end the mnk_ipm_get_* calls (regular and restoration phase) only
  * enqueue their reductions and return at once; batch_end synchronizes ONCE and then stores every result into the `out` pointer
  * its call was given (the pointers must stay valid until then; a scalar that divides a result -- sd, sc -- can be passed as 1
- * and applied by the caller).  At most 32 reductions per batch (each call uses one to four). */
+ * and applied by the caller).  At most 32 reductions per batch (each call uses one to four, mnk_ipm_quality_function four
+ * per sigma). */
 int mnk_ipm_batch_begin(mnk_ipm* ipm);
 int mnk_ipm_batch_end(mnk_ipm* ipm);
+/* Quality function of the adaptive barrier update (reference src/IPM/barrier.jl:152-201) for nsigma = 1..4 centering parameters
+ * (sigmas: HOST array) along d = aff + sigma cen, which is never stored: aff_x / cen_x are the primal blocks (ntot) of the two
+ * KKT vectors, aff_zl / cen_zl their dual_lb blocks (nlb), aff_zu / cen_zu their dual_ub blocks (nub); x, xl, xu, zl, zu full
+ * length.  out (host, 4 nsigma doubles): per sigma a_pr = get_alpha_max(x, xl, xu, d_x, tau), a_du = get_alpha_z(zl_r, zu_r,
+ * d_zl, d_zu, tau), S_lb = sum ((x_lr + a_pr d_x_lr - xl_r) (zl_r + a_du d_zl))^2, S_ub = sum ((xu_r - x_ur - a_pr d_x_ur)
+ * (zu_r + a_du d_zu))^2.  A NaN step entry gives NaN step lengths.  Four launches per call; the sums read the step lengths on
+ * the device.  Follows the batch protocol (4 nsigma of a batch's 32 reductions); nsigma outside 1..4 or a NULL pointer is an error. */
+int mnk_ipm_quality_function(mnk_ipm* ipm, int nsigma, const double* sigmas, const double* x, const double* xl,
+                             const double* xu, const double* zl, const double* zu, const double* aff_x, const double* aff_zl,
+                             const double* aff_zu, const double* cen_x, const double* cen_zl, const double* cen_zu, double tau,
+                             double* out);
 /* Elementwise pieces of the regular phase on device-resident vectors (asynchronous on the context's stream):
  *   mnk_ipm_set_aug_rhs            set_aug_rhs!  kernels.jl:113-131: px = -f + zl - zu - jacl, py = -c,
  *                                  pzl = (xl_r - x_lr) zl_r + mu, pzu = (xu_r - x_ur) zu_r - mu  (px ntot, py m, pzl nlb, pzu nub)

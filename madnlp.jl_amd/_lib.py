@@ -141,6 +141,7 @@ SIGNATURES = {
     "mnk_ipm_get_varphi": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_double)]),
     "mnk_ipm_get_inf_du": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_double)]),
     "mnk_ipm_get_inf_compl": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "mnk_ipm_quality_function": (C.c_int, [_vp, C.c_int, _vp] + [_vp] * 11 + [C.c_double, C.POINTER(C.c_double)]),
     "mnk_ipm_get_min_complementarity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "mnk_ipm_get_average_complementarity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "mnk_ipm_get_varphi_d": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_double)]),

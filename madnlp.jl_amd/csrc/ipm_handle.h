@@ -14,6 +14,7 @@ struct mnk_ipm {
     mnk::DevBuf<int64_t> ind_lb, ind_ub, ind_llb, ind_uub;
     mnk::DevBuf<double> gemv_part;   // column-slab partial sums of mnk_ipm_gemv (grown on demand)
     mnk::DevBuf<double> part;   // IPM_SLOTS x IPM_BLOCKS partials
+    mnk::DevBuf<double> qf_alpha;   // IPM_SLOTS step lengths of mnk_ipm_quality_function, read by its second pass on the device
     double* pin = nullptr;     // IPM_SLOTS pinned, device-mapped host words: the final reduction stores its result here
     double* pin_dev = nullptr;
     // batch mode (mnk_ipm_batch_begin / _end): the get_* calls only enqueue their reductions into successive slots and

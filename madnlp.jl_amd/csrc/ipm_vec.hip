@@ -18,7 +18,7 @@ using namespace mnk;
 namespace {
 
 constexpr int IPM_BLOCKS = 256;
-constexpr int IPM_SLOTS = 32;  // reductions in flight: up to four per call, several calls per batch
+constexpr int IPM_SLOTS = 32;  // reductions in flight: up to four per call (sixteen for the quality function), several calls per batch
 constexpr int IPM_THREADS = 256;
 enum { R_SUM = 0, R_MAX = 1, R_MIN = 2 };
 
@@ -163,7 +163,7 @@ int finish(mnk_ipm* h, int base, int count, Fin fin) {
     // the final reductions stored their results straight into pinned, device-mapped host memory
     MNK_HIP(mnk::stream_wait(h->ctx->stream));
     volatile double* pw = h->pin + base;
-    double r[4];
+    double r[IPM_SLOTS];
     for (int i = 0; i < count; ++i) r[i] = pw[i];
     fin(r);
     return 0;
@@ -191,7 +191,8 @@ int mnk_ipm_create(mnk_ctx* ctx, int64_t ntot, int64_t nlb, const int64_t* ind_l
     mnk_ipm* h = new mnk_ipm();
     h->ctx = ctx;
     h->ntot = ntot; h->nlb = nlb; h->nub = nub;
-    int rc = h->ind_lb.upload(lb, ctx->stream) | h->ind_ub.upload(ub, ctx->stream) | h->part.alloc(IPM_SLOTS * IPM_BLOCKS);
+    int rc = h->ind_lb.upload(lb, ctx->stream) | h->ind_ub.upload(ub, ctx->stream) | h->part.alloc(IPM_SLOTS * IPM_BLOCKS) |
+             h->qf_alpha.alloc(IPM_SLOTS);
     if (!rc && (hipHostMalloc((void**)&h->pin, IPM_SLOTS * sizeof(double), hipHostMallocMapped) != hipSuccess ||
                 hipHostGetDevicePointer((void**)&h->pin_dev, h->pin, 0) != hipSuccess)) {
         (void)hipGetLastError();
@@ -1086,6 +1087,156 @@ int mnk_ipm_gemv(mnk_ipm* h, int trans, int64_t m, int64_t n, double alpha, cons
                            beta, y);
     MNK_HIP(hipGetLastError());
     return 0;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Quality function of the adaptive barrier update (reference src/IPM/barrier.jl:152-201, [Nocedal2009] eq. 4.2): for up to
+// four centering parameters sigma at once, along d = aff + sigma cen (product and sum each rounded on its own; d is never
+// stored), the two step lengths
+//     a_pr = get_alpha_max(x, xl, xu, d_x, tau),   a_du = get_alpha_z(zl_r, zu_r, d_zl, d_zu, tau)      (both start from 1)
+// and, with them, the two sums of squared complementarity products
+//     S_lb = sum ((x_lr + a_pr d_x_lr - xl_r) (zl_r + a_du d_zl))^2,   S_ub = sum ((xu_r - x_ur - a_pr d_x_ur) (zu_r + a_du d_zu))^2.
+// Four launches whatever the number of sigmas (grid dimension y is the sigma index): per-block minima -> step lengths (to a
+// device buffer AND the pinned result slots) -> per-block sums, which read the step lengths from the device buffer -> sums
+// to the pinned slots.  Slot layout of one call: 4 s + (0 a_pr, 1 a_du, 2 S_lb, 3 S_ub).  The element expressions are
+// FAlphaMax / FAlphaZ with d in place of the stored step; a NaN step entry makes the step length NaN (it would fail both
+// comparisons and be skipped otherwise), NaN partials propagate as red_op_nan does.
+// =====================================================================================================================
+namespace {
+
+struct QfArgs {
+    const double *x, *xl, *xu, *zl, *zu;
+    const double *aff_x, *aff_zl, *aff_zu, *cen_x, *cen_zl, *cen_zu;
+    const int64_t *ind_lb, *ind_ub;
+    int64_t ntot, nlb, nub;
+    double tau;
+    double sigma[4];
+};
+
+// the block's reduction of v in thread 0 (fixed tree); may be called more than once per kernel
+template <int RED>
+__device__ __forceinline__ double block_reduce(double v) {
+    __shared__ double sh[IPM_THREADS];
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = IPM_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = red_op_nan<RED>(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__device__ __forceinline__ void store_result(double* res, double v) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(res), (unsigned long long)__double_as_longlong(v),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ __launch_bounds__(IPM_THREADS) void qf_alpha_kernel(QfArgs a, double* __restrict__ part /* first slot's */) {
+    const int sg = blockIdx.y;
+    const double sigma = a.sigma[sg], tau = a.tau;
+    const int64_t first = blockIdx.x * (int64_t)IPM_THREADS + threadIdx.x, stride = (int64_t)IPM_BLOCKS * IPM_THREADS;
+    double vp = INFINITY, vd = INFINITY;
+    for (int64_t i = first; i < a.ntot; i += stride) {
+        const double d = a.aff_x[i] + sigma * a.cen_x[i];
+        const double lo = d < 0 ? (-a.x[i] + a.xl[i]) * tau / d : INFINITY;
+        const double up = d > 0 ? (-a.x[i] + a.xu[i]) * tau / d : INFINITY;
+        vp = red_op_nan<R_MIN>(vp, d != d ? NAN : fmin(lo, up));
+    }
+    for (int64_t i = first; i < a.nlb; i += stride) {
+        const double d = a.aff_zl[i] + sigma * a.cen_zl[i];
+        vd = red_op_nan<R_MIN>(vd, d != d ? NAN : (d < 0 ? (-a.zl[a.ind_lb[i]]) * tau / d : INFINITY));
+    }
+    for (int64_t i = first; i < a.nub; i += stride) {
+        const double d = a.aff_zu[i] + sigma * a.cen_zu[i];
+        vd = red_op_nan<R_MIN>(vd, d != d ? NAN : (d < 0 ? (-a.zu[a.ind_ub[i]]) * tau / d : INFINITY));
+    }
+    vp = block_reduce<R_MIN>(vp);
+    vd = block_reduce<R_MIN>(vd);
+    if (threadIdx.x == 0) {
+        part[(4 * sg + 0) * IPM_BLOCKS + blockIdx.x] = vp;
+        part[(4 * sg + 1) * IPM_BLOCKS + blockIdx.x] = vd;
+    }
+}
+
+// block (k, s): slot 4 s + k.  k < 2: min(1, minimum of the partials) to the device buffer and the pinned slot
+__global__ __launch_bounds__(IPM_THREADS) void qf_alpha_final_kernel(const double* __restrict__ part, double* __restrict__ alpha,
+                                                                      double* __restrict__ res) {
+    const int slot = 4 * blockIdx.y + blockIdx.x;
+    double v = INFINITY;
+    for (int i = threadIdx.x; i < IPM_BLOCKS; i += IPM_THREADS) v = red_op_nan<R_MIN>(v, part[slot * IPM_BLOCKS + i]);
+    v = block_reduce<R_MIN>(v);
+    if (threadIdx.x == 0) {
+        v = red_op_nan<R_MIN>(1.0, v);
+        alpha[slot] = v;
+        store_result(res + slot, v);
+    }
+}
+
+__global__ __launch_bounds__(IPM_THREADS) void qf_sum_kernel(QfArgs a, const double* __restrict__ alpha,
+                                                              double* __restrict__ part) {
+    const int sg = blockIdx.y;
+    const double sigma = a.sigma[sg], a_pr = alpha[4 * sg + 0], a_du = alpha[4 * sg + 1];
+    const int64_t first = blockIdx.x * (int64_t)IPM_THREADS + threadIdx.x, stride = (int64_t)IPM_BLOCKS * IPM_THREADS;
+    double sl = 0.0, su = 0.0;
+    for (int64_t i = first; i < a.nlb; i += stride) {
+        const int64_t p = a.ind_lb[i];
+        const double dx = a.aff_x[p] + sigma * a.cen_x[p], dz = a.aff_zl[i] + sigma * a.cen_zl[i];
+        const double t = (a.x[p] + a_pr * dx - a.xl[p]) * (a.zl[p] + a_du * dz);
+        sl += t * t;
+    }
+    for (int64_t i = first; i < a.nub; i += stride) {
+        const int64_t p = a.ind_ub[i];
+        const double dx = a.aff_x[p] + sigma * a.cen_x[p], dz = a.aff_zu[i] + sigma * a.cen_zu[i];
+        const double t = (a.xu[p] - a.x[p] - a_pr * dx) * (a.zu[p] + a_du * dz);
+        su += t * t;
+    }
+    sl = block_reduce<R_SUM>(sl);
+    su = block_reduce<R_SUM>(su);
+    if (threadIdx.x == 0) {
+        part[(4 * sg + 2) * IPM_BLOCKS + blockIdx.x] = sl;
+        part[(4 * sg + 3) * IPM_BLOCKS + blockIdx.x] = su;
+    }
+}
+
+// block (k, s): slot 4 s + 2 + k, the sum of the partials to the pinned slot
+__global__ __launch_bounds__(IPM_THREADS) void qf_sum_final_kernel(const double* __restrict__ part, double* __restrict__ res) {
+    const int slot = 4 * blockIdx.y + 2 + blockIdx.x;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < IPM_BLOCKS; i += IPM_THREADS) v += part[slot * IPM_BLOCKS + i];
+    v = block_reduce<R_SUM>(v);
+    if (threadIdx.x == 0) store_result(res + slot, v);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mnk_ipm_quality_function(mnk_ipm* h, int nsigma, const double* sigmas, const double* x, const double* xl, const double* xu,
+                             const double* zl, const double* zu, const double* aff_x, const double* aff_zl,
+                             const double* aff_zu, const double* cen_x, const double* cen_zl, const double* cen_zu, double tau,
+                             double* out) {
+    IPM_ENTER(h, "mnk_ipm_quality_function");
+    MNK_REQUIRE(nsigma >= 1 && nsigma <= 4, "mnk_ipm_quality_function: nsigma must be 1 to 4");
+    MNK_REQUIRE(sigmas && x && xl && xu && zl && zu && aff_x && cen_x && (h->nlb == 0 || (aff_zl && cen_zl)) &&
+                    (h->nub == 0 || (aff_zu && cen_zu)), "mnk_ipm_quality_function: NULL argument");
+    IPM_BASE(4 * nsigma);
+    QfArgs a{x, xl, xu, zl, zu, aff_x, aff_zl, aff_zu, cen_x, cen_zl, cen_zu, h->ind_lb.p, h->ind_ub.p,
+             h->ntot, h->nlb, h->nub, tau, {0.0, 0.0, 0.0, 0.0}};
+    for (int i = 0; i < nsigma; ++i) a.sigma[i] = sigmas[i];
+    hipStream_t s = h->ctx->stream;
+    double* part = h->part.p + b * IPM_BLOCKS;
+    double* alpha = h->qf_alpha.p + b;
+    const dim3 wide(IPM_BLOCKS, (unsigned)nsigma), two(2, (unsigned)nsigma), threads(IPM_THREADS);
+    hipLaunchKernelGGL(qf_alpha_kernel, wide, threads, 0, s, a, part);
+    hipLaunchKernelGGL(qf_alpha_final_kernel, two, threads, 0, s, part, alpha, h->pin_dev + b);
+    hipLaunchKernelGGL(qf_sum_kernel, wide, threads, 0, s, a, alpha, part);
+    hipLaunchKernelGGL(qf_sum_final_kernel, two, threads, 0, s, part, h->pin_dev + b);
+    MNK_HIP(hipGetLastError());
+    const int cnt = 4 * nsigma;
+    return finish(h, b, cnt, [=](const double* r) { for (int i = 0; i < cnt; ++i) out[i] = r[i]; });
 }
 
 }  // extern "C"

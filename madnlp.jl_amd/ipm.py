@@ -8,7 +8,8 @@ reference closely enough that iteration counts and residual histories are meanin
 
   initialize!            src/IPM/solver.jl:14-77, src/Callbacks/nlpmodels.jl:593-636
   regular!               src/IPM/solver.jl:216-298
-  update_barrier!        src/IPM/barrier.jl:12-34 (monotone), src/IPM/kernels.jl:697-713
+  update_barrier!        src/IPM/barrier.jl:12-34 (monotone), src/IPM/kernels.jl:697-713; the adaptive rules (`barrier =
+                         "loqo" / "quality_function"`) barrier.jl:95-316 with the options of src/IPM/types.jl:76-146
   set_aug_diagonal!/rhs  src/IPM/kernels.jl:4-27,113-130,818-823
   inertia_correction!    src/IPM/solver.jl:611-670 (InertiaBased), :672-737 (InertiaFree, with curv_test :785-788),
                          :739-783 (InertiaIgnore); the method is chosen at construction as IPM.jl:203-207 does
@@ -111,6 +112,18 @@ class IPMOptions:
     # and profile of this project was made without scaling -- switching the default is a change of its own
     nlp_scaling: bool = False
     nlp_scaling_max_gradient: float = 100.0
+    # options.jl `barrier`: "monotone" (MonotoneUpdate), "loqo" (LOQOUpdate), "quality_function" (QualityFunctionUpdate); the
+    # fields of the two adaptive rules with the defaults of types.jl:101-143 (mu_init, mu_min and the two monotone decrease
+    # parameters above are shared by all three)
+    barrier: str = "monotone"
+    barrier_globalization: bool = True
+    barrier_mu_max: float = 1e5
+    qf_sigma_min: float = 1e-6
+    qf_sigma_max: float = 1e2
+    qf_sigma_tol: float = 1e-2
+    qf_max_gs_iter: int = 8
+    loqo_gamma: float = 0.1
+    loqo_r: float = 0.95
 
     @property
     def mu_min(self):
@@ -129,6 +142,9 @@ class Counters:
     t: int = 0
     lag_hess_cnt: int = 0     # exact Lagrangian Hessians evaluated: stays 0 in a quasi-Newton run (test/madnlp_quasi_newton.jl:33)
     obj_grad_cnt: int = 0     # objective gradients evaluated (the quasi-Newton update starts with the second one)
+    barrier_update_cnt: int = 0   # quality-function updates (`n_update`, barrier.jl:300)
+    probe_solve_cnt: int = 0      # plain KKT solves of the quality-function rule, two per update; not part of backsolve_cnt
+    quality_eval_cnt: int = 0     # quality-function values computed (6 to 14 per update)
 
 
 @dataclass
@@ -148,6 +164,86 @@ class RobustRestorer:
 
 
 INERTIA_CORRECTION_METHODS = ("auto", "inertia_based", "inertia_free", "ignore")
+BARRIER_UPDATES = ("monotone", "loqo", "quality_function")
+
+
+def _clamp(x, lo, hi):
+    """Julia's `clamp`: hi above it, lo below it, x itself otherwise (a NaN stays a NaN)."""
+    return hi if x > hi else lo if x < lo else x
+
+
+def _fdiv(a, b):
+    """a / b with IEEE results for b == 0 (Python raises ZeroDivisionError instead)."""
+    if b != 0:
+        return a / b
+    return float("nan") if a == 0 or a != a else math.copysign(INF, a) * math.copysign(1.0, b)
+
+
+def ordered_sum(v, blocks=256, threads=256):
+    """sum(v) in the fixed order of the library's sum reductions (`map_reduce_kernel` / `final_reduce_kernel`, csrc/ipm_vec.hip):
+    element i goes to lane i mod (blocks threads), every lane adds its elements in increasing order, the lanes of a block are
+    added by a halving tree (lane j += lane j + s for s = threads/2 ... 1), and so are the blocks' results.  The same bits as
+    `mnk_ipm_get_sum` on the same values; used where a sum enters the iterate and both back-ends must agree exactly."""
+    v = np.asarray(v, dtype=np.float64)
+    lanes = blocks * threads
+    trips = max(1, -(-len(v) // lanes))
+    a = np.zeros(trips * lanes)
+    a[:len(v)] = v
+    a = a.reshape(trips, blocks, threads)
+    acc = np.zeros((blocks, threads))
+    for t in range(trips):
+        acc = acc + a[t]
+    s = threads // 2
+    while s > 0:
+        acc[:, :s] = acc[:, :s] + acc[:, s:2 * s]
+        s //= 2
+    part = acc[:, 0].copy()
+    s = blocks // 2
+    while s > 0:
+        part[:s] = part[:s] + part[s:2 * s]
+        s //= 2
+    return float(part[0])
+
+
+def golden_section(q, lo, hi, max_iter, tol, bracket=None):
+    """`_run_golden_search!` barrier.jl:205-246, restated as written: the minimizer of a (supposedly unimodal) function over
+    [lo, hi] by at most `max_iter` golden-section steps, stopped early once the bracket is narrower than `tol` times its upper
+    end.  `q` takes a LIST of points and returns their values: the four initial points lo, hi, mid1, mid2 are asked for in one
+    call, every step asks for one more, so there are at most 4 + max_iter evaluations.  Two things are the reference's own:
+    after the re-evaluation in the else branch phi_mid2 receives the NEW phi_mid1 (:230-231, not the value that moved to mid2),
+    and the end-point correction (:240-244) returns an end of the initial interval that was never left and whose value is
+    below the search's.  `bracket`, if a list, receives the final (sigma_1, sigma_2)."""
+    gfac = 0.5 * (3.0 - math.sqrt(5.0))
+    sigma_1, sigma_2 = lo, hi
+    sigma_mid1 = lo + gfac * (hi - lo)
+    sigma_mid2 = lo + (1.0 - gfac) * (hi - lo)
+    phi_1, phi_2, phi_mid1, phi_mid2 = q([sigma_1, sigma_2, sigma_mid1, sigma_mid2])
+    sigma_1_in, sigma_2_in, phi_1_in, phi_2_in = sigma_1, sigma_2, phi_1, phi_2
+    for _ in range(max_iter):
+        if phi_mid1 > phi_mid2:
+            sigma_1 = sigma_mid1
+            phi_1 = phi_mid1
+            sigma_mid1 = sigma_mid2
+            sigma_mid2 = sigma_1 + (1.0 - gfac) * (sigma_2 - sigma_1)
+            phi_mid1 = phi_mid2
+            phi_mid2, = q([sigma_mid2])
+        else:
+            sigma_2 = sigma_mid2
+            phi_2 = phi_mid2
+            sigma_mid2 = sigma_mid1
+            sigma_mid1 = sigma_1 + gfac * (sigma_2 - sigma_1)
+            phi_mid1, = q([sigma_mid1])
+            phi_mid2 = phi_mid1
+        if sigma_2 - sigma_1 < tol * sigma_2:
+            break
+    sigma, phi = (sigma_mid1, phi_mid1) if phi_mid1 < phi_mid2 else (sigma_mid2, phi_mid2)
+    if sigma_2 == sigma_2_in and phi_2_in < phi:
+        sigma = sigma_2_in
+    elif sigma_1 == sigma_1_in and phi_1_in < phi:
+        sigma = sigma_1_in
+    if bracket is not None:
+        bracket.append((sigma_1, sigma_2))
+    return sigma
 
 
 @dataclass
@@ -273,6 +369,8 @@ BACKEND_PRIMITIVES = (
     "_norm_inf", "_norm2", "_regularize", "_sd_sc", "_inf_du", "_iteration_scalars", "_jtprod", "_alpha_z", "_bound_dual_axpy",
     "_bound_dual_fill", "_adjust_boundary", "_reset_bound_dual", "_get_F", "_set_initial_rhs", "_kkt_initialize",
     "_rel_search_norm", "_line_search_scalars", "_trial_scalars",
+    "_average_complementarity", "_min_complementarity", "_set_affine_rhs", "_set_centering_rhs", "_solve_kkt_plain",
+    "_quality_terms",
     "_rr_init_vectors", "_rr_obj_val", "_rr_theta", "_rr_inf_pr", "_rr_inf_du", "_rr_inf_compl", "_rr_varphi", "_rr_varphi_d",
     "_rr_alpha_max", "_rr_alpha_z", "_rr_set_aug", "_rr_set_rhs", "_rr_finish", "_rr_set_f", "_rr_reset_slack_duals",
     "solution",
@@ -310,6 +408,9 @@ class MadNLPSolver:
         if method == "auto":   # IPM.jl:203-207
             method = "inertia_based" if self.kkt.linear_solver.is_inertia() else "inertia_free"
         self.inertia_correction_method = method
+        if o.barrier not in BARRIER_UPDATES:
+            raise ValueError(f"barrier must be one of {BARRIER_UPDATES}, not {o.barrier!r}")
+        self.free_mode = True      # adaptive barrier rules: free mode / monotone mode (types.jl:113,141), solver state
         if method == "inertia_free":   # the corrector's storage, inertiacorrector.jl:7-20 / solver.jl:756-765
             self._ifr = InertiaFreeCorrector(V(), V(), np.zeros(nt), np.zeros(nt), np.zeros(nt))
             self._w3 = V()
@@ -632,8 +733,33 @@ class MadNLPSolver:
         ic.t[:] = self._dx() - ic.d0.primal()
         return ok
 
-    # ------------------------------------------------------------------ barrier (barrier.jl:12-34)
+    # ------------------------------------------------------------------ barrier (barrier.jl:12-34, :95-316)
     def update_barrier(self, sc):
+        """`update_barrier!`: the monotone rule alone (barrier.jl:90-92), or the mode switching the two adaptive rules share
+        (`update_barrier!(::AbstractAdaptiveUpdate)` :118-149).  In free mode mu comes from the rule; an iterate the filter
+        (with a margin) rejects sends the solver to monotone mode at 0.8 times the average complementarity, where it stays,
+        decreasing mu by the monotone rule, until an iterate is accepted again."""
+        o = self.opt
+        if o.barrier == "monotone":
+            return self._update_monotone(sc)
+        old_mu = self.mu
+        progress = self._check_progress()
+        if not self.free_mode:
+            if progress:
+                self.free_mode = True
+            else:
+                self._update_monotone(sc)
+        elif not progress:
+            self.free_mode = False
+            self.mu = _clamp(0.8 * self._average_complementarity(), o.mu_min, o.barrier_mu_max)   # get_fixed_mu :99-102
+        if self.free_mode:
+            self.mu = self._loqo_mu() if o.barrier == "loqo" else self._quality_function_mu()
+        if self.mu != old_mu:
+            self.tau = max(o.tau_min, 1 - self.mu)
+            self.filter = [(self.theta_max, -INF)]
+
+    def _update_monotone(self, sc):
+        """`_update_monotone!` barrier.jl:12-34."""
         o = self.opt
         inf_compl_mu = self.inf_compl(self.mu, sc)
         while self.mu > max(o.mu_min, o.tol / 10) and \
@@ -645,6 +771,79 @@ class MadNLPSolver:
             self.tau = max(o.tau_min, 1 - self.mu)
             self.mu = mu_new
             self.filter = [(self.theta_max, -INF)]
+
+    def _check_progress(self):
+        """`_check_progress` barrier.jl:104-116: the current iterate, pushed out by a margin of 1e-5 min(1, KKT error), must be
+        acceptable to the current filter.  Always true without globalization."""
+        if not self.opt.barrier_globalization:
+            return True
+        theta = self._theta(self.c)
+        varphi = self.varphi(self.obj_val, self.x)
+        delta = 1e-5 * min(1.0, max(self.inf_pr, self.inf_du, self.inf_compl_v))
+        return self._filter_ok(theta + delta, varphi + delta)
+
+    def _n_bounded(self):
+        return len(self.ind_lb) + len(self.ind_ub)
+
+    def _loqo_mu(self):
+        """`get_adaptive_mu(::LOQOUpdate)` barrier.jl:304-316 ([Nocedal2009] eq. 3.6): the centering parameter from the ratio
+        xi of the smallest to the average complementarity product."""
+        o = self.opt
+        if self._n_bounded() == 0:
+            return o.mu_min
+        mu = self._average_complementarity()
+        xi = _fdiv(self._min_complementarity(), mu)
+        t = min((1 - o.loqo_r) * _fdiv(1 - xi, xi), 2)
+        sigma = o.loqo_gamma * (t * t * t)
+        return _clamp(sigma * mu, o.mu_min, o.barrier_mu_max)
+
+    def _quality_function_mu(self):
+        """`get_adaptive_mu(::QualityFunctionUpdate)` barrier.jl:260-302 ([Nocedal2009] section 4): mu = sigma times the average
+        complementarity, sigma minimizing the quality function along d(sigma) = d_aff + sigma d_cen.  Both directions are
+        APPROXIMATE, as in the reference: one plain solve each (no refinement) against the factorization and the KKT-handle
+        state the previous iteration left -- the barrier update runs before set_aug_diagonal! (solver.jl:255-262), and nothing
+        here builds or factorizes.  One deviation: while nothing has been factorized yet (iteration 0 with dual_initialization
+        = "zero") the current mu is kept; the reference would solve against a factor that was never computed."""
+        o = self.opt
+        if self._n_bounded() == 0:
+            return o.mu_min
+        if self.cnt.factorization_cnt == 0:
+            return self.mu
+        step_aff, step_cen = self._w1, self._w4     # free here: the corrections and the refinement use them later
+        self._set_affine_rhs()
+        rp = self._norm2(self._dual(self.p))        # `res_primal` :270
+        rd = self._norm2(self._primal(self.p))      # `res_dual` :271
+        self._solve_kkt_plain(step_aff)
+        mu = self._average_complementarity()
+        self._set_centering_rhs(mu)
+        self._solve_kkt_plain(step_cen)
+        self.cnt.probe_solve_cnt += 2
+        q = lambda sigmas: self._quality_values(sigmas, step_aff, step_cen, rp, rd)  # noqa: E731
+        sigma_1m = 1.0 - 1e-4
+        phi1, phi1m = q([1.0, sigma_1m])
+        if phi1m > phi1:       # :289-296, Ipopt's heuristic: is the minimizer above 1?
+            sigma_min = 1.0
+            sigma_max = min(o.qf_sigma_max, _fdiv(o.barrier_mu_max, mu))
+        else:
+            sigma_min = max(o.qf_sigma_min, _fdiv(o.mu_min, mu))
+            sigma_max = min(max(sigma_min, sigma_1m), _fdiv(o.barrier_mu_max, mu))
+        sigma = golden_section(q, sigma_min, sigma_max, o.qf_max_gs_iter, o.qf_sigma_tol)
+        self.cnt.barrier_update_cnt += 1
+        return _clamp(sigma * mu, o.mu_min, o.barrier_mu_max)
+
+    def _quality_values(self, sigmas, step_aff, step_cen, rp, rd):
+        """`_evaluate_quality_function` barrier.jl:152-201 for a batch of sigmas, restated as written: the call sites
+        (:209-230, :286-288) pass (res_primal, res_dual) where the signature reads (res_dual, res_primal), so the DUAL step
+        length weighs the primal residual rp = ||p_dual||_2 (over the number of variables and slacks) and the PRIMAL step length
+        the dual residual rd = ||p_primal||_2 (over the number of constraints)."""
+        ntot, m, nb = self.n + self.ns, self.m, self._n_bounded()
+        self.cnt.quality_eval_cnt += len(sigmas)
+        out = []
+        for a_pr, a_du, s_lb, s_ub in self._quality_terms(sigmas, step_aff, step_cen):
+            inf_pr = (1.0 - a_pr) * (1.0 - a_pr) * (rd * rd) / m if m > 0 else 0.0
+            inf_du = (1.0 - a_du) * (1.0 - a_du) * (rp * rp) / ntot
+            out.append(inf_du + inf_pr + (s_lb + s_ub) / nb)
+        return out
 
     # ------------------------------------------------------------------ filter line search (line_search.jl:6-123)
     def _filter_ok(self, theta, varphi):
@@ -994,6 +1193,71 @@ class MadNLPSolver:
     def _trial_scalars(self):
         """theta and varphi of the trial point (`c_trial`, `x_trial`, `obj_val_trial`)."""
         return self._theta(self.c_trial), self.varphi(self.obj_val_trial, self.x_trial)
+
+    # adaptive barrier rules
+    def _average_complementarity(self):
+        """`get_average_complementarity` kernels.jl:305-320, as the sum of the products (x_lr - xl_r) zl_r and (xu_r - x_ur)
+        zu_r over nlb + nub on both back-ends (the device reduction computes exactly this).  The reference's difference of dot
+        products, dot(x_lr, zl_r) - dot(xl_r, zl_r), agrees with it to rounding and cancels badly at active bounds.  The two sums
+        are taken in the device reduction's order (`ordered_sum`): under the adaptive rules mu is a multiple of this value and
+        enters the iterate, so the two back-ends must produce the same bits, not the same value to rounding."""
+        nb = len(self.ind_lb) + len(self.ind_ub)
+        if nb == 0:
+            return 0.0
+        return float((ordered_sum((self.x_lr - self.xl_r) * self.zl_r) + ordered_sum((self.xu_r - self.x_ur) * self.zu_r)) / nb)
+
+    def _min_complementarity(self):
+        """`get_min_complementarity` kernels.jl:322-339."""
+        a = ((self.x_lr - self.xl_r) * self.zl_r).min(initial=INF)
+        b = ((self.xu_r - self.x_ur) * self.zu_r).min(initial=INF)
+        return float("nan") if a != a or b != b else float(min(a, b))
+
+    def _set_affine_rhs(self):
+        """The affine-scaling right-hand side, barrier.jl:268: `set_aug_rhs!` with mu = 0 (no dual-infeasibility perturbation)."""
+        p = self.p
+        p.primal()[:] = -self.f + self.zl - self.zu - self.jacl
+        p.dual()[:] = -self.c
+        p.dual_lb()[:] = (self.xl_r - self.x_lr) * self.zl_r + 0.0      # (+ mu, - mu with mu = 0: a -0.0 product becomes 0.0)
+        p.dual_ub()[:] = (self.xu_r - self.x_ur) * self.zu_r - 0.0
+
+    def _set_centering_rhs(self, mu):
+        """`set_centering_aug_rhs!` barrier.jl:248-258 and the perturbation of :280."""
+        p = self.p
+        p.primal()[:] = 0.0
+        p.dual()[:] = 0.0
+        p.dual_lb()[:] = mu
+        p.dual_ub()[:] = -mu
+        px = p.primal()
+        px[self.ind_llb] -= mu * self.opt.kappa_d
+        px[self.ind_uub] += mu * self.opt.kappa_d
+
+    def _solve_kkt_plain(self, w):
+        """w = K^-1 p by one `solve_kkt!` on the current factorization, without refinement (barrier.jl:273-274, :282-283)."""
+        w.values[:] = self.p.values
+        self.kkt.solve_kkt(w)
+
+    def _quality_terms(self, sigmas, step_aff, step_cen):
+        """Per sigma the four reductions of `_evaluate_quality_function` (barrier.jl:157-189) along d = step_aff + sigma
+        step_cen: (alpha_pr, alpha_du, sum over the lower bounds of ((x_lr + alpha_pr dx_lr - xl_r) (zl_r + alpha_du dzl))^2,
+        the same over the upper bounds).  The step lengths start from 1 (`get_alpha_max`, `get_alpha_z`); a NaN anywhere in
+        the step makes them NaN (the reference's loops skip it: its comparisons are false)."""
+        out = []
+        tau, lb, ub = self.tau, self.ind_lb, self.ind_ub
+        for sigma in sigmas:
+            dx = step_aff.primal() + sigma * step_cen.primal()
+            dzl = step_aff.dual_lb() + sigma * step_cen.dual_lb()
+            dzu = step_aff.dual_ub() + sigma * step_cen.dual_ub()
+            a_pr = float("nan") if np.isnan(dx).any() else float(self.alpha_max(dx))
+            a_du = 1.0
+            for z, dz in ((self.zl_r, dzl), (self.zu_r, dzu)):
+                neg = dz < 0
+                if neg.any():
+                    a_du = min(a_du, (-z[neg] * tau / dz[neg]).min())
+            a_du = float("nan") if np.isnan(dzl).any() or np.isnan(dzu).any() else float(a_du)
+            t = (self.x_lr + a_pr * dx[lb] - self.xl_r) * (self.zl_r + a_du * dzl)
+            u = (self.xu_r - self.x_ur - a_pr * dx[ub]) * (self.zu_r + a_du * dzu)
+            out.append((a_pr, a_du, float((t * t).sum()), float((u * u).sum())))
+        return out
 
     # ------------------------------------------------------------------ restore! (solver.jl:300-411)
     def restore(self):

@@ -8,6 +8,8 @@ nothing of its control flow except the first trial of the inertia correction.  T
                       work (`mnk_ipm_vec_*`, `mnk_ipm_get_dot`, `mnk_ipm_gemv`)
   * `mnk_ipm_vec_mul`, `mnk_ipm_scale_cons`, `mnk_ipm_scale_grad` (csrc/nlp_scale.hip): NLP scaling and the objective sense
                       around the callbacks' raw values, only when `nlp_scaling` is set or the model maximizes
+  * `mnk_ipm_quality_function`: the adaptive barrier update's quality function for up to four centering parameters per call
+                      (`barrier = "quality_function"`), the step `aff + sigma cen` never stored
   * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
   * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
@@ -748,6 +750,46 @@ class DeviceMadNLPSolver(MadNLPSolver):
             b_n = K.get_norms(self.c_trial)
             b_v = K.get_varphi(self.obj_val_trial, self.x_trial, self.xl, self.xu, self.mu)
         return b_n[1], b_v[0]
+
+    # adaptive barrier rules
+    def _average_complementarity(self):
+        return self.K.get_average_complementarity(self.x, self.xl, self.xu, self.zl, self.zu)
+
+    def _min_complementarity(self):
+        return self.K.get_min_complementarity(self.x, self.xl, self.xu, self.zl, self.zu)
+
+    def _set_affine_rhs(self):
+        p = self.p
+        self.K.set_aug_rhs(self.f, self.zl, self.zu, self.jacl, self.c, self.x, self.xl, self.xu, 0.0, self._primal(p),
+                           self._dual(p), self._dual_lb(p), self._dual_ub(p))
+
+    def _set_centering_rhs(self, mu):
+        p, K = self.p, self.K
+        K.vec_fill(self._primal(p), 0.0)
+        K.vec_fill(self._dual(p), 0.0)
+        K.vec_fill(self._dual_lb(p), mu)
+        K.vec_fill(self._dual_ub(p), -mu)
+        K.dual_inf_perturbation(self._primal(p), mu, self.opt.kappa_d)
+
+    def _solve_kkt_plain(self, w):
+        """One `solve_kkt!` of a copy of p on the device; the solver's verdict on a one-launch solve is read once the stream
+        is idle, and the solve repeated stepwise if it gave up (as `solve_refine` does)."""
+        from .linear_solver import SolveException
+        for attempt in (0, 1):
+            self.K.vec_copy(w, self.p)
+            self.kkt.solve_kkt_device(w)
+            self._sync()
+            try:
+                return self.kkt.linear_solver.check_solve()
+            except SolveException:
+                if attempt:
+                    raise
+
+    def _quality_terms(self, sigmas, step_aff, step_cen):
+        """`mnk_ipm_quality_function`: one call of four launches and one synchronization for the whole batch of sigmas."""
+        a, c = step_aff, step_cen
+        return self.K.quality_function(sigmas, self.x, self.xl, self.xu, self.zl, self.zu, self._primal(a), self._dual_lb(a),
+                                       self._dual_ub(a), self._primal(c), self._dual_lb(c), self._dual_ub(c), self.tau)
 
     # robust restorer (`mnk_ipm_*_R`)
     def _rr_init_vectors(self, RR, mu_R, rho):

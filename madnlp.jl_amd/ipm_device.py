@@ -73,6 +73,20 @@ class IPMDeviceKernels:
     def get_average_complementarity(self, x, xl, xu, zl, zu):
         return self._call("mnk_ipm_get_average_complementarity", _dev(x), _dev(xl), _dev(xu), _dev(zl), _dev(zu))
 
+    def quality_function(self, sigmas, x, xl, xu, zl, zu, aff_x, aff_zl, aff_zu, cen_x, cen_zl, cen_zu, tau):
+        """`_evaluate_quality_function`'s reductions (reference src/IPM/barrier.jl:157-189) for 1 to 4 centering parameters in
+        one call of four launches: per sigma (a_pr, a_du, S_lb, S_ub) along aff + sigma cen, given as the primal, dual_lb and
+        dual_ub blocks of the two KKT vectors.  Returns a list of 4-tuples; inside a batch the flat result buffer (4 values per
+        sigma), filled when the batch ends."""
+        ns = len(sigmas)
+        sg = (C.c_double * max(ns, 1))(*[float(s) for s in sigmas])
+        blk = lambda v: _dev(v) if v.numel() else None   # noqa: E731  (an empty bound block)
+        out = self._call("mnk_ipm_quality_function", ns, sg, _dev(x), _dev(xl), _dev(xu), _dev(zl), _dev(zu), _dev(aff_x),
+                         blk(aff_zl), blk(aff_zu), _dev(cen_x), blk(cen_zl), blk(cen_zu), float(tau), n=4 * max(ns, 1))
+        if self._batching:
+            return out
+        return [tuple(out[4 * i:4 * i + 4]) for i in range(ns)]
+
     def get_varphi_d(self, f, x, xl, xu, dx, mu):
         return self._call("mnk_ipm_get_varphi_d", _dev(f), _dev(x), _dev(xl), _dev(xu), _dev(dx), float(mu))
 
