@@ -532,6 +532,31 @@ int mnk_ipm_bound_dual_fill(mnk_ipm* ipm, double* zl, double* zu, double v);
 int mnk_ipm_gemv(mnk_ipm* ipm, int trans, int64_t m, int64_t n, double alpha, const double* A, int64_t lda, const double* x,
                  double beta, double* y);
 
+/* ---- vector kernels of the restarted GMRES refinement (csrc/krylov.hip) ---------------------------
+ * The capability of the reference's lib/MadNLPKrylov: GMRES around solve_kkt! / mul!, selected by the solver option
+ * `iterator = "krylov"`.  V is a device buffer of basis columns with leading dimension ldv >= n (column j starts at V + j ldv),
+ * u the vector being orthogonalized, k = 1..8 the number of columns a call uses.  Ordinary launches on the context's stream.
+ * Every sum is taken in the fixed order of the mnk_ipm_get_* sum reductions, every product, sum and difference is rounded
+ * on its own.  One Arnoldi step is dots -> project -> dots -> project -> normalize with one synchronization (a batch).
+ *   mnk_ipm_krylov_dots       out[j] = V_j . u (j < k), out[k] = u . u  (host, k + 1 doubles); one pass over u and the
+ *                             columns.  Follows the batch protocol (k + 1 of a batch's 32 reductions).  The results also
+ *                             stay on the device: mnk_ipm_krylov_last_dots gives their address
+ *   mnk_ipm_krylov_last_dots  *coef = device address of the k + 1 results of the most recent mnk_ipm_krylov_dots call; valid
+ *                             until the next batch reaches the same position (or the next call outside a batch)
+ *   mnk_ipm_krylov_project    u -= sum_j coef[j] V_j, the terms subtracted in the order j = 0 .. k-1; coef: DEVICE, k
+ *                             doubles (the preceding dots call's results: nothing goes to the host in between).  Leaves the
+ *                             block partial sums of the new u . u in the handle
+ *   mnk_ipm_krylov_axpy       x += sum_j y[j] V_j in the order j = 0 .. k-1; y_host: HOST, k doubles, passed by value
+ *   mnk_ipm_krylov_normalize  v = u / norm(u, 2), out[0] = norm(u, 2) (host; batch protocol, one reduction).
+ *                             after_project = 1: u . u is what the preceding mnk_ipm_krylov_project left, and the call is
+ *                             one launch; 0: a launch of its own sums it first.  A zero u gives a non-finite v
+ * A NULL pointer, k outside 1..8, n < 0 or ldv < n is an error and launches nothing. */
+int mnk_ipm_krylov_dots(mnk_ipm* ipm, const double* V, int64_t ldv, int k, const double* u, int64_t n, double* out);
+int mnk_ipm_krylov_last_dots(mnk_ipm* ipm, const double** coef);
+int mnk_ipm_krylov_project(mnk_ipm* ipm, double* u, const double* V, int64_t ldv, int k, int64_t n, const double* coef);
+int mnk_ipm_krylov_axpy(mnk_ipm* ipm, double* x, const double* V, int64_t ldv, int k, const double* y_host, int64_t n);
+int mnk_ipm_krylov_normalize(mnk_ipm* ipm, double* v, const double* u, int64_t n, int after_project, double* out);
+
 /* ---- NLP scaling and objective sense around a model's raw callback values (csrc/nlp_scale.hip) -------------------------
  * The factors the reference's callback wrappers apply (src/Callbacks/nlpmodels.jl:771-906, src/IPM/callbacks.jl:28-49), on
  * device vectors, asynchronous on the context's stream, one launch each; a length of 0 launches nothing.  Every product and

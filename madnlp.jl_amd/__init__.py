@@ -13,7 +13,7 @@ from .linear_solver import (  # noqa: F401
 from .kkt import (  # noqa: F401
     UnreducedKKTVector, SparseCondensedKKTSystem, DenseCondensedKKTSystem, DenseKKTSystem, ScenarioBatch,
 )
-from .backsolve import RichardsonIterator  # noqa: F401
+from .backsolve import ITERATORS, KrylovIterator, RichardsonIterator  # noqa: F401
 from ._lib import MNK_QN_BFGS, MNK_QN_DAMPED_BFGS  # noqa: F401
 from .quasi_newton import HESSIAN_APPROXIMATIONS  # noqa: F401
 HESSIAN_EXACT, HESSIAN_BFGS, HESSIAN_DAMPED_BFGS = HESSIAN_APPROXIMATIONS   # the values of IPMOptions.hessian_approximation

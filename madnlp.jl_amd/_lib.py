@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of another commit's build of the same ABI (tools/leaf_ab.py, tools/README.md); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip"]
 HEADERS = ["common.h", "ls.h", "dag_plan.h", "factor_plan.h", "solve_plan.h", "schur_plan.h", "stream_plan.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "ipm_handle.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
@@ -190,6 +190,11 @@ SIGNATURES = {
     "mnk_ipm_vec_mul": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64]),
     "mnk_ipm_scale_cons": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64]),
     "mnk_ipm_scale_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_double]),
+    "mnk_ipm_krylov_dots": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.POINTER(C.c_double)]),
+    "mnk_ipm_krylov_last_dots": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "mnk_ipm_krylov_project": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp]),
+    "mnk_ipm_krylov_axpy": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int64]),
+    "mnk_ipm_krylov_normalize": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "mnk_opf_create": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "mnk_opf_destroy": (C.c_int, [_vp]),
     "mnk_opf_sizes": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p]),

@@ -17,9 +17,6 @@ using namespace mnk;
 
 namespace {
 
-constexpr int IPM_BLOCKS = 256;
-constexpr int IPM_SLOTS = 32;  // reductions in flight: up to four per call (sixteen for the quality function), several calls per batch
-constexpr int IPM_THREADS = 256;
 enum { R_SUM = 0, R_MAX = 1, R_MIN = 2 };
 
 template <int RED>
@@ -140,34 +137,10 @@ int enqueue(mnk_ipm* h, F f, int64_t n, int slot) {
 
 inline double max0(double r) { return r != r ? r : fmax(0.0, r); }  // reference: max(zero, ...), NaN propagates
 
-// first slot of a call that needs `count` reductions (-1: the batch is full)
-int slot_base(mnk_ipm* h, int count) {
-    if (!h->batching) return 0;
-    if (h->next_slot + count > IPM_SLOTS) {
-        set_error("mnk_ipm: more than %d reductions in one batch", IPM_SLOTS);
-        return -1;
-    }
-    const int b = h->next_slot;
-    h->next_slot += count;
-    return b;
-}
-
-// Outside a batch: wait for the stream, read the `count` results that start at slot `base` and run the finalizer (which
-// writes the caller's `out`).  Inside a batch: keep the finalizer for mnk_ipm_batch_end.
+// the batch protocol lives in ipm_handle.h (krylov.hip follows it too)
+int slot_base(mnk_ipm* h, int count) { return ipm_slot_base(h, count); }
 template <class Fin>
-int finish(mnk_ipm* h, int base, int count, Fin fin) {
-    if (h->batching) {
-        h->pending.emplace_back(base, std::function<void(const double*)>(fin));
-        return 0;
-    }
-    // the final reductions stored their results straight into pinned, device-mapped host memory
-    MNK_HIP(mnk::stream_wait(h->ctx->stream));
-    volatile double* pw = h->pin + base;
-    double r[IPM_SLOTS];
-    for (int i = 0; i < count; ++i) r[i] = pw[i];
-    fin(r);
-    return 0;
-}
+int finish(mnk_ipm* h, int base, int count, Fin fin) { return ipm_finish(h, base, count, fin); }
 
 }  // namespace
 
@@ -192,7 +165,7 @@ int mnk_ipm_create(mnk_ctx* ctx, int64_t ntot, int64_t nlb, const int64_t* ind_l
     h->ctx = ctx;
     h->ntot = ntot; h->nlb = nlb; h->nub = nub;
     int rc = h->ind_lb.upload(lb, ctx->stream) | h->ind_ub.upload(ub, ctx->stream) | h->part.alloc(IPM_SLOTS * IPM_BLOCKS) |
-             h->qf_alpha.alloc(IPM_SLOTS);
+             h->qf_alpha.alloc(IPM_SLOTS) | h->kry_res.alloc(IPM_SLOTS) | h->kry_part.alloc(IPM_BLOCKS);
     if (!rc && (hipHostMalloc((void**)&h->pin, IPM_SLOTS * sizeof(double), hipHostMallocMapped) != hipSuccess ||
                 hipHostGetDevicePointer((void**)&h->pin_dev, h->pin, 0) != hipSuccess)) {
         (void)hipGetLastError();

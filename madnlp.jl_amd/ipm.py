@@ -40,7 +40,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .backsolve import RichardsonIterator
+from .backsolve import ITERATORS, KrylovIterator, RichardsonIterator
 from .kkt import UnreducedKKTVector
 from .quasi_newton import HESSIAN_APPROXIMATIONS, create_quasi_newton
 
@@ -124,6 +124,12 @@ class IPMOptions:
     qf_max_gs_iter: int = 8
     loqo_gamma: float = 0.1
     loqo_r: float = 0.95
+    # options.jl `iterator`: "richardson" (RichardsonIterator) or "krylov" (the restarted GMRES of lib/MadNLPKrylov, with its
+    # defaults restart = 5, max_iter = 10, tol = 1e-10; the stopping rules are relative here)
+    iterator: str = "richardson"
+    krylov_restart: int = 5
+    krylov_max_iter: int = 10
+    krylov_tol: float = 1e-10
 
     @property
     def mu_min(self):
@@ -414,7 +420,13 @@ class MadNLPSolver:
         if method == "inertia_free":   # the corrector's storage, inertiacorrector.jl:7-20 / solver.jl:756-765
             self._ifr = InertiaFreeCorrector(V(), V(), np.zeros(nt), np.zeros(nt), np.zeros(nt))
             self._w3 = V()
-        self.iterator = RichardsonIterator(self.kkt, tol=o.tol)
+        if o.iterator not in ITERATORS:
+            raise ValueError(f"iterator must be one of {ITERATORS}, not {o.iterator!r}")
+        if o.iterator == "krylov":   # (its constructor checks krylov_restart and krylov_max_iter)
+            self.iterator = KrylovIterator(self.kkt, tol=o.tol, restart=o.krylov_restart, max_iter=o.krylov_max_iter,
+                                           krylov_tol=o.krylov_tol)
+        else:
+            self.iterator = RichardsonIterator(self.kkt, tol=o.tol)
         self.cnt = Counters()
         self.filter = []
         self.history: list[IterRecord] = []

@@ -10,6 +10,8 @@ nothing of its control flow except the first trial of the inertia correction.  T
                       around the callbacks' raw values, only when `nlp_scaling` is set or the model maximizes
   * `mnk_ipm_quality_function`: the adaptive barrier update's quality function for up to four centering parameters per call
                       (`barrier = "quality_function"`), the step `aff + sigma cen` never stored
+  * `mnk_ipm_krylov_*` (csrc/krylov.hip): the Gram-Schmidt, normalization and solution updates of the GMRES refinement
+                      (`iterator = "krylov"`), one synchronization per Arnoldi step
   * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
   * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
@@ -497,15 +499,17 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self.cnt.factorization_cnt += 1
 
     def solve_refine(self, x, b, w):
-        """Richardson refinement (reference src/LinearSolvers/backsolve.jl:27-76) on device vectors."""
+        """Richardson refinement (reference src/LinearSolvers/backsolve.jl:27-76) or, with `iterator = "krylov"`, restarted
+        GMRES (the capability of lib/MadNLPKrylov) on device vectors."""
         from .linear_solver import SolveException
+        refine = self._solve_refine_krylov if self.opt.iterator == "krylov" else self._solve_refine
         try:
-            ok = self._solve_refine(x, b, w)
+            ok = refine(x, b, w)
             self.kkt.linear_solver.check_solve()   # the stream is idle here (the norms synchronized)
         except SolveException:
             # a one-launch solve gave up (its workgroups were not co-resident): the solver has switched to the stepwise
             # solve; the refinement is repeated from the right-hand side
-            ok = self._solve_refine(x, b, w)
+            ok = refine(x, b, w)
             self.kkt.linear_solver.check_solve()
         return ok
 
@@ -543,6 +547,80 @@ class DeviceMadNLPSolver(MadNLPSolver):
                 break
         it.residual_ratio = residual_ratio
         return residual_ratio < it.richardson_acceptable_tol
+
+    def _solve_refine_krylov(self, x, b, w):
+        """`KrylovIterator.solve_refine` (backsolve.py) on device vectors: the same operations in the
+        same order, the host scalars through the same `GmresCycle`.  One synchronization per `solve_kkt`: cycle 0 is
+        Richardson's first step with the 2-norm riding along; an Arnoldi step enqueues mul -> solve -> dots -> project ->
+        dots -> project -> normalize and reads h1, h2 and the norm together (the first step of a cycle also the cycle's
+        beta); the solution update and the residual ratio close a cycle with one more."""
+        it, K, kkt = self.iterator, self.K, self.kkt
+        it.ir = it.steps = it.cycles = 0
+        it.trace = []
+        K.vec_copy(w, b)
+        kkt.solve_kkt_device(w)               # cycle 0 (a zero right-hand side is solved once, as in _solve_refine)
+        K.vec_copy(x, w)
+        with K.batch():
+            b_b = K.get_norms(b)
+            b_0 = K.get_norm2(w)
+            b_w, b_x = self._krylov_residual(x, b, w)
+        norm_b, beta0 = b_b[0], b_0[0]
+        if norm_b == 0:
+            K.vec_fill(x, 0.0)
+            it.residual_ratio = 0.0
+            return True
+        it.ir = 1
+        r = b_w[0] / (min(b_x[0], 1e6 * norm_b) + norm_b)
+        while not (r < it.richardson_tol or it.ir >= it.max_iter):
+            self._krylov_cycle(x, w, beta0)
+            with K.batch():
+                b_w, b_x = self._krylov_residual(x, b, w)
+            r = b_w[0] / (min(b_x[0], 1e6 * norm_b) + norm_b)
+        it.residual_ratio = r
+        return r < it.richardson_acceptable_tol
+
+    def _krylov_residual(self, x, b, w):
+        """Enqueue w = b - K x and the two norms of the residual ratio (inside the caller's batch)."""
+        self.K.vec_copy(w, b)
+        self.kkt.mul_device(w, x, -1.0, 1.0)
+        return self.K.get_norms(w), self.K.get_norms(x)
+
+    def _krylov_cycle(self, x, w, beta0):
+        from .backsolve import GmresCycle
+        it, K, kkt = self.iterator, self.K, self.kkt
+        kkt.solve_kkt_device(w)               # z = K^-1 (b - K x)
+        it.ir += 1
+        if it.ir >= it.max_iter:              # a single solve left: a Richardson step
+            K.vec_axpby(x, 1.0, x, 1.0, w)
+            return
+        V = getattr(self, "_krylov_V", None)
+        if V is None or V.shape[0] != it.restart + 1:
+            V = self._krylov_V = self._new_vec((it.restart + 1) * self._lw).view(it.restart + 1, self._lw)   # the basis
+        it.cycles += 1
+        cyc = None
+        for j in range(it.restart):
+            k = j + 1
+            with K.batch():
+                b_beta = K.krylov_normalize(V[0], w, False) if j == 0 else None
+                kkt.mul_device(w, V[j], 1.0, 0.0)
+                kkt.solve_kkt_device(w)       # u = K^-1 K v_j
+                b_h1 = K.krylov_dots(V, k, w)
+                K.krylov_project(w, V, k)
+                b_h2 = K.krylov_dots(V, k, w)
+                K.krylov_project(w, V, k)
+                b_hn = K.krylov_normalize(V[k], w, True)
+            it.ir += 1
+            it.steps += 1
+            if cyc is None:
+                cyc = GmresCycle(b_beta[0], it.restart)
+                it.trace.append((b_beta[0], cyc.rho))
+                if not b_beta[0] > 0:         # (a singular solve: nothing to build a basis from)
+                    return
+            hn = b_hn[0]
+            rho = cyc.add_column(list(b_h1)[:k], list(b_h2)[:k], hn)
+            if rho <= it.krylov_tol * beta0 or hn == 0 or it.ir >= it.max_iter:
+                break
+        K.krylov_axpy(x, V, cyc.k, cyc.solution())
 
     def solve_refine_wrapper(self, d, p, w):
         if not self._on_device:

@@ -244,6 +244,45 @@ class IPMDeviceKernels:
         if out.numel():
             self._void("mnk_ipm_vec_gather", _dev(out), float(a), _dev(x), idx.data_ptr(), int(out.numel()))
 
+    # ---- restarted GMRES refinement (csrc/krylov.hip): V is a (columns, ldv) device tensor, column j = V[j]
+    @staticmethod
+    def _basis(V, k, n):
+        ldv = int(V.stride(0))
+        assert V.dim() == 2 and V.stride(1) == 1 and 1 <= k <= V.shape[0] and n <= V.shape[1], "basis too small for k, n"
+        return _dev(V), ldv
+
+    def krylov_dots(self, V, k, u, n=None):
+        """(V_j . u for j < k, u . u); inside a batch the result buffer of k + 1 values, filled when the batch ends."""
+        n = int(u.numel()) if n is None else int(n)
+        pv, ldv = self._basis(V, k, n)
+        return self._call("mnk_ipm_krylov_dots", pv, ldv, int(k), _dev(u), n, n=int(k) + 1)
+
+    def krylov_last_dots(self):
+        """Device address of the most recent `krylov_dots` results."""
+        p = C.c_void_p()
+        L.check(L.lib().mnk_ipm_krylov_last_dots(self._h, C.byref(p)), "mnk_ipm_krylov_last_dots")
+        return p
+
+    def krylov_project(self, u, V, k, n=None, coef=None):
+        """u -= sum_j coef[j] V_j; coef: a device tensor, or None for the results the preceding `krylov_dots` left on the
+        device."""
+        n = int(u.numel()) if n is None else int(n)
+        pv, ldv = self._basis(V, k, n)
+        self._void("mnk_ipm_krylov_project", _dev(u), pv, ldv, int(k), n, self.krylov_last_dots() if coef is None else _dev(coef))
+
+    def krylov_axpy(self, x, V, k, y, n=None):
+        """x += sum_j y[j] V_j, y: k host scalars."""
+        n = int(x.numel()) if n is None else int(n)
+        pv, ldv = self._basis(V, k, n)
+        assert len(y) >= k
+        self._void("mnk_ipm_krylov_axpy", _dev(x), pv, ldv, int(k), (C.c_double * int(k))(*[float(t) for t in y[:k]]), n)
+
+    def krylov_normalize(self, v, u, after_project, n=None):
+        """v = u / norm(u, 2); returns the norm (inside a batch: its result buffer)."""
+        n = int(u.numel()) if n is None else int(n)
+        assert v.numel() >= n
+        return self._call("mnk_ipm_krylov_normalize", _dev(v), _dev(u), n, int(bool(after_project)))
+
     # ---- NLP scaling and objective sense around the callbacks' raw values (csrc/nlp_scale.hip)
     def vec_mul(self, out, a, b):
         """out = a .* b; out may alias a or b."""
