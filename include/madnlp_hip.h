@@ -117,6 +117,54 @@ int mnk_sc_get_values(mnk_sc* sc, int which, double* out, int loc);
  * Symmetric(hess_com, :L) (which = MNK_SC_HESS).  x, y in device memory. */
 int mnk_sc_spmv(mnk_sc* sc, int which, int trans, double alpha, const double* x, double beta, double* y);
 
+/* Compact L-BFGS Hessians, hessian_approximation = CompactLBFGS, on the sparse condensed system (csrc/lbfgs.hip; reference
+ * `src/quasi_newton.jl:210-437`, `src/IPM/factorization.jl:76-140,253-276`).  B = sigma I - U U' + V V': the handle's Hessian
+ * has the DIAGONAL pattern and holds sigma; S, Y, U, V, E = [U V] and H = C^-1 E stay in the mnk_lbfgs handle on the device.
+ *
+ * mnk_lbfgs_create replaces `create_quasi_newton(CompactLBFGS, ...)` with the fields of `QuasiNewtonOptions`; max_history is
+ * 1 .. 32 (a larger value is an error).  mnk_lbfgs_init is `init!`: *xi = 2 rho0 init_value (rho0 as mnk_dc_qn_init, g0'g0 an
+ * ordered sum on the device).  mnk_lbfgs_update is `update!` with device vectors s, y: every dot product in one launch pair,
+ * ONE synchronization, the p x p algebra on the host, one launch that stores the pair and writes U and V.  *performed: 0 if
+ * the pair was skipped (|s| or |y| < 100 eps, or s'y < sqrt(eps) |s| |y|; the second skip since the last reset empties the
+ * memory); *sigma: the value the diagonal Hessian holds from now on.
+ *
+ * mnk_lbfgs_status (synchronizes): out[0 .. 8) = current_mem, updates, skipped, resets, builds of H / T, singular-T events,
+ * version (performed + resetting updates), max_history.  mnk_lbfgs_get copies S, Y, U, V (n x current_mem, oldest pair first),
+ * L, D (current_mem), T or W = T^-1 (2 current_mem square; after a solve_kkt) to the host, column-major with leading dimension ld.
+ * mnk_lbfgs_gram: out (host, qa x qb) = A'B; mnk_lbfgs_apply: y += alpha A (M (B'x)); device operands with n rows, q <= 64: the
+ * reduction and rank-q kernels on their own, every sum in the order of mnk_ipm_get_sum.
+ *
+ * mnk_sc_attach_lbfgs (qn = NULL detaches): mnk_sc_solve_kkt and mnk_sc_mul then include the low-rank term.  The first
+ * solve_kkt after a factorization of the solver it is given, or after a performed / resetting update, computes H = C^-1 E
+ * (one mnk_ls_solve with 2 current_mem columns), T = P + E'H and W = T^-1 on the device; every solve_kkt then applies
+ * w_x -= H (W (E'w_x)) to the condensed solution with two launches and no host round trip.  A zero pivot of T raises a flag:
+ * the correction is not applied, a solve_kkt on host vectors returns an error, one on device vectors reports it at the next
+ * call; mnk_lbfgs_status counts it.  mnk_sc_step_batch and mnk_ls_solve_batch refuse such a system.
+ * mnk_sc_keep_jacobian snapshots the compressed J' values; mnk_sc_spmv reads the snapshot with which = MNK_SC_JT_KEPT.
+ * mnk_sc_qn_secant is mnk_dc_qn_secant for this handle. */
+/* The handle is an opaque mnk_lbfgs*; like mnk_tape* below, the prototypes spell it void* (mnk_lbfgs_create: void* out =
+ * mnk_lbfgs**) because the static header check of tests/test_julia_glue.py knows the handle types by a fixed list of names. */
+typedef struct mnk_lbfgs mnk_lbfgs;
+enum { MNK_SC_JT_KEPT = 4 };
+enum { MNK_LBFGS_SCALAR1 = 1, MNK_LBFGS_SCALAR2 = 2, MNK_LBFGS_SCALAR3 = 3, MNK_LBFGS_SCALAR4 = 4 };
+enum { MNK_LBFGS_S = 0, MNK_LBFGS_Y = 1, MNK_LBFGS_U = 2, MNK_LBFGS_V = 3, MNK_LBFGS_L = 4, MNK_LBFGS_D = 5, MNK_LBFGS_T = 6,
+       MNK_LBFGS_W = 7 };
+int mnk_lbfgs_create(mnk_ctx* ctx, int64_t n, int max_history, int init_strategy, double init_value, double sigma_min,
+                     double sigma_max, void* out);
+int mnk_lbfgs_destroy(void* qn);
+int mnk_lbfgs_init(void* qn, const double* g0, double f0, double* xi);
+int mnk_lbfgs_update(void* qn, const double* s, const double* y, int* performed, double* sigma);
+int mnk_lbfgs_status(void* qn, int64_t* out);
+int mnk_lbfgs_get(void* qn, int which, double* out, int64_t ld);
+int mnk_lbfgs_gram(void* qn, const double* A, int64_t lda, int qa, const double* B, int64_t ldb, int qb, int64_t n,
+                   double* out);
+int mnk_lbfgs_apply(void* qn, double* y, double alpha, const double* A, int64_t lda, const double* M, const double* B,
+                    int64_t ldb, const double* x, int q, int64_t n);
+int mnk_sc_attach_lbfgs(mnk_sc* sc, void* qn);
+int mnk_sc_keep_jacobian(mnk_sc* sc);
+int mnk_sc_qn_secant(mnk_sc* sc, const double* x, const double* g, const double* jl, const double* jv, double* last_x,
+                     double* last_g, double* s, double* y);
+
 /* ------------------- DenseCondensedKKTSystem / DenseKKTSystem (dc) ---------- */
 /* Replaces `create_kkt_system(::Type{DenseCondensedKKTSystem}, ...)`
  * `src/KKT/Dense/condensed.jl:52-111` (condensed = 1, order n + n_eq) and

@@ -11,12 +11,13 @@ from .linear_solver import (  # noqa: F401
     LinearSolverException, SymbolicException, FactorizationException, SolveException, InertiaException,
 )
 from .kkt import (  # noqa: F401
-    UnreducedKKTVector, SparseCondensedKKTSystem, DenseCondensedKKTSystem, DenseKKTSystem, ScenarioBatch,
+    UnreducedKKTVector, SparseCondensedKKTSystem, DenseCondensedKKTSystem, DenseKKTSystem, ScenarioBatch, LowRankHessianKKT,
 )
 from .backsolve import ITERATORS, KrylovIterator, RichardsonIterator  # noqa: F401
 from ._lib import MNK_QN_BFGS, MNK_QN_DAMPED_BFGS  # noqa: F401
-from .quasi_newton import HESSIAN_APPROXIMATIONS  # noqa: F401
-HESSIAN_EXACT, HESSIAN_BFGS, HESSIAN_DAMPED_BFGS = HESSIAN_APPROXIMATIONS   # the values of IPMOptions.hessian_approximation
+from .quasi_newton import HESSIAN_APPROXIMATIONS, CompactLBFGS, QuasiNewtonOptions  # noqa: F401
+# the values of IPMOptions.hessian_approximation
+HESSIAN_EXACT, HESSIAN_BFGS, HESSIAN_DAMPED_BFGS, HESSIAN_COMPACT_LBFGS = HESSIAN_APPROXIMATIONS
 
 __version__ = "0.1.0"
 from .schur import SchurDenseStage  # noqa: F401,E402

@@ -14,13 +14,15 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of another commit's build of the same ABI (tools/leaf_ab.py, tools/README.md); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip", "lbfgs.hip"]
 HEADERS = ["common.h", "ls.h", "dag_plan.h", "factor_plan.h", "solve_plan.h", "schur_plan.h", "stream_plan.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "ipm_handle.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
 MNK_BUNCHKAUFMAN, MNK_LU, MNK_QR, MNK_CHOLESKY, MNK_LDL, MNK_EVD = 1, 2, 3, 4, 5, 6
 MNK_SC_JT, MNK_SC_HESS, MNK_SC_AUG, MNK_SC_DIAGBUF = 0, 1, 2, 3
 MNK_QN_BFGS, MNK_QN_DAMPED_BFGS = 1, 2
+MNK_SC_JT_KEPT = 4
+MNK_LBFGS_S, MNK_LBFGS_Y, MNK_LBFGS_U, MNK_LBFGS_V, MNK_LBFGS_L, MNK_LBFGS_D, MNK_LBFGS_T, MNK_LBFGS_W = range(8)
 
 
 def _stale() -> bool:
@@ -99,6 +101,17 @@ SIGNATURES = {
     "mnk_sc_build": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "mnk_sc_get_values": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "mnk_sc_spmv": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, C.c_double, _vp]),
+    "mnk_lbfgs_create": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "mnk_lbfgs_destroy": (C.c_int, [_vp]),
+    "mnk_lbfgs_init": (C.c_int, [_vp, _vp, C.c_double, C.POINTER(C.c_double)]),
+    "mnk_lbfgs_update": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "mnk_lbfgs_status": (C.c_int, [_vp, _i64p]),
+    "mnk_lbfgs_get": (C.c_int, [_vp, C.c_int, _vp, C.c_int64]),
+    "mnk_lbfgs_gram": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, C.c_int64, _vp]),
+    "mnk_lbfgs_apply": (C.c_int, [_vp, _vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_int64]),
+    "mnk_sc_attach_lbfgs": (C.c_int, [_vp, _vp]),
+    "mnk_sc_keep_jacobian": (C.c_int, [_vp]),
+    "mnk_sc_qn_secant": (C.c_int, [_vp] + [_vp] * 8),
     "mnk_dc_create": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, C.c_int,
                                 C.POINTER(_vp)]),
     "mnk_dc_destroy": (C.c_int, [_vp]),

@@ -40,6 +40,7 @@ struct mnk_sc {
     // device values
     mnk::DevBuf<double> jac_coo, hess_coo, jt_nz, h_nz, aug_nz, diag_buffer, pr_diag, du_diag;
     void* extra = nullptr;  // unit-private device structures (sparse_kkt.hip), owned by the handle
+    mnk_lbfgs* lbfgs = nullptr;   // attached compact L-BFGS handle (lbfgs.hip; not owned): solve_kkt! / mul! include its low-rank term
     // dies with the handle: a linear solver that keeps a way back to this handle's matrix (mnk_ls::src) holds a
     // weak reference and refuses to touch a destroyed handle
     std::shared_ptr<int> alive = std::make_shared<int>(0);
@@ -81,6 +82,11 @@ struct mnk_dc {
 void mnk_dc_qn_release(mnk_dc* dc);   // qn.hip: frees mnk_dc::qn
 
 struct mnk_ls;
+// lbfgs.hip, for the sparse condensed handle an mnk_lbfgs is attached to (w_x, x_x: the n leading entries of device KKT vectors)
+int64_t mnk_lbfgs_order(const mnk_lbfgs* qn);
+int mnk_lbfgs_solve_correct(mnk_lbfgs* qn, mnk_ls* ls, double* wx);   // w_x -= H W E'w_x behind the condensed solve with `ls` (builds H, T, W when `ls`, its factorization or the memory changed)
+int mnk_lbfgs_mul_add(mnk_lbfgs* qn, double* wx, const double* xx, double alpha);   // w_x += alpha E P E'x_x
+int mnk_lbfgs_check(mnk_lbfgs* qn, const char* who);   // -4 (and the message) if a singular T has been flagged since the last build; reads a pinned word, no synchronization
 
 // An algorithm that factors the transferred matrix by something other than the tiled Cholesky / LDL^T: QR (qr.hip), LU (lu.hip),
 // EVD (evd.hip).  It owns its buffers; the matrix, the factor buffer, dvec, xwork and the pinned words are the solver's.
@@ -194,7 +200,8 @@ struct FactorVerdict {
     int info = 0;
     int64_t npos = 0, nzero = 0, nneg = 0;
     int64_t early_rejects = 0, early_reject_col = -1, early_reject_redone = 0;
-    void queued() { stage = Stage::Queued; bk = false; }
+    int64_t serial = 0;   // factorizations queued by this solver: what a cache of something solved with the factor is keyed on (lbfgs.hip)
+    void queued() { stage = Stage::Queued; bk = false; ++serial; }
     void launch_failed() { stage = Stage::None; }
     void accept(int info_, int64_t npos_, int64_t nzero_, int64_t nneg_) { stage = Stage::Accepted; info = info_; npos = npos_; nzero = nzero_; nneg = nneg_; }
     void reject_early(int64_t npos_, int64_t nzero_, int64_t N, int64_t col) {   // the one place that writes an early-rejected verdict
@@ -390,6 +397,7 @@ struct mnk_ls {
                                  // of a rejected matrix is then not usable and its inertia is a lower bound on num_neg
     LeadingBlockProbe probe;
     int accept_only_pd = 0;      // option: the caller accepts positive definite matrices only: "not PD" from the static tier is final
+    bool src_lowrank = false;    // the KKT handle factored last has a compact L-BFGS handle attached: its solves need mnk_sc_solve_kkt (mnk_ls_solve_batch refuses)
     int dag_debug = 0;           // option: keep the progress words of a factorization that timed out (mnk_ls_debug_dag_state)
     mnk::DevBuf<int> dag_dbg;    // 8 words per chain strip (PpDag::dbg)
     std::vector<int> dbg_flags, dbg_chain;

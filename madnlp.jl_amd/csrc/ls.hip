@@ -571,6 +571,7 @@ int mnk_ls_factorize_sc_async(mnk_ls* ls, mnk_sc* sc) {
     MNK_REQUIRE(sc->n >= ls->N, "mnk_ls_factorize_sc: the solver's order exceeds the KKT system's");
     MNK_HIP(hipSetDevice(ls->ctx->device));
     { int rc_d = mnk_ls_sync_deferred(ls); if (rc_d) return rc_d; }   // (a factorize! of this solver pending in an open batch runs first)
+    ls->src_lowrank = sc->lbfgs != nullptr;
     int rc = ensure_wbuf(ls);
     if (rc) return rc;
     bool probe_rejected = false;
@@ -855,6 +856,8 @@ int mnk_ls_solve(mnk_ls* ls, double* x, int64_t nrhs, int64_t ldx, int loc) {
 int mnk_sc_step_batch(int n, mnk_sc* const* sc, mnk_ls* const* ls, const double* const* jac_coo, const double* const* hess_coo,
                       const double* const* pr_diag, const double* const* du_diag, int loc) {
     MNK_REQUIRE(n >= 0 && (n == 0 || (sc && ls && jac_coo && hess_coo && pr_diag && du_diag)), "mnk_sc_step_batch: NULL argument");
+    for (int i = 0; i < n; ++i)
+        MNK_REQUIRE(sc[i] == nullptr || sc[i]->lbfgs == nullptr, "mnk_sc_step_batch: a system with a compact L-BFGS handle attached is not batched");
     int rc = mnk_factorize_batch_begin();
     if (rc) return rc;
     for (int i = 0; i < n && !rc; ++i) {
@@ -878,6 +881,8 @@ int mnk_ls_inertia_batch(int n, mnk_ls* const* ls, int64_t* num_pos, int64_t* nu
 
 int mnk_ls_solve_batch(int n, mnk_ls* const* ls, double* const* x, int loc) {
     MNK_REQUIRE(n >= 0 && (n == 0 || (ls && x)), "mnk_ls_solve_batch: NULL argument");
+    for (int i = 0; i < n; ++i)
+        MNK_REQUIRE(ls[i] == nullptr || !ls[i]->src_lowrank, "mnk_ls_solve_batch: the system factored last has a compact L-BFGS handle attached (its solves go through mnk_sc_solve_kkt)");
     int rc = mnk_solve_batch_begin();
     if (rc) return rc;
     for (int i = 0; i < n && !rc; ++i) rc = mnk_ls_solve(ls[i], x[i], 1, ls[i]->N, loc);

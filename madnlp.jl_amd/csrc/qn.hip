@@ -386,6 +386,19 @@ int mnk_dc_qn_secant(mnk_dc* dc, const double* x, const double* g, const double*
     return 0;
 }
 
+// the same launch for the sparse condensed handle (compact L-BFGS, lbfgs.hip)
+int mnk_sc_qn_secant(mnk_sc* sc, const double* x, const double* g, const double* jl, const double* jv, double* last_x,
+                     double* last_g, double* sk, double* yk) {
+    MNK_REQUIRE(sc && sc->ctx && x && g && last_x && last_g && sk && yk, "mnk_sc_qn_secant: NULL argument or host-only handle");
+    MNK_REQUIRE((jl == nullptr) == (jv == nullptr), "mnk_sc_qn_secant: jl and jv are given together or not at all");
+    MNK_HIP(hipSetDevice(sc->ctx->device));
+    const int64_t blocks = std::min<int64_t>((sc->n + 255) / 256, QN_MAX_GRID);
+    hipLaunchKernelGGL(qn_secant_kernel, dim3((unsigned)blocks), dim3(256), 0, sc->ctx->stream, x, g, jl, jv, last_x, last_g, sk, yk,
+                       sc->n);
+    MNK_HIP(hipGetLastError());
+    return 0;
+}
+
 int mnk_dc_qn_status(mnk_dc* dc, int64_t* updates, int64_t* skipped, double* last) {
     MNK_REQUIRE(dc, "mnk_dc_qn_status: NULL argument");
     QnState* q = qn_of(dc);

@@ -171,6 +171,7 @@ struct mnk_sc_extra {
     DevBuf<int32_t> hs_ptr, hs_idx, hs_perm;      // rows of Symmetric(hess_com, :L)
     KktVecState st;                               // bound structure, barrier terms, work vectors (kkt_vec.h)
     DevBuf<double> buffer, buffer2;               // m, m: device-side solve_kkt!
+    DevBuf<double> jt_kept;                       // nnz_jt: the compressed J' values at mnk_sc_keep_jacobian (MNK_SC_JT_KEPT)
 };
 static mnk_sc_extra* extra_of(mnk_sc* sc) { return static_cast<mnk_sc_extra*>(sc->extra); }
 static const char* const SC_NULL = "NULL argument or host-only handle";
@@ -490,13 +491,16 @@ int mnk_sc_spmv(mnk_sc* sc, int which, int trans, double alpha, const double* x,
     mnk_sc_extra* sp = extra_of(sc);
     MNK_REQUIRE(sp != nullptr, "mnk_sc_spmv: unknown handle");
     hipStream_t s = sc->ctx->stream;
+    MNK_REQUIRE(which != MNK_SC_JT_KEPT || sp->jt_kept.p != nullptr, "mnk_sc_spmv: MNK_SC_JT_KEPT needs mnk_sc_keep_jacobian first");
+    const double* jt = which == MNK_SC_JT_KEPT ? sp->jt_kept.p : sc->jt_nz.p;
+    if (which == MNK_SC_JT_KEPT) which = MNK_SC_JT;
     if (which == MNK_SC_JT && trans == 0) {
         hipLaunchKernelGGL(gather_spmv_kernel, dim3((unsigned)((sc->n + 255) / 256)), dim3(256), 0, s, y, x,
-                           sc->jt_nz.p, sp->jtr_ptr.p, sp->jtr_idx.p, sp->jtr_perm.p, alpha, beta, sc->n);
+                           jt, sp->jtr_ptr.p, sp->jtr_idx.p, sp->jtr_perm.p, alpha, beta, sc->n);
     } else if (which == MNK_SC_JT) {
         if (sc->m > 0)
             hipLaunchKernelGGL(gather_spmv_kernel, dim3((unsigned)((sc->m + 255) / 256)), dim3(256), 0, s, y, x,
-                               sc->jt_nz.p, sc->d_jt_colptr.p, sc->d_jt_rowval.p, (const int32_t*)nullptr, alpha,
+                               jt, sc->d_jt_colptr.p, sc->d_jt_rowval.p, (const int32_t*)nullptr, alpha,
                                beta, sc->m);
     } else if (which == MNK_SC_HESS) {
         hipLaunchKernelGGL(gather_spmv_kernel, dim3((unsigned)((sc->n + 255) / 256)), dim3(256), 0, s, y, x,
@@ -506,6 +510,25 @@ int mnk_sc_spmv(mnk_sc* sc, int which, int trans, double alpha, const double* x,
         return -1;
     }
     MNK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- compact L-BFGS (lbfgs.hip): the attached handle, and the Jacobian of the previous iterate for y_k = ... - J(x_k)' l_+ ----
+int mnk_sc_attach_lbfgs(mnk_sc* sc, void* qn_) {
+    mnk_lbfgs* qn = static_cast<mnk_lbfgs*>(qn_);
+    MNK_REQUIRE(sc && sc->ctx, "mnk_sc_attach_lbfgs: NULL argument or host-only handle");
+    MNK_REQUIRE(qn == nullptr || mnk_lbfgs_order(qn) == sc->n, "mnk_sc_attach_lbfgs: the handle's n differs from the system's");
+    sc->lbfgs = qn;
+    return 0;
+}
+
+int mnk_sc_keep_jacobian(mnk_sc* sc) {
+    MNK_REQUIRE(sc && sc->ctx && extra_of(sc), "mnk_sc_keep_jacobian: NULL argument or host-only handle");
+    MNK_HIP(hipSetDevice(sc->ctx->device));
+    mnk_sc_extra* sp = extra_of(sc);
+    if (sp->jt_kept.p == nullptr && sp->jt_kept.alloc(sc->nnz_jt)) return -2;
+    if (sc->nnz_jt > 0)
+        MNK_HIP(hipMemcpyAsync(sp->jt_kept.p, sc->jt_nz.p, sc->nnz_jt * sizeof(double), hipMemcpyDeviceToDevice, sc->ctx->stream));
     return 0;
 }
 
@@ -586,7 +609,7 @@ int mnk_sc_solve_kkt(mnk_sc* sc, mnk_ls* ls, double* w, int loc) {
     mnk_sc_extra* sp = extra_of(sc);
     hipStream_t s = sc->ctx->stream;
     const int64_t n = sc->n, m = sc->m;
-    return kkt_solve_kkt(sp->st, sc->ctx, "mnk_sc_solve_kkt", ls, n + 2 * m, w, loc, [&](double* d) -> int {
+    rc = kkt_solve_kkt(sp->st, sc->ctx, "mnk_sc_solve_kkt", ls, n + 2 * m, w, loc, [&](double* d) -> int {
         double *ws = d + n, *wz = d + n + m;
         const double* Ss = sc->pr_diag.p + n;
         if (m > 0) {
@@ -596,6 +619,10 @@ int mnk_sc_solve_kkt(mnk_sc* sc, mnk_ls* ls, double* w, int loc) {
         }
         int rc = mnk_ls_solve(ls, d, 1, n, MNK_DEVICE);
         if (rc) return rc;
+        if (sc->lbfgs != nullptr) {   // the low-rank term of the Hessian, on the condensed solution (Sherman-Morrison-Woodbury)
+            rc = mnk_lbfgs_solve_correct(sc->lbfgs, ls, d);
+            if (rc) return rc;
+        }
         if (m > 0) {
             rc = mnk_sc_spmv(sc, MNK_SC_JT, 1, 1.0, d, 0.0, sp->buffer2.p);  // buffer2 = Jt' * wx
             if (rc) return rc;
@@ -603,6 +630,9 @@ int mnk_sc_solve_kkt(mnk_sc* sc, mnk_ls* ls, double* w, int loc) {
         }
         return 0;
     });
+    // host vectors: the frame has waited for the stream, a singular T of this call is known (device vectors: at the next call)
+    if (!rc && sc->lbfgs != nullptr && loc != MNK_DEVICE) rc = mnk_lbfgs_check(sc->lbfgs, "mnk_sc_solve_kkt");
+    return rc;
 }
 
 int mnk_sc_mul(mnk_sc* sc, double* w, const double* x, double alpha, double beta, int loc) {
@@ -622,6 +652,7 @@ int mnk_sc_mul(mnk_sc* sc, double* w, const double* x, double alpha, double beta
             if (rc) return rc;
         }
         hipLaunchKernelGGL(kktmul_diag_kernel, MNK_GRID(n + 2 * m), dw, dx, sp->st.reg.p, sc->du_diag.p, alpha, beta, n, m);
+        if (sc->lbfgs != nullptr) return mnk_lbfgs_mul_add(sc->lbfgs, dw, dx, alpha);   // wx += alpha E P E' xx
         return 0;
     });
 }

@@ -22,8 +22,8 @@ reference closely enough that iteration counts and residual histories are meanin
 NLP scaling (`nlp_scaling`, off by default) and the objective sense (a model's `minimize` attribute): `set_scaling!`
 src/IPM/solver.jl:37-49 with the factor functions of src/Callbacks/nlpmodels.jl:222-264, the callback wrappers :771-906 and
 src/IPM/callbacks.jl:9,28-30,82, un-scaled results (`solution()`) nlpmodels.jl:649-661.
-Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems):
-`quasi_newton.py` and `eval_lag_hess` below (src/IPM/callbacks.jl:145-190).
+Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems; `"compact_lbfgs"`, the sparse
+condensed system behind `kkt.LowRankHessianKKT`): `quasi_newton.py` and `eval_lag_hess` below (src/IPM/callbacks.jl:145-190).
 
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
 mirror (`madnlp_jl_amd.kkt`) or, in the tests, the CPU oracle.
@@ -41,8 +41,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .backsolve import ITERATORS, KrylovIterator, RichardsonIterator
-from .kkt import UnreducedKKTVector
-from .quasi_newton import HESSIAN_APPROXIMATIONS, create_quasi_newton
+from .kkt import LowRankHessianKKT, UnreducedKKTVector
+from .quasi_newton import HESSIAN_APPROXIMATIONS, QuasiNewtonOptions, create_quasi_newton
 
 INF = float("inf")
 EPS = np.finfo(np.float64).eps
@@ -105,9 +105,16 @@ class IPMOptions:
     inertia_free_tol: float = 0.0
     soft_resto_pderror_reduction_factor: float = 0.9999  # options.jl:178
     required_infeasibility_reduction: float = 0.9        # options.jl:179
-    # options.jl `hessian_approximation`: "exact" (ExactHessian), "bfgs" (BFGS), "damped_bfgs" (DampedBFGS); the last two on
-    # the dense KKT systems only (the reference has no dense BFGS for sparse systems, and CompactLBFGS is not part of this project)
+    # options.jl `hessian_approximation`: "exact" (ExactHessian), "bfgs" (BFGS), "damped_bfgs" (DampedBFGS) -- these two on
+    # the dense KKT systems only (the reference has no dense BFGS for sparse systems) -- and "compact_lbfgs" (CompactLBFGS) on
+    # the sparse condensed system only, with the fields of the reference's QuasiNewtonOptions (quasi_newton.jl:63-69;
+    # qn_init_strategy 1 .. 4 = SCALAR1 .. SCALAR4)
     hessian_approximation: str = "exact"
+    qn_max_history: int = 6
+    qn_init_strategy: int = 1
+    qn_init_value: float = 1.0
+    qn_sigma_min: float = 1e-8
+    qn_sigma_max: float = 1e8
     # options.jl:164-165.  The reference's default is `true`; here it is False because every recorded trajectory, golden file
     # and profile of this project was made without scaling -- switching the default is a change of its own
     nlp_scaling: bool = False
@@ -389,17 +396,28 @@ class MadNLPSolver:
         o = self.opt
         if o.hessian_approximation not in HESSIAN_APPROXIMATIONS:
             raise ValueError(f"hessian_approximation must be one of {HESSIAN_APPROXIMATIONS}, not {o.hessian_approximation!r}")
-        if o.hessian_approximation != "exact" and sparse:
+        self.lbfgs = o.hessian_approximation == "compact_lbfgs"
+        if self.lbfgs and not sparse:
+            raise ValueError("hessian_approximation = 'compact_lbfgs' needs the sparse condensed KKT system (sparse=True)")
+        if o.hessian_approximation != "exact" and sparse and not self.lbfgs:
             raise ValueError(f"hessian_approximation = {o.hessian_approximation!r} needs a dense KKT system (sparse=False)")
         n, m = nlp.n, nlp.m
-        self.qn = None if o.hessian_approximation == "exact" else create_quasi_newton(o.hessian_approximation, n)
+        qn_opt = QuasiNewtonOptions(init_strategy=o.qn_init_strategy, max_history=o.qn_max_history, init_value=o.qn_init_value,
+                                    sigma_min=o.qn_sigma_min, sigma_max=o.qn_sigma_max)
+        self.qn = None if o.hessian_approximation == "exact" else create_quasi_newton(o.hessian_approximation, n, qn_opt)
         idx = parse_indexes(np.asarray(nlp.lvar, float), np.asarray(nlp.uvar, float), np.asarray(nlp.lcon, float),
                             np.asarray(nlp.ucon, float), enforce_equality=not o.relax_equality)
         self.idx = idx
         self.n, self.m, self.ns = n, m, len(idx["ind_ineq"])
         self.ind_ineq, self.ind_lb, self.ind_ub = idx["ind_ineq"], idx["ind_lb"], idx["ind_ub"]
         self.ind_llb, self.ind_uub = idx["ind_llb"], idx["ind_uub"]
-        self.kkt = kkt_factory(dict(n=n, m=m, **idx))
+        if self.lbfgs:
+            # the diagonal Hessian pattern the reference's build_hessian_structure gives a quasi-Newton method: the n-vector
+            # `get_hessian()` holds sigma.  Factories written for exact Hessians read the model's own pattern instead
+            diag = np.arange(n, dtype=np.int64)
+            self.kkt = LowRankHessianKKT(kkt_factory(dict(n=n, m=m, hess_I=diag, hess_J=diag, **idx)), self.qn)
+        else:
+            self.kkt = kkt_factory(dict(n=n, m=m, **idx))
         nt = n + self.ns
         self.x, self.xl, self.xu = np.zeros(nt), idx["xl"].copy(), idx["xu"].copy()
         self.zl, self.zu, self.f = np.zeros(nt), np.zeros(nt), np.zeros(nt)
@@ -485,6 +503,11 @@ class MadNLPSolver:
         l = l * self.con_scale
         if hasattr(self.nlp, "jtprod"):
             return np.asarray(self.nlp.jtprod(x, l), dtype=float)
+        if self.sparse:
+            out = np.zeros(self.n)
+            np.add.at(out, np.asarray(self.nlp.jac_J, dtype=np.int64),
+                      self.nlp.jac_coord(x) * l[np.asarray(self.nlp.jac_I, dtype=np.int64)])
+            return out
         return self.nlp.jac_dense(x).T @ l
 
     def _eval_lag_hess_qn(self, x, y):
@@ -924,7 +947,16 @@ class MadNLPSolver:
             if norm_dx is None:   # at most one reduction per line search
                 norm_dx = self._norm2(dx)
             if self.alpha * norm_dx < EPS * 10:
-                return "SEARCH_DIRECTION_BECOMES_TOO_SMALL"
+                self.cnt.restoration_fail_count += 1
+                if self.cnt.restoration_fail_count >= 4:
+                    return "SOLVED_TO_ACCEPTABLE_LEVEL" if self.cnt.acceptable_cnt > 0 else "SEARCH_DIRECTION_BECOMES_TOO_SMALL"
+                # the reference's "second chance" (line_search.jl:79-96), as in filter_line_search_RR below: the first three
+                # times the regular phase starts again from the current iterate with y = 0, z = 1 and an empty filter
+                self._vfill(self.y, 0.0)
+                self._bound_dual_fill(1.0)
+                self.filter = [(self.theta_max, -INF)]
+                self.cnt.k += 1
+                return "REGULAR"
         if unsuccessful:
             self.cnt.unsuccessful_iterate += 1
             if self.cnt.unsuccessful_iterate >= 4:

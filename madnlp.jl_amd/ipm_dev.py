@@ -22,7 +22,9 @@ Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as t
 through `mnk_ipm_gemv` on device copies of P and A.  Initialization runs once on the host (the base class) and is uploaded.
 
 With `hessian_approximation = "bfgs" / "damped_bfgs"` (dense systems) the Hessian approximation lives in the KKT handle's
-device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model's Hessian is never loaded."""
+device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model's Hessian is never loaded.  With
+`"compact_lbfgs"` (sparse condensed system) the history, U and V live in an `mnk_lbfgs` handle attached to the KKT handle
+(csrc/lbfgs.hip), whose `solve_kkt!` / `mul!` apply the low-rank term: the loop below does not know about it."""
 from __future__ import annotations
 
 
@@ -40,13 +42,36 @@ def _up(a, dev, dtype=np.float64):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
 
 
+class DeviceHessianProduct:
+    """out = Symmetric(H, :L) x on the device for a fixed sparse H: a bare `mnk_sc` handle (no constraints, no solver) that is
+    used for its compressed Hessian and `mnk_sc_spmv` only.  `DeviceQPCallbacks` evaluates the objective through the KKT
+    handle's own Hessian; under a quasi-Newton method that handle holds the approximation, and the model's H lives here."""
+
+    def __init__(self, ctx, n, hess_I, hess_J, hv):
+        hI, hJ = np.ascontiguousarray(hess_I, dtype=np.int32), np.ascontiguousarray(hess_J, dtype=np.int32)
+        e = np.zeros(1, dtype=np.int32)
+        self._h = C.c_void_p()
+        L.check(L.lib().mnk_sc_create(ctx.handle, int(n), 0, 0, e.ctypes.data, e.ctypes.data, len(hI), hI.ctypes.data,
+                                      hJ.ctypes.data, 0, C.byref(self._h)), "mnk_sc_create")
+        L.check(L.lib().mnk_sc_compress_hessian(self._h, hv.data_ptr(), L.MNK_DEVICE), "mnk_sc_compress_hessian")
+
+    def mul(self, x, out):
+        L.check(L.lib().mnk_sc_spmv(self._h, L.MNK_SC_HESS, 0, 1.0, x.data_ptr(), 0.0, out.data_ptr()), "mnk_sc_spmv")
+
+    def close(self):
+        if self._h:
+            L.lib().mnk_sc_destroy(self._h)
+            self._h = C.c_void_p()
+
+
 class DeviceQPCallbacks:
     """f = 0.5 x'Hx + q'x, c = Jx with H = Symmetric(hess_com, :L) and J = jt_csc' held by the KKT handle.  The data ARE the
     handle's, so NLP scaling and the sense go into them once, on the host (`prescaled`): H and q times `obj_factor` = obj_sign
     obj_scale, the rows of J times `con_scale`; the solver applies no factor to what these callbacks return."""
     prescaled = True
 
-    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None):
+    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None, own_hessian=False):
+        """`own_hessian`: the KKT handle's Hessian is a quasi-Newton approximation; H gets a `DeviceHessianProduct`."""
         self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
         q, jv, hv = np.asarray(nlp.q, float), np.asarray(nlp.jac_coord(None), float), np.asarray(nlp.hess_coord(None, None, 1.0), float)
         if obj_factor != 1.0:
@@ -60,8 +85,12 @@ class DeviceQPCallbacks:
         K.vec_fill(self.hv0, 0.0)
         self.handle_has_H = True
         self._hx = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.H = DeviceHessianProduct(kkt.ctx, nlp.n, nlp.hess_I, nlp.hess_J, self.hv) if own_hessian else None
 
     def _hmul(self, x):
+        if self.H is not None:
+            self.H.mul(x, self._hx)
+            return self._hx
         # the SpMV runs on the handle's compressed Lagrangian Hessian: while that holds something else (zero after
         # initialize!(kkt), objective weight 0 in robust!) H is put back for the product
         if not self.handle_has_H:
@@ -99,7 +128,8 @@ class DeviceQPCallbacks:
         self.load_hess(sigma=0.0)
 
     def close(self):
-        pass
+        if self.H is not None:
+            self.H.close()
 
 
 class DeviceDenseQPCallbacks:
@@ -369,8 +399,12 @@ class DeviceMadNLPSolver(MadNLPSolver):
             cls = DeviceQPCallbacks if self.sparse else DeviceDenseQPCallbacks
         # NLP scaling / the sense: the scaled launches replace the plain ones only when there is something to apply
         self._scaled = bool(self.opt.nlp_scaling) or self.obj_sign != 1.0
+        if self.lbfgs:               # the host mirror (kkt.LowRankHessianKKT) comes off: the handle applies the low-rank term itself
+            self.kkt = self.iterator.kkt = self.kkt.inner
         if cls.prescaled:
             scaled_data = dict(obj_factor=self.obj_sign * self.obj_scale, con_scale=self.con_scale) if self._scaled else {}
+            if self.lbfgs:
+                scaled_data["own_hessian"] = True
             self.cb = cls(self.nlp, self.kkt, self.dev, self.K, **scaled_data)
         else:
             self.cb = cls(self.nlp, self.kkt, self.dev, self.K)
@@ -391,6 +425,8 @@ class DeviceMadNLPSolver(MadNLPSolver):
                 self.cb.load_hess()
             else:
                 self._qn_upload()
+        elif self.lbfgs:
+            self._lbfgs_upload()
         self._on_device = True
         self._sync = ctx.synchronize
 
@@ -442,6 +478,8 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_lag_hess(self, x, y, is_resto=False):
         if not self._on_device:
             return super().eval_lag_hess(x, y, is_resto)
+        if self.lbfgs:
+            return self._eval_lag_hess_lbfgs_device(x, y)
         if self.qn is not None:
             return self._eval_lag_hess_qn_device(x, y)
         w = 0.0 if is_resto else 1.0                                 # objective weight 0 in robust!
@@ -481,6 +519,42 @@ class DeviceMadNLPSolver(MadNLPSolver):
             jv = d.last_jv
         self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
         self.kkt.qn_update_device(d.sk, d.yk)
+
+    # ------------------------------------------------------------------ compact L-BFGS in a handle attached to the KKT handle
+    def _lbfgs_upload(self):
+        """The host initialization has run `init!` on the mirror; the device handle is created with the same options, attached
+        to the KKT handle and runs its own `init!` from the uploaded gradient (the same ordered sum, the same sigma).  The
+        backups of callbacks.jl:184-186 become device vectors, and the compressed Jacobian of the initial point is kept for
+        J(x_0)' l_1.  From here on no Hessian callback is launched."""
+        from types import SimpleNamespace
+        n = self.n
+        qd = self.kkt.attach_quasi_newton(self.qn.options)
+        d = SimpleNamespace(**{k: self._new_vec(n) for k in ("sk", "yk", "last_x", "last_g", "last_jv", "hess")})
+        self.K.vec_copy(d.last_x, self.x[:n])
+        self.K.vec_copy(d.last_g, self.f[:n])
+        self.K.vec_fill(d.hess, qd.init(self.f[:n], self.obj_val))
+        self.kkt.compress_hessian(d.hess)
+        self.kkt.keep_jacobian_device()
+        self.qn_dev = d
+
+    def _eval_lag_hess_lbfgs_device(self, x, y):
+        """`MadNLPSolver._eval_lag_hess_qn` for `CompactLBFGS` on device vectors.  J(x_k)' l_+ comes from the Jacobian values the
+        handle kept at the previous call (already scaled: no con_scale product, no model call), s, y and the backups from one
+        launch (`mnk_sc_qn_secant`), then `mnk_lbfgs_update` (one synchronization).  A performed update changes sigma: the
+        diagonal Hessian is refilled and compressed."""
+        n, d = self.n, self.qn_dev
+        assert self.cnt.obj_grad_cnt >= 2, "the first call (init!) belongs to the host initialization"
+        jl = jv = None
+        if self.m > 0:
+            jl = self.jacl[:n]
+            self.kkt.spmv_device(L.MNK_SC_JT_KEPT, 0, 1.0, y, 0.0, d.last_jv)
+            jv = d.last_jv
+        self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
+        self.kkt.keep_jacobian_device()
+        performed, sigma = self.kkt.qn_dev.update(d.sk, d.yk)
+        if performed:
+            self.K.vec_fill(d.hess, sigma)
+            self.kkt.compress_hessian(d.hess)
 
     def jtprod(self, out, y):
         """`jtprod!` reference src/KKT/Sparse/condensed.jl:150-156."""
@@ -803,7 +877,8 @@ class DeviceMadNLPSolver(MadNLPSolver):
         reg = pr_diag = 1, du_diag = 0, l_diag = u_diag = 1, l_lower = u_lower = 0 through the feeder (x = 0, xl = 1,
         xu = -1, zl = zu = 0, primal_reg = 1)."""
         self.kkt.initialize()
-        self.cb.zero_hess()        # (a quasi-Newton run too: the reference's initialize!(kkt) zeroes its approximation here)
+        if not self.lbfgs:         # (compact L-BFGS: the handle's diagonal Hessian was zeroed just above, the model's is never loaded)
+            self.cb.zero_hess()    # (a dense quasi-Newton run too: the reference's initialize!(kkt) zeroes its approximation here)
         nt = self.nt
         z = np.zeros(nt)
         self.kkt.set_aug_diagonal_device(z, np.ones(nt), -np.ones(nt), z, z, 1.0, 0.0)

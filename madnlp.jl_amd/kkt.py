@@ -193,6 +193,162 @@ class _KKTCommon:
         w.dual_ub()[:] = beta * w.dual_ub() + alpha * (xv[x.ind_ub] * self.u_lower + x.dual_ub() * self.u_diag)
 
 
+# ------------------------------------------------------------ compact L-BFGS around any KKT system
+class LowRankHessianKKT:
+    """A KKT system whose Hessian is B = sigma I - U U' + V V' (`quasi_newton.CompactLBFGS`): `inner` is any KKT object of this
+    tree with the diagonal Hessian pattern (its Hessian vector holds sigma), `qn` holds U and V.  Everything is forwarded to
+    `inner` except the three operations that see the Hessian.  With E = [U V] and P = diag(-I_p, I_p) the matrix is
+    K = K0 + E_ P E_' (E_ = E padded with zero rows to the length of a KKT vector), and as in the reference
+    (`src/IPM/factorization.jl:76-140`)
+
+        K^-1 w = K0^-1 w - HH T^-1 E'(K0^-1 w)_x,    HH = K0^-1 E_  (one `inner.solve_kkt` per column),    T = P + E' HH_x.
+
+    HH and T^-1 are rebuilt after a `build_kkt` or a performed / resetting update only (`builds` counts), never per solve.
+    The inertia is the inner system's.  This is the host mirror and comparator of the device path (`csrc/lbfgs.hip`,
+    `SparseCondensedKKTSystem.attach_quasi_newton`): the sums over n are `ordered_sum`s (`quasi_newton.lowrank_apply`)."""
+    _OWN = ("inner", "qn", "builds", "_key", "_epoch", "_HH", "_W", "T")
+
+    def __init__(self, inner, qn):
+        self.inner, self.qn = inner, qn
+        self.builds = 0
+        self._epoch = 0          # bumped by every build_kkt
+        self._key = None
+        self._HH = self._W = self.T = None
+
+    def __getattr__(self, name):
+        return getattr(self.inner, name)
+
+    def __setattr__(self, name, value):
+        if name in LowRankHessianKKT._OWN:
+            object.__setattr__(self, name, value)
+        else:
+            setattr(self.inner, name, value)
+
+    def build_kkt(self, *args, **kw):
+        self._epoch += 1
+        return self.inner.build_kkt(*args, **kw)
+
+    def build_kkt_device(self, *args, **kw):
+        self._epoch += 1
+        return self.inner.build_kkt_device(*args, **kw)
+
+    def _ensure(self, like):
+        from .quasi_newton import gram
+        key = (self._epoch, self.qn.version, id(getattr(self.inner, "linear_solver", None)))
+        if key == self._key:
+            return
+        qn, n = self.qn, self.qn.n
+        E = qn.E
+        q = E.shape[1]
+        HH = np.zeros((len(like.values), q))
+        for j in range(q):
+            v = like.copy()
+            v.values[:] = 0.0
+            v.values[:n] = E[:, j]
+            HH[:, j] = self.inner.solve_kkt(v).values
+        self.T = qn.P + gram(E, HH[:n])
+        try:
+            self._W = np.linalg.inv(self.T)
+        except np.linalg.LinAlgError:
+            from .linear_solver import SolveException
+            raise SolveException("LowRankHessianKKT: T = P + E' K0^-1 E is singular") from None
+        self._HH = HH
+        self._key = key
+        self.builds += 1
+
+    def solve_kkt(self, w):
+        from .quasi_newton import lowrank_apply
+        self.inner.solve_kkt(w)
+        if self.qn.current_mem > 0:
+            self._ensure(w)
+            lowrank_apply(w.values, -1.0, self._HH, self._W, self.qn.E, w.values[:self.qn.n].copy())
+        return w
+
+    def mul(self, w, x, alpha=1.0, beta=0.0):
+        from .quasi_newton import lowrank_apply
+        self.inner.mul(w, x, alpha, beta)
+        if self.qn.current_mem > 0:
+            n = self.qn.n
+            lowrank_apply(w.values[:n], alpha, self.qn.E, self.qn.P, self.qn.E, x.values[:n])
+        return w
+
+    def mul_hess_blk(self, wx, t):
+        from .quasi_newton import lowrank_apply
+        self.inner.mul_hess_blk(wx, t)
+        if self.qn.current_mem > 0:
+            n = self.qn.n
+            lowrank_apply(wx[:n], 1.0, self.qn.E, self.qn.P, self.qn.E, t[:n])
+        return wx
+
+
+class DeviceCompactLBFGS:
+    """The `mnk_lbfgs` handle (csrc/lbfgs.hip): `quasi_newton.CompactLBFGS` with S, Y, U, V on the device."""
+
+    def __init__(self, ctx, n, options=None):
+        from .quasi_newton import QuasiNewtonOptions
+        o = options or QuasiNewtonOptions()
+        self.ctx, self.n, self.options = ctx, int(n), o
+        self._h = C.c_void_p()
+        L.check(L.lib().mnk_lbfgs_create(ctx.handle, int(n), int(o.max_history), int(o.init_strategy), float(o.init_value),
+                                         float(o.sigma_min), float(o.sigma_max), C.byref(self._h)), "mnk_lbfgs_create")
+        _LIVE_OBJECTS.add(self)
+
+    def init(self, g0, f0):
+        """`init!`: the value of the diagonal Hessian, 2 rho0 init_value (`g0`: device tensor of n doubles)."""
+        xi = C.c_double()
+        L.check(L.lib().mnk_lbfgs_init(self._h, g0.data_ptr(), float(f0), C.byref(xi)), "mnk_lbfgs_init")
+        return xi.value
+
+    def update(self, s, y):
+        """`update!` with device tensors: (performed, sigma)."""
+        done, sigma = C.c_int(), C.c_double()
+        L.check(L.lib().mnk_lbfgs_update(self._h, s.data_ptr(), y.data_ptr(), C.byref(done), C.byref(sigma)), "mnk_lbfgs_update")
+        return bool(done.value), sigma.value
+
+    def status(self):
+        out = (C.c_int64 * 8)()
+        L.check(L.lib().mnk_lbfgs_status(self._h, out), "mnk_lbfgs_status")
+        keys = ("current_mem", "updates", "skipped", "resets", "builds", "singular", "version", "max_history")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def get(self, which):
+        """Host copy of "S", "Y", "U", "V" (n x p), "L" (p x p), "D" (p), "T" or "W" (2p x 2p)."""
+        p = self.status()["current_mem"]
+        code = {"S": L.MNK_LBFGS_S, "Y": L.MNK_LBFGS_Y, "U": L.MNK_LBFGS_U, "V": L.MNK_LBFGS_V, "L": L.MNK_LBFGS_L,
+                "D": L.MNK_LBFGS_D, "T": L.MNK_LBFGS_T, "W": L.MNK_LBFGS_W}[which]
+        rows = {"S": self.n, "Y": self.n, "U": self.n, "V": self.n, "L": p, "D": p, "T": 2 * p, "W": 2 * p}[which]
+        cols = 1 if which == "D" else 2 * p if which in "TW" else p
+        out = np.zeros((max(rows, 1), max(cols, 1)), order="F")
+        L.check(L.lib().mnk_lbfgs_get(self._h, code, out.ctypes.data, out.shape[0]), "mnk_lbfgs_get")
+        out = out[:rows, :cols]
+        return out[:, 0].copy() if which == "D" else out
+
+    def gram(self, A, B):
+        """A'B of device tensors holding column-major n x q matrices (shape (q, n), contiguous): host array q_a x q_b."""
+        qa, n = A.shape
+        qb = B.shape[0]
+        out = np.zeros((qa, qb), order="F")
+        L.check(L.lib().mnk_lbfgs_gram(self._h, A.data_ptr(), n, qa, B.data_ptr(), n, qb, n, out.ctypes.data), "mnk_lbfgs_gram")
+        return out
+
+    def apply(self, y, alpha, A, M, B, x):
+        """y += alpha A (M (B'x)) on device tensors (A, B as in `gram`, M of shape (q, q) holding M' row-major = M column-major)."""
+        q, n = A.shape
+        L.check(L.lib().mnk_lbfgs_apply(self._h, y.data_ptr(), float(alpha), A.data_ptr(), n, M.data_ptr(), B.data_ptr(), n,
+                                        x.data_ptr(), q, n), "mnk_lbfgs_apply")
+
+    def close(self):
+        if self._h:
+            L.lib().mnk_lbfgs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ------------------------------------------------------------ SparseCondensedKKTSystem
 class SparseCondensedKKTSystem(_KKTCommon):
     _PFX = "mnk_sc"
@@ -299,6 +455,37 @@ class SparseCondensedKKTSystem(_KKTCommon):
 
     def restore_diagonals_device(self):
         L.check(L.lib().mnk_sc_restore_diagonals(self._h), "mnk_sc_restore_diagonals")
+
+    # -- compact L-BFGS Hessian (csrc/lbfgs.hip; host mirror: LowRankHessianKKT) --------------------------------------------
+    def attach_quasi_newton(self, options=None):
+        """Create a `DeviceCompactLBFGS` for this system (its Hessian must have the diagonal pattern and holds sigma) and attach
+        it: the device-side `solve_kkt!` / `mul!` include -U U' + V V' from now on.  `options=False` detaches."""
+        old = getattr(self, "qn_dev", None)
+        L.check(L.lib().mnk_sc_attach_lbfgs(self._h, None), "mnk_sc_attach_lbfgs")
+        if old is not None:
+            old.close()
+        self.qn_dev = None
+        if options is False:
+            return None
+        self.qn_dev = DeviceCompactLBFGS(self.ctx, self.n, options)
+        L.check(L.lib().mnk_sc_attach_lbfgs(self._h, self.qn_dev._h), "mnk_sc_attach_lbfgs")
+        return self.qn_dev
+
+    def qn_status(self):
+        return self.qn_dev.status()
+
+    def qn_get(self, which):
+        return self.qn_dev.get(which)
+
+    def keep_jacobian_device(self):
+        """Snapshot of the compressed J' values (`spmv_device(MNK_SC_JT_KEPT, ...)` reads it): taken where the quasi-Newton
+        method backs up x and the gradient, for J(x_k)' l_+ of the next secant pair."""
+        L.check(L.lib().mnk_sc_keep_jacobian(self._h), "mnk_sc_keep_jacobian")
+
+    def qn_secant_device(self, x, g, jl, jv, last_x, last_g, s, y):
+        """`_DenseBase.qn_secant_device` for this handle (device tensors of n doubles; `jl`, `jv` both None without constraints)."""
+        p = [None if v is None else v.data_ptr() for v in (x, g, jl, jv, last_x, last_g, s, y)]
+        L.check(L.lib().mnk_sc_qn_secant(self._h, *p), "mnk_sc_qn_secant")
 
     # -- helpers -----------------------------------------------------------------------
     def _structure(self, which, ncol, nnz):
@@ -462,6 +649,8 @@ class SparseCondensedKKTSystem(_KKTCommon):
             ps.close()
         self._probes = {}
         if self._h:
+            if getattr(self, "qn_dev", None) is not None:
+                self.attach_quasi_newton(False)
             L.lib().mnk_sc_destroy(self._h)
             self._h = C.c_void_p()
 
