@@ -620,6 +620,36 @@ int mnk_ipm_scale_cons(mnk_ipm* ipm, double* c, const double* con_scale, const d
                        int64_t ns, const double* rhs, int64_t m);
 int mnk_ipm_scale_grad(mnk_ipm* ipm, double* f, int64_t n, int64_t ntot, double factor);
 
+/* ---- fixed variables made parameters, fixed_variable_treatment = MakeParameter (csrc/fixed_vars.hip) ---------------------
+ * The reference's MakeParameter callback wrappers (src/Callbacks/nlpmodels.jl:912-1033) on device vectors: the model is
+ * evaluated at its full length, the solver sees the free variables only.  Index arrays are host, 0-based, int64.
+ *   mnk_fix_create      n: the model's variables; free[nfree] and fixed[nfixed] (strictly increasing, disjoint, together all
+ *                       of 0 .. n-1) with the fixed values; ind_jac_free[njac]: the model's Jacobian COO entries (of nnzj_full)
+ *                       whose column is free; ind_hess_free[nhess]: the Hessian COO entries (of nnzh_full) whose row and column
+ *                       are free.  Every index is checked against its range.  Everything is uploaded once; the handle owns a
+ *                       device x_full of n entries whose fixed entries are written here and never again
+ *   mnk_fix_x_full      the device pointer of x_full (what the model's callbacks are given)
+ *   mnk_fix_get_x_full  x_full downloaded to n host doubles (synchronizes; tests and reporting)
+ *   mnk_fix_expand      x_full[free[i]] = x[i], i < nfree
+ *   mnk_fix_gather      dst[i] = (src_full[idx[i]] * scale[i]) * factor with idx = free / ind_jac_free / ind_hess_free for
+ *                       which = MNK_FIX_FREE / _JAC / _HESS; scale = NULL: ones.  Two rounded products (no FMA), the order of
+ *                       the host layer: gather, constraint scaling and the objective factor in one launch
+ *   mnk_fix_dense_grad  g[fixed[i]] = x[fixed[i]] - value[i]: the gradient entries of variables frozen in a dense system
+ * expand, gather and dense_grad are asynchronous on the context's stream, one launch each (none for an empty set), without
+ * allocation, atomics or host round trips.  The handle is an opaque mnk_fix*; like mnk_tape* below the prototypes spell it
+ * void* (mnk_fix_create: void* out = mnk_fix**). */
+typedef struct mnk_fix mnk_fix;
+enum { MNK_FIX_FREE = 0, MNK_FIX_JAC = 1, MNK_FIX_HESS = 2 };
+int mnk_fix_create(mnk_ctx* ctx, int64_t n, int64_t nfree, const int64_t* free_idx, int64_t nfixed, const int64_t* fixed_idx,
+                   const double* fixed_val, int64_t nnzj_full, int64_t njac, const int64_t* ind_jac_free, int64_t nnzh_full,
+                   int64_t nhess, const int64_t* ind_hess_free, void* out);
+int mnk_fix_destroy(void* fix);
+void* mnk_fix_x_full(void* fix);
+int mnk_fix_get_x_full(void* fix, double* out);
+int mnk_fix_expand(void* fix, const double* x);
+int mnk_fix_gather(void* fix, int which, const double* src_full, const double* scale, double factor, double* dst);
+int mnk_fix_dense_grad(void* fix, double* g, const double* x);
+
 /* ---- device evaluation of an NLP model's callbacks: polar AC optimal power flow (callback half) --------
  * What eval_f_wrapper / eval_grad_f_wrapper! / eval_cons_wrapper! / eval_jac_wrapper! / eval_lag_hess_wrapper!
  * (reference src/IPM/callbacks.jl:1-96) obtain from the model through NLPModels.obj / grad! / cons! / jac_coord! /

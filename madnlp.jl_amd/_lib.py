@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of another commit's build of the same ABI (tools/leaf_ab.py, tools/README.md); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip", "lbfgs.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip", "lbfgs.hip", "fixed_vars.hip"]
 HEADERS = ["common.h", "ls.h", "dag_plan.h", "factor_plan.h", "solve_plan.h", "schur_plan.h", "stream_plan.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "ipm_handle.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
@@ -22,6 +22,7 @@ MNK_BUNCHKAUFMAN, MNK_LU, MNK_QR, MNK_CHOLESKY, MNK_LDL, MNK_EVD = 1, 2, 3, 4, 5
 MNK_SC_JT, MNK_SC_HESS, MNK_SC_AUG, MNK_SC_DIAGBUF = 0, 1, 2, 3
 MNK_QN_BFGS, MNK_QN_DAMPED_BFGS = 1, 2
 MNK_SC_JT_KEPT = 4
+MNK_FIX_FREE, MNK_FIX_JAC, MNK_FIX_HESS = 0, 1, 2
 MNK_LBFGS_S, MNK_LBFGS_Y, MNK_LBFGS_U, MNK_LBFGS_V, MNK_LBFGS_L, MNK_LBFGS_D, MNK_LBFGS_T, MNK_LBFGS_W = range(8)
 
 
@@ -203,6 +204,14 @@ SIGNATURES = {
     "mnk_ipm_vec_mul": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64]),
     "mnk_ipm_scale_cons": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64]),
     "mnk_ipm_scale_grad": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_double]),
+    "mnk_fix_create": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64,
+                                 _vp, _vp]),
+    "mnk_fix_destroy": (C.c_int, [_vp]),
+    "mnk_fix_x_full": (_vp, [_vp]),
+    "mnk_fix_get_x_full": (C.c_int, [_vp, _vp]),
+    "mnk_fix_expand": (C.c_int, [_vp, _vp]),
+    "mnk_fix_gather": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, _vp]),
+    "mnk_fix_dense_grad": (C.c_int, [_vp, _vp, _vp]),
     "mnk_ipm_krylov_dots": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.POINTER(C.c_double)]),
     "mnk_ipm_krylov_last_dots": (C.c_int, [_vp, C.POINTER(_vp)]),
     "mnk_ipm_krylov_project": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp]),

@@ -25,6 +25,9 @@ src/IPM/callbacks.jl:9,28-30,82, un-scaled results (`solution()`) nlpmodels.jl:6
 Quasi-Newton Hessians (`hessian_approximation = "bfgs" / "damped_bfgs"`, dense KKT systems; `"compact_lbfgs"`, the sparse
 condensed system behind `kkt.LowRankHessianKKT`): `quasi_newton.py` and `eval_lag_hess` below (src/IPM/callbacks.jl:145-190).
 
+Fixed variables as parameters (`fixed_variable_treatment = "make_parameter"`, off by default): `fixed_vars.py` -- the solver
+evaluates `self.model`, the reduced (sparse) or frozen (dense) view of `self.nlp`, and `unpack_solution` un-reduces.
+
 It is backend agnostic: `kkt_factory(info)` builds any object with the KKT interface -- the HIP
 mirror (`madnlp_jl_amd.kkt`) or, in the tests, the CPU oracle.
 
@@ -41,6 +44,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .backsolve import ITERATORS, KrylovIterator, RichardsonIterator
+from .fixed_vars import TREATMENTS as FIXED_VARIABLE_TREATMENTS, FixedVariableHandler
 from .kkt import LowRankHessianKKT, UnreducedKKTVector
 from .quasi_newton import HESSIAN_APPROXIMATIONS, QuasiNewtonOptions, create_quasi_newton
 
@@ -137,6 +141,10 @@ class IPMOptions:
     krylov_restart: int = 5
     krylov_max_iter: int = 10
     krylov_tol: float = 1e-10
+    # options.jl `fixed_variable_treatment`: "relax_bound" (RelaxBound) or "make_parameter" (MakeParameter, fixed_vars.py).
+    # The reference's default is MakeParameter for every KKT system but the sparse condensed one (options.jl:146); here it is
+    # "relax_bound" for all of them because every recorded trajectory, golden file and profile was made with it
+    fixed_variable_treatment: str = "relax_bound"
 
     @property
     def mu_min(self):
@@ -365,10 +373,14 @@ class Solution:
 
 
 def unpack_solution(solver, x, y, zl, zu):
-    """`unpack_obj`, `unpack_x!`, `unpack_y!`, `unpack_z!` on host copies of the iterate."""
+    """`unpack_obj`, `unpack_x!`, `unpack_y!`, `unpack_z!` on host copies of the iterate.  With variables made parameters
+    (`solver.fixed_handler`) x, zl and zu come back with the model's full length: the fixed entries of x are lvar, those of
+    zl / zu come from `update_z!` (`FixedVariableHandler.unpack`), once per call, on the host."""
     n, s = solver.n, solver.obj_scale
-    return Solution(solver.status, solver.cnt.k, np.array(x[:n]), solver.obj_sign * solver.obj_val / s,
-                    (y * solver.con_scale) * (solver.obj_sign / s), zl[:n] / s, zu[:n] / s)
+    xs, ys, zls, zus = np.array(x[:n]), (y * solver.con_scale) * (solver.obj_sign / s), zl[:n] / s, zu[:n] / s
+    if solver.fixed_handler is not None:
+        xs, zls, zus = solver.fixed_handler.unpack(solver.nlp, xs, zls, zus, ys, solver.obj_sign)
+    return Solution(solver.status, solver.cnt.k, xs, solver.obj_sign * solver.obj_val / s, ys, zls, zus)
 
 
 # What a back-end of `MadNLPSolver` supplies: the methods that touch vectors.  The host class implements them with numpy; a
@@ -401,6 +413,18 @@ class MadNLPSolver:
             raise ValueError("hessian_approximation = 'compact_lbfgs' needs the sparse condensed KKT system (sparse=True)")
         if o.hessian_approximation != "exact" and sparse and not self.lbfgs:
             raise ValueError(f"hessian_approximation = {o.hessian_approximation!r} needs a dense KKT system (sparse=False)")
+        if o.fixed_variable_treatment not in FIXED_VARIABLE_TREATMENTS:
+            raise ValueError(f"fixed_variable_treatment must be one of {FIXED_VARIABLE_TREATMENTS}, not "
+                             f"{o.fixed_variable_treatment!r}")
+        # MakeParameter (fixed_vars.py): None for a model without fixed variables -- then nothing below differs from
+        # "relax_bound".  `self.model` is what the callbacks evaluate: the reduced (sparse) or frozen (dense) view of `nlp`
+        self.fixed_handler = FixedVariableHandler.create(nlp, sparse) if o.fixed_variable_treatment == "make_parameter" else None
+        if self.fixed_handler is not None and o.hessian_approximation != "exact":
+            raise ValueError(f"fixed_variable_treatment = 'make_parameter' with fixed variables present needs "
+                             f"hessian_approximation = 'exact', not {o.hessian_approximation!r}: the secant pair of a "
+                             "quasi-Newton method over frozen / eliminated variables is not implemented")
+        self.model = nlp if self.fixed_handler is None else self.fixed_handler.model
+        nlp = self.model
         n, m = nlp.n, nlp.m
         qn_opt = QuasiNewtonOptions(init_strategy=o.qn_init_strategy, max_history=o.qn_max_history, init_value=o.qn_init_value,
                                     sigma_min=o.qn_sigma_min, sigma_max=o.qn_sigma_max)
@@ -417,7 +441,8 @@ class MadNLPSolver:
             diag = np.arange(n, dtype=np.int64)
             self.kkt = LowRankHessianKKT(kkt_factory(dict(n=n, m=m, hess_I=diag, hess_J=diag, **idx)), self.qn)
         else:
-            self.kkt = kkt_factory(dict(n=n, m=m, **idx))
+            reduced = {} if self.fixed_handler is None else self.fixed_handler.structure_info()   # (fixed_vars.structure)
+            self.kkt = kkt_factory(dict(n=n, m=m, **idx, **reduced))
         nt = n + self.ns
         self.x, self.xl, self.xu = np.zeros(nt), idx["xl"].copy(), idx["xu"].copy()
         self.zl, self.zu, self.f = np.zeros(nt), np.zeros(nt), np.zeros(nt)
@@ -463,27 +488,31 @@ class MadNLPSolver:
     # The model's raw values take the scaling factors and the sense here (nlpmodels.jl:771-906); with the factors at one every
     # product below is exact.
     def eval_f(self, x):
-        return self.obj_sign * (self.nlp.obj(x[:self.n]) * self.obj_scale)
+        return self.obj_sign * (self.model.obj(x[:self.n]) * self.obj_scale)
 
     def eval_grad(self, x):
-        self.f[:self.n] = self.nlp.grad(x[:self.n])
+        self.f[:self.n] = self.model.grad(x[:self.n])
         self.f[:self.n] *= self.obj_scale
         if self.obj_sign != 1.0:
             self.f[:self.n] *= self.obj_sign
+        if self.fixed_handler is not None and not self.sparse:
+            # frozen variables: x - lvar, against the unit diagonal of their Hessian rows (nlpmodels.jl:1026-1031); written
+            # after the scale AND the sign, so that the Newton step pulls towards lvar in a maximization too
+            self.fixed_handler.dense_grad(self.f, x)
         self.f[self.n:] = 0.0
         self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
-        c[:] = self.nlp.cons(x[:self.n])
+        c[:] = self.model.cons(x[:self.n])
         c *= self.con_scale
         c[self.ind_ineq] -= x[self.n:]
         c -= self.rhs
 
     def eval_jac(self, x):
         if self.sparse:
-            self.kkt.get_jacobian()[:] = self.nlp.jac_coord(x[:self.n]) * self.jac_scale
+            self.kkt.get_jacobian()[:] = self.model.jac_coord(x[:self.n]) * self.jac_scale
         else:
-            self.kkt.get_jacobian()[...] = self.nlp.jac_dense(x[:self.n]) * self.con_scale[:, None]
+            self.kkt.get_jacobian()[...] = self.model.jac_dense(x[:self.n]) * self.con_scale[:, None]
         self.kkt.compress_jacobian()
 
     def eval_lag_hess(self, x, y, is_resto=False):
@@ -492,23 +521,23 @@ class MadNLPSolver:
             return self._eval_lag_hess_qn(x, y)
         w = (0.0 if is_resto else 1.0) * self.obj_sign * self.obj_scale
         if self.sparse:
-            self.kkt.get_hessian()[:] = self.nlp.hess_coord(x[:self.n], y * self.con_scale, w)
+            self.kkt.get_hessian()[:] = self.model.hess_coord(x[:self.n], y * self.con_scale, w)
         else:
-            self.kkt.get_hessian()[...] = self.nlp.hess_dense(x[:self.n], y * self.con_scale, w)
+            self.kkt.get_hessian()[...] = self.model.hess_dense(x[:self.n], y * self.con_scale, w)
         self.kkt.compress_hessian()
         self.cnt.lag_hess_cnt += 1
 
     def _model_jtprod(self, x, l):
         """`_eval_jtprod_wrapper!` nlpmodels.jl:791-801: J(x)' (l .* con_scale) through the model's `jtprod` where it has one."""
         l = l * self.con_scale
-        if hasattr(self.nlp, "jtprod"):
-            return np.asarray(self.nlp.jtprod(x, l), dtype=float)
+        if hasattr(self.model, "jtprod"):
+            return np.asarray(self.model.jtprod(x, l), dtype=float)
         if self.sparse:
             out = np.zeros(self.n)
-            np.add.at(out, np.asarray(self.nlp.jac_J, dtype=np.int64),
-                      self.nlp.jac_coord(x) * l[np.asarray(self.nlp.jac_I, dtype=np.int64)])
+            np.add.at(out, np.asarray(self.model.jac_J, dtype=np.int64),
+                      self.model.jac_coord(x) * l[np.asarray(self.model.jac_I, dtype=np.int64)])
             return out
-        return self.nlp.jac_dense(x).T @ l
+        return self.model.jac_dense(x).T @ l
 
     def _eval_lag_hess_qn(self, x, y):
         """The quasi-Newton method of `eval_lag_hess_wrapper!` (callbacks.jl:145-190): no second derivative is evaluated.
@@ -549,7 +578,7 @@ class MadNLPSolver:
 
     # ------------------------------------------------------------------ initialize! (solver.jl:14-77)
     def initialize(self):
-        o, nlp, n = self.opt, self.nlp, self.n
+        o, nlp, n = self.opt, self.model, self.n
         x0, lvar, uvar = self.x[:n], self.xl[:n], self.xu[:n]
         x0[:] = nlp.x0
         self.y[:] = nlp.y0
@@ -579,8 +608,9 @@ class MadNLPSolver:
                 self.con_scale[:] = set_con_scale_sparse(self.m, nlp.jac_I, nlp.jac_coord(x0), o.nlp_scaling_max_gradient)
                 self.jac_scale[:] = self.con_scale[np.asarray(nlp.jac_I, dtype=np.int64)]
             else:
-                self.con_scale[:] = set_con_scale_dense(nlp.jac_dense(x0), o.nlp_scaling_max_gradient)
-            self.obj_scale = set_obj_scale(nlp.grad(x0), o.nlp_scaling_max_gradient)
+                # (the dense set_scaling! reads the model itself, not the frozen wrappers: nlpmodels.jl:752-756)
+                self.con_scale[:] = set_con_scale_dense(self.nlp.jac_dense(x0), o.nlp_scaling_max_gradient)
+            self.obj_scale = set_obj_scale((nlp if self.sparse else self.nlp).grad(x0), o.nlp_scaling_max_gradient)
             con_scale_slk = self.con_scale[self.ind_ineq]
             self.y /= self.con_scale
             self.rhs *= self.con_scale

@@ -14,6 +14,9 @@ nothing of its control flow except the first trial of the inertia correction.  T
                       (`iterator = "krylov"`), one synchronization per Arnoldi step
   * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
   * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
+  * `mnk_fix_*` (csrc/fixed_vars.hip): fixed variables made parameters (`fixed_variable_treatment = "make_parameter"`): one
+                      expand and one gather launch around a callback of the full model (`DeviceFixedVariableCallbacks`), the
+                      frozen gradient entries of the dense path
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
 
 Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as the reference's preset does) and
@@ -62,6 +65,69 @@ class DeviceHessianProduct:
         if self._h:
             L.lib().mnk_sc_destroy(self._h)
             self._h = C.c_void_p()
+
+
+class _DevicePointer:
+    """A device vector the library owns, as the callbacks take their arguments: by address."""
+
+    def __init__(self, ptr, n):
+        self._ptr, self._n = int(ptr), int(n)
+
+    def data_ptr(self):
+        return self._ptr
+
+    def numel(self):
+        return self._n
+
+
+class DeviceFixedVariables:
+    """The `mnk_fix` handle (csrc/fixed_vars.hip) of a host `fixed_vars.FixedVariableHandler`: its index sets and the fixed
+    values uploaded once, and the device `x_full` the handle owns.  Every call is one asynchronous launch on the context's
+    stream."""
+
+    def __init__(self, ctx, handler):
+        h = handler
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)   # noqa: E731
+        free, fixed, ij, ih = i64(h.free), i64(h.fixed), i64(h.ind_jac_free), i64(h.ind_hess_free)
+        val = np.ascontiguousarray(h.values, dtype=np.float64)
+        self.n, self.nfree, self.nfixed, self.njac, self.nhess = h.n_full, len(free), len(fixed), len(ij), len(ih)
+        self._h = C.c_void_p()
+        L.check(L.lib().mnk_fix_create(ctx.handle, h.n_full, len(free), free.ctypes.data, len(fixed), fixed.ctypes.data,
+                                       val.ctypes.data, h.nnzj_full, len(ij), ij.ctypes.data, h.nnzh_full, len(ih),
+                                       ih.ctypes.data, C.byref(self._h)), "mnk_fix_create")
+        self.x_full = _DevicePointer(L.lib().mnk_fix_x_full(self._h), h.n_full)
+
+    def expand(self, x):
+        assert x.numel() == self.nfree
+        L.check(L.lib().mnk_fix_expand(self._h, x.data_ptr()), "mnk_fix_expand")
+        return self.x_full
+
+    def gather(self, which, src_full, dst, scale=None, factor=1.0):
+        count = (self.nfree, self.njac, self.nhess)[which]
+        assert dst.numel() == count and (scale is None or scale.numel() == count)
+        L.check(L.lib().mnk_fix_gather(self._h, which, src_full.data_ptr(), None if scale is None else scale.data_ptr(),
+                                       float(factor), dst.data_ptr()), "mnk_fix_gather")
+
+    def dense_grad(self, g, x):
+        assert g.numel() >= self.n and x.numel() >= self.n
+        L.check(L.lib().mnk_fix_dense_grad(self._h, g.data_ptr(), x.data_ptr()), "mnk_fix_dense_grad")
+
+    def x_full_host(self):
+        """x_full downloaded (synchronizes; tests and reporting)."""
+        out = np.empty(self.n)
+        L.check(L.lib().mnk_fix_get_x_full(self._h, out.ctypes.data), "mnk_fix_get_x_full")
+        return out
+
+    def close(self):
+        if self._h:
+            L.lib().mnk_fix_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceQPCallbacks:
@@ -138,7 +204,11 @@ class DeviceDenseQPCallbacks:
     `DeviceQPCallbacks`: P and q are uploaded times `obj_factor`, the rows of A times `con_scale`."""
     prescaled = True
 
-    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None):
+    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None, fixed=None):
+        """`fixed`: the host `FixedVariableHandler` of variables frozen in place (MakeParameter on a dense system).  The KKT
+        handle is then loaded from masked copies made once, here -- zero Jacobian columns, zero Hessian rows and columns with a
+        unit diagonal, also under objective weight 0 --, J'y uses the masked A, while f, grad f and c keep the model's own P
+        and A and `grad` ends with `mnk_fix_dense_grad`."""
         self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
         P, A, q = np.asarray(nlp.P, float), np.asarray(nlp.A, float), np.asarray(nlp.q, float)
         if obj_factor != 1.0:
@@ -149,8 +219,18 @@ class DeviceDenseQPCallbacks:
         self.P_cm = _up(P.T, dev)
         self.A_cm = _up(A.T, dev)        # (n, m) row-major == (m, n) column-major
         self.q = _up(q, dev)
-        self.P0_cm = torch.empty_like(self.P_cm)
-        K.vec_fill(self.P0_cm, 0.0)
+        self.fix = None
+        if fixed is None:
+            self.P_kkt_cm, self.A_kkt_cm = self.P_cm, self.A_cm
+            self.P0_cm = torch.empty_like(self.P_cm)
+            K.vec_fill(self.P0_cm, 0.0)
+        else:
+            Am = np.array(A)
+            Am[:, fixed.fixed] = 0.0
+            self.P_kkt_cm = _up(fixed.mask_hessian(np.array(P)).T, dev)
+            self.A_kkt_cm = _up(Am.T, dev)
+            self.P0_cm = _up(fixed.mask_hessian(np.zeros_like(P)), dev)
+            self.fix = DeviceFixedVariables(K.ctx, fixed)
         self.handle_has_H = True
         self._px = torch.empty(self.n, dtype=torch.float64, device=dev)
 
@@ -168,6 +248,8 @@ class DeviceDenseQPCallbacks:
     def grad(self, g, x):
         self._pmul(x, g)
         self.K.vec_axpby(g, 1.0, g, 1.0, self.q)
+        if self.fix is not None:
+            self.fix.dense_grad(g, x)
 
     def cons(self, c, x):
         if self.m > 0:
@@ -175,7 +257,7 @@ class DeviceDenseQPCallbacks:
 
     def jtprod_x(self, out_x, y):
         if self.m > 0:
-            self.K.gemv(1, self.m, self.n, 1.0, self.A_cm, self.m, y, 0.0, out_x)
+            self.K.gemv(1, self.m, self.n, 1.0, self.A_kkt_cm, self.m, y, 0.0, out_x)
         else:
             self.K.vec_fill(out_x, 0.0)
 
@@ -186,11 +268,11 @@ class DeviceDenseQPCallbacks:
 
     def load_jac(self, x=None):
         if self.m > 0:
-            L.check(L.lib().mnk_dc_set_jac(self.kkt._h, self.A_cm.data_ptr(), self.m, L.MNK_DEVICE), "mnk_dc_set_jac")
+            L.check(L.lib().mnk_dc_set_jac(self.kkt._h, self.A_kkt_cm.data_ptr(), self.m, L.MNK_DEVICE), "mnk_dc_set_jac")
 
     def load_hess(self, x=None, y=None, sigma=1.0):
         zero = sigma == 0.0
-        src = self.P0_cm if zero else self.P_cm
+        src = self.P0_cm if zero else self.P_kkt_cm
         L.check(L.lib().mnk_dc_set_hess(self.kkt._h, src.data_ptr(), self.n, L.MNK_DEVICE), "mnk_dc_set_hess")
         self.handle_has_H = not zero
 
@@ -198,7 +280,8 @@ class DeviceDenseQPCallbacks:
         self.load_hess(sigma=0.0)
 
     def close(self):
-        pass
+        if self.fix is not None:
+            self.fix.close()
 
 
 class DeviceOPFCallbacks:
@@ -362,12 +445,75 @@ class DeviceTapeCallbacks:
             pass
 
 
+class DeviceFixedVariableCallbacks:
+    """Any raw-value callbacks object (`prescaled = False`: `DeviceTapeCallbacks`, `DeviceOPFCallbacks`) built on the FULL model,
+    seen over the free variables of a `fixed_vars.FixedVariableHandler` (MakeParameter on the sparse condensed system; reference
+    nlpmodels.jl:912-1013).  Same method set as the inner object, on the reduced problem.  Every call expands the reduced iterate
+    into the handle's `x_full` (one launch), runs the inner callback at full length into full-length scratch, and gathers the
+    reduced values (one launch; objective and constraints need none).  `fused_scaling`: `grad` takes the objective factor and
+    `jac_coord` the per-entry constraint scale, applied inside the gather -- the solver launches no `vec_mul` / `scale_grad`
+    behind them.  `jtprod_x` is the reduced KKT handle's own transposed SpMV."""
+    prescaled = False
+    fused_scaling = True
+
+    def __init__(self, inner, handler, kkt, dev, K):
+        assert not inner.prescaled, "the wrapped callbacks must return the model's raw values"
+        self.inner, self.kkt, self.K = inner, kkt, K
+        self.n, self.m = len(handler.free), inner.m
+        self.fix = DeviceFixedVariables(K.ctx, handler)
+        E = lambda k: torch.empty(max(k, 1), dtype=torch.float64, device=dev)[:k]  # noqa: E731
+        self.g_full = E(handler.n_full)
+        self.jv, self.hv, self.hv0 = E(self.fix.njac), E(self.fix.nhess), E(self.fix.nhess)
+        K.vec_fill(self.hv0, 0.0)
+
+    def obj(self, x):
+        return self.inner.obj(self.fix.expand(x))
+
+    def grad(self, g, x, factor=1.0):
+        self.inner.grad(self.g_full, self.fix.expand(x))
+        self.fix.gather(L.MNK_FIX_FREE, self.g_full, g, None, factor)
+
+    def cons(self, c, x):
+        self.inner.cons(c, self.fix.expand(x))
+
+    def jac_coord(self, x, scale=None):
+        self.fix.gather(L.MNK_FIX_JAC, self.inner.jac_coord(self.fix.expand(x)), self.jv, scale)
+        return self.jv
+
+    def hess_coord(self, x, y, sigma=1.0):
+        self.fix.gather(L.MNK_FIX_HESS, self.inner.hess_coord(self.fix.expand(x), y, sigma), self.hv)
+        return self.hv
+
+    def jtprod_x(self, out_x, y):
+        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
+
+    def load_jac(self, x):
+        self.kkt.compress_jacobian(self.jac_coord(x))
+
+    def load_hess(self, x, y, sigma=1.0):
+        self.kkt.compress_hessian(self.hess_coord(x, y, sigma))
+
+    def zero_hess(self):
+        self.kkt.compress_hessian(self.hv0)
+
+    def close(self):
+        self.fix.close()
+        self.inner.close()
+
+
 class DeviceMadNLPSolver(MadNLPSolver):
     def __init__(self, nlp, kkt_factory, opt: IPMOptions | None = None, device="cuda", sparse=True):
         if getattr(nlp, "is_tape_model", False) and not sparse:
             raise NotImplementedError("DeviceMadNLPSolver evaluates a TapeModel for the sparse condensed KKT handle only "
                                       "(DeviceTapeCallbacks feed COO values to its compressors): use sparse=True with "
                                       "relax_equality, or MadNLPSolver with host callbacks")
+        if (opt is not None and opt.fixed_variable_treatment == "make_parameter" and sparse
+                and self._callbacks_class(nlp, sparse) is DeviceQPCallbacks
+                and (np.asarray(nlp.lvar, float) == np.asarray(nlp.uvar, float)).any()):
+            raise NotImplementedError("fixed_variable_treatment = 'make_parameter' with fixed variables on the sparse QP device "
+                                      "callbacks (DeviceQPCallbacks): they evaluate f, grad f and c through the reduced KKT "
+                                      "handle's SpMV, and the fixed part of H x and J x would need constant offsets that are "
+                                      "not implemented; use 'relax_bound', a TapeModel, or MadNLPSolver")
         super().__init__(nlp, kkt_factory, opt, sparse=sparse)
         if self.inertia_correction_method != "inertia_based":
             if hasattr(self.kkt, "close"):
@@ -390,13 +536,8 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self.K = IPMDeviceKernels(nt, self.ind_lb, self.ind_ub, ctx=ctx)
         self.K.set_perturbation_sets(self.ind_llb, self.ind_uub)
         self.d, self.p, self._w1, self._w4 = (self._new_vec(self._lw) for _ in range(4))   # flat device KKT vectors
-        if getattr(self.nlp, "is_tape_model", False):
-            cls = DeviceTapeCallbacks
-        elif hasattr(self.nlp, "arc_coef"):
-            assert self.sparse, "the AC-OPF callbacks feed the sparse condensed handle"
-            cls = DeviceOPFCallbacks
-        else:
-            cls = DeviceQPCallbacks if self.sparse else DeviceDenseQPCallbacks
+        cls = self._callbacks_class(self.nlp, self.sparse)
+        fixed = self.fixed_handler        # variables made parameters: the callbacks are built on the FULL model (self.nlp)
         # NLP scaling / the sense: the scaled launches replace the plain ones only when there is something to apply
         self._scaled = bool(self.opt.nlp_scaling) or self.obj_sign != 1.0
         if self.lbfgs:               # the host mirror (kkt.LowRankHessianKKT) comes off: the handle applies the low-rank term itself
@@ -405,9 +546,14 @@ class DeviceMadNLPSolver(MadNLPSolver):
             scaled_data = dict(obj_factor=self.obj_sign * self.obj_scale, con_scale=self.con_scale) if self._scaled else {}
             if self.lbfgs:
                 scaled_data["own_hessian"] = True
+            if fixed is not None:
+                scaled_data["fixed"] = fixed
             self.cb = cls(self.nlp, self.kkt, self.dev, self.K, **scaled_data)
         else:
             self.cb = cls(self.nlp, self.kkt, self.dev, self.K)
+            if fixed is not None:
+                self.cb = DeviceFixedVariableCallbacks(self.cb, fixed, self.kkt, self.dev, self.K)
+        self._fused = getattr(self.cb, "fused_scaling", False)
         self.ind_ineq_t = _up(self.ind_ineq, self.dev, np.int64)
         if self._scaled:
             self.con_scale_t = None if cls.prescaled else _up(self.con_scale, self.dev)
@@ -430,6 +576,16 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self._on_device = True
         self._sync = ctx.synchronize
 
+    @staticmethod
+    def _callbacks_class(nlp, sparse):
+        """The device callbacks of a model: by what the model is, not by what the run needs."""
+        if getattr(nlp, "is_tape_model", False):
+            return DeviceTapeCallbacks
+        if hasattr(nlp, "arc_coef"):
+            assert sparse, "the AC-OPF callbacks feed the sparse condensed handle"
+            return DeviceOPFCallbacks
+        return DeviceQPCallbacks if sparse else DeviceDenseQPCallbacks
+
     # slices of a flat KKT vector (reference src/KKT/rhs.jl:90-150)
     def _primal(self, v): return v[:self.nt]
     def _dual(self, v): return v[self.nt:self.nt + self.m]
@@ -447,6 +603,11 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_grad(self, x):
         if not self._on_device:
             return super().eval_grad(x)
+        if self._fused:                                # gather and factor in one launch (DeviceFixedVariableCallbacks)
+            self.cb.grad(self.f[:self.n], x[:self.n], self.obj_sign * self.obj_scale if self._scaled else 1.0)
+            self.K.vec_fill(self.f[self.n:], 0.0)
+            self.cnt.obj_grad_cnt += 1
+            return
         self.cb.grad(self.f[:self.n], x[:self.n])
         if self._scaled and not self.cb.prescaled:     # the factor and the zero slack part in one launch
             self.K.scale_grad(self.f, self.n, self.obj_sign * self.obj_scale)
@@ -469,6 +630,8 @@ class DeviceMadNLPSolver(MadNLPSolver):
     def eval_jac(self, x):
         if not self._on_device:
             return super().eval_jac(x)
+        if self._scaled and self._fused:               # gather and con_scale[jac_I] in one launch
+            return self.kkt.compress_jacobian(self.cb.jac_coord(x[:self.n], self.jac_scale_t))
         if self._scaled and not self.cb.prescaled:
             jv = self.cb.jac_coord(x[:self.n])
             self.K.vec_mul(jv, jv, self.jac_scale_t)

@@ -616,6 +616,20 @@ def lootsma_tape_model():
     return M.finalize()
 
 
+def lootsma_fixed_tape_model():
+    """The reference's `lootsma` as it is written there (lib/MadNLPTests/src/MadNLPTests.jl:155-164): FOUR variables, the
+    first one `par`, fixed at 6 by its bounds, then x1 .. x3 -- the model `fixed_variable_treatment = "make_parameter"` is
+    for.  `LootsmaModel.LOOTSMA_X` is entries 1 .. 3 of its solution."""
+    from .problems import LootsmaModel as Lo
+    M = TapeModel(4, 2, np.concatenate(([6.0], Lo.x0)), np.concatenate(([6.0], Lo.lvar)), np.concatenate(([6.0], Lo.uvar)),
+                  Lo.lcon, Lo.ucon, name="tape_lootsma_par")
+    M.add_objective(V(1) ** 3 + 11.0 * V(1) - V(0) * sqrt(V(1)) + V(2), np.array([[0, 1, 3]]))
+    xyz = np.array([[1, 2, 3]])
+    M.add_constraint(-sqrt(V(0)) - sqrt(V(1)) + sqrt(V(2)), np.array([0]), xyz)
+    M.add_constraint(sqrt(V(0)) + sqrt(V(1)) + sqrt(V(2)), np.array([1]), xyz)
+    return M.finalize()
+
+
 def simplex_lp_tape_model(big=1.0, minimize=True):
     """`problems.SimplexLPModel` as patterns (the LP of the reference's `test_scaling` / `test_max_problem`); it has no
     second derivatives, so its Hessian pattern is empty."""
