@@ -6,23 +6,18 @@ nothing of its control flow except the first trial of the inertia correction.  T
   * the KKT handle:   `set_aug_diagonal!`, `regularize_diagonal!`, `build_kkt!`, `factorize!`, `solve_kkt!`, `mul!`, SpMV
   * `mnk_ipm_*`:      the reductions and elementwise pieces of reference `src/IPM/kernels.jl`, and the loop's plain vector
                       work (`mnk_ipm_vec_*`, `mnk_ipm_get_dot`, `mnk_ipm_gemv`)
-  * `mnk_ipm_vec_mul`, `mnk_ipm_scale_cons`, `mnk_ipm_scale_grad` (csrc/nlp_scale.hip): NLP scaling and the objective sense
-                      around the callbacks' raw values, only when `nlp_scaling` is set or the model maximizes
   * `mnk_ipm_quality_function`: the adaptive barrier update's quality function for up to four centering parameters per call
                       (`barrier = "quality_function"`), the step `aff + sigma cen` never stored
   * `mnk_ipm_krylov_*` (csrc/krylov.hip): the Gram-Schmidt, normalization and solution updates of the GMRES refinement
                       (`iterator = "krylov"`), one synchronization per Arnoldi step
-  * `mnk_opf_*`:      the callbacks of the polar AC-OPF model (`problems.ACOPFModel`) evaluated on the device
-  * `mnk_tape_*`:     the callbacks of any model written as patterns (`tape_model.TapeModel`): expression tapes interpreted on the device
-  * `mnk_fix_*` (csrc/fixed_vars.hip): fixed variables made parameters (`fixed_variable_treatment = "make_parameter"`): one
-                      expand and one gather launch around a callback of the full model (`DeviceFixedVariableCallbacks`), the
-                      frozen gradient entries of the dense path
+  * `device_callbacks`: each `eval_*` is one call into the callbacks object, which evaluates the model on the device (`mnk_opf_*`,
+                      `mnk_tape_*`, `mnk_fix_*`, the QPs through the KKT handle's SpMV or `mnk_ipm_gemv`) and owns NLP scaling
+                      and the objective sense (`mnk_ipm_vec_mul`, `mnk_ipm_scale_cons`, `mnk_ipm_scale_grad`, csrc/nlp_scale.hip)
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
 
 Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as the reference's preset does) and
-`DenseCondensedKKTSystem` (equalities allowed), with models whose callbacks can be evaluated on the device: the AC-OPF NLP
-(`DeviceOPFCallbacks`), any `TapeModel` on the sparse condensed system (`DeviceTapeCallbacks`), the sparse QP through the KKT handle's own SpMV on the compressed Jacobian / Hessian, the dense QP
-through `mnk_ipm_gemv` on device copies of P and A.  Initialization runs once on the host (the base class) and is uploaded.
+`DenseCondensedKKTSystem` (equalities allowed), with the models of `device_callbacks.callbacks_class`: the AC-OPF NLP, any
+`TapeModel` (sparse condensed only), the sparse and the dense QP.  Initialization runs once on the host and is uploaded.
 
 With `hessian_approximation = "bfgs" / "damped_bfgs"` (dense systems) the Hessian approximation lives in the KKT handle's
 device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model's Hessian is never loaded.  With
@@ -30,475 +25,17 @@ device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model'
 (csrc/lbfgs.hip), whose `solve_kkt!` / `mul!` apply the low-rank term: the loop below does not know about it."""
 from __future__ import annotations
 
-
-import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .device_callbacks import (DeviceDenseQPCallbacks, DeviceFixedVariableCallbacks, DeviceFixedVariables,  # noqa: F401
+                               DeviceHessianProduct, DeviceOPFCallbacks, DeviceQPCallbacks, DeviceScaling, DeviceTapeCallbacks,
+                               _DevicePointer, _up, callbacks_class, device_callbacks)
 from .ipm import IPMOptions, MadNLPSolver, unpack_solution
 from .ipm_device import IPMDeviceKernels
-
-
-def _up(a, dev, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
-class DeviceHessianProduct:
-    """out = Symmetric(H, :L) x on the device for a fixed sparse H: a bare `mnk_sc` handle (no constraints, no solver) that is
-    used for its compressed Hessian and `mnk_sc_spmv` only.  `DeviceQPCallbacks` evaluates the objective through the KKT
-    handle's own Hessian; under a quasi-Newton method that handle holds the approximation, and the model's H lives here."""
-
-    def __init__(self, ctx, n, hess_I, hess_J, hv):
-        hI, hJ = np.ascontiguousarray(hess_I, dtype=np.int32), np.ascontiguousarray(hess_J, dtype=np.int32)
-        e = np.zeros(1, dtype=np.int32)
-        self._h = C.c_void_p()
-        L.check(L.lib().mnk_sc_create(ctx.handle, int(n), 0, 0, e.ctypes.data, e.ctypes.data, len(hI), hI.ctypes.data,
-                                      hJ.ctypes.data, 0, C.byref(self._h)), "mnk_sc_create")
-        L.check(L.lib().mnk_sc_compress_hessian(self._h, hv.data_ptr(), L.MNK_DEVICE), "mnk_sc_compress_hessian")
-
-    def mul(self, x, out):
-        L.check(L.lib().mnk_sc_spmv(self._h, L.MNK_SC_HESS, 0, 1.0, x.data_ptr(), 0.0, out.data_ptr()), "mnk_sc_spmv")
-
-    def close(self):
-        if self._h:
-            L.lib().mnk_sc_destroy(self._h)
-            self._h = C.c_void_p()
-
-
-class _DevicePointer:
-    """A device vector the library owns, as the callbacks take their arguments: by address."""
-
-    def __init__(self, ptr, n):
-        self._ptr, self._n = int(ptr), int(n)
-
-    def data_ptr(self):
-        return self._ptr
-
-    def numel(self):
-        return self._n
-
-
-class DeviceFixedVariables:
-    """The `mnk_fix` handle (csrc/fixed_vars.hip) of a host `fixed_vars.FixedVariableHandler`: its index sets and the fixed
-    values uploaded once, and the device `x_full` the handle owns.  Every call is one asynchronous launch on the context's
-    stream."""
-
-    def __init__(self, ctx, handler):
-        h = handler
-        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)   # noqa: E731
-        free, fixed, ij, ih = i64(h.free), i64(h.fixed), i64(h.ind_jac_free), i64(h.ind_hess_free)
-        val = np.ascontiguousarray(h.values, dtype=np.float64)
-        self.n, self.nfree, self.nfixed, self.njac, self.nhess = h.n_full, len(free), len(fixed), len(ij), len(ih)
-        self._h = C.c_void_p()
-        L.check(L.lib().mnk_fix_create(ctx.handle, h.n_full, len(free), free.ctypes.data, len(fixed), fixed.ctypes.data,
-                                       val.ctypes.data, h.nnzj_full, len(ij), ij.ctypes.data, h.nnzh_full, len(ih),
-                                       ih.ctypes.data, C.byref(self._h)), "mnk_fix_create")
-        self.x_full = _DevicePointer(L.lib().mnk_fix_x_full(self._h), h.n_full)
-
-    def expand(self, x):
-        assert x.numel() == self.nfree
-        L.check(L.lib().mnk_fix_expand(self._h, x.data_ptr()), "mnk_fix_expand")
-        return self.x_full
-
-    def gather(self, which, src_full, dst, scale=None, factor=1.0):
-        count = (self.nfree, self.njac, self.nhess)[which]
-        assert dst.numel() == count and (scale is None or scale.numel() == count)
-        L.check(L.lib().mnk_fix_gather(self._h, which, src_full.data_ptr(), None if scale is None else scale.data_ptr(),
-                                       float(factor), dst.data_ptr()), "mnk_fix_gather")
-
-    def dense_grad(self, g, x):
-        assert g.numel() >= self.n and x.numel() >= self.n
-        L.check(L.lib().mnk_fix_dense_grad(self._h, g.data_ptr(), x.data_ptr()), "mnk_fix_dense_grad")
-
-    def x_full_host(self):
-        """x_full downloaded (synchronizes; tests and reporting)."""
-        out = np.empty(self.n)
-        L.check(L.lib().mnk_fix_get_x_full(self._h, out.ctypes.data), "mnk_fix_get_x_full")
-        return out
-
-    def close(self):
-        if self._h:
-            L.lib().mnk_fix_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceQPCallbacks:
-    """f = 0.5 x'Hx + q'x, c = Jx with H = Symmetric(hess_com, :L) and J = jt_csc' held by the KKT handle.  The data ARE the
-    handle's, so NLP scaling and the sense go into them once, on the host (`prescaled`): H and q times `obj_factor` = obj_sign
-    obj_scale, the rows of J times `con_scale`; the solver applies no factor to what these callbacks return."""
-    prescaled = True
-
-    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None, own_hessian=False):
-        """`own_hessian`: the KKT handle's Hessian is a quasi-Newton approximation; H gets a `DeviceHessianProduct`."""
-        self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
-        q, jv, hv = np.asarray(nlp.q, float), np.asarray(nlp.jac_coord(None), float), np.asarray(nlp.hess_coord(None, None, 1.0), float)
-        if obj_factor != 1.0:
-            q, hv = q * obj_factor, hv * obj_factor
-        if con_scale is not None:
-            jv = jv * con_scale[np.asarray(nlp.jac_I, dtype=np.int64)]
-        self.q = _up(q, dev)
-        self.jv = _up(jv, dev)
-        self.hv = _up(hv, dev)
-        self.hv0 = torch.empty_like(self.hv)
-        K.vec_fill(self.hv0, 0.0)
-        self.handle_has_H = True
-        self._hx = torch.empty(self.n, dtype=torch.float64, device=dev)
-        self.H = DeviceHessianProduct(kkt.ctx, nlp.n, nlp.hess_I, nlp.hess_J, self.hv) if own_hessian else None
-
-    def _hmul(self, x):
-        if self.H is not None:
-            self.H.mul(x, self._hx)
-            return self._hx
-        # the SpMV runs on the handle's compressed Lagrangian Hessian: while that holds something else (zero after
-        # initialize!(kkt), objective weight 0 in robust!) H is put back for the product
-        if not self.handle_has_H:
-            self.kkt.compress_hessian(self.hv)
-        self.kkt.spmv_device(L.MNK_SC_HESS, 0, 1.0, x, 0.0, self._hx)
-        if not self.handle_has_H:
-            self.kkt.compress_hessian(self.hv0)
-        return self._hx
-
-    def obj(self, x):
-        hx = self._hmul(x)
-        with self.K.batch():
-            a = self.K.get_dot(x, hx)
-            b = self.K.get_dot(self.q, x)
-        return 0.5 * a[0] + b[0]
-
-    def grad(self, g, x):
-        self.K.vec_axpby(g, 1.0, self._hmul(x), 1.0, self.q)
-
-    def cons(self, c, x):
-        self.kkt.spmv_device(L.MNK_SC_JT, 1, 1.0, x, 0.0, c)
-
-    def jtprod_x(self, out_x, y):
-        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
-
-    def load_jac(self, x=None):
-        self.kkt.compress_jacobian(self.jv)
-
-    def load_hess(self, x=None, y=None, sigma=1.0):
-        zero = sigma == 0.0            # linear constraints: the Lagrangian Hessian is sigma H
-        self.kkt.compress_hessian(self.hv0 if zero else self.hv)
-        self.handle_has_H = not zero
-
-    def zero_hess(self):
-        self.load_hess(sigma=0.0)
-
-    def close(self):
-        if self.H is not None:
-            self.H.close()
-
-
-class DeviceDenseQPCallbacks:
-    """f = 0.5 x'Px + q'x, c = Ax with dense P, A on the device (`DenseQPModel`); Hessian / Jacobian of the KKT handle are
-    loaded from these device copies (`mnk_dc_set_hess` / `mnk_dc_set_jac` with device pointers).  `prescaled` as
-    `DeviceQPCallbacks`: P and q are uploaded times `obj_factor`, the rows of A times `con_scale`."""
-    prescaled = True
-
-    def __init__(self, nlp, kkt, dev, K, obj_factor=1.0, con_scale=None, fixed=None):
-        """`fixed`: the host `FixedVariableHandler` of variables frozen in place (MakeParameter on a dense system).  The KKT
-        handle is then loaded from masked copies made once, here -- zero Jacobian columns, zero Hessian rows and columns with a
-        unit diagonal, also under objective weight 0 --, J'y uses the masked A, while f, grad f and c keep the model's own P
-        and A and `grad` ends with `mnk_fix_dense_grad`."""
-        self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
-        P, A, q = np.asarray(nlp.P, float), np.asarray(nlp.A, float), np.asarray(nlp.q, float)
-        if obj_factor != 1.0:
-            P, q = P * obj_factor, q * obj_factor
-        if con_scale is not None:
-            A = A * con_scale[:, None]
-        # column-major device images (a row-major upload of the transpose IS the column-major matrix)
-        self.P_cm = _up(P.T, dev)
-        self.A_cm = _up(A.T, dev)        # (n, m) row-major == (m, n) column-major
-        self.q = _up(q, dev)
-        self.fix = None
-        if fixed is None:
-            self.P_kkt_cm, self.A_kkt_cm = self.P_cm, self.A_cm
-            self.P0_cm = torch.empty_like(self.P_cm)
-            K.vec_fill(self.P0_cm, 0.0)
-        else:
-            Am = np.array(A)
-            Am[:, fixed.fixed] = 0.0
-            self.P_kkt_cm = _up(fixed.mask_hessian(np.array(P)).T, dev)
-            self.A_kkt_cm = _up(Am.T, dev)
-            self.P0_cm = _up(fixed.mask_hessian(np.zeros_like(P)), dev)
-            self.fix = DeviceFixedVariables(K.ctx, fixed)
-        self.handle_has_H = True
-        self._px = torch.empty(self.n, dtype=torch.float64, device=dev)
-
-    def _pmul(self, x, out):
-        self.K.gemv(0, self.n, self.n, 1.0, self.P_cm, self.n, x, 0.0, out)
-        return out
-
-    def obj(self, x):
-        px = self._pmul(x, self._px)
-        with self.K.batch():
-            a = self.K.get_dot(x, px)
-            b = self.K.get_dot(self.q, x)
-        return 0.5 * a[0] + b[0]
-
-    def grad(self, g, x):
-        self._pmul(x, g)
-        self.K.vec_axpby(g, 1.0, g, 1.0, self.q)
-        if self.fix is not None:
-            self.fix.dense_grad(g, x)
-
-    def cons(self, c, x):
-        if self.m > 0:
-            self.K.gemv(0, self.m, self.n, 1.0, self.A_cm, self.m, x, 0.0, c)
-
-    def jtprod_x(self, out_x, y):
-        if self.m > 0:
-            self.K.gemv(1, self.m, self.n, 1.0, self.A_kkt_cm, self.m, y, 0.0, out_x)
-        else:
-            self.K.vec_fill(out_x, 0.0)
-
-    def jtprod_at(self, x, y, out_x):
-        """out_x = J(x)' y (`_eval_jtprod_wrapper!` of the quasi-Newton update, callbacks.jl:172); the constraints are linear:
-        `x` is not used."""
-        self.jtprod_x(out_x, y)
-
-    def load_jac(self, x=None):
-        if self.m > 0:
-            L.check(L.lib().mnk_dc_set_jac(self.kkt._h, self.A_kkt_cm.data_ptr(), self.m, L.MNK_DEVICE), "mnk_dc_set_jac")
-
-    def load_hess(self, x=None, y=None, sigma=1.0):
-        zero = sigma == 0.0
-        src = self.P0_cm if zero else self.P_kkt_cm
-        L.check(L.lib().mnk_dc_set_hess(self.kkt._h, src.data_ptr(), self.n, L.MNK_DEVICE), "mnk_dc_set_hess")
-        self.handle_has_H = not zero
-
-    def zero_hess(self):
-        self.load_hess(sigma=0.0)
-
-    def close(self):
-        if self.fix is not None:
-            self.fix.close()
-
-
-class DeviceOPFCallbacks:
-    """Callbacks of `problems.ACOPFModel` on the device (`mnk_opf_*`, csrc/opf_eval.hip): objective, gradient, constraints,
-    Jacobian and Lagrangian-Hessian COO values are computed from the device iterate and handed to the KKT handle's
-    compressors without leaving HBM (reference `eval_*_wrapper!`, src/IPM/callbacks.jl:1-96, with a device model).  The values
-    are the model's raw ones (`prescaled = False`): the solver's `eval_*` apply NLP scaling and the sense around them."""
-    prescaled = False
-
-    def __init__(self, nlp, kkt, dev, K):
-        self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)   # noqa: E731
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-        fr, to, gb, coef, bus, cost = i32(nlp.fr), i32(nlp.to), i32(nlp.gen_bus), f64(nlp.arc_coef), f64(nlp.bus_data), f64(nlp.gen_cost)
-        self._h = C.c_void_p()
-        L.check(L.lib().mnk_opf_create(K.ctx.handle, nlp.nbus, nlp.ngen, nlp.nbr, fr.ctypes.data, to.ctypes.data, gb.ctypes.data,
-                                       coef.ctypes.data, bus.ctypes.data, cost.ctypes.data, C.byref(self._h)), "mnk_opf_create")
-        sz = [C.c_int64() for _ in range(4)]
-        L.check(L.lib().mnk_opf_sizes(self._h, *[C.byref(v) for v in sz]), "mnk_opf_sizes")
-        assert (sz[0].value, sz[1].value, sz[2].value, sz[3].value) == (nlp.n, nlp.m, len(nlp.jac_I), len(nlp.hess_I))
-        E = lambda k: torch.empty(k, dtype=torch.float64, device=dev)  # noqa: E731
-        self.jv, self.hv, self.hv0, self.terms = E(len(nlp.jac_I)), E(len(nlp.hess_I)), E(len(nlp.hess_I)), E(nlp.ngen)
-        K.vec_fill(self.hv0, 0.0)
-
-    def obj(self, x):
-        L.check(L.lib().mnk_opf_obj_terms(self._h, x.data_ptr(), self.terms.data_ptr()), "mnk_opf_obj_terms")
-        return self.K.get_sum(self.terms)
-
-    def grad(self, g, x):
-        L.check(L.lib().mnk_opf_grad(self._h, x.data_ptr(), g.data_ptr()), "mnk_opf_grad")
-
-    def cons(self, c, x):
-        L.check(L.lib().mnk_opf_cons(self._h, x.data_ptr(), c.data_ptr()), "mnk_opf_cons")
-
-    def jac_coord(self, x):
-        L.check(L.lib().mnk_opf_jac_coord(self._h, x.data_ptr(), self.jv.data_ptr()), "mnk_opf_jac_coord")
-        return self.jv
-
-    def hess_coord(self, x, y, sigma=1.0):
-        L.check(L.lib().mnk_opf_hess_coord(self._h, x.data_ptr(), y.data_ptr(), float(sigma), self.hv.data_ptr()),
-                "mnk_opf_hess_coord")
-        return self.hv
-
-    def jtprod_x(self, out_x, y):
-        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
-
-    def load_jac(self, x):
-        self.kkt.compress_jacobian(self.jac_coord(x))
-
-    def load_hess(self, x, y, sigma=1.0):
-        self.kkt.compress_hessian(self.hess_coord(x, y, sigma))
-
-    def zero_hess(self):
-        self.kkt.compress_hessian(self.hv0)
-
-    def close(self):
-        if self._h:
-            L.lib().mnk_opf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceTapeCallbacks:
-    """Callbacks of ANY model written as patterns (`tape_model.TapeModel`) on the device (`mnk_tape_*`, csrc/tape_eval.hip): the
-    model's expression tapes are handed to the library once; objective terms, gradient, constraints, Jacobian and
-    Lagrangian-Hessian COO values are then interpreted from the device iterate, in the model's own COO order (the KKT handle is
-    created from the model's `jac_I .. hess_J`).  Same method set as `DeviceOPFCallbacks`, raw values too."""
-    prescaled = False
-
-    def __init__(self, nlp, kkt, dev, K):
-        nlp.finalize()
-        self.kkt, self.K, self.n, self.m = kkt, K, nlp.n, nlp.m
-        lib = L.lib()
-        self._h = C.c_void_p()
-        L.check(lib.mnk_tape_create(K.ctx.handle, nlp.n, nlp.m, C.byref(self._h)), "mnk_tape_create")
-        try:
-            for p in nlp.patterns:
-                args = []
-                for t in p.tapes:
-                    args += [len(t.code), t.code.ctypes.data, len(t.consts), t.consts.ctypes.data, t.nout, t.out_operand.ctypes.data,
-                             t.out_j.ctypes.data, t.out_l.ctypes.data, t.nslot]
-                L.check(lib.mnk_tape_add_pattern(self._h, p.kind, p.R, p.k, p.q, p.var_index.ctypes.data, p.params.ctypes.data,
-                                                 p.rows.ctypes.data if p.kind == 1 else None, *args), "mnk_tape_add_pattern")
-            L.check(lib.mnk_tape_finalize(self._h), "mnk_tape_finalize")
-            sz = [C.c_int64() for _ in range(5)]
-            L.check(lib.mnk_tape_sizes(self._h, *[C.byref(v) for v in sz]), "mnk_tape_sizes")
-            nnzj, nnzh = len(nlp.jac_I), len(nlp.hess_I)
-            if tuple(v.value for v in sz) != (nlp.n, nlp.m, nlp.nterms, nnzj, nnzh):
-                raise RuntimeError(f"mnk_tape_sizes {tuple(v.value for v in sz)} differs from the host model's "
-                                   f"{(nlp.n, nlp.m, nlp.nterms, nnzj, nnzh)}")
-            st = [np.zeros(max(k, 1), dtype=np.int32) for k in (nnzj, nnzj, nnzh, nnzh)]
-            L.check(lib.mnk_tape_get_structure(self._h, *[a.ctypes.data for a in st]), "mnk_tape_get_structure")
-            for name, a, b in zip(("jac_I", "jac_J", "hess_I", "hess_J"), st, (nlp.jac_I, nlp.jac_J, nlp.hess_I, nlp.hess_J)):
-                if not np.array_equal(a[:len(b)], b):   # (values would land in the wrong KKT entries)
-                    raise RuntimeError(f"the library's COO structure ({name}) differs from the host model's")
-        except Exception:
-            self.close()
-            raise
-        E = lambda k: torch.empty(max(k, 1), dtype=torch.float64, device=dev)[:k]  # noqa: E731
-        self.jv, self.hv, self.hv0, self.terms = E(nnzj), E(nnzh), E(nnzh), E(nlp.nterms)
-        if nnzh:
-            K.vec_fill(self.hv0, 0.0)
-
-    EXT_OBJ, EXT_GRAD, EXT_CONS, EXT_JAC, EXT_HESS = 1, 2, 4, 8, 16
-
-    def extended(self):
-        """Which callback launches run the interpreter kernel that knows the opcodes from 16 on -- pow tan atan tanh abs sign step
-        min max -- (`mnk_tape_extended`): the sum of EXT_OBJ .. EXT_HESS; 0 for a model that uses none of them."""
-        mask = C.c_int(-1)
-        L.check(L.lib().mnk_tape_extended(self._h, C.byref(mask)), "mnk_tape_extended")
-        return mask.value
-
-    def obj_terms(self, x):
-        L.check(L.lib().mnk_tape_obj_terms(self._h, x.data_ptr(), self.terms.data_ptr()), "mnk_tape_obj_terms")
-        return self.terms
-
-    def obj(self, x):
-        return self.K.get_sum(self.obj_terms(x)) if len(self.terms) else 0.0
-
-    def grad(self, g, x):
-        L.check(L.lib().mnk_tape_grad(self._h, x.data_ptr(), g.data_ptr()), "mnk_tape_grad")
-
-    def cons(self, c, x):
-        L.check(L.lib().mnk_tape_cons(self._h, x.data_ptr(), c.data_ptr()), "mnk_tape_cons")
-
-    def jac_coord(self, x):
-        L.check(L.lib().mnk_tape_jac_coord(self._h, x.data_ptr(), self.jv.data_ptr()), "mnk_tape_jac_coord")
-        return self.jv
-
-    def hess_coord(self, x, y, sigma=1.0):
-        L.check(L.lib().mnk_tape_hess_coord(self._h, x.data_ptr(), y.data_ptr(), float(sigma), self.hv.data_ptr()),
-                "mnk_tape_hess_coord")
-        return self.hv
-
-    def jtprod_x(self, out_x, y):
-        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
-
-    def load_jac(self, x):
-        self.kkt.compress_jacobian(self.jac_coord(x))
-
-    def load_hess(self, x, y, sigma=1.0):
-        self.kkt.compress_hessian(self.hess_coord(x, y, sigma))
-
-    def zero_hess(self):
-        self.kkt.compress_hessian(self.hv0)
-
-    def close(self):
-        if self._h:
-            L.lib().mnk_tape_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceFixedVariableCallbacks:
-    """Any raw-value callbacks object (`prescaled = False`: `DeviceTapeCallbacks`, `DeviceOPFCallbacks`) built on the FULL model,
-    seen over the free variables of a `fixed_vars.FixedVariableHandler` (MakeParameter on the sparse condensed system; reference
-    nlpmodels.jl:912-1013).  Same method set as the inner object, on the reduced problem.  Every call expands the reduced iterate
-    into the handle's `x_full` (one launch), runs the inner callback at full length into full-length scratch, and gathers the
-    reduced values (one launch; objective and constraints need none).  `fused_scaling`: `grad` takes the objective factor and
-    `jac_coord` the per-entry constraint scale, applied inside the gather -- the solver launches no `vec_mul` / `scale_grad`
-    behind them.  `jtprod_x` is the reduced KKT handle's own transposed SpMV."""
-    prescaled = False
-    fused_scaling = True
-
-    def __init__(self, inner, handler, kkt, dev, K):
-        assert not inner.prescaled, "the wrapped callbacks must return the model's raw values"
-        self.inner, self.kkt, self.K = inner, kkt, K
-        self.n, self.m = len(handler.free), inner.m
-        self.fix = DeviceFixedVariables(K.ctx, handler)
-        E = lambda k: torch.empty(max(k, 1), dtype=torch.float64, device=dev)[:k]  # noqa: E731
-        self.g_full = E(handler.n_full)
-        self.jv, self.hv, self.hv0 = E(self.fix.njac), E(self.fix.nhess), E(self.fix.nhess)
-        K.vec_fill(self.hv0, 0.0)
-
-    def obj(self, x):
-        return self.inner.obj(self.fix.expand(x))
-
-    def grad(self, g, x, factor=1.0):
-        self.inner.grad(self.g_full, self.fix.expand(x))
-        self.fix.gather(L.MNK_FIX_FREE, self.g_full, g, None, factor)
-
-    def cons(self, c, x):
-        self.inner.cons(c, self.fix.expand(x))
-
-    def jac_coord(self, x, scale=None):
-        self.fix.gather(L.MNK_FIX_JAC, self.inner.jac_coord(self.fix.expand(x)), self.jv, scale)
-        return self.jv
-
-    def hess_coord(self, x, y, sigma=1.0):
-        self.fix.gather(L.MNK_FIX_HESS, self.inner.hess_coord(self.fix.expand(x), y, sigma), self.hv)
-        return self.hv
-
-    def jtprod_x(self, out_x, y):
-        self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
-
-    def load_jac(self, x):
-        self.kkt.compress_jacobian(self.jac_coord(x))
-
-    def load_hess(self, x, y, sigma=1.0):
-        self.kkt.compress_hessian(self.hess_coord(x, y, sigma))
-
-    def zero_hess(self):
-        self.kkt.compress_hessian(self.hv0)
-
-    def close(self):
-        self.fix.close()
-        self.inner.close()
 
 
 class DeviceMadNLPSolver(MadNLPSolver):
@@ -508,7 +45,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
                                       "(DeviceTapeCallbacks feed COO values to its compressors): use sparse=True with "
                                       "relax_equality, or MadNLPSolver with host callbacks")
         if (opt is not None and opt.fixed_variable_treatment == "make_parameter" and sparse
-                and self._callbacks_class(nlp, sparse) is DeviceQPCallbacks
+                and callbacks_class(nlp, sparse) is DeviceQPCallbacks
                 and (np.asarray(nlp.lvar, float) == np.asarray(nlp.uvar, float)).any()):
             raise NotImplementedError("fixed_variable_treatment = 'make_parameter' with fixed variables on the sparse QP device "
                                       "callbacks (DeviceQPCallbacks): they evaluate f, grad f and c through the reduced KKT "
@@ -536,34 +73,16 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self.K = IPMDeviceKernels(nt, self.ind_lb, self.ind_ub, ctx=ctx)
         self.K.set_perturbation_sets(self.ind_llb, self.ind_uub)
         self.d, self.p, self._w1, self._w4 = (self._new_vec(self._lw) for _ in range(4))   # flat device KKT vectors
-        cls = self._callbacks_class(self.nlp, self.sparse)
-        fixed = self.fixed_handler        # variables made parameters: the callbacks are built on the FULL model (self.nlp)
-        # NLP scaling / the sense: the scaled launches replace the plain ones only when there is something to apply
-        self._scaled = bool(self.opt.nlp_scaling) or self.obj_sign != 1.0
         if self.lbfgs:               # the host mirror (kkt.LowRankHessianKKT) comes off: the handle applies the low-rank term itself
             self.kkt = self.iterator.kkt = self.kkt.inner
-        if cls.prescaled:
-            scaled_data = dict(obj_factor=self.obj_sign * self.obj_scale, con_scale=self.con_scale) if self._scaled else {}
-            if self.lbfgs:
-                scaled_data["own_hessian"] = True
-            if fixed is not None:
-                scaled_data["fixed"] = fixed
-            self.cb = cls(self.nlp, self.kkt, self.dev, self.K, **scaled_data)
-        else:
-            self.cb = cls(self.nlp, self.kkt, self.dev, self.K)
-            if fixed is not None:
-                self.cb = DeviceFixedVariableCallbacks(self.cb, fixed, self.kkt, self.dev, self.K)
-        self._fused = getattr(self.cb, "fused_scaling", False)
-        self.ind_ineq_t = _up(self.ind_ineq, self.dev, np.int64)
-        if self._scaled:
-            self.con_scale_t = None if cls.prescaled else _up(self.con_scale, self.dev)
-            self.jac_scale_t = _up(self.jac_scale, self.dev) if self.sparse and not cls.prescaled else None
-            self.ybuf = self._new_vec(m)          # y .* con_scale, what the model's Hessian / J' product is given
-            self.slack_pos_t = None
-            if 0 < self.ns < m:                   # the inverse of ind_ineq: a row's slack, -1 for an equality row
-                pos = np.full(m, -1, dtype=np.int64)
-                pos[self.ind_ineq] = np.arange(self.ns)
-                self.slack_pos_t = _up(pos, self.dev, np.int64)
+        # NLP scaling / the sense: the scaled launches replace the plain ones only when there is something to apply
+        self._scaled = bool(self.opt.nlp_scaling) or self.obj_sign != 1.0
+        scaling = DeviceScaling(self.K, self.dev, self.n, self.ns, self.ind_ineq, self.rhs, self._scaled, self.obj_sign,
+                                self.obj_scale, self.con_scale, self.jac_scale)
+        self.ind_ineq_t, self.slack_pos_t = scaling.ind_ineq, scaling.slack_pos
+        # variables made parameters (`fixed_handler`): the callbacks are built on the FULL model (self.nlp)
+        self.cb = device_callbacks(self.nlp, self.kkt, self.dev, self.K, self.sparse, scaling, fixed=self.fixed_handler,
+                                   own_hessian=self.lbfgs)
         self.kkt.device_kkt_ops = True
         if not self.sparse:          # the dense handle reads Hessian / Jacobian from its own device copies
             self.cb.load_jac()
@@ -576,67 +95,27 @@ class DeviceMadNLPSolver(MadNLPSolver):
         self._on_device = True
         self._sync = ctx.synchronize
 
-    @staticmethod
-    def _callbacks_class(nlp, sparse):
-        """The device callbacks of a model: by what the model is, not by what the run needs."""
-        if getattr(nlp, "is_tape_model", False):
-            return DeviceTapeCallbacks
-        if hasattr(nlp, "arc_coef"):
-            assert sparse, "the AC-OPF callbacks feed the sparse condensed handle"
-            return DeviceOPFCallbacks
-        return DeviceQPCallbacks if sparse else DeviceDenseQPCallbacks
-
     # slices of a flat KKT vector (reference src/KKT/rhs.jl:90-150)
     def _primal(self, v): return v[:self.nt]
     def _dual(self, v): return v[self.nt:self.nt + self.m]
     def _dual_lb(self, v): return v[self.nt + self.m:self.nt + self.m + len(self.ind_lb)]
     def _dual_ub(self, v): return v[self.nt + self.m + len(self.ind_lb):]
 
-    # ------------------------------------------------------------------ callbacks
+    # ------------------------------------------------------------------ callbacks: scaling and the sense are `self.cb`'s
     def eval_f(self, x):
-        if not self._on_device:
-            return super().eval_f(x)
-        if self.cb.prescaled:
-            return self.cb.obj(x[:self.n])
-        return self.obj_sign * (self.cb.obj(x[:self.n]) * self.obj_scale)
+        return self.cb.eval_f(x) if self._on_device else super().eval_f(x)
 
     def eval_grad(self, x):
         if not self._on_device:
             return super().eval_grad(x)
-        if self._fused:                                # gather and factor in one launch (DeviceFixedVariableCallbacks)
-            self.cb.grad(self.f[:self.n], x[:self.n], self.obj_sign * self.obj_scale if self._scaled else 1.0)
-            self.K.vec_fill(self.f[self.n:], 0.0)
-            self.cnt.obj_grad_cnt += 1
-            return
-        self.cb.grad(self.f[:self.n], x[:self.n])
-        if self._scaled and not self.cb.prescaled:     # the factor and the zero slack part in one launch
-            self.K.scale_grad(self.f, self.n, self.obj_sign * self.obj_scale)
-        else:
-            self.K.vec_fill(self.f[self.n:], 0.0)
+        self.cb.eval_grad(self.f, x)
         self.cnt.obj_grad_cnt += 1
 
     def eval_cons(self, c, x):
-        if not self._on_device:
-            return super().eval_cons(c, x)
-        self.cb.cons(c, x[:self.n])
-        if self._scaled:                               # c .* con_scale - slack - rhs in one launch
-            return self.K.scale_cons(c, self.con_scale_t, x[self.n:], self.slack_pos_t, self.rhs)
-        if self.ns == self.m:
-            self.K.vec_axpby(c, 1.0, c, -1.0, x[self.n:])      # ind_ineq = all constraints, in order
-        else:
-            self.K.vec_scatter_axpy(c, self.ind_ineq_t, -1.0, x[self.n:])
-        self.K.vec_axpby(c, 1.0, c, -1.0, self.rhs)
+        return self.cb.eval_cons(c, x) if self._on_device else super().eval_cons(c, x)
 
     def eval_jac(self, x):
-        if not self._on_device:
-            return super().eval_jac(x)
-        if self._scaled and self._fused:               # gather and con_scale[jac_I] in one launch
-            return self.kkt.compress_jacobian(self.cb.jac_coord(x[:self.n], self.jac_scale_t))
-        if self._scaled and not self.cb.prescaled:
-            jv = self.cb.jac_coord(x[:self.n])
-            self.K.vec_mul(jv, jv, self.jac_scale_t)
-            return self.kkt.compress_jacobian(jv)
-        self.cb.load_jac(x[:self.n])
+        return self.cb.eval_jac(x) if self._on_device else super().eval_jac(x)
 
     def eval_lag_hess(self, x, y, is_resto=False):
         if not self._on_device:
@@ -645,26 +124,24 @@ class DeviceMadNLPSolver(MadNLPSolver):
             return self._eval_lag_hess_lbfgs_device(x, y)
         if self.qn is not None:
             return self._eval_lag_hess_qn_device(x, y)
-        w = 0.0 if is_resto else 1.0                                 # objective weight 0 in robust!
-        if self._scaled and not self.cb.prescaled:
-            self.K.vec_mul(self.ybuf, y, self.con_scale_t)
-            self.kkt.compress_hessian(self.cb.hess_coord(x[:self.n], self.ybuf, w * self.obj_sign * self.obj_scale))
-        else:
-            self.cb.load_hess(x[:self.n], y, w)
+        self.cb.eval_lag_hess(x, y, 0.0 if is_resto else 1.0)        # objective weight 0 in robust!
         self.cnt.lag_hess_cnt += 1
+
+    def _qn_backups(self, *more):
+        """The backups of callbacks.jl:184-186 as device vectors (`qn_dev`), x and grad f saved; `more`: further n-vectors."""
+        n = self.n
+        d = self.qn_dev = SimpleNamespace(**{k: self._new_vec(n) for k in ("sk", "yk", "last_x", "last_g", "last_jv") + more})
+        self.K.vec_copy(d.last_x, self.x[:n])
+        self.K.vec_copy(d.last_g, self.f[:n])
+        return d
 
     # ------------------------------------------------------------------ quasi-Newton Hessian in the handle's device buffer
     def _qn_upload(self):
         """The host initialization has run `init!` on the host copy; the device buffer gets its own `init!` from the
         uploaded gradient and objective (`mnk_dc_qn_init`), and the backups of callbacks.jl:184-186 become device vectors.
         From here on the approximation exists on the device only: it is never loaded from the host or from the model."""
-        from types import SimpleNamespace
-        n = self.n
-        self.kkt.qn_init_device(self.qn.kind, self.f[:n], self.obj_val)
-        d = SimpleNamespace(**{k: self._new_vec(n) for k in ("sk", "yk", "last_x", "last_g", "last_jv")})
-        self.K.vec_copy(d.last_x, self.x[:n])
-        self.K.vec_copy(d.last_g, self.f[:n])
-        self.qn_dev = d
+        self.kkt.qn_init_device(self.qn.kind, self.f[:self.n], self.obj_val)
+        self._qn_backups()
 
     def _eval_lag_hess_qn_device(self, x, y):
         """`MadNLPSolver._eval_lag_hess_qn` on device vectors: one transposed Jacobian product of the callbacks, one launch for
@@ -675,10 +152,7 @@ class DeviceMadNLPSolver(MadNLPSolver):
         jl = jv = None
         if self.m > 0:
             jl = self.jacl[:n]                                      # J(x+)' l+ (current: see the host mirror)
-            if self._scaled and not self.cb.prescaled:              # J(x)' (l .* con_scale), nlpmodels.jl:791-801
-                self.K.vec_mul(self.ybuf, y, self.con_scale_t)
-                y = self.ybuf
-            self.cb.jtprod_at(d.last_x, y, d.last_jv)
+            self.cb.eval_jtprod_at(d.last_x, y, d.last_jv)
             jv = d.last_jv
         self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
         self.kkt.qn_update_device(d.sk, d.yk)
@@ -689,16 +163,11 @@ class DeviceMadNLPSolver(MadNLPSolver):
         to the KKT handle and runs its own `init!` from the uploaded gradient (the same ordered sum, the same sigma).  The
         backups of callbacks.jl:184-186 become device vectors, and the compressed Jacobian of the initial point is kept for
         J(x_0)' l_1.  From here on no Hessian callback is launched."""
-        from types import SimpleNamespace
-        n = self.n
         qd = self.kkt.attach_quasi_newton(self.qn.options)
-        d = SimpleNamespace(**{k: self._new_vec(n) for k in ("sk", "yk", "last_x", "last_g", "last_jv", "hess")})
-        self.K.vec_copy(d.last_x, self.x[:n])
-        self.K.vec_copy(d.last_g, self.f[:n])
-        self.K.vec_fill(d.hess, qd.init(self.f[:n], self.obj_val))
+        d = self._qn_backups("hess")
+        self.K.vec_fill(d.hess, qd.init(self.f[:self.n], self.obj_val))
         self.kkt.compress_hessian(d.hess)
         self.kkt.keep_jacobian_device()
-        self.qn_dev = d
 
     def _eval_lag_hess_lbfgs_device(self, x, y):
         """`MadNLPSolver._eval_lag_hess_qn` for `CompactLBFGS` on device vectors.  J(x_k)' l_+ comes from the Jacobian values the
@@ -1176,6 +645,12 @@ class DeviceMadNLPSolver(MadNLPSolver):
             self.initialize()          # host (numpy), once
             self._upload()
         return super().solve()
+
+    def close(self):
+        """Release the callbacks, the vector kernels and the KKT handle, in that order; before `_upload` only the last exists."""
+        for name in ("cb", "K", "kkt"):
+            if hasattr(getattr(self, name, None), "close"):
+                getattr(self, name).close()
 
     def solution(self):
         """`MadNLPSolver.solution` from a download of the iterate."""

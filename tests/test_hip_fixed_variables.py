@@ -1,5 +1,5 @@
 """`fixed_variable_treatment = "make_parameter"` on the device: the `mnk_fix_*` kernels behind
-`ipm_dev.DeviceFixedVariableCallbacks` against the host layer (`madnlp_jl_amd.fixed_vars`), and `DeviceMadNLPSolver` against
+`device_callbacks.DeviceFixedVariableCallbacks` against the host layer (`madnlp_jl_amd.fixed_vars`), and `DeviceMadNLPSolver` against
 `MadNLPSolver` on the same HIP back-end, sparse (reduced) and dense (frozen)."""
 import dataclasses
 
@@ -29,10 +29,7 @@ def sparse_factory(ctx, nlp):
 
 def close(*solvers):
     for s in solvers:
-        if hasattr(s, "cb"):
-            s.cb.close()
-            s.K.close()
-        s.kkt.close()
+        (s if hasattr(s, "cb") else s.kkt).close()       # a device solver closes its callbacks, kernels and KKT handle
 
 
 def assert_same_run(sd, sh):

@@ -155,10 +155,7 @@ def _dense_factory(ctx):
 
 def _close(*solvers):
     for s in solvers:
-        if hasattr(s, "cb"):
-            s.cb.close()
-            s.K.close()
-        s.kkt.close()
+        (s if hasattr(s, "cb") else s.kkt).close()       # a device solver closes its callbacks, kernels and KKT handle
 
 
 # ------------------------------------------------------------------------------------------ G2. factors of one change no bit

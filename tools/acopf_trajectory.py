@@ -174,4 +174,4 @@ if os.environ.get("PIVOTS", "0") != "0" and replay:
                             pivot=pv, d_hip=Dh[pv], d_fp64=float(d64[pv]), d_ld=float(d80[pv]))
         ls.close()
         break
-sd.cb.close(); sd.K.close(); sd.kkt.close()
+sd.close()

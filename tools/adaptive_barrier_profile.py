@@ -63,7 +63,7 @@ def run(barrier, timing=False):
                wall_s=wall)
     if timing:
         rec["quality_function_call"] = time_quality_function(s)
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec
 
 

@@ -20,7 +20,8 @@ import madnlp_jl_amd as mj  # noqa: E402
 from madnlp_jl_amd import fixed_vars as FV  # noqa: E402
 from madnlp_jl_amd import tape_model as T  # noqa: E402
 from madnlp_jl_amd.ipm import IPMOptions  # noqa: E402
-from madnlp_jl_amd.ipm_dev import DeviceFixedVariableCallbacks, DeviceMadNLPSolver, DeviceTapeCallbacks, _up  # noqa: E402
+from madnlp_jl_amd.device_callbacks import DeviceFixedVariableCallbacks, DeviceTapeCallbacks, _up  # noqa: E402
+from madnlp_jl_amd.ipm_dev import DeviceMadNLPSolver  # noqa: E402
 from madnlp_jl_amd.ipm_device import IPMDeviceKernels  # noqa: E402
 
 CASE = sys.argv[2] if len(sys.argv) > 2 else "case1354pegase"
@@ -48,7 +49,7 @@ def solve(nlp, treatment, tol=1e-6):
     r = s.solution()
     rec = dict(status=s.status, objective=r.objective, n=s.n, iterations=s.cnt.k, factorizations=s.cnt.factorization_cnt,
                backsolves=s.cnt.backsolve_cnt, obj_grad_evals=s.cnt.obj_grad_cnt, wall_s=wall)
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec, r
 
 

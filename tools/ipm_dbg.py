@@ -28,4 +28,4 @@ for rep in range(2):
     t0 = time.perf_counter(); s.solve(); torch.cuda.synchronize(); w = time.perf_counter() - t0
     ls = s.kkt.linear_solver
     print(mode, rep, s.status, s.cnt.k, s.cnt.factorization_cnt, s.cnt.backsolve_cnt, f"{w:.3f}s", "algo", ls.get_stat("panel_algo"), "bk", ls.bk_info()[1], "growth", ls.get_stat("growth"))
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()

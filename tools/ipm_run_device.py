@@ -74,8 +74,5 @@ for label, cls in drivers:
                "factorizations": s.cnt.factorization_cnt, "backsolves": s.cnt.backsolve_cnt, "wall_s_regular_phase": wall,
                "ms_per_iteration_wall": 1e3 * wall / max(1, s.cnt.k), "it_per_s": s.cnt.k / wall, "obj": float(s.obj_val)}
         print(json.dumps(rec), flush=True)
-        if cls is DeviceMadNLPSolver:
-            s.cb.close()
-            s.K.close()
-        s.kkt.close()
+        (s if cls is DeviceMadNLPSolver else s.kkt).close()
 ctx.close()

@@ -1,4 +1,5 @@
-"""Bit-exact record of IPM runs, for A/B comparisons of two versions of the driver (`madnlp.jl_amd/ipm.py`, `ipm_dev.py`).
+"""Bit-exact record of IPM runs, for A/B comparisons of two versions of the driver (`madnlp.jl_amd/ipm.py`, `ipm_dev.py`,
+`device_callbacks.py`).
 
   python tools/ipm_trajectory_dump.py --out A.json                       host driver (MadNLPSolver) on the CPU oracle back-end
   python tools/ipm_trajectory_dump.py --device --out A.json              DeviceMadNLPSolver on the HIP KKT systems (needs a GPU)
@@ -13,7 +14,8 @@ Two versions that perform the same IEEE operations in the same order write ident
 
 By wrapping (nothing in the product counts), per run: which branches of the line search and of the inertia correction were
 reached; in --device mode also the result-returning `mnk_ipm_*` calls made outside a batch (one host synchronization each),
-the `mnk_ipm_batch_end` calls (one synchronization per batch) and the `vec_*` launches -- integers fixed by the control flow.
+the `mnk_ipm_batch_end` calls (one synchronization per batch), the `vec_*` launches and the `scale_grad`, `scale_cons` and `gemv`
+launches of the callbacks' scaling layer -- integers fixed by the control flow.
 The host mode refuses to write unless its runs reach every branch a driver refactor moves (`REQUIRED`)."""
 import argparse
 import hashlib
@@ -212,8 +214,12 @@ def run_host(args):
 
 
 # ------------------------------------------------------------------------------------------------ device: HIP KKT systems
+LAUNCH_KEYS = ("unbatched_results", "batch_ends", "vec_launches", "scale_grad", "scale_cons", "gemv")
+
+
 def count_launches(mj_ipm_device, counts):
-    """Wrap `IPMDeviceKernels` so that `counts` holds: unbatched result calls, batch ends, vec_* launches."""
+    """Wrap `IPMDeviceKernels` so that `counts` holds: unbatched result calls, batch ends, vec_* launches, and the `scale_grad`,
+    `scale_cons` and `gemv` launches under their own names."""
     K, B = mj_ipm_device.IPMDeviceKernels, mj_ipm_device._Batch
     call, leave = K._call, B.__exit__
 
@@ -226,20 +232,57 @@ def count_launches(mj_ipm_device, counts):
         counts["batch_ends"] += 1
         return leave(self, *exc)
     K._call, B.__exit__ = _call, __exit__
-    for name in [n for n in vars(K) if n.startswith("vec_")]:
-        def wrap(f):
+    for name in [n for n in vars(K) if n.startswith("vec_")] + list(LAUNCH_KEYS[3:]):
+        def wrap(f, key):
             def g(self, *a, **k):
-                counts["vec_launches"] += 1
+                counts[key] += 1
                 return f(self, *a, **k)
             return g
-        setattr(K, name, wrap(getattr(K, name)))
+        setattr(K, name, wrap(getattr(K, name), "vec_launches" if name.startswith("vec_") else name))
+
+
+def acopf_case30_fixed():
+    """tests/test_hip_fixed_variables.py's model: the tape AC-OPF with variables fixed at the (CPU oracle's) unfixed optimum."""
+    from madnlp_jl_amd.ipm import MadNLPSolver
+    from madnlp_jl_amd.tape_model import acopf_tape_model
+    from tests.test_fixed_variables_cpu import acopf_fixed, factory, sparse_options
+    M0 = acopf_tape_model("case30")
+    s0 = MadNLPSolver(M0, factory("sparse_condensed", M0), sparse_options(), sparse=True)
+    assert s0.solve() == "SOLVE_SUCCEEDED"
+    return acopf_fixed("case30", s0.solution().solution)[0]
 
 
 def device_cases(mj):
+    """(name, model, sparse, forced, options, solver attributes).  Between them the runs reach every way the callbacks are
+    evaluated: raw values (hand-written and tape), prescaled data (sparse and dense QP) and the fixed-variable wrapper, each
+    scaled and unscaled; equalities beside inequalities; exact, BFGS and compact L-BFGS Hessians; a maximization."""
+    from madnlp_jl_amd import tape_model as T
     from madnlp_jl_amd.problems import ACOPFModel, DenseQPModel, InfeasibleModel, SparseQPModel
+    from tests.nlp_scaling_cases import rescaled_dense_qp
+    from tests.test_fixed_variables_cpu import qp_fixed
     acopf = lambda: ACOPFModel("case1354pegase")  # noqa: E731
     dqp = lambda: DenseQPModel(20, 15, 2)  # noqa: E731
-    return [("acopf-case1354pegase", acopf, True, False, {}, {}),
+    rqp = lambda: rescaled_dense_qp(20, 15, 2)  # noqa: E731
+    scaled, mp = {"nlp_scaling": True}, {"fixed_variable_treatment": "make_parameter"}
+    scaled10 = {"nlp_scaling": True, "nlp_scaling_max_gradient": 10.0}
+    fixed30 = acopf_case30_fixed()
+    small = [("hs15-tape-scaled", T.hs15_tape_model, True, False, scaled, {}),
+             ("hs15-tape-unscaled", T.hs15_tape_model, True, False, {"nlp_scaling": False}, {}),
+             ("acopf-case30-scaled", lambda: ACOPFModel("case30"), True, False, scaled10, {}),
+             ("acopf-case30-tape-scaled", lambda: T.acopf_tape_model("case30"), True, False, scaled10, {}),
+             ("acopf-case30-tape-fixed-scaled", lambda: fixed30, True, False, {**mp, **scaled10}, {}),
+             ("acopf-case30-tape-fixed-unscaled", lambda: fixed30, True, False, mp, {}),
+             ("lootsma-tape-fixed-scaled", T.lootsma_fixed_tape_model, True, False, {**mp, **scaled}, {}),
+             ("lootsma-tape-fixed-unscaled", T.lootsma_fixed_tape_model, True, False, mp, {}),
+             ("simplex-lp-tape-max-scaled", lambda: T.simplex_lp_tape_model(1.0, minimize=False), True, False, scaled, {}),
+             ("simplex-lp-tape-max-unscaled", lambda: T.simplex_lp_tape_model(1.0, minimize=False), True, False, {}, {}),
+             ("rescaled-dense-qp-scaled-exact", rqp, False, False, scaled, {}),
+             ("rescaled-dense-qp-scaled-bfgs", rqp, False, False, {**scaled, "hessian_approximation": "bfgs"}, {}),
+             ("dense-qp-frozen", lambda: qp_fixed(2), False, False, mp, {}),
+             ("dense-qp-frozen-scaled", lambda: qp_fixed(2), False, False, {**mp, **scaled}, {}),
+             ("sparse-qp-case30-lbfgs-scaled", lambda: SparseQPModel("case30"), True, False,
+              {**scaled, "hessian_approximation": "compact_lbfgs"}, {})]
+    return small + [("acopf-case1354pegase", acopf, True, False, {}, {}),
             ("acopf-case1354pegase-speculate", acopf, True, False, {}, {"speculate": True}),
             ("sparse-qp-case30-forced", lambda: SparseQPModel("case30"), True, True, {}, {}),
             ("sparse-qp-case118-forced", lambda: SparseQPModel("case118"), True, True, {}, {}),
@@ -249,11 +292,12 @@ def device_cases(mj):
 
 
 def hip_factory(mj, nlp, ctx, sparse):
+    from madnlp_jl_amd.fixed_vars import structure
     opt = lambda: mj.HipSolverOptions(lapack_algorithm=mj.BUNCHKAUFMAN)  # noqa: E731
 
     def make(info):
-        if sparse:
-            return mj.SparseCondensedKKTSystem(info["n"], info["m"], nlp.jac_I, nlp.jac_J, nlp.hess_I, nlp.hess_J, info["ind_ineq"],
+        if sparse:       # (`structure`: the reduced problem's under make_parameter, the diagonal Hessian's under compact L-BFGS)
+            return mj.SparseCondensedKKTSystem(info["n"], info["m"], *structure(nlp, info), info["ind_ineq"],
                                                info["ind_lb"], info["ind_ub"], ctx=ctx, opt_linear_solver=opt(), device_kkt_ops=True)
         return mj.DenseCondensedKKTSystem(info["n"], info["m"], info["ind_ineq"], info["ind_eq"], info["ind_lb"], info["ind_ub"],
                                           ctx=ctx, opt_linear_solver=opt(), device_kkt_ops=True)
@@ -261,7 +305,9 @@ def hip_factory(mj, nlp, ctx, sparse):
 
 
 def close(s):
-    s.cb.close()
+    if hasattr(s, "close"):
+        return s.close()
+    s.cb.close()          # (--package: a driver from before `DeviceMadNLPSolver.close`)
     s.K.close()
     s.kkt.close()
 
@@ -283,7 +329,7 @@ def run_device(args, mj):
         cls = counted(DeviceMadNLPSolver, counts)
         if forced:
             cls = type("ForcedDevice", (Forced, cls), {})
-        launches.update(unbatched_results=0, batch_ends=0, vec_launches=0)
+        launches.update(dict.fromkeys(LAUNCH_KEYS, 0))
         s = cls(nlp, hip_factory(mj, nlp, ctx, sparse), options(IPMOptions, sparse, **kw), sparse=sparse)
         for k, v in attrs.items():
             setattr(s, k, v)

@@ -100,7 +100,7 @@ def run(iterator, timing=False):
                backsolves=s.cnt.backsolve_cnt, **tally, wall_s=wall)
     if timing:
         rec["step_pieces"] = time_step_pieces(s)
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec
 
 

@@ -59,7 +59,7 @@ def run(approx, keep=False):
         rec["lbfgs"] = s.kkt.qn_status()
     if keep:
         return rec, s
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec, None
 
 
@@ -137,7 +137,7 @@ for phase in ("cold", "warm"):
 if s.kkt.qn_status()["current_mem"] > 0:
     out["pieces"] = pieces(s)
     print(json.dumps(out["pieces"], indent=1), flush=True)
-s.cb.close(); s.K.close(); s.kkt.close()
+s.close()
 ctx.close()
 dest = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                           "lbfgs_case1354.json")

@@ -40,7 +40,7 @@ def run(scaling):
     wall = time.perf_counter() - t0
     rec = dict(status=s.status, objective=s.obj_val, iterations=s.cnt.k, factorizations=s.cnt.factorization_cnt,
                backsolves=s.cnt.backsolve_cnt, wall_s=wall)
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec
 
 

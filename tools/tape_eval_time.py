@@ -21,7 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import madnlp_jl_amd as mj  # noqa: E402
 from madnlp_jl_amd import tape_model as T  # noqa: E402
 from madnlp_jl_amd.ipm import IPMOptions  # noqa: E402
-from madnlp_jl_amd.ipm_dev import DeviceMadNLPSolver, DeviceOPFCallbacks, DeviceTapeCallbacks, _up  # noqa: E402
+from madnlp_jl_amd.device_callbacks import DeviceOPFCallbacks, DeviceTapeCallbacks, _up  # noqa: E402
+from madnlp_jl_amd.ipm_dev import DeviceMadNLPSolver  # noqa: E402
 from madnlp_jl_amd.ipm_device import IPMDeviceKernels  # noqa: E402
 from madnlp_jl_amd.problems import ACOPFModel  # noqa: E402
 
@@ -228,7 +229,7 @@ def run(nlp):
     wall = time.perf_counter() - t0
     rec = dict(status=s.status, objective=s.obj_val, iterations=s.cnt.k, factorizations=s.cnt.factorization_cnt,
                backsolves=s.cnt.backsolve_cnt, wall_s=wall)
-    s.cb.close(); s.K.close(); s.kkt.close()
+    s.close()
     return rec
 
 

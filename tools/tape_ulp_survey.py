@@ -106,7 +106,7 @@ def step_host():
 def step_device():
     import torch
     import madnlp_jl_amd as mj
-    from madnlp_jl_amd.ipm_dev import DeviceTapeCallbacks, _up
+    from madnlp_jl_amd.device_callbacks import DeviceTapeCallbacks, _up
     from madnlp_jl_amd.ipm_device import IPMDeviceKernels
     args = arguments()
     M, x = model(args)
