@@ -228,10 +228,26 @@ class DeviceFixedVariables(_LibraryHandle):
 
 
 class _QuadraticCallbacks(DeviceCallbacks):
-    """f = 0.5 x'Hx + q'x with linear constraints: `_hmul(x)` is the subclass's H x; the Lagrangian Hessian is sigma H, zero under
-    objective weight 0, and `handle_has_H` says which of the two the KKT handle holds."""
+    """f = 0.5 x'Hx + q'x with linear constraints: `_hmul(x)` is the subclass's H x; the Lagrangian Hessian is sigma H: the
+    uploaded H under objective weight 1, zero under 0, a scaled copy (`_weighted`, one launch into scratch) under any other
+    weight.  `handle_has_H` says whether the KKT handle holds H itself, `_held` what it holds otherwise."""
     handle_has_H = True
+    _held = _scratch = None
     H = fix = None                     # what a subclass owns besides its tensors: a `DeviceHessianProduct`, a `DeviceFixedVariables`
+
+    def _weighted(self, sigma, full, zero, masked):
+        """The source of the Lagrangian Hessian sigma H: `zero`, `full`, or sigma * `full` in scratch.  `masked`: `zero` carries
+        the unit diagonal of frozen variables, which the weight must not touch: sigma (full - zero) + zero."""
+        if sigma == 0.0 or sigma == 1.0:
+            return zero if sigma == 0.0 else full
+        if self._scratch is None:
+            self._scratch = torch.empty_like(full)
+        if masked:
+            self.K.vec_axpby(self._scratch, sigma, full, -sigma, zero)
+            self.K.vec_axpby(self._scratch, 1.0, self._scratch, 1.0, zero)
+        else:
+            self.K.vec_axpby(self._scratch, sigma, full)
+        return self._scratch
 
     def obj(self, x):
         hx = self._hmul(x)
@@ -271,12 +287,12 @@ class DeviceQPCallbacks(_QuadraticCallbacks):
             self.H.mul(x, self._hx)
             return self._hx
         # the SpMV runs on the handle's compressed Lagrangian Hessian: while that holds something else (zero after
-        # initialize!(kkt), objective weight 0 in robust!) H is put back for the product
+        # initialize!(kkt), objective weight 0 in robust!, another weight) H is put back for the product, then what was held
         if not self.handle_has_H:
             self.kkt.compress_hessian(self.hv)
         self.kkt.spmv_device(L.MNK_SC_HESS, 0, 1.0, x, 0.0, self._hx)
         if not self.handle_has_H:
-            self.kkt.compress_hessian(self.hv0)
+            self.kkt.compress_hessian(self._held)
         return self._hx
 
     def grad(self, g, x):
@@ -292,9 +308,9 @@ class DeviceQPCallbacks(_QuadraticCallbacks):
         self.kkt.compress_jacobian(self.jv)
 
     def load_hess(self, x=None, y=None, sigma=1.0):
-        zero = sigma == 0.0            # linear constraints: the Lagrangian Hessian is sigma H
-        self.kkt.compress_hessian(self.hv0 if zero else self.hv)
-        self.handle_has_H = not zero
+        self._held = self._weighted(sigma, self.hv, self.hv0, False)      # linear constraints: the Lagrangian Hessian is sigma H
+        self.kkt.compress_hessian(self._held)
+        self.handle_has_H = sigma == 1.0
 
 
 class DeviceDenseQPCallbacks(_QuadraticCallbacks):
@@ -357,10 +373,9 @@ class DeviceDenseQPCallbacks(_QuadraticCallbacks):
             L.check(L.lib().mnk_dc_set_jac(self.kkt._h, self.A_kkt_cm.data_ptr(), self.m, L.MNK_DEVICE), "mnk_dc_set_jac")
 
     def load_hess(self, x=None, y=None, sigma=1.0):
-        zero = sigma == 0.0
-        src = self.P0_cm if zero else self.P_kkt_cm
+        src = self._held = self._weighted(sigma, self.P_kkt_cm, self.P0_cm, self.fix is not None)
         L.check(L.lib().mnk_dc_set_hess(self.kkt._h, src.data_ptr(), self.n, L.MNK_DEVICE), "mnk_dc_set_hess")
-        self.handle_has_H = not zero
+        self.handle_has_H = sigma == 1.0
 
 
 class DeviceOPFCallbacks(DeviceCOOCallbacks):
