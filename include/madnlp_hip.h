@@ -834,6 +834,13 @@ int mnk_debug_dag_merged_tasks(int ntile, int chunk, int band_tiles, int js2, in
  * queue after queue, first phase first; off: 2 x (nq + 1) offsets into `order`.  Returns the number of tasks. */
 int mnk_debug_dag_deal(int ntile, int chunk, int band_tiles, int js2, int taper0, int fill, int ninst, int period, int nq, int gang,
                        int* tasks_out, int* order, int cap, int* off, int* first_phase);
+/* The plan shape of that schedule for a padded order Np (a multiple of 64; host only): js2, the first strip-column (256 columns) from
+ * which every remaining row is a 64-row strip of the pivot chain's deep band -- 0: from the first column on, ceil(Np / 256): never
+ * (band + bulk kernel throughout).  dag_cus2: the CUs of the deep band's partition (0: there is none, js2 = ceil(Np / 256));
+ * dag_deep_rows, js2_override: the options "dag_deep_rows" and "dag_js2" (negative: by size).  A js2 that would leave more than
+ * dag_cus2 strips to the deep band is raised to ceil((Np - 64 dag_cus2) / 256).  Returns js2 (the statistic "dag_js2"), -1 on bad
+ * arguments. */
+int mnk_debug_dag_js2(int64_t Np, int dag_cus2, int64_t dag_deep_rows, int js2_override);
 
 /* Diagnostics / tests (host only): the envelope per 128-row tile row that a solver of order `order` (<= the handle's n) uses when
  * it factors this KKT handle's condensed matrix: tile_env[I] = (first nonzero column over the rows of tile I) / 128, truncated to

@@ -279,6 +279,7 @@ SIGNATURES = {
     "mnk_debug_dag_tasks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "mnk_debug_dag_merged_tasks": (C.c_int, [C.c_int] * 8 + [_vp, C.c_int]),
     "mnk_debug_dag_deal": (C.c_int, [C.c_int] * 10 + [_vp, _vp, C.c_int, _vp, _vp]),
+    "mnk_debug_dag_js2": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int]),
     "mnk_sc_debug_tile_env": (C.c_int, [_vp, C.c_int64, _vp, C.c_int]),
     "mnk_debug_tile_env_csc": (C.c_int, [C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int]),
     "mnk_sc_debug_tile_envh": (C.c_int, [_vp, C.c_int64, _vp, C.c_int]),

@@ -942,7 +942,7 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
     hipStream_t s = ctx->stream;
     const int64_t Np = ls->Np, ld = ls->ld;
     const bool ldl = ls->algo == MNK_LDL;
-    const int ntile = (int)(Np / 128), nsc = (int)((Np + 255) / 256);
+    const int ntile = (int)(Np / 128);
     auto give_up = [&]() {
         (void)hipGetLastError();
         ls->plan.invalidate();
@@ -965,9 +965,8 @@ int mnk_ls_dag_prepare(mnk_ls* ls) {
         // N = 4096 1.61 vs 1.73 ms, 4608 1.86 vs 1.99, 5120 2.20 vs 2.27, 5632 2.70 vs 2.59, 6144 3.24 vs 2.93 (Cholesky 5632: 2.75 vs 2.46) --
         // above that every strip's left-looking prologue on its one CU costs more than the bulk kernel's closing tasks; the limit
         // was the partition's 96 strips = 6144 rows: dag_deep_rows)
-        const int64_t deep_rows = std::min<int64_t>((int64_t)ctx->dag_cus2 * NBI, ls->dag_deep_rows);
-        ls->plan.key.js2 = (ctx->dag_cus2 > 0 && Np <= deep_rows) ? 0 : nsc;
-        if (ls->dag_js2_override >= 0) ls->plan.key.js2 = std::min(nsc, ls->dag_js2_override);
+        // (the rule, with the bound on an override that would leave the deep band more strips than it has CUs: dag_plan.h)
+        ls->plan.key.js2 = mnk::dag_choose_js2(Np, ctx->dag_cus2, ls->dag_deep_rows, ls->dag_js2_override);
         mnk::DagTaskList& h = ls->plan.list;
         ls->plan.key.chunk = ls->dag_chunk; ls->plan.key.taper0 = ls->dag_taper0; ls->plan.key.band = ls->dag_band;
         h = mnk::dag_build_tasks(ntile, ls->dag_chunk, ls->dag_band / 2, ls->plan.key.js2, ls->dag_taper0);

@@ -72,6 +72,14 @@ struct DagTaskList {
     int size() const { return (int)tasks.size(); }
 };
 
+// js2 of a factorization of padded order `Np` (a multiple of 64): the first strip-column (256 columns) of the second phase, from
+// which every remaining row is a 64-row strip of the chain's deep band.  0: every row in the band from the first column on (orders
+// up to `deep_rows` that fit the `cus2` CUs of the deep band's partition); nsc = ceil(Np / 256): band + bulk kernel throughout
+// (also whenever cus2 == 0: there is no deep band); `js2_override` >= 0 (option dag_js2) asks for a strip-column in between.
+// Every strip of the deep band needs a CU to itself and they wait on one another, so a request that would leave more than `cus2`
+// strips to it is raised to the smallest admissible strip-column, ceil((Np - 64 cus2) / 256), capped at nsc.
+int dag_choose_js2(int64_t Np, int cus2, int64_t deep_rows, int js2_override);
+
 // The list of one factorization of `ntile` 128-row tiles: chunks of at most `chunk` tile columns, tapered from `taper0`; strip-
 // columns Js < js2 have a band of `band_tiles` tile rows, the others a band that covers every remaining row.
 DagTaskList dag_build_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0);

@@ -8,6 +8,17 @@
 
 namespace mnk {
 
+int dag_choose_js2(int64_t Np, int cus2, int64_t deep_rows, int js2_override) {
+    const int64_t nsc = (Np + 255) / 256;
+    if (cus2 <= 0) return (int)nsc;
+    int64_t js2 = Np <= std::min<int64_t>(64 * (int64_t)cus2, deep_rows) ? 0 : nsc;
+    if (js2_override >= 0) js2 = std::min<int64_t>(nsc, js2_override);
+    // (Np - 256 js2) / 64 strips of the deep band on cus2 CUs
+    const int64_t over = Np - 64 * (int64_t)cus2;
+    const int64_t least = over > 0 ? std::min(nsc, (over + 255) / 256) : 0;
+    return (int)std::max(js2, least);
+}
+
 // The tasks come in the order of the queue: sorted by the chain position at which they become ready (the last tile column they
 // read), band tiles and rows next to the band first.
 DagTaskList dag_build_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0) {
@@ -241,6 +252,13 @@ int plan_write(const mnk::DagTaskList& list, int* out, int cap) {
     return list.size();
 }
 }  // namespace
+
+// js2 of a factorization of padded order Np (dag_choose_js2) on a context with `dag_cus2` deep-band CUs, under the options
+// dag_deep_rows and dag_js2 (`js2_override`; negative: by size).
+extern "C" int mnk_debug_dag_js2(int64_t Np, int dag_cus2, int64_t dag_deep_rows, int js2_override) {
+    if (Np <= 0 || Np % 64 != 0 || dag_cus2 < 0 || dag_deep_rows < 0) return -1;
+    return mnk::dag_choose_js2(Np, dag_cus2, dag_deep_rows, js2_override);
+}
 
 // The task list of one factorization; *first_phase receives the number of first-phase tasks.
 extern "C" int mnk_debug_dag_tasks(int ntile, int chunk, int band_tiles, int js2, int taper0, int* out, int cap, int* first_phase) {

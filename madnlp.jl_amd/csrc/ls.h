@@ -367,7 +367,7 @@ struct mnk_ls {
     mnk::DevBuf<unsigned long long> dag_trace;  // diagnostics (option dag_trace): time stamps per bulk task / chain strip
     bool dag_trace_on = false;
     int64_t inv_done = 0;         // strip-columns whose diagonal blocks the current factorization has already inverted for the solves
-    int dag_band = 16;            // 64-row strips per band of the persistent pivot chain (8, 12 or 16; <= the chain's CUs)
+    int dag_band = 16;            // 64-row strips per band of the persistent pivot chain (a multiple of 4 in 8..64, i.e. dag_band / 2 tiles; with more strips than the chain has CUs -- 16 unless MNK_DAG_CUS says otherwise -- choose_schedule keeps schedule 4; 8, 12 and 16 run under test)
     int dag_taper0 = 2;           // (1: -0.5 .. -1 % slower, alternating runs on two boxes) length of the last chunk in front of a tile's closing task; the chunks double from there (1, 2, 4, ...)
     long dag_spin_limit = 0;  // option: polls (~0.17 us each) a device-side wait of the schedule may take before it gives up
                               // (info = -7); 0 = by the order of the matrix (mnk_ls_dag_spin_limit)

@@ -232,7 +232,7 @@ int mnk_ls_set_option(mnk_ls* ls, const char* key, double value) {
     if (!strcmp(key, "pivot_tol")) { ls->pivot_tol = value; return 0; }
     if (!strcmp(key, "envelope_half")) { ls->envelope_half = value != 0.0; return 0; }   // 0: the waves of a bulk chunk multiply the k-tiles left of their own 64-row halves' envelopes and the upper quadrant of a diagonal tile too (ignored with envelope = 0)
     if (!strcmp(key, "envelope")) { ls->envelope = value != 0.0; return 0; }   // 0: the task-DAG bulk kernel multiplies the structurally zero tiles of sparse sources too
-    if (!strcmp(key, "dag_js2")) { ls->dag_js2_override = (int)value; return 0; }   // experiments: strip-column at which every row joins the band (-1: by size)
+    if (!strcmp(key, "dag_js2")) { ls->dag_js2_override = (int)value; ls->plan.invalidate(); return 0; }   // experiments: strip-column at which every row joins the band (-1: by size; raised where the deep band would get more strips than CUs: dag_plan.h); the task list is rebuilt
     if (!strcmp(key, "outer_block")) {
         int64_t v = (int64_t)value;
         MNK_REQUIRE(v == 0 || (v >= NBI && v % NBI == 0), "outer_block must be 0 (by size) or a positive multiple of 64");

@@ -6,7 +6,8 @@
 //
 // Runs the grid of tools/dag_plan_lists.py through the planner functions and the four host-only entries and checks what must hold
 // for every list: a deal is a partition into subsequences, a dealt task carries the position it was dealt from, a merged list holds
-// every instance's tasks in their order, the field accessors return what a task was built with.  Prints the number of lists; any
+// every instance's tasks in their order, the field accessors return what a task was built with; and the plan shape (dag_choose_js2)
+// never leaves the deep band more strips than its partition has CUs.  Prints the number of lists; any
 // sanitizer report or failed check ends it with a non-zero status.  `--quick`: orders up to 44 tiles.
 #include <algorithm>
 #include <cstdio>
@@ -115,6 +116,22 @@ int main(int argc, char** argv) {
                         CHECK(out[4 * cap] == -77 && order[cap] == -77);
                     }
     }
+    // the plan shape (dag_choose_js2): within [0, nsc], never more strips in the deep band than its partition has CUs, the request
+    // itself where that is admissible, and the entry the tests call returns the same
+    for (int64_t Np = 128; Np <= 12288; Np += 128)
+        for (int cus2 : {0, 42, 96})
+            for (int64_t deep : {(int64_t)0, (int64_t)5376, (int64_t)1 << 40}) {
+                const int nsc = (int)((Np + 255) / 256);
+                for (int ovr = -1; ovr <= nsc + 1; ++ovr) {
+                    const int js2 = dag_choose_js2(Np, cus2, deep, ovr);
+                    CHECK(js2 >= 0 && js2 <= nsc && Np - 256 * (int64_t)js2 <= 64 * (int64_t)cus2);
+                    if (cus2 == 0) CHECK(js2 == nsc);
+                    if (cus2 > 0 && ovr >= 0 && Np - 256 * (int64_t)std::min(ovr, nsc) <= 64 * (int64_t)cus2) CHECK(js2 == std::min(ovr, nsc));
+                    if (js2 > 0 && js2 < nsc && (ovr < 0 || js2 != ovr)) CHECK(Np - 256 * (int64_t)(js2 - 1) > 64 * (int64_t)cus2);   // (raised no further than needed)
+                    CHECK(mnk_debug_dag_js2(Np, cus2, deep, ovr) == js2);
+                }
+            }
+    CHECK(mnk_debug_dag_js2(100, 96, 5376, -1) == -1 && mnk_debug_dag_js2(128, -1, 5376, -1) == -1);
     std::printf("dag_plan_check: %ld dealt lists, all checks passed\n", g_lists);
     return 0;
 }
