@@ -219,6 +219,37 @@ int mnk_dc_qn_secant(mnk_dc* dc, const double* x, const double* g, const double*
                      double* last_g, double* s, double* y);
 int mnk_dc_get_hess(mnk_dc* dc, double* out, int64_t ld, int loc);
 
+/* COO callbacks into the dense systems: the reference's SparseCallback on a dense KKT system (`src/Callbacks/nlpmodels.jl:829-842`,
+ * `:863-881`) zeroes the dense Jacobian / Hessian and adds the values of jac_coord! / hess_coord! entry by entry in COO order,
+ * the Hessian entry (i, j) also to (j, i).  csrc/dense_coo.hip.
+ *
+ * mnk_dc_coo_attach (once per handle, host work and uploads only) validates the indices (`base` 0 or 1; a Hessian entry may
+ * lie in either triangle: its destination is the unordered pair {i, j}) and builds, per matrix, the distinct destinations
+ * sorted column-major with an int32 CSR of the COO positions feeding each, ascending, plus one CSR by Jacobian column.  It
+ * fails with a message on an index out of range, a second attach, or a count that does not fit int32.  Every entry below
+ * fails before it if called before the attach, and launches nothing when it fails.
+ *
+ * mnk_dc_compress_jacobian / mnk_dc_compress_hessian (values on the host or the device, `loc`): one launch, one thread per
+ * destination, no atomics, no contraction: acc = 0.0; acc += v[k] over the destination's positions in COO order; the sum is
+ * stored to kkt.jac (column-major, ld = m), resp. to both (i, j) and (j, i) of kkt.hess (ld = n): bit for bit the reference's
+ * sequential loop.  Entries outside the structure read as zero: the buffers are zeroed at creation, and the handle remembers
+ * whether mnk_dc_set_jac / mnk_dc_set_hess or mnk_dc_qn_init / mnk_dc_qn_update has written one since; only then the scatter
+ * is preceded by a clear of the buffer.  nnz = 0 launches nothing.  The Jacobian values given (scaled by the caller, if at all)
+ * stay in the handle; mnk_dc_keep_jacobian snapshots them (the twin of mnk_sc_keep_jacobian).
+ *
+ * mnk_dc_coo_jtprod: out[j] = sum over the COO entries of column j, in COO order, of v[k] * y[jac_I[k]], from 0.0 (n entries;
+ * a column nothing feeds gives 0), on the current (MNK_DC_JAC_CURRENT) or the kept (MNK_DC_JAC_KEPT) values; y, out on the device.
+ * mnk_dc_get_jac copies kkt.jac (m x n, column-major, leading dimension ld) out.  All asynchronous on the context's stream except
+ * for host-resident arguments. */
+enum { MNK_DC_JAC_CURRENT = 0, MNK_DC_JAC_KEPT = 1 };
+int mnk_dc_coo_attach(mnk_dc* dc, int64_t nnzj, const int32_t* jac_I, const int32_t* jac_J, int64_t nnzh, const int32_t* hess_I,
+                      const int32_t* hess_J, int base);
+int mnk_dc_compress_jacobian(mnk_dc* dc, const double* jac_coo, int loc);
+int mnk_dc_compress_hessian(mnk_dc* dc, const double* hess_coo, int loc);
+int mnk_dc_keep_jacobian(mnk_dc* dc);
+int mnk_dc_coo_jtprod(mnk_dc* dc, int which, const double* y, double* out);
+int mnk_dc_get_jac(mnk_dc* dc, double* out, int64_t ld, int loc);
+
 /* ------------------------------------------------- linear solver (ls) ------- */
 /* Replaces `LapackCPUSolver(A; opt)` `src/LinearSolvers/lapack.jl:21-43` /
  * `LapackROCmSolver` `lib/MadNLPGPU/ext/MadNLPGPUAMDGPUExt/rocsolver.jl`:

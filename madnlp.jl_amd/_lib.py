@@ -14,7 +14,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libmadnlp_hip.so")
 _LIB_OVERRIDE = os.environ.get("MNK_LIBPATH")   # A/B runs of another commit's build of the same ABI (tools/leaf_ab.py, tools/README.md); never a fallback
-SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip", "lbfgs.hip", "fixed_vars.hip"]
+SOURCES = ["gemm_f64.hip", "dag.hip", "dag_plan.hip", "dag_batch.hip", "factor.hip", "factor_plan.hip", "solve.hip", "solve_multi.hip", "solve_plan.hip", "schur_plan.hip", "stream_plan.hip", "ctx.hip", "ls.hip", "ls_alt.hip", "sparse_kkt.hip", "dense_kkt.hip", "bk.hip", "schur.hip", "ipm_vec.hip", "opf_eval.hip", "qr.hip", "lu.hip", "evd.hip", "qn.hip", "dense_coo.hip", "tape_eval.hip", "nlp_scale.hip", "krylov.hip", "lbfgs.hip", "fixed_vars.hip"]
 HEADERS = ["common.h", "ls.h", "dag_plan.h", "factor_plan.h", "solve_plan.h", "schur_plan.h", "stream_plan.h", "kkt_vec.h", "gemm_tile.h", "leaf64.h", "ipm_handle.h", os.path.join("..", "..", "include", "madnlp_hip.h")]
 
 MNK_HOST, MNK_DEVICE = 0, 1
@@ -22,6 +22,7 @@ MNK_BUNCHKAUFMAN, MNK_LU, MNK_QR, MNK_CHOLESKY, MNK_LDL, MNK_EVD = 1, 2, 3, 4, 5
 MNK_SC_JT, MNK_SC_HESS, MNK_SC_AUG, MNK_SC_DIAGBUF = 0, 1, 2, 3
 MNK_QN_BFGS, MNK_QN_DAMPED_BFGS = 1, 2
 MNK_SC_JT_KEPT = 4
+MNK_DC_JAC_CURRENT, MNK_DC_JAC_KEPT = 0, 1
 MNK_FIX_FREE, MNK_FIX_JAC, MNK_FIX_HESS = 0, 1, 2
 MNK_LBFGS_S, MNK_LBFGS_Y, MNK_LBFGS_U, MNK_LBFGS_V, MNK_LBFGS_L, MNK_LBFGS_D, MNK_LBFGS_T, MNK_LBFGS_W = range(8)
 
@@ -126,6 +127,12 @@ SIGNATURES = {
     "mnk_dc_qn_secant": (C.c_int, [_vp] + [_vp] * 8),
     "mnk_dc_qn_status": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_double)]),
     "mnk_dc_get_hess": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
+    "mnk_dc_coo_attach": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int]),
+    "mnk_dc_compress_jacobian": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_dc_compress_hessian": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_dc_keep_jacobian": (C.c_int, [_vp]),
+    "mnk_dc_coo_jtprod": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "mnk_dc_get_jac": (C.c_int, [_vp, _vp, C.c_int64, C.c_int]),
     "mnk_ls_create": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(_vp)]),
     "mnk_ls_destroy": (C.c_int, [_vp]),
     "mnk_ls_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),

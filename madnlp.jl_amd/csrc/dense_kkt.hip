@@ -305,6 +305,7 @@ int mnk_dc_destroy(mnk_dc* dc) {
     delete extra_of(dc);
     dc->extra = nullptr;
     mnk_dc_qn_release(dc);
+    mnk_dc_coo_release(dc);
     mnk_ctx* ctx = dc->ctx;
     delete dc;
     mnk_ctx_child_gone(ctx);
@@ -327,12 +328,14 @@ static int copy_in_2d(mnk_ctx* ctx, double* dst, int64_t rows, int64_t cols, con
 int mnk_dc_set_hess(mnk_dc* dc, const double* hess, int64_t ld, int loc) {
     MNK_REQUIRE(dc && hess, "mnk_dc_set_hess: NULL argument");
     MNK_HIP(hipSetDevice(dc->ctx->device));
+    dc->hess_dirty = true;
     return copy_in_2d(dc->ctx, dc->hess.p, dc->n, dc->n, hess, ld, loc);
 }
 
 int mnk_dc_set_jac(mnk_dc* dc, const double* jac, int64_t ld, int loc) {
     MNK_REQUIRE(dc && (jac || dc->m == 0), "mnk_dc_set_jac: NULL argument");
     MNK_HIP(hipSetDevice(dc->ctx->device));
+    dc->jac_dirty = true;
     return copy_in_2d(dc->ctx, dc->jac.p, dc->m, dc->n, jac, ld, loc);
 }
 

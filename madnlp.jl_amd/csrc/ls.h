@@ -77,9 +77,14 @@ struct mnk_dc {
     int64_t ld_jis = 0, kpad = 0, npad = 0;
     void* extra = nullptr;  // unit-private device structures (dense_kkt.hip), owned by the handle
     void* qn = nullptr;     // quasi-Newton state (qn.hip: scalar block + workspace), owned by the handle; NULL until mnk_dc_qn_init
+    void* coo = nullptr;    // COO structure and values (dense_coo.hip), owned by the handle; NULL until mnk_dc_coo_attach
+    // something other than the COO scatter has written jac / hess since they were last all zero outside the COO structure
+    // (mnk_dc_set_jac / mnk_dc_set_hess, a quasi-Newton init or update): mnk_dc_compress_* clears the buffer first, then only
+    bool jac_dirty = false, hess_dirty = false;
     std::shared_ptr<int> alive = std::make_shared<int>(0);  // (see mnk_sc::alive)
 };
 void mnk_dc_qn_release(mnk_dc* dc);   // qn.hip: frees mnk_dc::qn
+void mnk_dc_coo_release(mnk_dc* dc);  // dense_coo.hip: frees mnk_dc::coo
 
 struct mnk_ls;
 // lbfgs.hip, for the sparse condensed handle an mnk_lbfgs is attached to (w_x, x_x: the n leading entries of device KKT vectors)

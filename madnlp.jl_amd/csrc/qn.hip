@@ -349,6 +349,7 @@ int mnk_dc_qn_init(mnk_dc* dc, int kind, const double* g0, double f0) {
     } else {
         hipLaunchKernelGGL(qn_init_scal_kernel, dim3(1), dim3(256), 0, s, q->scal.p, g0, n, f0, kind);
         const int64_t blocks = std::min<int64_t>((n * n + 255) / 256, QN_MAX_GRID);
+        dc->hess_dirty = true;
         hipLaunchKernelGGL(qn_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dc->hess.p, n, q->scal.p);
     }
     MNK_HIP(hipGetLastError());
@@ -364,6 +365,7 @@ int mnk_dc_qn_update(mnk_dc* dc, const double* sk, const double* yk) {
     const int64_t n = dc->n;
     const int64_t ntiles = (int64_t)q->nt * (q->nt + 1) / 2;
     const unsigned tgrid = (unsigned)std::min<int64_t>(ntiles, QN_MAX_GRID);
+    dc->hess_dirty = true;
     hipLaunchKernelGGL(qn_dots_kernel, dim3(1), dim3(256), 0, s, q->scal.p, sk, yk, n);
     hipLaunchKernelGGL(qn_symv_kernel, dim3(tgrid), dim3(256), 0, s, dc->hess.p, n, sk, q->scal.p, q->slab.p, q->nt);
     hipLaunchKernelGGL(qn_bs_kernel, dim3((unsigned)q->nblk), dim3(256), 0, s, q->bs.p, q->slab.p, q->nt, n, sk, q->scal.p,

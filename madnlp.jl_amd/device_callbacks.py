@@ -112,12 +112,15 @@ class DeviceCallbacks(_LibraryHandle):
 
 
 class DeviceCOOCallbacks(DeviceCallbacks):
-    """Callbacks that compute the model's raw COO values (`jac_coord`, `hess_coord` into `jv`, `hv`) for the sparse condensed
-    handle's compressors; J'y is its transposed SpMV on the compressed Jacobian.  Scaling and the sense are launches behind the raw
+    """Callbacks that compute the model's raw COO values (`jac_coord`, `hess_coord` into `jv`, `hv`) for the compressors of the
+    sparse condensed handle, or of a dense handle with the COO structure attached (`kkt.coo_attached`, csrc/dense_coo.hip); J'y
+    is the handle's transposed product on the Jacobian values it holds.  Scaling and the sense are launches behind the raw
     values: `scale_grad`, `vec_mul` by `jac_scale`; the model gets y .* con_scale (nlpmodels.jl:791-801) and w obj_sign obj_scale."""
     prescaled = False
 
     def jtprod_x(self, out_x, y):
+        if getattr(self.kkt, "coo_attached", False):
+            return self.kkt.jtprod_coo_device(L.MNK_DC_JAC_CURRENT, y, out_x)
         self.kkt.spmv_device(L.MNK_SC_JT, 0, 1.0, y, 0.0, out_x)
 
     def load_jac(self, x):
@@ -536,20 +539,21 @@ class DeviceFixedVariableCallbacks(DeviceCOOCallbacks):
         self.inner.close()
 
 
-def callbacks_class(nlp, sparse):
-    """The device callbacks of a model: by what the model is, not by what the run needs."""
+def callbacks_class(nlp, sparse, callback="auto"):
+    """The device callbacks of a model: by what the model is, not by what the run needs.  `callback` is `IPMOptions.callback`:
+    with "sparse" the COO classes feed a dense handle too."""
     if getattr(nlp, "is_tape_model", False):
         return DeviceTapeCallbacks
     if hasattr(nlp, "arc_coef"):
-        assert sparse, "the AC-OPF callbacks feed the sparse condensed handle"
+        assert sparse or callback == "sparse", "the AC-OPF callbacks feed the sparse condensed handle, or a dense one with callback = 'sparse'"
         return DeviceOPFCallbacks
     return DeviceQPCallbacks if sparse else DeviceDenseQPCallbacks
 
 
-def device_callbacks(nlp, kkt, dev, K, sparse, scaling, fixed=None, own_hessian=False):
+def device_callbacks(nlp, kkt, dev, K, sparse, scaling, fixed=None, own_hessian=False, callback="auto"):
     """The callbacks object of a run, attached to the solver's `DeviceScaling`.  `nlp` is the FULL model; `fixed` (the host
     handler of variables made parameters) wraps raw-value callbacks and masks the dense QP's; `own_hessian`: compact L-BFGS."""
-    cls = callbacks_class(nlp, sparse)
+    cls = callbacks_class(nlp, sparse, callback)
     if cls is DeviceQPCallbacks:
         cb = cls(nlp, kkt, dev, K, own_hessian=own_hessian, **scaling.host_factors())
     elif cls is DeviceDenseQPCallbacks:

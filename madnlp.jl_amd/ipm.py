@@ -145,6 +145,10 @@ class IPMOptions:
     # The reference's default is MakeParameter for every KKT system but the sparse condensed one (options.jl:146); here it is
     # "relax_bound" for all of them because every recorded trajectory, golden file and profile was made with it
     fixed_variable_treatment: str = "relax_bound"
+    # options.jl `callback`: "sparse" (SparseCallback: the model's COO callbacks, scattered in COO order into the dense Jacobian
+    # and Hessian where the KKT system is dense, nlpmodels.jl:829-842, :863-881), "dense" (DenseCallback: the model's own
+    # `jac_dense` / `hess_dense`), or "auto": sparse callbacks for the sparse KKT system, dense ones for the dense systems
+    callback: str = "auto"
 
     @property
     def mu_min(self):
@@ -186,6 +190,7 @@ class RobustRestorer:
 
 INERTIA_CORRECTION_METHODS = ("auto", "inertia_based", "inertia_free", "ignore")
 BARRIER_UPDATES = ("monotone", "loqo", "quality_function")
+CALLBACKS = ("auto", "sparse", "dense")
 
 
 def _clamp(x, lo, hi):
@@ -360,6 +365,30 @@ def set_con_scale_dense(jac, max_gradient):
     return np.minimum(1.0, max_gradient / np.abs(jac).max(axis=1, initial=1.0))
 
 
+def scatter_jac_coo(jac, I, J, values):
+    """`_eval_jac_wrapper!` of SparseCallback on a dense Jacobian (nlpmodels.jl:829-842): zero, then the COO values added
+    entry by entry in COO order (`np.add.at` is that loop)."""
+    jac[...] = 0.0
+    np.add.at(jac, (I, J), values)
+
+
+def hess_mirror_coo(I, J):
+    """(rows, columns, COO positions) of the reference's Hessian loop (nlpmodels.jl:863-881) unrolled: every entry (i, j)
+    followed by its mirror image (j, i), diagonal entries once."""
+    k = np.repeat(np.arange(len(I)), 2)
+    swap = np.arange(len(k)) % 2 == 1
+    keep = ~(swap & (I[k] == J[k]))
+    return np.where(swap, J[k], I[k])[keep], np.where(swap, I[k], J[k])[keep], k[keep]
+
+
+def scatter_hess_coo(hess, mirror, values):
+    """`_eval_lag_hess_wrapper!` of SparseCallback on a dense Hessian: zero, then (i, j) and, off the diagonal, (j, i), entry
+    by entry in COO order; both triangles are written, whichever the model gives."""
+    r, c, k = mirror
+    hess[...] = 0.0
+    np.add.at(hess, (r, c), values[k])
+
+
 @dataclass
 class Solution:
     """What the reference hands back in `MadNLPExecutionStats`, un-scaled (nlpmodels.jl:649-661).  `constraints` is left out."""
@@ -418,6 +447,19 @@ class MadNLPSolver:
                              f"{o.fixed_variable_treatment!r}")
         # MakeParameter (fixed_vars.py): None for a model without fixed variables -- then nothing below differs from
         # "relax_bound".  `self.model` is what the callbacks evaluate: the reduced (sparse) or frozen (dense) view of `nlp`
+        if o.callback not in CALLBACKS:
+            raise ValueError(f"callback must be one of {CALLBACKS}, not {o.callback!r}")
+        # `coo_dense`: the model's COO callbacks feed a dense KKT system (`scatter_jac_coo`, `scatter_hess_coo`)
+        self.coo_dense = o.callback == "sparse" and not sparse
+        if o.callback == "dense" and (sparse or not hasattr(nlp, "jac_dense")):
+            raise NotImplementedError("callback = 'dense' " + ("with the sparse KKT system (sparse=True)" if sparse else
+                                      f"with a model that has no jac_dense / hess_dense ({type(nlp).__name__})")
+                                      + ": use callback = 'sparse'")
+        if (self.coo_dense and o.fixed_variable_treatment == "make_parameter"
+                and (np.asarray(nlp.lvar, float) == np.asarray(nlp.uvar, float)).any()):
+            raise NotImplementedError("callback = 'sparse' on a dense KKT system (sparse=False) with fixed_variable_treatment = "
+                                      "'make_parameter' and fixed variables present: frozen variables are written for the "
+                                      "model's dense callbacks only; use 'relax_bound' or callback = 'dense'")
         self.fixed_handler = FixedVariableHandler.create(nlp, sparse) if o.fixed_variable_treatment == "make_parameter" else None
         if self.fixed_handler is not None and o.hessian_approximation != "exact":
             raise ValueError(f"fixed_variable_treatment = 'make_parameter' with fixed variables present needs "
@@ -481,7 +523,10 @@ class MadNLPSolver:
         self.obj_scale = 1.0
         self.obj_sign = 1.0 if getattr(nlp, "minimize", True) else -1.0
         self.con_scale = np.ones(m)
-        self.jac_scale = np.ones(len(nlp.jac_I)) if sparse else None     # con_scale[jac_I]
+        self.jac_scale = np.ones(len(nlp.jac_I)) if sparse or self.coo_dense else None     # con_scale[jac_I]
+        if self.coo_dense:
+            self._coo = tuple(np.asarray(getattr(nlp, k), dtype=np.int64) for k in ("jac_I", "jac_J", "hess_I", "hess_J"))
+            self._coo_mirror = hess_mirror_coo(*self._coo[2:])
         self.status = "INITIAL"
 
     # ------------------------------------------------------------------ callbacks (src/IPM/callbacks.jl)
@@ -511,6 +556,8 @@ class MadNLPSolver:
     def eval_jac(self, x):
         if self.sparse:
             self.kkt.get_jacobian()[:] = self.model.jac_coord(x[:self.n]) * self.jac_scale
+        elif self.coo_dense:
+            scatter_jac_coo(self.kkt.get_jacobian(), *self._coo[:2], self.model.jac_coord(x[:self.n]) * self.jac_scale)
         else:
             self.kkt.get_jacobian()[...] = self.model.jac_dense(x[:self.n]) * self.con_scale[:, None]
         self.kkt.compress_jacobian()
@@ -522,6 +569,8 @@ class MadNLPSolver:
         w = (0.0 if is_resto else 1.0) * self.obj_sign * self.obj_scale
         if self.sparse:
             self.kkt.get_hessian()[:] = self.model.hess_coord(x[:self.n], y * self.con_scale, w)
+        elif self.coo_dense:
+            scatter_hess_coo(self.kkt.get_hessian(), self._coo_mirror, self.model.hess_coord(x[:self.n], y * self.con_scale, w))
         else:
             self.kkt.get_hessian()[...] = self.model.hess_dense(x[:self.n], y * self.con_scale, w)
         self.kkt.compress_hessian()
@@ -532,7 +581,7 @@ class MadNLPSolver:
         l = l * self.con_scale
         if hasattr(self.model, "jtprod"):
             return np.asarray(self.model.jtprod(x, l), dtype=float)
-        if self.sparse:
+        if self.sparse or self.coo_dense:
             out = np.zeros(self.n)
             np.add.at(out, np.asarray(self.model.jac_J, dtype=np.int64),
                       self.model.jac_coord(x) * l[np.asarray(self.model.jac_I, dtype=np.int64)])
@@ -604,7 +653,7 @@ class MadNLPSolver:
         if o.nlp_scaling:
             # set_scaling! (solver.jl:37-49, nlpmodels.jl:693-765): the factors from the model's raw Jacobian and gradient at the
             # pushed starting point (this gradient is not one of `cnt.obj_grad_cnt`), then y0, rhs and the slacks with their bounds
-            if self.sparse:
+            if self.sparse or self.coo_dense:
                 self.con_scale[:] = set_con_scale_sparse(self.m, nlp.jac_I, nlp.jac_coord(x0), o.nlp_scaling_max_gradient)
                 self.jac_scale[:] = self.con_scale[np.asarray(nlp.jac_I, dtype=np.int64)]
             else:

@@ -16,8 +16,9 @@ nothing of its control flow except the first trial of the inertia correction.  T
   * torch:            device memory only (allocation, uploads, the final download) -- no torch kernel runs in the loop
 
 Scope: `SparseCondensedKKTSystem` (all constraints relaxed to inequalities, as the reference's preset does) and
-`DenseCondensedKKTSystem` (equalities allowed), with the models of `device_callbacks.callbacks_class`: the AC-OPF NLP, any
-`TapeModel` (sparse condensed only), the sparse and the dense QP.  Initialization runs once on the host and is uploaded.
+`DenseCondensedKKTSystem` (equalities allowed), with the models of `device_callbacks.callbacks_class`: the AC-OPF NLP and any
+`TapeModel` (the sparse condensed system, or with `callback = "sparse"` the dense one: their COO values are scattered into its
+device buffers, csrc/dense_coo.hip), the sparse and the dense QP.  Initialization runs once on the host and is uploaded.
 
 With `hessian_approximation = "bfgs" / "damped_bfgs"` (dense systems) the Hessian approximation lives in the KKT handle's
 device buffer and is updated there (`mnk_dc_qn_update`, csrc/qn.hip): the model's Hessian is never loaded.  With
@@ -40,10 +41,16 @@ from .ipm_device import IPMDeviceKernels
 
 class DeviceMadNLPSolver(MadNLPSolver):
     def __init__(self, nlp, kkt_factory, opt: IPMOptions | None = None, device="cuda", sparse=True):
-        if getattr(nlp, "is_tape_model", False) and not sparse:
+        callback = "auto" if opt is None else opt.callback
+        if getattr(nlp, "is_tape_model", False) and not sparse and callback == "auto":
             raise NotImplementedError("DeviceMadNLPSolver evaluates a TapeModel for the sparse condensed KKT handle only "
                                       "(DeviceTapeCallbacks feed COO values to its compressors): use sparse=True with "
-                                      "relax_equality, or MadNLPSolver with host callbacks")
+                                      "relax_equality, callback = 'sparse' for the dense condensed handle, or MadNLPSolver "
+                                      "with host callbacks")
+        if callback == "sparse" and not sparse and callbacks_class(nlp, sparse, callback) is DeviceDenseQPCallbacks:
+            raise NotImplementedError(f"callback = 'sparse' on a dense system with the dense QP device callbacks "
+                                      f"({type(nlp).__name__}): they load dense P and A; use callback = 'auto', a TapeModel or "
+                                      "the AC-OPF model")
         if (opt is not None and opt.fixed_variable_treatment == "make_parameter" and sparse
                 and callbacks_class(nlp, sparse) is DeviceQPCallbacks
                 and (np.asarray(nlp.lvar, float) == np.asarray(nlp.uvar, float)).any()):
@@ -81,10 +88,21 @@ class DeviceMadNLPSolver(MadNLPSolver):
                                 self.obj_scale, self.con_scale, self.jac_scale)
         self.ind_ineq_t, self.slack_pos_t = scaling.ind_ineq, scaling.slack_pos
         # variables made parameters (`fixed_handler`): the callbacks are built on the FULL model (self.nlp)
+        if self.coo_dense:           # the model's COO callbacks scatter into the dense handle's device buffers
+            self.kkt.attach_coo(*self._coo)
         self.cb = device_callbacks(self.nlp, self.kkt, self.dev, self.K, self.sparse, scaling, fixed=self.fixed_handler,
-                                   own_hessian=self.lbfgs)
+                                   own_hessian=self.lbfgs, callback=self.opt.callback)
         self.kkt.device_kkt_ops = True
-        if not self.sparse:          # the dense handle reads Hessian / Jacobian from its own device copies
+        if self.coo_dense:
+            # the device buffers get what the host initialization evaluated: J(x0), scaled, and the Lagrangian Hessian at
+            # (x0, y0) -- or the quasi-Newton init!, with J(x0) kept for J(x_0)' l_1 of the first secant pair
+            self.cb.eval_jac(self.x)
+            if self.qn is None:
+                self.cb.eval_lag_hess(self.x, self.y, 1.0)
+            else:
+                self._qn_upload()
+                self.kkt.keep_jacobian_device()
+        elif not self.sparse:        # the dense handle reads Hessian / Jacobian from its own device copies
             self.cb.load_jac()
             if self.qn is None:
                 self.cb.load_hess()
@@ -152,9 +170,14 @@ class DeviceMadNLPSolver(MadNLPSolver):
         jl = jv = None
         if self.m > 0:
             jl = self.jacl[:n]                                      # J(x+)' l+ (current: see the host mirror)
-            self.cb.eval_jtprod_at(d.last_x, y, d.last_jv)
+            if self.coo_dense:       # from the COO values kept at the previous call, already scaled: no callback launch
+                self.kkt.jtprod_coo_device(L.MNK_DC_JAC_KEPT, y, d.last_jv)
+            else:
+                self.cb.eval_jtprod_at(d.last_x, y, d.last_jv)
             jv = d.last_jv
         self.kkt.qn_secant_device(x[:n], self.f[:n], jl, jv, d.last_x, d.last_g, d.sk, d.yk)
+        if self.coo_dense:
+            self.kkt.keep_jacobian_device()
         self.kkt.qn_update_device(d.sk, d.yk)
 
     # ------------------------------------------------------------------ compact L-BFGS in a handle attached to the KKT handle

@@ -675,9 +675,48 @@ class _DenseBase(_KKTCommon):
         self._order = L.lib().mnk_dc_order(self._h)
         _LIVE_OBJECTS.add(self)
 
-    def compress_jacobian(self):
-        """no-op, reference `src/KKT/Dense/utils.jl:25-27`."""
-        return
+    def compress_jacobian(self, jv=None):
+        """no-op, reference `src/KKT/Dense/utils.jl:25-27`; with `jv`, a device tensor of the Jacobian's COO values (scaled by
+        the caller), the ordered scatter into the device `jac` buffer (`mnk_dc_compress_jacobian`; `attach_coo` first)."""
+        if jv is not None:
+            p, loc = _ptr(jv)
+            L.check(L.lib().mnk_dc_compress_jacobian(self._h, p, loc), "mnk_dc_compress_jacobian")
+
+    def _compress_hessian_coo(self, hv):
+        p, loc = _ptr(hv)
+        L.check(L.lib().mnk_dc_compress_hessian(self._h, p, loc), "mnk_dc_compress_hessian")
+
+    # ---- COO callbacks into the device buffers (csrc/dense_coo.hip): the reference's SparseCallback on a dense KKT system
+    coo_attached = False
+
+    def attach_coo(self, jac_I, jac_J, hess_I, hess_J):
+        """Hand the model's COO structure (0-based) to the handle, once (`mnk_dc_coo_attach`): `compress_jacobian(jv)`,
+        `compress_hessian(hv)`, `keep_jacobian_device`, `jtprod_coo_device` need it."""
+        a = [np.ascontiguousarray(v, dtype=np.int32) for v in (jac_I, jac_J, hess_I, hess_J)]
+        assert len(a[0]) == len(a[1]) and len(a[2]) == len(a[3])
+        L.check(L.lib().mnk_dc_coo_attach(self._h, len(a[0]), a[0].ctypes.data, a[1].ctypes.data, len(a[2]), a[2].ctypes.data,
+                                          a[3].ctypes.data, 0), "mnk_dc_coo_attach")
+        self.coo_attached = True
+
+    def keep_jacobian_device(self):
+        """Snapshot of the Jacobian's current COO values (`jtprod_coo_device(MNK_DC_JAC_KEPT, ...)` reads it): the twin of the
+        sparse handle's `keep_jacobian_device`."""
+        L.check(L.lib().mnk_dc_keep_jacobian(self._h), "mnk_dc_keep_jacobian")
+
+    def jtprod_coo_device(self, which, y, out):
+        """out = J' y (n entries) from the current (`MNK_DC_JAC_CURRENT`) or kept (`MNK_DC_JAC_KEPT`) COO values, each column
+        summed in COO order (`mnk_dc_coo_jtprod`); device tensors."""
+        py, ly = _ptr(y)
+        po, lo = _ptr(out)
+        assert ly == lo == L.MNK_DEVICE
+        L.check(L.lib().mnk_dc_coo_jtprod(self._h, int(which), py, po), "mnk_dc_coo_jtprod")
+
+    def get_jac(self):
+        """Host copy of the device `jac` buffer (m x n, Fortran order); tests."""
+        m, n = self.jac.shape
+        out = np.zeros((m, n), order="F")
+        L.check(L.lib().mnk_dc_get_jac(self._h, out.ctypes.data, m, L.MNK_HOST), "mnk_dc_get_jac")
+        return out
 
     device_kkt_ops = False
 
@@ -840,8 +879,11 @@ class DenseKKTSystem(_DenseBase):
     def num_variables(self):
         return len(self.pr_diag)
 
-    def compress_hessian(self):
-        """`compress_hessian!` reference `src/KKT/Dense/augmented.jl:158-161` (diag!)."""
+    def compress_hessian(self, hv=None):
+        """`compress_hessian!` reference `src/KKT/Dense/augmented.jl:158-161` (diag!); with `hv`, a device tensor of the
+        Lagrangian Hessian's COO values, the ordered scatter into the device `hess` buffer (`mnk_dc_compress_hessian`)."""
+        if hv is not None:
+            return self._compress_hessian_coo(hv)
         self.diag_hess[:] = np.diagonal(self.hess)
 
     def is_inertia_correct(self, num_pos, num_zero, num_neg):
@@ -895,8 +937,10 @@ class DenseCondensedKKTSystem(_DenseBase):
     def num_variables(self):
         return self.hess.shape[0]
 
-    def compress_hessian(self):
-        return
+    def compress_hessian(self, hv=None):
+        """no-op; with `hv`, as `DenseKKTSystem.compress_hessian`."""
+        if hv is not None:
+            self._compress_hessian_coo(hv)
 
     def build_kkt(self):
         n, ns = self.n, self.n_ineq
