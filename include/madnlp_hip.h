@@ -793,7 +793,8 @@ void* mnk_schur_s_buffer(mnk_schur* h);
  *                            and S0 (nd x nd), the list of its sources in the reference's scatter order.  ns_global / local_scen:
  *                            the global scenario of every local block when the scenarios are sharded over ranks (NULL: all local);
  *                            own_design: this rank adds H_dd + Sigma_d to its S0 (exactly one rank does).
- *   mnk_schur_assemble       per build_kkt!: hess / jac (COO values), pr_diag (n + n_ineq), du_diag (m), host or device -> A_k, C_dk of
+ *   mnk_schur_assemble       per build_kkt!: hess / jac (COO values), pr_diag (n + n_ineq), du_diag (m), host or device (pr_diag =
+ *                            du_diag = NULL: the handle's own, see mnk_schur_set_aug_diagonal below) -> A_k, C_dk of
  *                            every local scenario and S0 (mnk_schur_s0_buffer, device) in one launch, every entry summed by one thread
  *                            in the reference's order (the bits of a sequential scatter-add, the same in every run); then
  *                            mnk_schur_build_local(h, mnk_schur_s0_buffer(h), nd, MNK_DEVICE, ...)
@@ -820,6 +821,55 @@ int mnk_schur_solve(mnk_schur* h, double* rhs_k, double* rhs_d, int loc);
  *                                 out[4] = the threshold in force; cap >= 5 */
 int mnk_schur_set_gram_threshold(mnk_schur* h, int64_t row_entries);
 int mnk_schur_assembly_stats(mnk_schur* h, int64_t* out, int cap);
+/* The KKT-handle contract on the Schur handle (what mnk_sc_* / mnk_dc_* give the condensed and dense systems): bound / barrier state,
+ * device-side feeders, solve_kkt!, mul!, jtprod! and mul_hess_blk! on host (loc = MNK_HOST) or device vectors.  SINGLE RANK only: all
+ * scenarios local and the design block owned (local_scen = NULL, own_design = 1 in mnk_schur_set_structure); a sharded handle is
+ * refused.  Vectors are laid out as the reference's UnreducedKKTVector: w = (x (n), s (n_ineq), y (m), z_l (nlb), z_u (nub)).
+ *   mnk_schur_set_bounds           once: the positions of the bounded entries in the primal block [0, n + n_ineq)
+ *   mnk_schur_set_barrier_terms    reg (n + n_ineq), l_diag, u_diag, l_lower, u_lower of the iterate
+ *   mnk_schur_set_aug_diagonal     set_aug_diagonal! inside the handle (x, xl, xu, zl, zu of length n + n_ineq): the handle then owns
+ *   mnk_schur_regularize_diagonal  reg, pr_diag (n + n_ineq) and du_diag (m); mnk_schur_assemble with pr_diag = du_diag = NULL uses them
+ *   mnk_schur_get_diagonals        host copies (any pointer may be NULL)
+ * mnk_schur_assemble keeps device copies of the COO values and diagonals it was given and of the condensation weights D; the
+ * products below read the values of the LAST assemble and are refused before the first.  They run over three row lists built once
+ * by mnk_schur_set_structure (J, J' and Symmetric(H, :L) with a permutation into the COO value arrays: duplicates stay separate terms
+ * in COO order).  A row with at most `row_entries` entries is summed by one thread in list order; a longer one (the design rows of J'
+ * and H collect entries from every scenario) by one 64-lane wavefront: lane l sums entries l, l + 64, ... in ascending order, a fixed
+ * xor-butterfly (offsets 32, 16, ..., 1) combines the partials.  Every multiply and add is rounded on its own and nothing is added
+ * atomically: the bits depend on the lists and the values alone.  y = alpha acc (+ beta y when beta != 0).
+ *   mnk_schur_compress_jacobian    compress_jacobian! / compress_hessian! (:917-923): the kept COO values of the Jacobian / the Hessian as
+ *   mnk_schur_compress_hessian     of now, without an assemble (the interior-point loop calls jtprod! on a fresh Jacobian before it
+ *                                  builds the next KKT system); mnk_schur_jtprod works from the first compress_jacobian on
+ *   mnk_schur_set_spmv_threshold   `row_entries` of the NEXT mnk_schur_set_structure; negative: the default (64), INT64_MAX: never
+ *   mnk_schur_solve_kkt            solve_kkt! (reference src/KKT/Schur/schur.jl:1007-1109) after mnk_schur_build_local and
+ *                                  mnk_schur_factorize_s; a scenario or design solve that gave up ends the call with its error, as
+ *                                  mnk_schur_solve does
+ *   mnk_schur_mul                  w = alpha K x + beta w (:1112-1139)
+ *   mnk_schur_jtprod               y (n + n_ineq) = [J' x ; -x[ind_ineq]], x (m) (:907-915)
+ *   mnk_schur_mul_hess_blk         wx = [Symmetric(H, :L) t[0:n] ; 0] + t .* pr_diag (:1141-1146)
+ *   mnk_schur_spmv_plan            host only, no device is opened: the row lists mnk_schur_set_structure would build from the same
+ *                                  pattern arguments with threshold T, for `which` = 0 (J, m rows), 1 (J', n rows), 2 (H, n rows):
+ *                                  counts = {rows, entries, long rows, T in force}; row_ptr (rows + 1), col_idx, perm (entries) and
+ *                                  long_rows (ascending) may each be NULL (a first call sizes the arrays) */
+int mnk_schur_set_bounds(mnk_schur* h, int64_t nlb, const int64_t* ind_lb, int64_t nub, const int64_t* ind_ub, int index_base);
+int mnk_schur_set_barrier_terms(mnk_schur* h, const double* reg, const double* l_diag, const double* u_diag, const double* l_lower,
+                                const double* u_lower, int loc);
+int mnk_schur_set_aug_diagonal(mnk_schur* h, const double* x, const double* xl, const double* xu, const double* zl, const double* zu,
+                               double primal_reg, double dual_reg, int loc);
+int mnk_schur_regularize_diagonal(mnk_schur* h, double primal, double dual);
+int mnk_schur_get_diagonals(mnk_schur* h, double* pr_diag, double* du_diag, double* reg, double* l_diag, double* u_diag, double* l_lower,
+                            double* u_lower);
+int mnk_schur_compress_jacobian(mnk_schur* h, const double* jac, int loc);
+int mnk_schur_compress_hessian(mnk_schur* h, const double* hess, int loc);
+int mnk_schur_set_spmv_threshold(mnk_schur* h, int64_t row_entries);
+int mnk_schur_solve_kkt(mnk_schur* h, double* w, int loc);
+int mnk_schur_mul(mnk_schur* h, double* w, const double* x, double alpha, double beta, int loc);
+int mnk_schur_jtprod(mnk_schur* h, double* y, const double* x, int loc);
+int mnk_schur_mul_hess_blk(mnk_schur* h, double* wx, const double* t, int loc);
+int mnk_schur_spmv_plan(int64_t n, int64_t m, int64_t nv, int64_t nc, int64_t nnzh, const int32_t* hess_I, const int32_t* hess_J,
+                        int64_t nnzj, const int32_t* jac_I, const int32_t* jac_J, int64_t n_ineq, const int64_t* ind_ineq, int64_t n_eq,
+                        const int64_t* ind_eq, int index_base, int64_t ns_global, const int64_t* local_scen, int own_design, int64_t T,
+                        int which, int32_t* row_ptr, int32_t* col_idx, int32_t* perm, int32_t* long_rows, int64_t* counts);
 
 /* Diagnostics: with option "solve_trace" = 1 the persistent solve kernel stamps the forward sweep's critical
  * path (8 x 100 MHz timer values per 64-row block); this copies them out (n = number of uint64 to copy). */

@@ -778,12 +778,17 @@ constraint), the inequality rows in slack order and the equality rows.  The libr
 `_build_schur_symbolic` checks, schur.jl:140-236) and builds the source list of every touched entry of `A_k` / `C_dk` / `S0`.
 An inequality row with more than `gram_row_threshold` COO entries adds no pairs to the lists: its condensation runs as weighted
 Gram products on the matrix cores (`mnk_schur_set_gram_threshold`; negative: the library's default, `typemax(Int64)`: never).
+On a single rank the library also builds the row lists of J, J' and Symmetric(H, :L) for the device-side `solve_kkt!` / `mul!` /
+`jtprod!` / `mul_hess_blk!`; a row with more than `spmv_row_threshold` entries is summed by one wavefront instead of one thread
+(`mnk_schur_set_spmv_threshold`; same conventions).
 """
 function set_structure!(st::HipSchurStage, n::Integer, m::Integer, nv::Integer, nc::Integer, hess_I::Vector{Int32},
                         hess_J::Vector{Int32}, jac_I::Vector{Int32}, jac_J::Vector{Int32}, ind_ineq::Vector{Int64},
                         ind_eq::Vector{Int64}; ns_global::Integer = st.ns_local, local_scen::Union{Nothing, Vector{Int64}} = nothing,
-                        own_design::Bool = true, gram_row_threshold::Integer = -1)
+                        own_design::Bool = true, gram_row_threshold::Integer = -1, spmv_row_threshold::Integer = -1)
     rc = ccall((:mnk_schur_set_gram_threshold, libmadnlp_hip), Cint, (Ptr{Cvoid}, Int64), st.handle, gram_row_threshold)
+    check(rc, SymbolicException)
+    rc = ccall((:mnk_schur_set_spmv_threshold, libmadnlp_hip), Cint, (Ptr{Cvoid}, Int64), st.handle, spmv_row_threshold)
     check(rc, SymbolicException)
     rc = ccall((:mnk_schur_set_structure, libmadnlp_hip), Cint,
                (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int64},
@@ -854,11 +859,11 @@ end
 # ------------------------------------------------------------------ SchurComplementKKTSystem on the HIP stage
 # Reference: `SchurComplementKKTSystem` (src/KKT/Schur/schur.jl:72-1146).  The host side of that type -- COO / CSC copies of the
 # Hessian and the Jacobian, the per-scenario index maps of `_build_schur_symbolic` (:140-700), the scatter of the callback
-# values into the scenario blocks `A_kk` / `C_dk` and into S (:935-972, :993-996), the vector algebra of `solve_kkt!`
-# (:1040-1110), `mul!` / `jtprod!` -- is exactly the reference's: this type WRAPS a reference system (built with a scenario
-# solver that does nothing) and replaces what the reference does with one sparse solver per scenario and a host LAPACK call:
-# the ns block factorizations (one batch on the device), `S -= sum_k C_dk A_k^-1 C_dk'` (matrix cores), the factorization of S,
-# and steps 3-5 of the solve (`mnk_schur_build_local`, `_factorize_s`, `_solve`).  `madnlp(nlp; kkt_system =
+# values into the scenario blocks `A_kk` / `C_dk` and into S (:935-972, :993-996) -- is exactly the reference's: this type WRAPS
+# a reference system (built with a scenario solver that does nothing) and replaces what the reference does with one sparse solver
+# per scenario and a host LAPACK call: the ns block factorizations (one batch on the device), `S -= sum_k C_dk A_k^-1 C_dk'`
+# (matrix cores), the factorization of S (`mnk_schur_build_local`, `_factorize_s`), and all of `solve_kkt!`, `mul!`, `jtprod!`
+# and `mul_hess_blk!` (`mnk_schur_solve_kkt`, `_mul`, `_jtprod`, `_mul_hess_blk`: the vector algebra runs on the device).  `madnlp(nlp; kkt_system =
 # HipSchurComplementKKTSystem, linear_solver = HipLinearSolver, kkt_options = schur_opts(; ns, nv, nd, nc))`.
 "A scenario solver that is never asked to factorize (the device stage owns the blocks)."
 struct HipNoScenarioSolver{T} <: AbstractLinearSolver{T}
@@ -882,14 +887,13 @@ MadNLP.introduce(::HipSchurDesignSolver) = "HIP-MI355X Schur stage (batched scen
 
 struct HipSchurComplementKKTSystem{T, VT, MT, QN, K <: MadNLP.SchurComplementKKTSystem{T, VT, MT, QN}} <:
        AbstractCondensedKKTSystem{T, VT, MT, QN}
-    inner::K                       # the reference system: value buffers, diagonals, host-side algebra of solve_kkt! / mul!
+    inner::K                       # the reference system: value buffers and diagonals the callbacks and the IPM kernels write
     stage::HipSchurStage
     linear_solver::HipSchurDesignSolver{T}
-    rhs_all::Matrix{T}             # blk x ns: the scenarios' right-hand sides, column k = scenario k
 end
 # every field the generic IPM code reads by name (KKTsystem.jl:210-234, kernels.jl) lives in the reference system
 function Base.getproperty(kkt::HipSchurComplementKKTSystem, f::Symbol)
-    f in (:inner, :stage, :linear_solver, :rhs_all) && return getfield(kkt, f)
+    f in (:inner, :stage, :linear_solver) && return getfield(kkt, f)
     return getproperty(getfield(kkt, :inner), f)
 end
 
@@ -897,7 +901,7 @@ function MadNLP.create_kkt_system(
     ::Type{HipSchurComplementKKTSystem}, cb::SparseCallback{T, VT}, linear_solver::Type;
     opt_linear_solver = default_options(linear_solver), hessian_approximation = ExactHessian, qn_options = QuasiNewtonOptions(),
     schur_ns::Int = 0, schur_nv::Int = 0, schur_nd::Int = 0, schur_nc::Int = 0, device::Integer = 0,
-    schur_gram_row_threshold::Int = -1,
+    schur_gram_row_threshold::Int = -1, schur_spmv_row_threshold::Int = -1,
 ) where {T <: Float64, VT <: Vector{T}}
     inner = MadNLP.create_kkt_system(MadNLP.SchurComplementKKTSystem, cb, MadNLP.LapackCPUSolver;
                                      hessian_approximation = hessian_approximation, qn_options = qn_options,
@@ -912,8 +916,13 @@ function MadNLP.create_kkt_system(
     set_structure!(stage, MadNLP.num_variables(inner), length(inner.du_diag), inner.nv, inner.nc,
                    Vector{Int32}(inner.hess_raw.I), Vector{Int32}(inner.hess_raw.J), Vector{Int32}(inner.jt_coo.J),
                    Vector{Int32}(inner.jt_coo.I), Vector{Int64}(inner.ind_ineq), Vector{Int64}(inner.ind_eq);
-                   gram_row_threshold = schur_gram_row_threshold)
-    return HipSchurComplementKKTSystem(inner, stage, HipSchurDesignSolver{T}(stage, Sdev), zeros(T, inner.blk_size, inner.ns))
+                   gram_row_threshold = schur_gram_row_threshold, spmv_row_threshold = schur_spmv_row_threshold)
+    # the bound structure of the device-side solve_kkt! / mul! (1-based positions in the primal block), once
+    ind_lb, ind_ub = Vector{Int64}(inner.ind_lb), Vector{Int64}(inner.ind_ub)
+    rc = ccall((:mnk_schur_set_bounds, libmadnlp_hip), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Cint),
+               stage.handle, length(ind_lb), ind_lb, length(ind_ub), ind_ub, 1)
+    check(rc, SymbolicException)
+    return HipSchurComplementKKTSystem(inner, stage, HipSchurDesignSolver{T}(stage, Sdev))
 end
 
 MadNLP.num_variables(kkt::HipSchurComplementKKTSystem) = MadNLP.num_variables(kkt.inner)
@@ -921,17 +930,46 @@ MadNLP.get_slack_regularization(kkt::HipSchurComplementKKTSystem) = MadNLP.get_s
 MadNLP.is_inertia_correct(kkt::HipSchurComplementKKTSystem, num_pos, num_zero, num_neg) =
     (num_zero == 0) && (num_pos == kkt.inner.nd)                                          # schur.jl:901-903
 MadNLP.should_regularize_dual(::HipSchurComplementKKTSystem, num_pos, num_zero, num_neg) = true   # :905
-MadNLP.jtprod!(y::AbstractVector, kkt::HipSchurComplementKKTSystem, x::AbstractVector) = MadNLP.jtprod!(y, kkt.inner, x)
-MadNLP.compress_jacobian!(kkt::HipSchurComplementKKTSystem) = MadNLP.compress_jacobian!(kkt.inner)
-MadNLP.compress_hessian!(kkt::HipSchurComplementKKTSystem) = MadNLP.compress_hessian!(kkt.inner)
+# compress_jacobian! / compress_hessian! (schur.jl:917-923): the reference's transfer, and the handle's copy of the COO values
+# (jtprod! runs on it before the next build_kkt!)
+function MadNLP.compress_jacobian!(kkt::HipSchurComplementKKTSystem)
+    MadNLP.compress_jacobian!(kkt.inner)
+    rc = ccall((:mnk_schur_compress_jacobian, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint), kkt.stage.handle, kkt.inner.jac, MNK_HOST)
+    check(rc, SymbolicException)
+    return
+end
+function MadNLP.compress_hessian!(kkt::HipSchurComplementKKTSystem)
+    MadNLP.compress_hessian!(kkt.inner)
+    rc = ccall((:mnk_schur_compress_hessian, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint), kkt.stage.handle, kkt.inner.hess, MNK_HOST)
+    check(rc, SymbolicException)
+    return
+end
 MadNLP.nnz_jacobian(kkt::HipSchurComplementKKTSystem) = MadNLP.nnz_jacobian(kkt.inner)
 MadNLP.get_jacobian(kkt::HipSchurComplementKKTSystem) = kkt.inner.jac
 MadNLP.get_hessian(kkt::HipSchurComplementKKTSystem) = kkt.inner.hess
 MadNLP.initialize!(kkt::HipSchurComplementKKTSystem) = MadNLP.initialize!(kkt.inner)
 Base.size(kkt::HipSchurComplementKKTSystem, n::Int) = kkt.inner.nd
-mul!(w::AbstractKKTVector{T}, kkt::HipSchurComplementKKTSystem, x::AbstractKKTVector, alpha = one(T), beta = zero(T)) where T =
-    mul!(w, kkt.inner, x, alpha, beta)
-MadNLP.mul_hess_blk!(wx, kkt::HipSchurComplementKKTSystem, t) = MadNLP.mul_hess_blk!(wx, kkt.inner, t)
+
+# mul! (schur.jl:1112-1139), jtprod! (:907-915) and mul_hess_blk! (:1141-1146) inside the handle: the row-list products over the
+# COO values of the last `assemble!` (one thread per short row, one wavefront per long one; include/madnlp_hip.h).  Host vectors
+# are staged once each way.
+function mul!(w::AbstractKKTVector{T}, kkt::HipSchurComplementKKTSystem, x::AbstractKKTVector, alpha = one(T), beta = zero(T)) where T
+    rc = ccall((:mnk_schur_mul, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cint),
+               kkt.stage.handle, full(w), full(x), alpha, beta, MNK_HOST)
+    check(rc, SolveException)
+    return w
+end
+function MadNLP.jtprod!(y::AbstractVector, kkt::HipSchurComplementKKTSystem, x::AbstractVector)
+    rc = ccall((:mnk_schur_jtprod, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint), kkt.stage.handle, y, x, MNK_HOST)
+    check(rc, SolveException)
+    return y
+end
+function MadNLP.mul_hess_blk!(wx, kkt::HipSchurComplementKKTSystem, t)
+    rc = ccall((:mnk_schur_mul_hess_blk, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint), kkt.stage.handle, wx, t,
+               MNK_HOST)
+    check(rc, SolveException)
+    return wx
+end
 
 # build_kkt! (schur.jl:927-1001).  Round 6: the scatter of the callback values into A_kk / C_dk / S0 (:935-972) is ONE call -- the
 # library sums every touched entry of the dense blocks on the device, in the reference's own order, from the four value vectors;
@@ -947,62 +985,22 @@ function MadNLP.build_kkt!(kkt::HipSchurComplementKKTSystem{T}) where T
     end
     assemble!(kkt.stage, k0.hess, k0.jac, k0.pr_diag, k0.du_diag)
     build_local_assembled!(kkt.stage, kkt.linear_solver.S)   # blocks factored as one batch, S = S0 - sum_k C_dk A_k^-1 C_dk'
+    # the barrier terms of this iterate, for the device-side solve_kkt! / mul!
+    rc = ccall((:mnk_schur_set_barrier_terms, libmadnlp_hip), Cint,
+               (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint),
+               kkt.stage.handle, k0.reg, k0.l_diag, k0.u_diag, k0.l_lower, k0.u_lower, MNK_HOST)
+    check(rc, SymbolicException)
     return
 end
 
 MadNLP.factorize_kkt!(kkt::HipSchurComplementKKTSystem) = MadNLP.factorize!(kkt.linear_solver)
 
-# solve_kkt! (schur.jl:1040-1110): the reference's steps 1-2 and 6-7 on the host, steps 3-5 in one device call
+# solve_kkt! (schur.jl:1007-1109) in one call: reduce_rhs!, the condensation of the inequality rows, the gather of the scenarios'
+# right-hand sides, steps 3-5, the scatter back, the recovery of inequality duals and slacks and finish_aug_solve! all run on the
+# device (`mnk_schur_solve_kkt`); the vector travels once each way.
 function MadNLP.solve_kkt!(kkt::HipSchurComplementKKTSystem, w::AbstractKKTVector{T}) where T
-    k0 = kkt.inner
-    ns, nv, nd, n, blk, nc_eq = k0.ns, k0.nv, k0.nd, MadNLP.num_variables(k0), k0.blk_size, k0.nc_eq_per_s
-    wx = view(full(w), 1:n)
-    ws = view(full(w), n+1:n+k0.n_ineq)
-    wy = dual(w)
-    Sigma_s = MadNLP.get_slack_regularization(k0)
-    MadNLP.reduce_rhs!(k0, w)
-    fill!(k0.buffer, zero(T))
-    if k0.n_ineq > 0
-        k0.buffer[k0.ind_ineq] .= k0.diag_buffer .* (wy[k0.ind_ineq] .+ ws ./ Sigma_s)
-        mul!(wx, k0.jt_csc, k0.buffer, one(T), one(T))
-    end
-    R = kkt.rhs_all
-    @inbounds for k in 1:ns
-        for i in 1:nv
-            R[i, k] = wx[(k-1)*nv + i]
-        end
-        for ci in 1:nc_eq
-            R[nv+ci, k] = wy[k0.eq_global_indices[(k-1)*nc_eq + ci]]
-        end
-    end
-    @inbounds for i in 1:nd
-        k0.rhs_d[i] = wx[ns*nv+i]
-    end
-    rc = ccall((:mnk_schur_solve, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint),
-               kkt.stage.handle, R, k0.rhs_d, MNK_HOST)
+    rc = ccall((:mnk_schur_solve_kkt, libmadnlp_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint), kkt.stage.handle, full(w), MNK_HOST)
     check(rc, SolveException)
-    @inbounds for k in 1:ns
-        for i in 1:nv
-            wx[(k-1)*nv + i] = R[i, k]
-        end
-        for ci in 1:nc_eq
-            wy[k0.eq_global_indices[(k-1)*nc_eq + ci]] = R[nv+ci, k]
-        end
-    end
-    @inbounds for i in 1:nd
-        wx[ns*nv+i] = k0.rhs_d[i]
-    end
-    if k0.n_ineq > 0
-        copyto!(k0.wy_eq_buf, view(wy, k0.ind_eq))
-        mul!(wy, k0.jt_csc', wx)
-        view(wy, k0.ind_eq) .= k0.wy_eq_buf
-        @inbounds for idx in 1:length(k0.ind_ineq)
-            gi = k0.ind_ineq[idx]
-            wy[gi] = k0.diag_buffer[idx] * wy[gi] - k0.buffer[gi]
-        end
-        ws .= (ws .+ view(wy, k0.ind_ineq)) ./ Sigma_s
-    end
-    MadNLP.finish_aug_solve!(k0, w)
     return w
 end
 

@@ -277,6 +277,20 @@ SIGNATURES = {
     "mnk_schur_solve": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "mnk_schur_set_gram_threshold": (C.c_int, [_vp, C.c_int64]),
     "mnk_schur_assembly_stats": (C.c_int, [_vp, _i64p, C.c_int]),
+    "mnk_schur_set_bounds": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int]),
+    "mnk_schur_set_barrier_terms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "mnk_schur_set_aug_diagonal": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int]),
+    "mnk_schur_regularize_diagonal": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "mnk_schur_get_diagonals": (C.c_int, [_vp] + [_vp] * 7),
+    "mnk_schur_compress_jacobian": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_schur_compress_hessian": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_schur_set_spmv_threshold": (C.c_int, [_vp, C.c_int64]),
+    "mnk_schur_solve_kkt": (C.c_int, [_vp, _vp, C.c_int]),
+    "mnk_schur_mul": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, C.c_int]),
+    "mnk_schur_jtprod": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+    "mnk_schur_mul_hess_blk": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+    "mnk_schur_spmv_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp,
+                                      C.c_int64, _vp, C.c_int, C.c_int64, _vp, C.c_int, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mnk_ls_debug_solve_trace": (C.c_int, [_vp, _vp, C.c_int64]),
     "mnk_ls_debug_dag_state": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "mnk_debug_grid_at_launch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -2,6 +2,8 @@
 // mul! (reduce_rhs!, finish_aug_solve!, the bound part of _kktmul!), the bound / barrier state of a handle with the entry points
 // that only touch it, and the frames of solve_kkt! / mul! around each unit's matrix part.
 #pragma once
+#include <cstring>
+
 #include "ls.h"
 
 namespace mnk {
@@ -67,8 +69,9 @@ static __global__ void vec_shift2_kernel(double* __restrict__ a, double* __restr
 // ---- the bound / barrier state of a KKT handle (sparse condensed, dense condensed, dense augmented) and the entry points
 // that touch nothing else.  The handles differ in their matrix; each unit's private struct embeds one KktVecState and passes
 // its own sizes: npr = length of the primal block (n + m sparse, n + ns dense), npd = primal + dual length of w (n + 2m sparse,
-// n + ns + m dense).  `who` is the C entry point's name: errors read "<who>: ...", and where a message names another entry
-// point of the same handle kind it takes the kind's prefix from who's first six characters ("mnk_sc" / "mnk_dc").
+// n + ns + m dense; the Schur handle: n + n_ineq and n + n_ineq + m).  `who` is the C entry point's name: errors read "<who>: ...",
+// and where a message names another entry point of the same handle kind it takes the kind's prefix from who: the name up to its
+// second underscore ("mnk_sc" / "mnk_dc" / "mnk_schur": kkt_pfx).
 struct KktVecState {
     int64_t nlb = 0, nub = 0;
     DevBuf<int64_t> ind_lb, ind_ub;               // positions in the primal block [0, npr)
@@ -79,6 +82,11 @@ struct KktVecState {
     DevBuf<double> saved_diag;                    // reg | pr_diag | du_diag of kkt_save_diagonals
     bool have_saved_diag = false;
 };
+
+static inline int kkt_pfx(const char* who) {
+    const char* u = std::strchr(who + 4, '_');
+    return u ? (int)(u - who) : (int)std::strlen(who);
+}
 
 #define KKT_REQUIRE(cond, ...) do { if (!(cond)) { mnk::set_error(__VA_ARGS__); return -1; } } while (0)
 
@@ -123,7 +131,7 @@ static inline int kkt_set_bounds(KktVecState& st, mnk_ctx* ctx, const char* who,
 static inline int kkt_set_barrier_terms(KktVecState& st, mnk_ctx* ctx, const char* who, int64_t npr, const double* reg,
                                         const double* l_diag, const double* u_diag, const double* l_lower,
                                         const double* u_lower, int loc) {
-    KKT_REQUIRE(st.have_bounds, "%s: call %.6s_set_bounds first", who, who);
+    KKT_REQUIRE(st.have_bounds, "%s: call %.*s_set_bounds first", who, kkt_pfx(who), who);
     hipStream_t s = ctx->stream;
     auto put = [&](double* dst, const double* src, int64_t cnt) -> int {
         if (cnt <= 0) return 0;
@@ -155,7 +163,7 @@ struct AugDiagView {
 
 static inline int kkt_diag_view(AugDiagView& v, KktVecState& st, mnk_ctx* ctx, const char* who, int64_t npr, int64_t ndu,
                                 double* pr_diag, double* du_diag) {
-    KKT_REQUIRE(st.have_bounds, "%s: call %.6s_set_bounds first", who, who);
+    KKT_REQUIRE(st.have_bounds, "%s: call %.*s_set_bounds first", who, kkt_pfx(who), who);
     v = AugDiagView{ctx, &st, npr, ndu, st.nlb, st.nub, st.reg.p, pr_diag, du_diag, st.l_diag.p,
                     st.u_diag.p, st.l_lower.p, st.u_lower.p, st.ind_lb.p, st.ind_ub.p, &st.feed};
     return 0;
@@ -228,7 +236,7 @@ static inline int kkt_set_aug_RR(const AugDiagView& v, const char* who, const do
 }
 
 static inline int kkt_regularize_diagonal(const AugDiagView& v, const char* who, double primal, double dual) {
-    KKT_REQUIRE(v.st->have_diag, "%s: call %.6s_set_aug_diagonal first", who, who);
+    KKT_REQUIRE(v.st->have_diag, "%s: call %.*s_set_aug_diagonal first", who, kkt_pfx(who), who);
     hipStream_t s = v.ctx->stream;
     hipLaunchKernelGGL(vec_shift2_kernel, MNK_G1(v.npr), v.reg, v.pr_diag, primal, v.npr);
     if (v.ndu > 0) hipLaunchKernelGGL(vec_shift2_kernel, MNK_G1(v.ndu), v.du_diag, (double*)nullptr, -dual, v.ndu);
@@ -256,7 +264,7 @@ static inline int kkt_get_diagonals(const AugDiagView& v, double* pr_diag, doubl
 // -- pr_diag + dw - dw would not)
 static inline int kkt_save_diagonals(const AugDiagView& v, const char* who) {
     KktVecState& st = *v.st;
-    KKT_REQUIRE(st.have_diag, "%s: call %.6s_set_aug_diagonal first", who, who);
+    KKT_REQUIRE(st.have_diag, "%s: call %.*s_set_aug_diagonal first", who, kkt_pfx(who), who);
     const size_t npr = (size_t)v.npr, ndu = (size_t)v.ndu;
     if (st.saved_diag.n < 2 * npr + ndu && st.saved_diag.alloc(2 * npr + ndu)) {
         const std::string why = mnk_last_error_string();   // (the allocation's own message: which hipMalloc failed and why)
@@ -273,7 +281,7 @@ static inline int kkt_save_diagonals(const AugDiagView& v, const char* who) {
 
 static inline int kkt_restore_diagonals(const AugDiagView& v, const char* who) {
     const KktVecState& st = *v.st;
-    KKT_REQUIRE(st.have_saved_diag, "%s: nothing saved (%.6s_save_diagonals)", who, who);
+    KKT_REQUIRE(st.have_saved_diag, "%s: nothing saved (%.*s_save_diagonals)", who, kkt_pfx(who), who);
     const size_t npr = (size_t)v.npr, ndu = (size_t)v.ndu;
     hipStream_t s = v.ctx->stream;
     MNK_HIP(hipMemcpyAsync(v.reg, st.saved_diag.p, npr * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -288,8 +296,8 @@ static inline int kkt_restore_diagonals(const AugDiagView& v, const char* who) {
 template <class Middle>
 static inline int kkt_solve_kkt(KktVecState& st, mnk_ctx* ctx, const char* who, mnk_ls* ls, int64_t npd, double* w, int loc,
                                 Middle&& middle) {
-    KKT_REQUIRE(st.have_bounds && st.have_terms, "%s: call %.6s_set_bounds / %.6s_set_barrier_terms / %.6s_build first", who, who,
-                who, who);
+    KKT_REQUIRE(st.have_bounds && st.have_terms, "%s: call %.*s_set_bounds / %.*s_set_barrier_terms / %.*s_build first", who,
+                kkt_pfx(who), who, kkt_pfx(who), who, kkt_pfx(who), who);
     hipStream_t s = ctx->stream;
     const int64_t nlb = st.nlb, nub = st.nub, lw = npd + nlb + nub;
     // Host-resident caller: the host still owns `w` until the final copy-back, so a persistent solve that gave
@@ -323,7 +331,8 @@ static inline int kkt_solve_kkt(KktVecState& st, mnk_ctx* ctx, const char* who, 
 template <class Matrix>
 static inline int kkt_mul(KktVecState& st, mnk_ctx* ctx, const char* who, int64_t npd, double* w, const double* x, double alpha,
                           double beta, int loc, Matrix&& matrix) {
-    KKT_REQUIRE(st.have_bounds && st.have_terms, "%s: call %.6s_set_bounds / %.6s_set_barrier_terms first", who, who, who);
+    KKT_REQUIRE(st.have_bounds && st.have_terms, "%s: call %.*s_set_bounds / %.*s_set_barrier_terms first", who, kkt_pfx(who), who,
+                kkt_pfx(who), who);
     hipStream_t s = ctx->stream;
     const int64_t nlb = st.nlb, nub = st.nub, lw = npd + nlb + nub;
     double* dw = w;

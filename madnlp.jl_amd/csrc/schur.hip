@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gemm_tile.h"
+#include "kkt_vec.h"
 #include "ls.h"
 #include "schur_plan.h"
 
@@ -71,6 +72,32 @@ struct mnk_schur {
         mnk::DevBuf<double> P;                  // nchunk x (nd x nd): the partial sums of the S0 product, one per K chunk
     } as;
     int64_t gram_T = -1;                        // Gram row threshold of the next mnk_schur_set_structure (negative: the default)
+    // ---- device-side solve_kkt! / mul! / jtprod! / mul_hess_blk! on ONE rank (mnk_schur_solve_kkt and its kin): the bound / barrier
+    // state every KKT handle has (kkt_vec.h; npr = n + n_ineq, npd = n + n_ineq + m), the row lists of J, J' and Symmetric(H, :L)
+    // over the COO values of the last mnk_schur_assemble (schur_plan.h), and the work vectors of the solve.  The handle's own
+    // pr_diag / du_diag are the last two parts of as.vals: an assemble with explicit diagonals copies them there, one without uses
+    // what the feeders (mnk_schur_set_aug_diagonal, mnk_schur_regularize_diagonal) left.
+    struct SpmvDev {
+        int64_t rows = 0, nlong = 0;
+        mnk::DevBuf<int32_t> ptr, idx, perm, long_rows;
+    };
+    struct {
+        bool have = false;                      // false: no structure yet, or a sharded handle
+        bool have_vals = false;                 // an assemble has filled as.vals
+        bool have_jac = false, have_hess = false;   // ... or a compress call its Jacobian / Hessian part
+        mnk::KktVecState st;
+        SpmvDev op[3];                          // SCHUR_OP_J, SCHUR_OP_JT, SCHUR_OP_H
+        int64_t T = 0, n_eq = 0;
+        mnk::DevBuf<int64_t> eq_rows;           // ascending: scenario k's equality rows at [k * nc_eq, (k + 1) * nc_eq)
+        mnk::DevBuf<double> buffer, buffer2;    // m each: the condensed inequality right-hand side | J wx
+        mnk::DevBuf<double> rk, rd;             // ns x blk | nd: the stage's right-hand sides
+        mnk::DevBuf<double> va, vb;             // staging of host vectors of jtprod! / mul_hess_blk! (n + n_ineq + m each)
+    } kv;
+    int64_t spmv_T = -1;                        // product row threshold of the next mnk_schur_set_structure (negative: the default)
+    double* hess_v() { return as.vals.p; }
+    double* jac_v() { return as.vals.p + as.nnzh; }
+    double* pr_diag() { return as.vals.p + as.nnzh + as.nnzj; }
+    double* du_diag() { return as.vals.p + as.nnzh + as.nnzj + as.n + as.n_ineq; }
 };
 
 namespace mnk {
@@ -266,6 +293,131 @@ __global__ void schur_gram_reduce_kernel(double* __restrict__ S0, const double* 
     double v = S0[i];
     for (int64_t c = 0; c < nchunk; ++c) v = __dadd_rn(v, P[c * n + i]);
     S0[i] = v;
+}
+
+// ---- the sparse products of solve_kkt! / mul! / jtprod! / mul_hess_blk! (row lists: schur_plan.h) ----
+// hipcc contracts a * b + c into one fma by default, and __dmul_rn / __dadd_rn do not stop it: HIP defines them as the plain
+// operators in a header that is itself compiled with contraction (schur_condense_weights_kernel's 1 - Sd Ss above IS one fma).  The
+// kernels below therefore spell their arithmetic with the operators and switch contraction off in their bodies (`#pragma clang fp
+// contract(off)`): every multiply and add is rounded on its own -- the compiled code holds no fma outside the division sequences --
+// and the numpy mirror of schur_kkt.py needs no fused operation for them.
+// y[r] = alpha acc (+ beta y[r] when beta != 0), acc = the row's terms vals[perm[q]] * x[idx[q]], every multiply and add rounded on
+// its own (see above): the bits depend on the lists and the values alone (no atomics, no dependence on the grid).
+__device__ __forceinline__ void schur_spmv_store(double* __restrict__ y, int64_t r, double acc, double alpha, double beta) {
+#pragma clang fp contract(off)
+    double v = alpha * acc;
+    if (beta != 0.0) v = v + beta * y[r];
+    y[r] = v;
+}
+// rows of at most T entries: one thread per row, the terms in list order
+__global__ void schur_spmv_rows_kernel(int64_t rows, int64_t T, const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                                       const int32_t* __restrict__ perm, const double* __restrict__ vals, const double* __restrict__ x,
+                                       double alpha, double beta, double* __restrict__ y) {
+#pragma clang fp contract(off)
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const int32_t q0 = ptr[r], q1 = ptr[r + 1];
+    if ((int64_t)q1 - q0 > T) return;   // a long row: schur_spmv_long_kernel's
+    double acc = 0.0;
+    for (int32_t q = q0; q < q1; ++q) acc = acc + vals[perm[q]] * x[idx[q]];
+    schur_spmv_store(y, r, acc, alpha, beta);
+}
+// rows of more than T entries: one 64-lane wavefront per row (four rows per workgroup).  Lane l sums the entries l, l + 64, ... in
+// ascending order; a fixed xor-butterfly (offsets 32, 16, ..., 1) combines the 64 partials -- both operands of every addition are
+// the same pair on both sides of an exchange, so all lanes end with the same bits; lane 0 stores.  A wavefront leaves as a whole
+// (w >= nlong is uniform over it) and the lanes reconverge behind the loop: all 64 take part in every exchange.
+__global__ __launch_bounds__(256) void schur_spmv_long_kernel(int64_t nlong, const int32_t* __restrict__ long_rows,
+                                                              const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+                                                              const int32_t* __restrict__ perm, const double* __restrict__ vals,
+                                                              const double* __restrict__ x, double alpha, double beta, double* __restrict__ y) {
+#pragma clang fp contract(off)
+    const int64_t w = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (w >= nlong) return;
+    const int64_t r = long_rows[w];
+    const int32_t q1 = ptr[r + 1];
+    double acc = 0.0;
+    for (int32_t q = ptr[r] + lane; q < q1; q += 64) acc = acc + vals[perm[q]] * x[idx[q]];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+    if (lane == 0) schur_spmv_store(y, r, acc, alpha, beta);
+}
+// solve_kkt! step 1 (reference schur.jl:1028-1030): buffer[ind_ineq[p]] = D_p (wy[ind_ineq[p]] + ws_p / Sigma_s,p) (the rest of
+// buffer was zeroed)
+__global__ void schur_condense_rhs_kernel(double* __restrict__ buffer, const double* __restrict__ D, const double* __restrict__ ws,
+                                          const double* __restrict__ wy, const double* __restrict__ Ss, const int64_t* __restrict__ ind_ineq,
+                                          int64_t n_ineq) {
+#pragma clang fp contract(off)
+    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p >= n_ineq) return;
+    const int64_t r = ind_ineq[p];
+    buffer[r] = D[p] * (wy[r] + ws[p] / Ss[p]);
+}
+// steps 2 and 6 (:1035-1052, :1072-1086): the per-scenario right-hand sides (wx_k ; wy[equality rows of k]) and the design part, to
+// the stage's buffers (back = 0) or back from them (back = 1); one thread per entry of rk | rd
+__global__ void schur_rhs_blocks_kernel(double* __restrict__ wx, double* __restrict__ wy, double* __restrict__ rk, double* __restrict__ rd,
+                                        const int64_t* __restrict__ eq_rows, int64_t ns, int64_t nv, int64_t blk, int64_t nd, int back) {
+    const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    double *a, *b;
+    if (t < ns * blk) {
+        const int64_t k = t / blk, i = t - k * blk;
+        a = i < nv ? wx + k * nv + i : wy + eq_rows[k * (blk - nv) + (i - nv)];
+        b = rk + t;
+    } else if (t < ns * blk + nd) {
+        a = wx + ns * nv + (t - ns * blk);
+        b = rd + (t - ns * blk);
+    } else {
+        return;
+    }
+    if (back) *a = *b;
+    else *b = *a;
+}
+// step 7 (:1088-1105) with jx = J wx in a vector of its own (the equality duals in wy stay as the stage left them):
+// wy[ind_ineq[p]] = D_p jx[ind_ineq[p]] - buffer[ind_ineq[p]] ; ws_p = (ws_p + wy[ind_ineq[p]]) / Sigma_s,p
+__global__ void schur_expand_kernel(double* __restrict__ ws, double* __restrict__ wy, const double* __restrict__ jx,
+                                    const double* __restrict__ buffer, const double* __restrict__ D, const double* __restrict__ Ss,
+                                    const int64_t* __restrict__ ind_ineq, int64_t n_ineq) {
+#pragma clang fp contract(off)
+    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p >= n_ineq) return;
+    const int64_t r = ind_ineq[p];
+    const double y = D[p] * jx[r] - buffer[r];
+    wy[r] = y;
+    ws[p] = (ws[p] + y) / Ss[p];
+}
+// mul! (:1135-1136): ws_p = beta ws_p - alpha xy[ind_ineq[p]] ; wy[ind_ineq[p]] -= alpha xs_p
+__global__ void schur_mul_slack_kernel(double* __restrict__ ws, double* __restrict__ wy, const double* __restrict__ xs,
+                                       const double* __restrict__ xy, const int64_t* __restrict__ ind_ineq, double alpha, double beta,
+                                       int64_t n_ineq) {
+#pragma clang fp contract(off)
+    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p >= n_ineq) return;
+    const int64_t r = ind_ineq[p];
+    ws[p] = beta * ws[p] - alpha * xy[r];
+    wy[r] = wy[r] - alpha * xs[p];
+}
+// _kktmul!, diagonal part: w[i] += (alpha d_i) x[i] with d = reg on the primal block [0, npr) and du_diag on the dual block
+__global__ void schur_mul_diag_kernel(double* __restrict__ w, const double* __restrict__ x, const double* __restrict__ reg,
+                                      const double* __restrict__ du_diag, double alpha, int64_t npr, int64_t npd) {
+#pragma clang fp contract(off)
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= npd) return;
+    const double d = i < npr ? reg[i] : du_diag[i - npr];
+    w[i] = w[i] + (alpha * d) * x[i];
+}
+// jtprod! (:907-915), slack part: y[n + p] = -x[ind_ineq[p]]
+__global__ void schur_jtprod_slack_kernel(double* __restrict__ ys, const double* __restrict__ x, const int64_t* __restrict__ ind_ineq,
+                                          int64_t n_ineq) {
+    const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p < n_ineq) ys[p] = -x[ind_ineq[p]];
+}
+// mul_hess_blk! (:1141-1146) behind the Hessian product: wx[i] = (i < n ? wx[i] : 0) + t[i] pr_diag[i]
+__global__ void schur_hess_blk_diag_kernel(double* __restrict__ wx, const double* __restrict__ t, const double* __restrict__ pr_diag,
+                                           int64_t n, int64_t npr) {
+#pragma clang fp contract(off)
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= npr) return;
+    wx[i] = (i < n ? wx[i] : 0.0) + t[i] * pr_diag[i];
 }
 }  // namespace mnk
 
@@ -598,9 +750,19 @@ int mnk_schur_set_structure(mnk_schur* h, int64_t n, int64_t m, int64_t nv, int6
     MNK_REQUIRE(!err, err);
     MNK_REQUIRE(plan.long_rows == 0 || (h->ns <= 65535 && h->ns * plan.Kp / GRAM_BK <= (int64_t)65535 * GRAM_S0_CHUNK),
                 "mnk_schur_set_structure: too many local scenarios / long rows for the Gram products' grids");
+    // the row lists of the device-side products: a single rank's only (a sharded handle keeps the stage and the assembly)
+    const bool single_rank = local_scen == nullptr && own_design;
+    SchurSpmvPlan sp;
+    if (single_rank) {
+        err = schur_spmv_plan(in, h->spmv_T, sp);
+        MNK_REQUIRE(!err, err);
+    }
     MNK_HIP(hipSetDevice(h->ctx->device));
     auto& as = h->as;
+    auto& kv = h->kv;
     as.have = false;
+    kv.have = kv.have_vals = kv.have_jac = kv.have_hess = false;
+    kv.st.have_diag = kv.st.have_saved_diag = false;   // (the handle's diagonals live in as.vals, allocated anew below)
     as.n = n; as.m = m; as.nv = nv; as.nc = nc; as.nnzh = nnzh; as.nnzj = nnzj; as.n_ineq = n_ineq;
     as.nseg = plan.nseg(); as.nsrc = plan.nsrc();
     plan.stats(as.stats);
@@ -625,24 +787,52 @@ int mnk_schur_set_structure(mnk_schur* h, int64_t n, int64_t m, int64_t nv, int6
         as.slot_dst.release(); as.slot_ptr.release(); as.slot_src.release(); as.slot_p.release();
         as.W.release(); as.DW.release(); as.P.release();
     }
+    if (!rc && single_rank) {
+        for (int w = 0; w < 3 && !rc; ++w) {
+            auto& d = kv.op[w];
+            d.rows = sp.op[w].rows;
+            d.nlong = (int64_t)sp.op[w].long_rows.size();
+            rc = d.ptr.upload(sp.op[w].ptr, st) | d.idx.upload(sp.op[w].idx, st) | d.perm.upload(sp.op[w].perm, st) |
+                 d.long_rows.upload(sp.op[w].long_rows, st);
+        }
+        kv.T = sp.T;
+        kv.n_eq = n_eq;
+        const size_t npd = (size_t)(n + n_ineq + m);
+        if (!rc)
+            rc = kv.eq_rows.upload(sp.eq_rows, st) | kv.buffer.alloc((size_t)m + 8) | kv.buffer2.alloc((size_t)m + 8) |
+                 kv.rk.alloc((size_t)(h->ns * h->blk) + 8) | kv.rd.alloc((size_t)nd + 8) | kv.va.alloc(npd + 8) | kv.vb.alloc(npd + 8);
+    }
     if (rc) { (void)hipGetLastError(); set_error("mnk_schur_set_structure: out of device memory"); return -2; }
     as.have = true;
+    kv.have = single_rank;
     return 0;
 }
 
 int mnk_schur_assemble(mnk_schur* h, const double* hess, const double* jac, const double* pr_diag, const double* du_diag, int loc) {
     MNK_REQUIRE(h && h->as.have, "mnk_schur_assemble: call mnk_schur_set_structure first");
     auto& as = h->as;
-    MNK_REQUIRE((hess || as.nnzh == 0) && (jac || as.nnzj == 0) && pr_diag && (du_diag || as.m == 0), "mnk_schur_assemble: NULL argument");
+    // NULL pr_diag and du_diag: the handle's own (what mnk_schur_set_aug_diagonal / mnk_schur_regularize_diagonal left), as
+    // mnk_sc_build(NULL, NULL)
+    const bool own_diag = pr_diag == nullptr && du_diag == nullptr;
+    MNK_REQUIRE((hess || as.nnzh == 0) && (jac || as.nnzj == 0) && (own_diag || (pr_diag && (du_diag || as.m == 0))),
+                "mnk_schur_assemble: NULL argument");
+    MNK_REQUIRE(!own_diag || h->kv.st.have_diag, "mnk_schur_assemble: NULL diagonals: call mnk_schur_set_aug_diagonal first");
     MNK_HIP(hipSetDevice(h->ctx->device));
     hipStream_t s = h->ctx->stream;
-    if (loc != MNK_DEVICE) {   // host callbacks: one staging buffer, four copies
-        double* v = as.vals.p;
-        if (as.nnzh > 0) MNK_HIP(mnk::h2d_copy(v, hess, (size_t)as.nnzh * sizeof(double), s));
-        if (as.nnzj > 0) MNK_HIP(mnk::h2d_copy(v + as.nnzh, jac, (size_t)as.nnzj * sizeof(double), s));
-        MNK_HIP(mnk::h2d_copy(v + as.nnzh + as.nnzj, pr_diag, (size_t)(as.n + as.n_ineq) * sizeof(double), s));
-        if (as.m > 0) MNK_HIP(mnk::h2d_copy(v + as.nnzh + as.nnzj + as.n + as.n_ineq, du_diag, (size_t)as.m * sizeof(double), s));
-        hess = v; jac = v + as.nnzh; pr_diag = v + as.nnzh + as.nnzj; du_diag = v + as.nnzh + as.nnzj + as.n + as.n_ineq;
+    {   // the handle keeps the values it assembles from (as.vals: hess | jac | pr_diag | du_diag): the device-side products of
+        // solve_kkt! / mul! read "the values of the last assemble" (the role of jt_csc / hess_csc in the reference)
+        const size_t np = (size_t)(as.n + as.n_ineq);
+        auto put = [&](double* dst, const double* src, size_t cnt) -> int {
+            if (cnt == 0 || src == nullptr) return 0;
+            if (loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+            else MNK_HIP(mnk::h2d_copy(dst, src, cnt * sizeof(double), s));
+            return 0;
+        };
+        int rc = put(h->hess_v(), hess, (size_t)as.nnzh) | put(h->jac_v(), jac, (size_t)as.nnzj);
+        if (!own_diag) rc |= put(h->pr_diag(), pr_diag, np) | put(h->du_diag(), du_diag, (size_t)as.m);
+        if (rc) return rc;
+        hess = h->hess_v(); jac = h->jac_v(); pr_diag = h->pr_diag(); du_diag = h->du_diag();
+        h->kv.have_vals = h->kv.have_jac = h->kv.have_hess = true;
     }
     const int64_t sizeA = h->ns * h->blk * h->blk, sizeC = h->ns * h->nd * h->blk;
     if (sizeA > 0) MNK_HIP(hipMemsetAsync(h->A.p, 0, (size_t)sizeA * sizeof(double), s));
@@ -736,6 +926,212 @@ int mnk_schur_solve(mnk_schur* h, double* rhs_k, double* rhs_d, int loc) {
         if (nk > 0) MNK_HIP(mnk::d2h_copy(rhs_k, rk, nk * sizeof(double), s));
         MNK_HIP(mnk::d2h_copy(rhs_d, rd, (size_t)h->nd * sizeof(double), s));
     }
+    return 0;
+}
+
+// ---- the KKT-handle contract on the Schur handle (single rank): bound / barrier state, feeders, solve_kkt!, mul!, jtprod!,
+// mul_hess_blk! on host or device vectors.  State and frames are kkt_vec.h's; the matrix parts are the row-list products above.
+int mnk_schur_set_spmv_threshold(mnk_schur* h, int64_t row_entries) {
+    MNK_REQUIRE(h, "mnk_schur_set_spmv_threshold: NULL handle");
+    h->spmv_T = row_entries < 0 ? -1 : row_entries;
+    return 0;
+}
+
+static int schur_kkt_enter(mnk_schur* h, bool args_ok, const char* who) {
+    KKT_REQUIRE(h && args_ok, "%s: NULL argument", who);
+    KKT_REQUIRE(h->as.have, "%s: call mnk_schur_set_structure first", who);
+    KKT_REQUIRE(h->kv.have, "%s: single rank only: this handle is sharded (scenarios on other ranks or a design block it does not own)", who);
+    MNK_HIP(hipSetDevice(h->ctx->device));
+    return 0;
+}
+
+// compress_jacobian! / compress_hessian! (reference schur.jl:917-923: the transfer of the callbacks' COO values to jt_csc / hess_csc):
+// the kept values of one operator as of NOW, without an assemble -- the interior-point loop calls jtprod! on a fresh Jacobian
+// before it builds the next KKT system.
+static int schur_keep_values(mnk_schur* h, double* dst, const double* src, int64_t cnt, int loc, const char* who) {
+    int rc = schur_kkt_enter(h, src != nullptr || cnt == 0, who);
+    if (rc) return rc;
+    hipStream_t s = h->ctx->stream;
+    if (cnt > 0 && loc == MNK_DEVICE) MNK_HIP(hipMemcpyAsync(dst, src, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else if (cnt > 0) MNK_HIP(mnk::h2d_copy(dst, src, (size_t)cnt * sizeof(double), s));
+    return 0;
+}
+
+int mnk_schur_compress_jacobian(mnk_schur* h, const double* jac, int loc) {
+    int rc = schur_keep_values(h, h ? h->jac_v() : nullptr, jac, h ? h->as.nnzj : 0, loc, "mnk_schur_compress_jacobian");
+    if (!rc) h->kv.have_jac = true;
+    return rc;
+}
+
+int mnk_schur_compress_hessian(mnk_schur* h, const double* hess, int loc) {
+    int rc = schur_keep_values(h, h ? h->hess_v() : nullptr, hess, h ? h->as.nnzh : 0, loc, "mnk_schur_compress_hessian");
+    if (!rc) h->kv.have_hess = true;
+    return rc;
+}
+
+int mnk_schur_set_bounds(mnk_schur* h, int64_t nlb, const int64_t* ind_lb, int64_t nub, const int64_t* ind_ub, int index_base) {
+    int rc = schur_kkt_enter(h, nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub), "mnk_schur_set_bounds");
+    if (rc) return rc;
+    const int64_t npr = h->as.n + h->as.n_ineq;
+    return kkt_set_bounds(h->kv.st, h->ctx, "mnk_schur_set_bounds", npr, npr + h->as.m, nlb, ind_lb, nub, ind_ub, index_base);
+}
+
+int mnk_schur_set_barrier_terms(mnk_schur* h, const double* reg, const double* l_diag, const double* u_diag, const double* l_lower,
+                                const double* u_lower, int loc) {
+    int rc = schur_kkt_enter(h, true, "mnk_schur_set_barrier_terms");
+    if (rc) return rc;
+    return kkt_set_barrier_terms(h->kv.st, h->ctx, "mnk_schur_set_barrier_terms", h->as.n + h->as.n_ineq, reg, l_diag, u_diag, l_lower,
+                                 u_lower, loc);
+}
+
+static int schur_diag_view(mnk_schur* h, AugDiagView& v, const char* who) {
+    int rc = schur_kkt_enter(h, true, who);
+    if (rc) return rc;
+    return kkt_diag_view(v, h->kv.st, h->ctx, who, h->as.n + h->as.n_ineq, h->as.m, h->pr_diag(), h->du_diag());
+}
+
+int mnk_schur_set_aug_diagonal(mnk_schur* h, const double* x, const double* xl, const double* xu, const double* zl, const double* zu,
+                               double primal_reg, double dual_reg, int loc) {
+    AugDiagView v;
+    int rc = schur_diag_view(h, v, "mnk_schur_set_aug_diagonal");
+    return rc ? rc : kkt_set_aug_diagonal(v, "mnk_schur_set_aug_diagonal", x, xl, xu, zl, zu, primal_reg, dual_reg, loc);
+}
+
+int mnk_schur_regularize_diagonal(mnk_schur* h, double primal, double dual) {
+    AugDiagView v;
+    int rc = schur_diag_view(h, v, "mnk_schur_regularize_diagonal");
+    return rc ? rc : kkt_regularize_diagonal(v, "mnk_schur_regularize_diagonal", primal, dual);
+}
+
+int mnk_schur_get_diagonals(mnk_schur* h, double* pr_diag, double* du_diag, double* reg, double* l_diag, double* u_diag, double* l_lower,
+                            double* u_lower) {
+    AugDiagView v;
+    int rc = schur_diag_view(h, v, "mnk_schur_get_diagonals");
+    return rc ? rc : kkt_get_diagonals(v, pr_diag, du_diag, reg, l_diag, u_diag, l_lower, u_lower);
+}
+
+// y = alpha Op x (+ beta y): the short rows, then the long ones (disjoint rows: the order of the two launches does not matter)
+static int schur_spmv(mnk_schur* h, int which, const double* vals, double alpha, const double* x, double beta, double* y) {
+    const auto& op = h->kv.op[which];
+    hipStream_t s = h->ctx->stream;
+    if (op.rows > 0)
+        hipLaunchKernelGGL(schur_spmv_rows_kernel, MNK_GRID1(op.rows), op.rows, h->kv.T, op.ptr.p, op.idx.p, op.perm.p, vals, x, alpha, beta, y);
+    if (op.nlong > 0)
+        hipLaunchKernelGGL(schur_spmv_long_kernel, dim3((unsigned)((op.nlong + 3) / 4)), dim3(256), 0, s, op.nlong, op.long_rows.p, op.ptr.p,
+                           op.idx.p, op.perm.p, vals, x, alpha, beta, y);
+    MNK_HIP(hipGetLastError());
+    return 0;
+}
+
+// solve_kkt! (reference schur.jl:1007-1109) on w = (x, s, y, z_l, z_u), host or device.  A scenario or design solve that gave up
+// ends the call with its error, as mnk_schur_solve does (the solver has then switched to the stepwise solve: the caller repeats).
+int mnk_schur_solve_kkt(mnk_schur* h, double* w, int loc) {
+    const char* who = "mnk_schur_solve_kkt";
+    int rc = schur_kkt_enter(h, w != nullptr, who);
+    if (rc) return rc;
+    auto& kv = h->kv;
+    KKT_REQUIRE(kv.st.have_bounds, "%s: call mnk_schur_set_bounds first", who);
+    KKT_REQUIRE(kv.st.have_terms, "%s: call mnk_schur_set_barrier_terms first", who);
+    KKT_REQUIRE(kv.have_vals, "%s: call mnk_schur_assemble first", who);
+    hipStream_t s = h->ctx->stream;
+    const int64_t n = h->as.n, m = h->as.m, ni = h->as.n_ineq, ns = h->ns, nv = h->as.nv, nd = h->nd, blk = h->blk;
+    return kkt_solve_kkt(kv.st, h->ctx, who, h->ls_s, n + ni + m, w, loc, [&](double* d) -> int {
+        double *wx = d, *ws = d + n, *wy = d + n + ni;
+        const double* Ss = h->pr_diag() + n;
+        if (ni > 0) {   // step 1: condense the inequality rows into wx
+            MNK_HIP(hipMemsetAsync(kv.buffer.p, 0, (size_t)m * sizeof(double), s));
+            hipLaunchKernelGGL(schur_condense_rhs_kernel, MNK_GRID1(ni), kv.buffer.p, h->as.D.p, ws, wy, Ss, h->as.ind_ineq.p, ni);
+            int rc = schur_spmv(h, SCHUR_OP_JT, h->jac_v(), 1.0, kv.buffer.p, 1.0, wx);
+            if (rc) return rc;
+        }
+        const int64_t nt = ns * blk + nd;
+        hipLaunchKernelGGL(schur_rhs_blocks_kernel, MNK_GRID1(nt), wx, wy, kv.rk.p, kv.rd.p, kv.eq_rows.p, ns, nv, blk, nd, 0);
+        MNK_HIP(hipGetLastError());
+        int rc = mnk_schur_solve(h, kv.rk.p, kv.rd.p, MNK_DEVICE);   // steps 3-5
+        if (rc) return rc;
+        hipLaunchKernelGGL(schur_rhs_blocks_kernel, MNK_GRID1(nt), wx, wy, kv.rk.p, kv.rd.p, kv.eq_rows.p, ns, nv, blk, nd, 1);
+        if (ni > 0) {   // step 7: inequality duals and slacks from J wx
+            rc = schur_spmv(h, SCHUR_OP_J, h->jac_v(), 1.0, wx, 0.0, kv.buffer2.p);
+            if (rc) return rc;
+            hipLaunchKernelGGL(schur_expand_kernel, MNK_GRID1(ni), ws, wy, kv.buffer2.p, kv.buffer.p, h->as.D.p, Ss, h->as.ind_ineq.p, ni);
+        }
+        MNK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// mul!(w, kkt, x, alpha, beta) (reference :1112-1139): the slack coupling goes through ind_ineq
+int mnk_schur_mul(mnk_schur* h, double* w, const double* x, double alpha, double beta, int loc) {
+    const char* who = "mnk_schur_mul";
+    int rc = schur_kkt_enter(h, w && x, who);
+    if (rc) return rc;
+    auto& kv = h->kv;
+    KKT_REQUIRE(kv.st.have_bounds, "%s: call mnk_schur_set_bounds first", who);
+    KKT_REQUIRE(kv.st.have_terms, "%s: call mnk_schur_set_barrier_terms first", who);
+    KKT_REQUIRE(kv.have_vals, "%s: call mnk_schur_assemble first", who);
+    hipStream_t s = h->ctx->stream;
+    const int64_t n = h->as.n, m = h->as.m, ni = h->as.n_ineq;
+    return kkt_mul(kv.st, h->ctx, who, n + ni + m, w, x, alpha, beta, loc, [&](double* dw, const double* dx) -> int {
+        // wx = alpha Sym(H) xx + beta wx ; wx += alpha J' xy ; wy = alpha J xx + beta wy
+        int rc = schur_spmv(h, SCHUR_OP_H, h->hess_v(), alpha, dx, beta, dw);
+        if (rc) return rc;
+        if (m > 0) {
+            rc = schur_spmv(h, SCHUR_OP_JT, h->jac_v(), alpha, dx + n + ni, 1.0, dw);
+            if (rc) return rc;
+            rc = schur_spmv(h, SCHUR_OP_J, h->jac_v(), alpha, dx, beta, dw + n + ni);
+            if (rc) return rc;
+        }
+        if (ni > 0)
+            hipLaunchKernelGGL(schur_mul_slack_kernel, MNK_GRID1(ni), dw + n, dw + n + ni, dx + n, dx + n + ni, h->as.ind_ineq.p, alpha, beta, ni);
+        hipLaunchKernelGGL(schur_mul_diag_kernel, MNK_GRID1(n + ni + m), dw, dx, kv.st.reg.p, h->du_diag(), alpha, n + ni, n + ni + m);
+        MNK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// jtprod!(y, kkt, x) (reference :907-915): y (n + n_ineq) = [J' x ; -x[ind_ineq]], x (m)
+int mnk_schur_jtprod(mnk_schur* h, double* y, const double* x, int loc) {
+    int rc = schur_kkt_enter(h, y && x, "mnk_schur_jtprod");
+    if (rc) return rc;
+    auto& kv = h->kv;
+    KKT_REQUIRE(kv.have_jac, "%s: call mnk_schur_assemble first (or mnk_schur_compress_jacobian: the Jacobian's values alone)", "mnk_schur_jtprod");
+    hipStream_t s = h->ctx->stream;
+    const int64_t n = h->as.n, m = h->as.m, ni = h->as.n_ineq;
+    double* dy = y;
+    const double* dx = x;
+    if (loc != MNK_DEVICE) {
+        dy = kv.va.p;
+        dx = kv.vb.p;
+        MNK_HIP(mnk::h2d_copy(kv.vb.p, x, (size_t)m * sizeof(double), s));
+    }
+    rc = schur_spmv(h, SCHUR_OP_JT, h->jac_v(), 1.0, dx, 0.0, dy);
+    if (rc) return rc;
+    if (ni > 0) hipLaunchKernelGGL(schur_jtprod_slack_kernel, MNK_GRID1(ni), dy + n, dx, h->as.ind_ineq.p, ni);
+    MNK_HIP(hipGetLastError());
+    if (loc != MNK_DEVICE) MNK_HIP(mnk::d2h_copy(y, dy, (size_t)(n + ni) * sizeof(double), s));
+    return 0;
+}
+
+// mul_hess_blk!(wx, kkt, t) (reference :1141-1146): wx, t of length n + n_ineq; pr_diag: the handle's (the last assemble's)
+int mnk_schur_mul_hess_blk(mnk_schur* h, double* wx, const double* t, int loc) {
+    int rc = schur_kkt_enter(h, wx && t, "mnk_schur_mul_hess_blk");
+    if (rc) return rc;
+    auto& kv = h->kv;
+    KKT_REQUIRE(kv.have_vals && kv.have_hess, "%s: call mnk_schur_assemble first", "mnk_schur_mul_hess_blk");
+    hipStream_t s = h->ctx->stream;
+    const int64_t n = h->as.n, npr = h->as.n + h->as.n_ineq;
+    double* dw = wx;
+    const double* dt = t;
+    if (loc != MNK_DEVICE) {
+        dw = kv.va.p;
+        dt = kv.vb.p;
+        MNK_HIP(mnk::h2d_copy(kv.vb.p, t, (size_t)npr * sizeof(double), s));
+    }
+    rc = schur_spmv(h, SCHUR_OP_H, h->hess_v(), 1.0, dt, 0.0, dw);
+    if (rc) return rc;
+    hipLaunchKernelGGL(schur_hess_blk_diag_kernel, MNK_GRID1(npr), dw, dt, h->pr_diag(), n, npr);
+    MNK_HIP(hipGetLastError());
+    if (loc != MNK_DEVICE) MNK_HIP(mnk::d2h_copy(wx, dw, (size_t)npr * sizeof(double), s));
     return 0;
 }
 

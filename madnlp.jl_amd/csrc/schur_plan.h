@@ -71,4 +71,30 @@ struct SchurAssemblyPlan {
 // check that failed (a string literal).
 const char* schur_assembly_plan(const SchurPatterns& in, SchurAssemblyPlan& out);
 
+// ---- the sparse products of the device-side solve_kkt! / mul! / jtprod! / mul_hess_blk! (mnk_schur_solve_kkt and its kin) ----
+// Three operators over the COO value arrays of the last mnk_schur_assemble, each a ROW LIST: the entries of row r are
+// q in [ptr[r], ptr[r + 1]), entry q multiplies x[idx[q]] by vals[perm[q]] (perm: position in the COO value array -- there is
+// no compress step, duplicates stay separate terms), in COO order within a row.  J: m rows over jac; Jt: n rows over jac;
+// H = Symmetric(hess, :L): n rows over hess, every entry forced to the lower triangle and mirrored, a diagonal entry once.
+// A row with more than T entries is LONG (the design rows of Jt and H collect entries of every scenario): schur_spmv_long_kernel
+// gives it one 64-lane wavefront, the others are summed by one thread each.  `long_rows`: the long rows, ascending.
+constexpr int64_t SCHUR_SPMV_DEFAULT_T = 64;   // one entry per lane at the break-even
+enum { SCHUR_OP_J = 0, SCHUR_OP_JT = 1, SCHUR_OP_H = 2 };
+
+struct SchurSpmvOp {
+    int64_t rows = 0;
+    std::vector<int32_t> ptr, idx, perm, long_rows;
+    int64_t nnz() const { return (int64_t)idx.size(); }
+};
+
+struct SchurSpmvPlan {
+    int64_t T = 0;              // the threshold in force
+    SchurSpmvOp op[3];          // SCHUR_OP_J, SCHUR_OP_JT, SCHUR_OP_H
+    std::vector<int64_t> eq_rows;   // the equality rows in ascending order: scenario k's are [k * nc_eq, (k + 1) * nc_eq) of it
+};
+
+// Single rank only (all scenarios local, the design block owned).  T negative: SCHUR_SPMV_DEFAULT_T; INT64_MAX: no long rows.
+// Returns nullptr, or the message of the check that failed (a string literal).
+const char* schur_spmv_plan(const SchurPatterns& in, int64_t T, SchurSpmvPlan& out);
+
 }  // namespace mnk

@@ -205,6 +205,69 @@ const char* schur_assembly_plan(const SchurPatterns& in, SchurAssemblyPlan& out)
     return nullptr;
 }
 
+namespace {
+// rows of `op` from (row, column, COO position) triples given in COO order: a counting sort keeps that order within a row
+void spmv_rows(SchurSpmvOp& op, int64_t rows, const std::vector<int32_t>& r, const std::vector<int32_t>& c, const std::vector<int32_t>& e,
+               int64_t T) {
+    op.rows = rows;
+    op.ptr.assign((size_t)rows + 1, 0);
+    for (int32_t x : r) ++op.ptr[(size_t)x + 1];
+    for (int64_t i = 0; i < rows; ++i) op.ptr[(size_t)i + 1] += op.ptr[(size_t)i];
+    op.idx.resize(r.size());
+    op.perm.resize(r.size());
+    std::vector<int32_t> next(op.ptr.begin(), op.ptr.end() - 1);
+    for (size_t q = 0; q < r.size(); ++q) {
+        const int32_t at = next[(size_t)r[q]]++;
+        op.idx[(size_t)at] = c[q];
+        op.perm[(size_t)at] = e[q];
+    }
+    op.long_rows.clear();
+    for (int64_t i = 0; i < rows; ++i)
+        if ((int64_t)op.ptr[(size_t)i + 1] - op.ptr[(size_t)i] > T) op.long_rows.push_back((int32_t)i);
+}
+}  // namespace
+
+const char* schur_spmv_plan(const SchurPatterns& in, int64_t T_in, SchurSpmvPlan& out) {
+    const int64_t n = in.n, m = in.m, nnzh = in.nnzh, nnzj = in.nnzj;
+    const int base = in.index_base;
+    SCHUR_PLAN_REQUIRE(in.local_scen == nullptr && in.own_design,
+                       "mnk_schur_set_structure: the device-side products need a single rank (a sharded handle -- scenarios on other ranks "
+                       "or a design block it does not own -- has none)");
+    SCHUR_PLAN_REQUIRE(base == 0 || base == 1, "mnk_schur_set_structure: index_base must be 0 or 1");
+    SCHUR_PLAN_REQUIRE(n > 0 && m >= 0 && nnzh >= 0 && nnzj >= 0 && in.n_eq >= 0, "mnk_schur_set_structure: bad dimensions");
+    SCHUR_PLAN_REQUIRE((nnzh == 0 || (in.hess_I && in.hess_J)) && (nnzj == 0 || (in.jac_I && in.jac_J)) && (in.n_eq == 0 || in.ind_eq),
+                       "mnk_schur_set_structure: NULL pattern");
+    SCHUR_PLAN_REQUIRE(2 * nnzh < 2000000000 && nnzj < 2000000000 && n < 2000000000 && m < 2000000000,
+                       "mnk_schur_set_structure: structure exceeds int32 range");
+    const int64_t T = T_in < 0 ? SCHUR_SPMV_DEFAULT_T : T_in;
+    out.T = T;
+    std::vector<int32_t> r, c, e;
+    r.reserve((size_t)nnzj); c.reserve((size_t)nnzj); e.reserve((size_t)nnzj);
+    for (int64_t q = 0; q < nnzj; ++q) {
+        const int64_t i = in.jac_I[q] - base, j = in.jac_J[q] - base;
+        SCHUR_PLAN_REQUIRE(i >= 0 && i < m && j >= 0 && j < n, "mnk_schur_set_structure: Jacobian index out of range");
+        r.push_back((int32_t)i); c.push_back((int32_t)j); e.push_back((int32_t)q);
+    }
+    spmv_rows(out.op[SCHUR_OP_J], m, r, c, e, T);
+    spmv_rows(out.op[SCHUR_OP_JT], n, c, r, e, T);
+    r.clear(); c.clear(); e.clear();
+    for (int64_t q = 0; q < nnzh; ++q) {   // Symmetric(H, :L): the entry and, off the diagonal, its mirror image, in COO order
+        int64_t i = in.hess_I[q] - base, j = in.hess_J[q] - base;
+        SCHUR_PLAN_REQUIRE(i >= 0 && i < n && j >= 0 && j < n, "mnk_schur_set_structure: Hessian index out of range");
+        if (j > i) std::swap(i, j);
+        r.push_back((int32_t)i); c.push_back((int32_t)j); e.push_back((int32_t)q);
+        if (i != j) { r.push_back((int32_t)j); c.push_back((int32_t)i); e.push_back((int32_t)q); }
+    }
+    spmv_rows(out.op[SCHUR_OP_H], n, r, c, e, T);
+    out.eq_rows.assign(in.ind_eq, in.ind_eq + in.n_eq);
+    for (auto& x : out.eq_rows) {
+        x -= base;
+        SCHUR_PLAN_REQUIRE(x >= 0 && x < m, "mnk_schur_set_structure: equality index out of range");
+    }
+    std::sort(out.eq_rows.begin(), out.eq_rows.end());
+    return nullptr;
+}
+
 }  // namespace mnk
 
 // ---- host-only entry for tests and tools (include/madnlp_hip.h) ----
@@ -219,5 +282,26 @@ extern "C" int mnk_debug_schur_assembly_plan(int64_t n, int64_t m, int64_t nv, i
     mnk::SchurAssemblyPlan plan;
     if (const char* err = mnk::schur_assembly_plan(in, plan)) { mnk::set_error("%s", err); return -1; }
     plan.stats(out);
+    return 0;
+}
+
+// The row lists of one operator (which: 0 J, 1 J', 2 Symmetric(H, :L)) as mnk_schur_set_structure would build them with the
+// product threshold T: counts = {rows, entries, long rows, T in force}; any of the four arrays may be NULL (a first call sizes them).
+extern "C" int mnk_schur_spmv_plan(int64_t n, int64_t m, int64_t nv, int64_t nc, int64_t nnzh, const int32_t* hess_I, const int32_t* hess_J,
+                                   int64_t nnzj, const int32_t* jac_I, const int32_t* jac_J, int64_t n_ineq, const int64_t* ind_ineq,
+                                   int64_t n_eq, const int64_t* ind_eq, int index_base, int64_t ns_global, const int64_t* local_scen,
+                                   int own_design, int64_t T, int which, int32_t* row_ptr, int32_t* col_idx, int32_t* perm,
+                                   int32_t* long_rows, int64_t* counts) {
+    if (which < 0 || which > 2 || !counts) { mnk::set_error("mnk_schur_spmv_plan: which must be 0 (J), 1 (J') or 2 (H), counts not NULL"); return -1; }
+    const mnk::SchurPatterns in{ns_global, 0, 0, n, m, nv, nc, nnzh, hess_I, hess_J, nnzj, jac_I, jac_J, n_ineq, ind_ineq,
+                                n_eq, ind_eq, index_base, ns_global, local_scen, own_design, -1};
+    mnk::SchurSpmvPlan plan;
+    if (const char* err = mnk::schur_spmv_plan(in, T, plan)) { mnk::set_error("%s", err); return -1; }
+    const mnk::SchurSpmvOp& op = plan.op[which];
+    counts[0] = op.rows; counts[1] = op.nnz(); counts[2] = (int64_t)op.long_rows.size(); counts[3] = plan.T;
+    if (row_ptr) std::copy(op.ptr.begin(), op.ptr.end(), row_ptr);
+    if (col_idx) std::copy(op.idx.begin(), op.idx.end(), col_idx);
+    if (perm) std::copy(op.perm.begin(), op.perm.end(), perm);
+    if (long_rows) std::copy(op.long_rows.begin(), op.long_rows.end(), long_rows);
     return 0;
 }

@@ -84,7 +84,7 @@ class _KKTCommon:
         self.pr_diag[self.ind_lb] -= self.l_lower / self.l_diag
         self.pr_diag[self.ind_ub] -= self.u_lower / self.u_diag
 
-    # ---- the handle's bound / barrier state and device-side solve_kkt! / mul! (`_PFX` = "mnk_sc" / "mnk_dc")
+    # ---- the handle's bound / barrier state and device-side solve_kkt! / mul! (`_PFX` = "mnk_sc" / "mnk_dc" / "mnk_schur")
     def _call(self, name, *args):
         L.check(getattr(L.lib(), self._PFX + name)(self._h, *args), self._PFX + name)
 
@@ -98,11 +98,15 @@ class _KKTCommon:
         self._call("_set_barrier_terms", self.reg.ctypes.data, self.l_diag.ctypes.data, self.u_diag.ctypes.data,
                    self.l_lower.ctypes.data, self.u_lower.ctypes.data, L.MNK_HOST)
 
+    def _solve_kkt_solver(self):
+        """The solver argument of `<_PFX>_solve_kkt` (the Schur handle owns its solvers and takes none)."""
+        return (self.linear_solver._h,)
+
     def solve_kkt_device(self, w):
         """`solve_kkt!` on the device (reference `src/IPM/factorization.jl:143-167` sparse condensed, `:190-229` dense
         condensed, `:41-46` dense); `w` is an UnreducedKKTVector (host values) or a device tensor holding its values."""
         p, loc = _ptr(w.values if isinstance(w, UnreducedKKTVector) else w)
-        rc = getattr(L.lib(), self._PFX + "_solve_kkt")(self._h, self.linear_solver._h, p, loc)
+        rc = getattr(L.lib(), self._PFX + "_solve_kkt")(self._h, *self._solve_kkt_solver(), p, loc)
         if rc:
             from .linear_solver import SolveException
             raise SolveException(L.lib().mnk_last_error_string().decode())

@@ -16,6 +16,36 @@ from .linear_solver import BUNCHKAUFMAN, _ALGO, _LIVE_OBJECTS, FactorizationExce
 
 
 GRAM_NEVER = 2 ** 63 - 1   # `gram_row_threshold`: no inequality row is long (INT64_MAX of mnk_schur_set_gram_threshold)
+SPMV_NEVER = 2 ** 63 - 1   # `spmv_row_threshold`: no row of J, J' or H takes the wavefront path (mnk_schur_set_spmv_threshold)
+SPMV_DEFAULT_T = 64
+OP_J, OP_JT, OP_H = 0, 1, 2
+
+
+def spmv_plan(n, m, nv, nc, hess_I, hess_J, jac_I, jac_J, ind_ineq, ind_eq, T, which, ns_global=None, local_scen=None, own_design=True):
+    """The row lists `mnk_schur_set_structure` builds for the device-side products (`mnk_schur_spmv_plan`: host only, no device):
+    `which` = OP_J (m rows), OP_JT (n rows) or OP_H (Symmetric(H, :L), n rows) -> (row_ptr, col_idx, perm, long_rows, T in force).
+    Entry q of row r multiplies x[col_idx[q]] by the COO value perm[q]; `long_rows` are the rows with more than T entries
+    (T None or negative: the library's default).  Raises ValueError on a bad pattern or a sharded layout."""
+    hI, hJ = (np.ascontiguousarray(a, dtype=np.int32) for a in (hess_I, hess_J))
+    jI, jJ = (np.ascontiguousarray(a, dtype=np.int32) for a in (jac_I, jac_J))
+    ii, ie = (np.ascontiguousarray(a, dtype=np.int64) for a in (ind_ineq, ind_eq))
+    ls = None if local_scen is None else np.ascontiguousarray(local_scen, dtype=np.int64)
+    nsg = n // max(nv, 1) if ns_global is None else ns_global
+    counts = (C.c_int64 * 4)()
+
+    def call(ptr, idx, perm, lng):
+        rc = L.lib().mnk_schur_spmv_plan(n, m, nv, nc, len(hI), hI.ctypes.data, hJ.ctypes.data, len(jI), jI.ctypes.data, jJ.ctypes.data,
+                                         len(ii), ii.ctypes.data, len(ie), ie.ctypes.data, 0, nsg, None if ls is None else ls.ctypes.data,
+                                         1 if own_design else 0, -1 if T is None else int(T), int(which),
+                                         *(None if a is None else a.ctypes.data for a in (ptr, idx, perm, lng)), counts)
+        if rc:
+            raise ValueError(L.lib().mnk_last_error_string().decode())
+
+    call(None, None, None, None)
+    rows, nnz, nlong, t = (int(v) for v in counts)
+    ptr, idx, perm, lng = (np.zeros(k, dtype=np.int32) for k in (rows + 1, nnz, nnz, nlong))
+    call(ptr, idx, perm, lng)
+    return ptr, idx, perm, lng, t
 
 
 def shard(ns: int, rank: int, world: int):
@@ -60,12 +90,16 @@ class SchurDenseStage:
 
     # ---- device-side assembly (mnk_schur_set_structure / mnk_schur_assemble)
     def set_structure(self, n, m, nv, nc, hess_I, hess_J, jac_I, jac_J, ind_ineq, ind_eq, ns_global=None, local_scen=None, own_design=True,
-                      gram_row_threshold=None):
+                      gram_row_threshold=None, spmv_row_threshold=None):
         """Once: the COO patterns (0-based) from which the library builds, per touched entry of A_k / C_dk / S0, the list of its
         sources in the reference's scatter order (schur.jl:935-972).  Raises ValueError where the reference's
         `_build_schur_symbolic` throws (:140-236).  `gram_row_threshold`: an inequality row with more COO entries than this adds
         no pairs to the lists -- its condensation runs as weighted Gram products on the matrix cores (`mnk_schur_set_gram_threshold`;
-        None: the library's default, `GRAM_NEVER`: every row keeps its pairs)."""
+        None: the library's default, `GRAM_NEVER`: every row keeps its pairs).  `spmv_row_threshold`: a row of J, J' or
+        Symmetric(H, :L) with more entries than this is summed by one wavefront instead of one thread in the device-side products
+        (`mnk_schur_set_spmv_threshold`; None: the default, `SPMV_NEVER`: one thread per row throughout)."""
+        L.check(L.lib().mnk_schur_set_spmv_threshold(self._h, -1 if spmv_row_threshold is None else int(spmv_row_threshold)),
+                "mnk_schur_set_spmv_threshold")
         L.check(L.lib().mnk_schur_set_gram_threshold(self._h, -1 if gram_row_threshold is None else int(gram_row_threshold)),
                 "mnk_schur_set_gram_threshold")
         hI, hJ = (np.ascontiguousarray(a, dtype=np.int32) for a in (hess_I, hess_J))

@@ -4,6 +4,9 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -x c++
 //       madnlp.jl_amd/csrc/schur_plan.hip tools/schur_plan_check.cpp -o /tmp/schur_plan_check && /tmp/schur_plan_check
 //
+// The same structures go through schur_spmv_plan (the row lists of the device-side products of solve_kkt! / mul!): see the checks
+// at the end of the loop.
+//
 // Random two-stage structures (one row mask for all scenarios, duplicated COO entries, every subset of the scenarios local, with
 // and without the design block, thresholds from 0 to never) through schur_assembly_plan and mnk_debug_schur_assembly_plan: checks
 // what the kernels of schur.hip need of a plan -- every segment inside [A | C | S0] and its sources inside the value arrays, every
@@ -149,6 +152,45 @@ int main() {
                 for (int64_t v : p.seg_dst) mix(v);
                 for (int64_t v : p.slot_dst) mix(v);
                 ++nplans; nlong += p.long_rows; nslots += (long)p.slot_dst.size(); nterms += (long)pairs;
+                // the row lists of the device-side products (schur_spmv_plan): a single rank's only; what schur_spmv_rows_kernel and
+                // schur_spmv_long_kernel need of them -- pointers ascending from 0 to the entry count, every column inside the
+                // operand vector, every position inside the COO value array and ascending within a row (COO order), the long rows
+                // exactly the rows above the threshold, ascending
+                SchurPatterns whole = in;
+                whole.local_scen = nullptr;
+                whole.ns_local = ns;
+                SchurSpmvPlan sp;
+                if (nl < ns || !own) {
+                    CHECK(schur_spmv_plan(in, Tin, sp) != nullptr);
+                }
+                whole.own_design = 1;
+                CHECK(schur_spmv_plan(whole, Tin, sp) == nullptr && sp.T == T);
+                const int64_t nnzj = (int64_t)jI.size(), nnzh = (int64_t)hI.size();
+                const int64_t rows_of[3] = {m, n, n}, cols_of[3] = {n, m, n}, vals_of[3] = {nnzj, nnzj, nnzh};
+                for (int w = 0; w < 3; ++w) {
+                    const SchurSpmvOp& op = sp.op[w];
+                    CHECK(op.rows == rows_of[w] && (int64_t)op.ptr.size() == op.rows + 1 && op.ptr.front() == 0 && op.ptr.back() == op.nnz() &&
+                          op.perm.size() == op.idx.size());
+                    CHECK(w == SCHUR_OP_H ? op.nnz() >= nnzh && op.nnz() <= 2 * nnzh : op.nnz() == nnzj);
+                    std::vector<int32_t> lng;
+                    for (int64_t r = 0; r < op.rows; ++r) {
+                        CHECK(op.ptr[r] <= op.ptr[r + 1]);
+                        if ((int64_t)op.ptr[r + 1] - op.ptr[r] > T) lng.push_back((int32_t)r);
+                        for (int32_t q = op.ptr[r]; q < op.ptr[r + 1]; ++q) {
+                            CHECK(op.idx[q] >= 0 && op.idx[q] < cols_of[w] && op.perm[q] >= 0 && op.perm[q] < vals_of[w]);
+                            CHECK(q == op.ptr[r] || op.perm[q - 1] <= op.perm[q]);
+                            const int32_t e = op.perm[q];
+                            if (w == SCHUR_OP_J) CHECK(jI[e] - base == r && jJ[e] - base == op.idx[q]);
+                            if (w == SCHUR_OP_JT) CHECK(jJ[e] - base == r && jI[e] - base == op.idx[q]);
+                            if (w == SCHUR_OP_H)
+                                CHECK((hI[e] - base == r && hJ[e] - base == op.idx[q]) || (hJ[e] - base == r && hI[e] - base == op.idx[q]));
+                        }
+                    }
+                    CHECK(lng == op.long_rows);
+                    mix(op.nnz());
+                    for (int32_t v : op.long_rows) mix(v);
+                }
+                CHECK((int64_t)sp.eq_rows.size() == (int64_t)ind_eq.size() && std::is_sorted(sp.eq_rows.begin(), sp.eq_rows.end()));
             }
         }
     }
